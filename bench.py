@@ -7,7 +7,13 @@ One "step" = one `vcycle!(implicit, base, ops, levels, L, 3)` (3 CG smoothing st
 BASELINE config 3: 32^3 unit cubes x 6 tets, refinements=5 (L=6, Nf=6545, 1.287e9 fine DOFs), FP64,
 synthetic seeded inputs already resident in HBM.  value = Nf_L * Ne / t_vcycle, whole job.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds what takes runs of its own
+behind the timed region: the roofline of the finest-level applies, the per-level report, the placement tuner, the CPU
+oracle's baseline and the whole-driver time-to-tolerance runs.  --dump-outputs DIR writes what the last timed step left in
+the finest level's x and r (a fixed, seeded sample of their entries in the reference's hierarchical order) as DIR/x.npy,
+DIR/r.npy and the residual norm as DIR/residual_norm.npy, all float64.
 
 N > 1 is launched by the driver through torch.distributed.run (one rank per GPU, RCCL): the mesh
 grows with N (weak scaling, 32^3 cubes per GPU) and is partitioned by coarse-cell ownership.
@@ -24,6 +30,22 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0    # MI355X spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
+DUMP_SAMPLE = 3_000_000  # entries kept per dumped level vector (2 x 24 MB in float64; config 3's are 1.29e9 entries each)
+
+
+def dump_outputs(out_dir, top, rnorm):
+    """x and r of the finest level after the last timed step, as a caller gets them (to_host: the reference's hierarchical
+    order), flattened column-major; a vector larger than DUMP_SAMPLE is sampled at distinct indices drawn from a fixed seed, so
+    two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, vec in (("x", top.x), ("r", top.r)):
+        flat = vec.to_host().ravel(order="F")
+        if flat.size > DUMP_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(flat, dtype=np.float64))
+        del flat
+    np.save(os.path.join(out_dir, "residual_norm.npy"), np.array([rnorm], dtype=np.float64))
 
 
 def cpu_baseline(sample_width, levels, steps_top):
@@ -318,8 +340,13 @@ def preflight(ctx, hmg, hdist, dist, world, rank, width=None, levels=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed V-cycles")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure behind the timed region: roofline, per-level report, placement tuner, CPU baseline, "
+                         "time to tolerance (the options below that tune these apply to --full runs only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the finest level's x and r after the last timed step (rank 0's columns) to DIR/*.npy")
     ap.add_argument("--width", type=int, default=32, help="unit cubes per axis per GPU")
     ap.add_argument("--levels", type=int, default=6, help="refinements + 1")
     ap.add_argument("--smoothing-steps", type=int, default=3)
@@ -340,6 +367,8 @@ def main():
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="context option for an A/B run (hmg_ctx_set_option), e.g. --option apply_slab2=0; recorded in config.options")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher.  The ranks are CHILD processes of
@@ -479,20 +508,24 @@ def main():
         print(f"[rank {rank}] exchange ({ex.backend}): {ncalls} collectives, {ndoubles * 8 / 1e6:.1f} MB, "
               f"{ex.seconds:.3f} s host time inside them (warm-up included)", file=sys.stderr, flush=True)
     rnorm = hmg.norm_unique(top.r)            # first copies only; summed over ranks by the library
-    # roofline of the dominant kernel: two more V-cycles with HIP events around the finest-level operator applies (events of the
-    # library's own stream, include/hmg.h "time_apply")
-    ctx.set_option("time_apply", L)
-    for _ in range(2):
-        hmg.vcycle(implicit, base_level, ops, states, L, args.smoothing_steps)
-    launches, ms, nbytes = ctx.apply_timing()
-    ctx.set_option("time_apply", 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, top, rnorm)
+    # the roofline, the per-level report and the placement tuner below run with --full only
+    if args.full:
+        # roofline of the dominant kernel: two more V-cycles with HIP events around the finest-level operator applies (events of
+        # the library's own stream, include/hmg.h "time_apply")
+        ctx.set_option("time_apply", L)
+        for _ in range(2):
+            hmg.vcycle(implicit, base_level, ops, states, L, args.smoothing_steps)
+        launches, ms, nbytes = ctx.apply_timing()
+        ctx.set_option("time_apply", 0)
 
     # Outside the timed region: every level's operator applies between HIP events (two more V-cycles with the timer on for all
     # levels -- inside the timed region only the finest level is timed, an event pair per launch of the launch-bound small levels
     # would move the headline), and each level's whole share of a V-cycle (vector kernels, interface sums, transfers included)
     # from V-cycles started one level lower each time.
     level_rows = []
-    if args.level_report:
+    if args.full and args.level_report:
         ctx.set_option("time_apply", 1)
         nrep = 2
         for _ in range(nrep):
@@ -517,7 +550,7 @@ def main():
                                "apply_TBps": (by_k / 1e12) / (ms_k * 1e-3) if ms_k > 0 else None,
                                "level_share_ms": from_level[k] - from_level.get(k - 1, 0.0)})
 
-    if args.tune_placement > 0 and world == 1 and not force_part:
+    if args.full and args.tune_placement > 0 and world == 1 and not force_part:
         # An option of the library, reported beside the headline, never in it: which of the finest level's memory blocks (+ 2 spare
         # ones, freed again) plays x, b, r, p, Ap is chosen by timing that level's share of a V-cycle per candidate (include/hmg.h,
         # hmg_level_tune_placement) -- like an FFT plan.  It costs more than 18 V-cycles gain, so the driver leaves it off.
@@ -559,32 +592,6 @@ def main():
     if rank == 0:
         ms_step = 1e3 * dt / args.steps
         value = nf * ne_total * args.steps / dt
-        avg_ms = ms / max(launches, 1)
-        achieved = (nbytes / max(launches, 1)) / (avg_ms * 1e-3) / 1e9 if launches else 0.0
-        # HBM bytes per launch from the rocprofv3 PMC passes committed under profiles/ (FETCH_SIZE doubled
-        # as MI355X_MICROARCH.md prescribes for gfx950, + WRITE_SIZE); cannot be collected inside this process.
-        # ... and only next to the build they were collected on: the record carries the sha256 of the library file and of its
-        # sources (homogenization_jl_amd._lib.fingerprint, written by tools/collect_profiles.sh on the GPU box)
-        traffic, traffic_src = None, None
-        pmc = os.path.join(ROOT, "profiles", "apply_traffic.json")
-        fp = hmg._lib.fingerprint()
-        if not (world == 1 and w == 32 and L == 6):
-            traffic_src = "not collected for this workload (profiles/apply_traffic.json is BASELINE config 3 on one GPU)"
-        elif not os.path.exists(pmc):
-            traffic_src = "profiles/apply_traffic.json missing"
-        else:
-            try:
-                rec = json.load(open(pmc))
-                if rec.get("lib_sha256") and rec.get("lib_sha256") == fp["lib_sha256"]:
-                    traffic, traffic_src = rec.get("hbm_bytes_per_launch"), rec.get("source") + " [same library file as this run]"
-                elif rec.get("src_sha256") and rec.get("src_sha256") == fp["src_sha256"]:
-                    traffic, traffic_src = rec.get("hbm_bytes_per_launch"), rec.get("source") + " [same kernel sources as this run]"
-                else:
-                    traffic_src = ("stale: profiles/apply_traffic.json was collected on another build (its lib/src sha256 " +
-                                   f"{str(rec.get('lib_sha256'))[:12]}/{str(rec.get('src_sha256'))[:12]}, this run " +
-                                   f"{str(fp['lib_sha256'])[:12]}/{str(fp['src_sha256'])[:12]})")
-            except Exception as e:
-                traffic_src = f"unreadable: {e}"
         out = {
             "metric": "fine-DOF updates/sec per V-cycle (3D Tet64)",
             "value": value,
@@ -605,23 +612,50 @@ def main():
                        "setup_seconds": setup_seconds, "placement": placement,
                        "residual_norm_after": rnorm, "options": list(args.option),
                        "spare_vector_bytes": ctx.counter("spare_bytes"), "lazy_top_form": ctx.counter("lazy_top_form")},
-            "roofline": {"bound": "hbm",
-                         "kernel": ("hmg::k_apply<3,512,13,*,6> (finest-level operator apply, three 512-thread workgroups per CU"
-                                    if L == 6 else "hmg::k_apply_slab2<*> (finest-level operator apply, rolling LDS windows filled by loader waves, evaluated by evaluator waves"
-                                    if L == 7 else "hmg::k_apply (finest-level operator apply") +
-                                   "; per V-cycle: 1 residual, 6 fused CG passes, the local residual with the pending x-updates and the restriction in its "
-                                   "epilogue, the residual with the coarse-grid correction staged in the LDS image)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "launches": int(launches), "avg_launch_ms": avg_ms,
-                         "algorithmic_bytes_per_launch": nbytes / max(launches, 1),
-                         "levels": level_rows,
-                         "levels_note": "outside the timed region: operator applies of every level between HIP events over 2 more "
-                                        "V-cycles (level 5: one wave per cell, hmg::k_apply_wave), and each level's whole share of "
-                                        "a V-cycle from V-cycles started one level lower each time (as the TOP level of such a V-cycle a lower level pays a full "
-                                        "residual and live smoother tails it does not pay inside a V-cycle started above: an upper bound)"},
-            "build": fp,
+            "build": hmg._lib.fingerprint(),
         }
+        if args.full:
+            avg_ms = ms / max(launches, 1)
+            achieved = (nbytes / max(launches, 1)) / (avg_ms * 1e-3) / 1e9 if launches else 0.0
+            # HBM bytes per launch from the rocprofv3 PMC passes committed under profiles/ (FETCH_SIZE doubled
+            # as MI355X_MICROARCH.md prescribes for gfx950, + WRITE_SIZE); cannot be collected inside this process.
+            # ... and only next to the build they were collected on: the record carries the sha256 of the library file and of its
+            # sources (homogenization_jl_amd._lib.fingerprint, written by tools/collect_profiles.sh on the GPU box)
+            traffic, traffic_src = None, None
+            pmc = os.path.join(ROOT, "profiles", "apply_traffic.json")
+            fp = out["build"]
+            if not (world == 1 and w == 32 and L == 6):
+                traffic_src = "not collected for this workload (profiles/apply_traffic.json is BASELINE config 3 on one GPU)"
+            elif not os.path.exists(pmc):
+                traffic_src = "profiles/apply_traffic.json missing"
+            else:
+                try:
+                    rec = json.load(open(pmc))
+                    if rec.get("lib_sha256") and rec.get("lib_sha256") == fp["lib_sha256"]:
+                        traffic, traffic_src = rec.get("hbm_bytes_per_launch"), rec.get("source") + " [same library file as this run]"
+                    elif rec.get("src_sha256") and rec.get("src_sha256") == fp["src_sha256"]:
+                        traffic, traffic_src = rec.get("hbm_bytes_per_launch"), rec.get("source") + " [same kernel sources as this run]"
+                    else:
+                        traffic_src = ("stale: profiles/apply_traffic.json was collected on another build (its lib/src sha256 " +
+                                       f"{str(rec.get('lib_sha256'))[:12]}/{str(rec.get('src_sha256'))[:12]}, this run " +
+                                       f"{str(fp['lib_sha256'])[:12]}/{str(fp['src_sha256'])[:12]})")
+                except Exception as e:
+                    traffic_src = f"unreadable: {e}"
+            out["roofline"] = {"bound": "hbm",
+                               "kernel": ("hmg::k_apply<3,512,13,*,6> (finest-level operator apply, three 512-thread workgroups per CU"
+                                          if L == 6 else "hmg::k_apply_slab2<*> (finest-level operator apply, rolling LDS windows filled by loader waves, evaluated by evaluator waves"
+                                          if L == 7 else "hmg::k_apply (finest-level operator apply") +
+                                         "; per V-cycle: 1 residual, 6 fused CG passes, the local residual with the pending x-updates and the restriction in its "
+                                         "epilogue, the residual with the coarse-grid correction staged in the LDS image)",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                               "launches": int(launches), "avg_launch_ms": avg_ms,
+                               "algorithmic_bytes_per_launch": nbytes / max(launches, 1),
+                               "levels": level_rows,
+                               "levels_note": "outside the timed region: operator applies of every level between HIP events over 2 more "
+                                              "V-cycles (level 5: one wave per cell, hmg::k_apply_wave), and each level's whole share of "
+                                              "a V-cycle from V-cycles started one level lower each time (as the TOP level of such a V-cycle a lower level pays a full "
+                                              "residual and live smoother tails it does not pay inside a V-cycle started above: an upper bound)"}
         out["ms_per_step_ranks"] = {"min": 1e3 * dt_rank_min / args.steps, "max": ms_step}
         if world > 1 or force_part:
             ex = prob.exchange
@@ -635,9 +669,9 @@ def main():
                            "attempt": int(os.environ.get("HMG_BENCH_ATTEMPT", "1"))}
         if pre is not None:
             out["preflight"] = pre
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample_width, L, args.smoothing_steps)
-        if world == 1 and not args.no_time_to_tolerance and (w, L) == (32, 6):
+        if args.full and world == 1 and not args.no_time_to_tolerance and (w, L) == (32, 6):
             # outside the timed region: wall-clock to tolerance = 1e-5 of the whole driver (north_star).  n = 2,
             # refinements = 5 IS BASELINE config 3 (width 2 (2^2 + 4 * 3) = 32); n = 1, refinements = 4 is config 2,
             # the largest the CPU oracle finishes in about a minute.  The bench's own level vectors go back first.

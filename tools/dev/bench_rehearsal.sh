@@ -3,8 +3,8 @@
 # rank supervises its child, preflight parity on a small brick): gpurun_out/rehearsal/
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/rehearsal; rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 500 python3 bench.py > $O/bench_default.log 2> $O/bench_default.err; echo "default rc=$?"
-HMG_SINGLE_DEVICE=1 HMG_DIST_BACKEND=gloo HMG_PREFLIGHT_WIDTH=4 HMG_BENCH_ATTEMPT_SECONDS=300 timeout -k 10 700 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --width 8 --levels 5 --steps 3 --warmup 1 --no-cpu-baseline --no-time-to-tolerance > $O/bench_2rank_gloo.log 2> $O/bench_2rank_gloo.err; echo "2rank rc=$?"
+timeout -k 10 500 python3 bench.py --full > $O/bench_default.log 2> $O/bench_default.err; echo "default rc=$?"
+HMG_SINGLE_DEVICE=1 HMG_DIST_BACKEND=gloo HMG_PREFLIGHT_WIDTH=4 HMG_BENCH_ATTEMPT_SECONDS=300 timeout -k 10 700 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --width 8 --levels 5 --steps 3 --warmup 1 --no-cpu-baseline --no-time-to-tolerance > $O/bench_2rank_gloo.log 2> $O/bench_2rank_gloo.err; echo "2rank rc=$?"
 python3 - <<PY
 import json
 for f in ("bench_default", "bench_2rank_gloo"):

@@ -4,7 +4,7 @@
 set -e
 cd /tmp; export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/l7sq; rm -rf $O; mkdir -p $O
-CMD="python3 $R/bench.py --levels 7 --width 16 --sigma-high 100 --steps 2 --warmup 1 --no-cpu-baseline --no-time-to-tolerance --no-level-report --tune-placement 0"
+CMD="python3 $R/bench.py --full --levels 7 --width 16 --sigma-high 100 --steps 2 --warmup 1 --no-cpu-baseline --no-time-to-tolerance --no-level-report --tune-placement 0"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $O/a -- $CMD > $O/a.log 2>&1
 rocprofv3 --pmc SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM --output-format csv -d $O/b -- $CMD > $O/b.log 2>&1
 python3 - <<PY | tee $R/gpurun_out/r05_level7_sq.txt

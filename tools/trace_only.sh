@@ -4,7 +4,7 @@ set -e
 T=${1:-trace}
 cd /tmp; export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$T; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $O/trace.log 2>&1
 F=$(ls -t $O/trace/*/*kernel_stats.csv | head -1)
 python3 - "$F" > $O/stats.txt <<'PY'
 import csv, sys
