@@ -485,7 +485,7 @@ void launch_weight_cache(const Launch &L, const LevelDev &lv, const double *coef
 
 bool apply_wave_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused)
 {
-    if (!L.apply_wave || L.apply_threads != 0 || L.apply_unblocked) return false;
+    if (!L.apply_wave || L.apply_threads != 0) return false;
     if (!lv.wave_tab || !lv.wave_lpos || !lv.wcache || !mesh.cell_class) return false;
     if (lv.dim != 3 || lv.m != WM || lv.nf != WNF || lv.nfi != WNFI || lv.nei != WNEI || lv.ncorner != WNCORNER || lv.nedge != 6 ||
         lv.nface != 4 || lv.nblk != WNBLK || lv.blk_R != WR || lv.off_edge != WOFF_EDGE || lv.off_face != WOFF_FACE ||

@@ -188,14 +188,14 @@ struct hmg_ctx {
     ApplyTimer timer;
     bool fuse_cg_default = true;
     bool fold_x = true;   // V-cycle: pre-smoother's last x-update rides with the local residual
-    bool swap_rp = true;  // V-cycle: step 0 of a smoother takes r itself as p (pointer exchange), see smooth()
+    bool swap_rp = true;  // V-cycle: step 0 of a smoother takes r itself as p (pointer exchange), see smooth_form()
     bool fold_prolong = true;   // V-cycle: prolongation folded into the post-smoother's first residual
-    bool lazy_dead = true;      // V-cycle: the pre-smoother's dead last step writes nothing (see smooth())
+    bool lazy_dead = true;      // V-cycle: the pre-smoother's dead last step writes nothing (see smooth_form())
     bool fold_faces = true;     // fused CG: the face part of Ap's interface sum rides in the r-update (all steps but a live last one)
-    bool lean_post = true;      // V-cycle: the post-smoother's dead tail is dropped too (see vcycle_up())
+    bool lean_post = true;      // V-cycle: the post-smoother's dead tail is dropped too (see smooth_form())
     bool lazy_post = true;      // ... and below the finest level its dead last step writes nothing: both x-updates in one pass
-    int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth())
-    bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see vcycle_down())
+    int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
+    bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
     bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
     bool prolong_in_image = true;  // folded prolongation, level 6: the coarse column is staged at the even nodes of the lattice image
                                    // instead of in LDS of its own behind it (three workgroups per CU stay resident)
@@ -1360,7 +1360,38 @@ void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, in
     cut_pack(g, lv, a.out, 1);
 }
 
-// What a pre-smoother leaves to its caller when defer_x is set (see smooth()).
+// Who runs a smoother, and so what of its state is read afterwards: inside a V-cycle the reference overwrites part of it
+// unread (src/multigrid.jl:46-50,100-115).  With option lean_post = 0 the post-smoothers leave what Plain leaves.
+enum class Role {
+    Plain,       // hmg_smooth: x, r, p and Ap as the reference leaves them
+    Pre,         // vcycle_down: x only, and its last x-update(s) may be handed back (DeferredX)
+    PostTop,     // vcycle_up on the finest level: x and r; p and Ap are scratch
+    PostBelow,   // vcycle_up below the finest level: x only
+};
+
+// The form of the last CG step.  A dead step keeps only alpha = rs / p.Ap and x += alpha p: the interface sum of Ap,
+// r -= alpha Ap, r.r and the last p-update (src/multigrid.jl:60-68) go, and the fused kernel does not store Ap.
+enum class Tail {
+    Full,        // regular step, then x += alpha p and the reference's last p-update
+    ScratchP,    // ... without that p-update; Ap stays unsummed on the faces (option lean_post)
+    Top2,        // p formed in LDS only, Ap written alone, both pending x-updates ride in the r-update (lazy_top = 1)
+    Top3,        // ... and step steps - 2 writes its direction into the spare vector and leaves its x-update too (lazy_top = 2)
+    DeadXp,      // dead step, then x += alpha p
+    DeadDefer,   // dead step, x += alpha p left to the caller's local residual (fold_x)
+    DeadDefer2,  // dead step that writes nothing (p formed in LDS only), both pending x-updates left to the caller (lazy_dead)
+    DeadX2,      // dead step that writes nothing, then one pass does both x-updates (lazy_post)
+};
+
+struct SmoothForm {
+    bool swap_rp = false;   // step 0 takes r_0 itself as p_0 by exchanging the handles' device pointers (an even number of
+                            // times per V-cycle: wrapped buffers end up holding what their names say)
+    bool ride = false;      // the face part of Ap's interface sum rides in the r-update (every step but a live last one)
+    Tail tail = Tail::Full;
+    bool x_zero = false;    // (set by the caller) x is a coarse level's zero initial guess that is not in memory
+                            // (zero_entry_ok): the first residual is the constrained copy of b, b - A 0 to the last bit
+};
+
+// What a pre-smoother leaves to its caller (tails DeadDefer and DeadDefer2).
 struct DeferredX {
     int rs = -1;         // >= 0: x += (scal[rs] / scal[pap]) * p_last is still to be done
     int pap = S_PAP;
@@ -1370,30 +1401,36 @@ struct DeferredX {
     int a_num = -1, a_den = -1, b_num = -1, b_den = -1;
 };
 
-// live_tail = false drops the work of the last CG step whose results nobody can read: inside a V-cycle the
-// pre-smoother's r, p and Ap are overwritten (local residual, post-smoother's `p = r`, its first `Ap`) before
-// control returns to the caller, so of step `steps-1` only alpha = rs / p.Ap and x += alpha p are live -- the
-// interface sum of Ap, r -= alpha Ap, r.r and the last p-update (src/multigrid.jl:60-68) are skipped, and the fused
-// kernel does not even store Ap (p.Ap comes from the cell-local products and the multiplicities).
-// defer_x (with live_tail = false, fused path): the last x += alpha p is left to the caller, which folds it into
-// its next operator apply (vcycle: the local residual); returns the scalar slot of rs (alpha = scal[slot] /
-// scal[S_PAP]), or -1 if x is already up to date.
-// swap_rp (fused path): step 0 does not copy r into p.  p_0 = r_0 stays where it is, r_1 = r_0 - alpha Ap is written
-// into the other buffer and the device pointers of the two handles are exchanged (8 B/DOF less at step 0).  Only
-// for callers that smooth a level an even number of times before anybody looks at the handles' memory (vcycle: pre-
-// and post-smoother), so that wrapped external buffers end up holding what their names say.
-// xcoarse (fused path, cells that fit the LDS): x += P xcoarse (the coarse-grid correction, src/multigrid.jl:113) is
-// applied in the load phase of the first residual instead of by a separate prolongation pass.
-// With defer_x and lazy a dead last step i > 0 writes nothing at all: it forms p_i only in
-// LDS for the operator apply and the p.Ap reduction, and leaves both pending x-updates to the caller (DeferredX).
-// scratch_p (with live_tail = true): x and r are what the reference leaves, p and Ap are not -- the last p-update
-// (src/multigrid.jl:68) is skipped and Ap stays unsummed on the faces (its face sums ride in the r-update).  For the
-// post-smoother of the finest level inside hmg_vcycle: the caller reads x and r (the driver's residual norm,
-// src/examples/homogenized_coefficients.jl:286), the next smoothing_steps! starts with p <- r and Ap <- 0.
-// The spare direction vector of smooth()'s three-update form (lazy_top = 2) is SETUP: reserved when the first vector of the finest
-// level is created or wrapped (or by hmg_grid_reserve_spare), never inside a smoother.  Without it (reservation refused for lack of
-// memory, option lazy_top < 2 at that time, hmg_grid_reserve_spare(grid, 0)) smooth() takes the two-update form -- which form the
-// last finest-level post-smoother took is reported by hmg_ctx_counter "lazy_top_form", the bytes held by "spare_bytes".
+// Every context option that shapes the smoother is read here, before the first launch.
+SmoothForm smooth_form(const hmg_grid *g, int level, int steps, Role role)
+{
+    const LevelDev &lv = lev(g, level);
+    const hmg_ctx *c = g->ctx;
+    const bool lean = c->lean_post && (role == Role::PostTop || role == Role::PostBelow);
+    const bool dead = role == Role::Pre || (lean && role == Role::PostBelow);
+    SmoothForm f;
+    if (!g->fuse_cg) {
+        f.tail = dead ? Tail::DeadXp : lean ? Tail::ScratchP : Tail::Full;
+        return f;
+    }
+    const bool faces = c->fold_faces && lv.dim == 3 && lv.nfi > 0;
+    f.swap_rp = role != Role::Plain && c->swap_rp && steps > 0;
+    f.ride = faces;
+    if (role == Role::Pre && c->fold_x)
+        f.tail = steps >= 2 && c->lazy_dead ? Tail::DeadDefer2 : Tail::DeadDefer;
+    else if (dead)
+        f.tail = steps >= 2 && c->lazy_post ? Tail::DeadX2 : Tail::DeadXp;
+    else if (lean && steps >= 2 && c->lazy_top > 0 && faces)
+        f.tail = steps >= 3 && c->lazy_top > 1 && g->top_spare.n >= (size_t)lv.ld * (size_t)g->md.ncells ? Tail::Top3 : Tail::Top2;
+    else if (lean)
+        f.tail = Tail::ScratchP;
+    return f;
+}
+
+// The spare direction vector of the Top3 form is SETUP: reserved when the first vector of the finest level is created or
+// wrapped (or by hmg_grid_reserve_spare), never inside a smoother.  Without it (reservation refused for lack of memory,
+// option lazy_top < 2 at that time, hmg_grid_reserve_spare(grid, 0)) smooth_form() picks Top2 -- which form the last
+// finest-level post-smoother took is reported by hmg_ctx_counter "lazy_top_form", the bytes held by "spare_bytes".
 bool reserve_top_spare(hmg_grid *g, bool must)
 {
     hmg_ctx *c = g->ctx;
@@ -1434,20 +1471,15 @@ void release_top_spare(hmg_grid *g)
     g->top_spare.release();
 }
 
-// the three-update form applies to: 3D grids whose finest level has face interiors (smooth(): top_form)
+// the three-update form applies to: 3D grids whose finest level has face interiors (smooth_form(): Top3)
 bool wants_top_spare(const hmg_grid *g, int level)
 {
     return g->ctx && g->ctx->lazy_top > 1 && level == g->nlevels && g->dim == 3 && g->ld[(size_t)level - 1].nfi > 0;
 }
 
 DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
-                 bool live_tail = true, bool defer_x = false, bool swap_rp = false, const hmg_vec *xcoarse = nullptr,
-                 bool lazy = false, bool scratch_p = false, bool x_zero = false)
+                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr)
 {
-    // x_zero: x is the zero initial guess of a coarse level (src/multigrid.jl:106) and its memory does not hold the zeros:
-    // the first residual is r = b under the constraint (b - A 0 = b to the last bit), and the caller must not let anything
-    // read x before the deferred x-updates write it (vcycle_down checks that the step pattern guarantees this)
-    DeferredX none;
     // ref: src/multigrid.jl:46-71
     const LevelDev &lv = lev(g, level);
     const Launch &L = g->ctx->L;
@@ -1460,12 +1492,13 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.src = b->d;
         a.out = r->d;
         a.flags = 1;
-        if (x_zero) {
+        if (f.x_zero) {
             need(!xcoarse, "zero initial guess with a coarse-grid correction");
             launch_copy(L, r->d, b->d, n);
             launch_mask(L, lv, g->md, r->d, 0);
             interface_sum(g, lv, r->d);
         } else if (xcoarse) {
+            // (xcoarse: x += P xcoarse, the coarse-grid correction of src/multigrid.jl:113, rides in the load phase)
             a.xcoarse = xcoarse->d;
             a.ldc = lev(g, level - 1).ld;
             a.xout = x->d;
@@ -1477,152 +1510,134 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         }
     }
     int cur = S_RS, other = S_RS2;
-    if (g->fuse_cg) {
-        // p-update and both reductions ride along with the operator apply (see k_apply<.., FUSED>)
-        // Per step:  fused apply  [x += alpha_prev p_old;  p = r + beta p_old;  Ap = A p;  p.Ap (, r.r)]
-        //            interface sum of Ap
-        //            r -= alpha Ap;  r.r'
-        // The x-update of step i rides with the fused apply of step i+1 (which reads p anyway); the last one
-        // is done together with the reference's final p-update.
-        bool top3 = false;
+    if (!g->fuse_cg || steps <= 0) {
+        launch_copy_dot(L, p->d, r->d, n, cur);                          // p = r; rs = r.r
+        scalar_sum(g, cur, 1);
         for (int i = 0; i < steps; ++i) {
-            const bool dead = !live_tail && i == steps - 1;
-            ApplyArgs a{};
-            a.alpha = 1.0;
-            a.lambda = g->lambda;
-            a.x = r->d;
-            const bool lazy_dead = dead && defer_x && lazy && i > 0;
-            // the same dead step when nobody defers the x-updates (a post-smoother below the finest level inside hmg_vcycle, of
-            // which only x is read): p_i is formed in LDS only, neither p nor x is written by the apply (16 B/DOF instead of 40),
-            // and one pass does both x-updates, p_i formed on the fly (32 B/DOF instead of 24): 48 instead of 64 B/DOF, x the
-            // same to the last bit (round 4, option lazy_post)
-            const bool lazy_x2 = dead && !defer_x && g->ctx->lazy_post && i > 0;
-            // the face part of Ap's interface sum rides in the r-update below, except on the last step of a smoother
-            // whose state is handed back (Ap must then hold what the reference leaves)
-            const bool ride = g->ctx->fold_faces && lv.dim == 3 && lv.nfi > 0 && !dead &&
-                              !(live_tail && !scratch_p && i == steps - 1);
-            // the last step of a smoother of which x and r are read and p is scratch (the finest level's post-smoother inside
-            // hmg_vcycle): the apply forms p_i in LDS only and writes Ap alone (24 instead of 48 B/DOF), the r-update carries both
-            // pending x-updates with p_i formed on the fly (48 B/DOF instead of 26 + the 24 of the final x-update): 72 instead of 98
-            // B/DOF for that step, x and r the same to the last bit (round 4, option lazy_top)
-            const bool top_form = live_tail && scratch_p && steps >= 2 && g->ctx->lazy_top > 0 && g->ctx->fold_faces && lv.dim == 3 && lv.nfi > 0;
-            const bool lazy_top = top_form && i == steps - 1;
-            // ... and the step before it (three steps or more) writes its direction into a spare vector next to the previous one
-            // instead of over it, so that ITS x-update can wait as well (the apply no longer reads and writes x: 32 instead of
-            // 48 B/DOF; the last pass reads one stream more: 56 instead of 48): 8 B/DOF less again (option lazy_top = 2, the
-            // default; the spare vector is allocated at first use -- if that fails the form above is taken)
-            if (top_form && steps >= 3 && g->ctx->lazy_top > 1 && i == steps - 2 && g->top_spare.n >= (size_t)n) top3 = true;
-            if (top_form && i == steps - 1) g->ctx->last_top_form = top3 ? 2 : 1;   // (hmg_vcycle sets it to 0 in front of the post-smoother)
-            const bool top3_here = top3 && i == steps - 2;
-            a.x2 = i == 0 ? nullptr : (top3 && lazy_top) ? g->top_spare.p : p->d;       // p = r  /  p = r + beta p, beta = rs'/rs
-            a.xout = (i == 0 && swap_rp) || lazy_dead || lazy_x2 || lazy_top ? nullptr : top3_here ? g->top_spare.p : p->d;   // (swap_rp: r_0 itself becomes p_0)
-            a.xacc = i == 0 || lazy_dead || lazy_x2 || lazy_top || top3_here ? nullptr : x->d;     // x += alpha_{i-1} p_{i-1}
-            a.a_num = other;                                              // rs_{i-1} (after the swap below)
-            a.a_den = S_PAP;                                              // p_{i-1}.Ap_{i-1}: still the old value here
-            a.out = dead ? nullptr : Ap->d;
-            a.s_num = cur;
-            a.s_den = other;
-            a.flags = 1;
-            // (the kernels above read the previous p.Ap from S_PAP; the reduction that overwrites it is enqueued
-            //  behind them on the same stream)
-            if (lazy_x2) {
-                apply_then_sum(g, lv, a, true, S_PAP2, -1);        // (S_PAP keeps the previous step's p.Ap, as below)
-                launch_cg_x2_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, cur, S_PAP2);
-                return none;
-            }
-            if (lazy_dead) {
-                // p.Ap of this step goes to its own slot: S_PAP still holds the previous step's, which the caller
-                // needs for the first of the two pending x-updates
-                apply_then_sum(g, lv, a, true, S_PAP2, -1);
-                DeferredX d;
-                d.rs = cur;
-                d.pap = S_PAP2;
-                d.two_updates = true;
-                d.a_num = other;   // rs_{i-1}
-                d.a_den = S_PAP;   // p_{i-1}.Ap_{i-1}
-                d.b_num = cur;     // beta_i = rs_i / rs_{i-1}
-                d.b_den = other;
-                return d;
-            }
-            if (top3_here) {
-                // slots: rs_{i-1} in `other`, p.Ap_{i-1} in S_PAP (both kept for the deferred x-update), rs_i in `cur`;
-                // this step's p.Ap goes to S_PAP2 and its r.r to S_RS3
-                apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
-                launch_cg_rupdate_faces(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, S_RS3);
-                scalar_sum(g, S_RS3, 1);
-                continue;
-            }
-            if (lazy_top && top3) {
-                // rs_{i-2} in `other`, rs_{i-1} in `cur`, rs_i in S_RS3;  p.Ap_{i-2} in S_PAP, p.Ap_{i-1} in S_PAP2;  p_{i-2} in p, p_{i-1} in the spare
-                a.s_num = S_RS3;
-                a.s_den = cur;
-                apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
-                launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, S_RS3, S_PAP3, other, x->d, g->top_spare.p, cur, S_PAP2,
-                                          S_RS3, cur, p->d, other, S_PAP);
-                scalar_sum(g, other, 1);
-                return none;
-            }
-            if (lazy_top) {
-                // (p.Ap of this step to its own slot: S_PAP keeps the previous step's for the first of the two x-updates)
-                apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
-                launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, other, x->d, p->d, other, S_PAP, cur, other,
-                                          nullptr, 0, 0);
-                scalar_sum(g, other, 1);
-                return none;
-            }
-            apply_then_sum(g, lv, a, true, S_PAP, i == 0 ? cur : -1, true, !ride);
-            const double *r_in = r->d;
-            if (i == 0 && swap_rp) {
-                std::swap(r->d, p->d);                                    // p now names r_0, r the spare buffer
-                std::swap(r->own, p->own);
-                std::swap(r->alloc_cells, p->alloc_cells);
-                std::swap(r->bytes, p->bytes);
-                r_in = p->d;
-            }
-            if (dead) {
-                if (defer_x) {
-                    DeferredX d;
-                    d.rs = cur;
-                    return d;
-                }
+            apply(g, lv, 1.0, p->d, nullptr, Ap->d, 1);                        // Ap = A p, constraint
+            interface_sum(g, lv, Ap->d);
+            launch_dot(L, p->d, Ap->d, n, S_PAP);
+            scalar_sum(g, S_PAP, 1);
+            const bool last = i == steps - 1;
+            if (last && f.tail == Tail::DeadXp) {
                 launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rs / p.Ap) p
-                return none;
+                return {};
             }
-            if (ride)
-                launch_cg_rupdate_faces(L, lv, g->md, r_in, r->d, Ap->d, n, cur, S_PAP, other);
-            else
-                launch_cg_rupdate(L, r_in, r->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs / p.Ap
+            launch_cg_update(L, x->d, r->d, p->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs/pAp
             scalar_sum(g, other, 1);
+            if (last && f.tail == Tail::ScratchP) return {};
+            launch_cg_pupdate(L, p->d, r->d, n, other, cur);                   // beta = rs'/rs
             std::swap(cur, other);
         }
-        if (steps > 0) {
-            // x += alpha_last p (alpha_last = rs_{s-1} / p.Ap: `other` holds rs_{s-1} after the swap) and the
-            // reference's last p-update p = r + (rs_s / rs_{s-1}) p
-            launch_cg_xp_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, scratch_p ? 0 : 1);
-        } else {
-            launch_copy_dot(L, p->d, r->d, n, cur);
-            scalar_sum(g, cur, 1);
-        }
-        return none;
+        return {};
     }
-    launch_copy_dot(L, p->d, r->d, n, cur);                              // p = r; rs = r.r
-    scalar_sum(g, cur, 1);
-    for (int i = 0; i < steps; ++i) {
-        apply(g, lv, 1.0, p->d, nullptr, Ap->d, 1);                            // Ap = A p, constraint
-        interface_sum(g, lv, Ap->d);
-        launch_dot(L, p->d, Ap->d, n, S_PAP);
-        scalar_sum(g, S_PAP, 1);
-        if (!live_tail && i == steps - 1) {
-            launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);       // x += (rs / p.Ap) p
-            return none;
+    // Fused path: the p-update and both reductions ride along with the operator apply (see k_apply<.., FUSED>).
+    // Per step:  fused apply  [x += alpha_prev p_old;  p = r + beta p_old;  Ap = A p;  p.Ap (, r.r)]
+    //            interface sum of Ap
+    //            r -= alpha Ap;  r.r'
+    // The x-update of step i rides with the fused apply of step i+1 (which reads p anyway); the tail decides the last one.
+    // (The kernels read the previous p.Ap from S_PAP; the reduction that overwrites it is enqueued behind them.)
+    auto args = [&](int i) {
+        ApplyArgs a{};
+        a.alpha = 1.0;
+        a.lambda = g->lambda;
+        a.x = r->d;
+        a.x2 = i == 0 ? nullptr : p->d;                                   // p = r  /  p = r + beta p, beta = rs'/rs
+        a.xout = i == 0 && f.swap_rp ? nullptr : p->d;                   // (swap_rp: r_0 itself becomes p_0)
+        a.xacc = i == 0 ? nullptr : x->d;                                 // x += alpha_{i-1} p_{i-1}
+        a.a_num = other;                                                  // rs_{i-1} (after the swap below)
+        a.a_den = S_PAP;                                                  // p_{i-1}.Ap_{i-1}: still the old value here
+        a.out = Ap->d;
+        a.s_num = cur;
+        a.s_den = other;
+        a.flags = 1;
+        return a;
+    };
+    auto exchange_rp = [&]() {                                            // p now names r_0, r the spare buffer
+        std::swap(r->d, p->d);
+        std::swap(r->own, p->own);
+        std::swap(r->alloc_cells, p->alloc_cells);
+        std::swap(r->bytes, p->bytes);
+    };
+    auto step = [&](int i, bool ride) {
+        apply_then_sum(g, lv, args(i), true, S_PAP, i == 0 ? cur : -1, true, !ride);
+        const double *r_in = r->d;
+        if (i == 0 && f.swap_rp) {
+            exchange_rp();
+            r_in = p->d;
         }
-        launch_cg_update(L, x->d, r->d, p->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs/pAp
+        if (ride)
+            launch_cg_rupdate_faces(L, lv, g->md, r_in, r->d, Ap->d, n, cur, S_PAP, other);
+        else
+            launch_cg_rupdate(L, r_in, r->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs / p.Ap
         scalar_sum(g, other, 1);
-        if (scratch_p && i == steps - 1) return none;
-        launch_cg_pupdate(L, p->d, r->d, n, other, cur);                       // beta = rs'/rs
         std::swap(cur, other);
+    };
+    const int last = steps - 1;
+    for (int i = 0; i < last; ++i) {
+        if (f.tail == Tail::Top3 && i == last - 1) {
+            // slots: rs_{i-1} in `other`, p.Ap_{i-1} in S_PAP (both kept for the deferred x-update), rs_i in `cur`;
+            // this step's p.Ap goes to S_PAP2 and its r.r to S_RS3
+            ApplyArgs a = args(i);
+            a.xout = g->top_spare.p;
+            a.xacc = nullptr;
+            apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
+            launch_cg_rupdate_faces(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, S_RS3);
+            scalar_sum(g, S_RS3, 1);
+            continue;
+        }
+        step(i, f.ride);
     }
-    return none;
+    if (f.tail == Tail::Top2 || f.tail == Tail::Top3) g->ctx->last_top_form = f.tail == Tail::Top3 ? 2 : 1;
+    ApplyArgs a = args(last);
+    switch (f.tail) {
+    case Tail::Full:
+    case Tail::ScratchP:
+        step(last, f.ride && f.tail == Tail::ScratchP);
+        // x += alpha_last p (alpha_last = rs_{s-1} / p.Ap: `other` holds rs_{s-1} after the swap) and, Full only, the
+        // reference's last p-update p = r + (rs_s / rs_{s-1}) p
+        launch_cg_xp_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, f.tail == Tail::Full ? 1 : 0);
+        return {};
+    case Tail::DeadXp:
+    case Tail::DeadDefer:
+        a.out = nullptr;
+        apply_then_sum(g, lv, a, true, S_PAP, last == 0 ? cur : -1, true, true);
+        if (last == 0 && f.swap_rp) exchange_rp();
+        if (f.tail == Tail::DeadDefer) return DeferredX{cur};
+        launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rs / p.Ap) p
+        return {};
+    case Tail::DeadDefer2:
+    case Tail::DeadX2:
+        // p_i is formed in LDS only, for the apply and the p.Ap reduction: neither p nor x nor Ap is written.  p.Ap of this
+        // step goes to its own slot: S_PAP still holds the previous step's, which the first of the two x-updates needs.
+        a.out = a.xout = a.xacc = nullptr;
+        apply_then_sum(g, lv, a, true, S_PAP2, -1);
+        if (f.tail == Tail::DeadX2) {
+            launch_cg_x2_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, cur, S_PAP2);
+            return {};
+        }
+        return DeferredX{cur, S_PAP2, true, other, S_PAP, cur, other};   // alpha_i; alpha_{i-1} = rs_{i-1} / p.Ap_{i-1}, beta_i
+    case Tail::Top2:
+        // (p.Ap of this step to its own slot: S_PAP keeps the previous step's for the first of the two x-updates)
+        a.xout = a.xacc = nullptr;
+        apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
+        launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, other, x->d, p->d, other, S_PAP, cur, other,
+                                  nullptr, 0, 0);
+        scalar_sum(g, other, 1);
+        return {};
+    case Tail::Top3:
+        // rs_{i-2} in `other`, rs_{i-1} in `cur`, rs_i in S_RS3;  p.Ap_{i-2} in S_PAP, p.Ap_{i-1} in S_PAP2;  p_{i-2} in p, p_{i-1} in the spare
+        a.x2 = g->top_spare.p;
+        a.xout = a.xacc = nullptr;
+        a.s_num = S_RS3;
+        a.s_den = cur;
+        apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
+        launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, S_RS3, S_PAP3, other, x->d, g->top_spare.p, cur, S_PAP2,
+                                  S_RS3, cur, p->d, other, S_PAP);
+        scalar_sum(g, other, 1);
+        return {};
+    }
+    return {};
 }
 
 void coarse_probe_drop(hmg_grid *g);
@@ -1700,8 +1715,7 @@ void coarse_pcg(hmg_grid *g)
     // Convergence is decided on the device: k_coarse_pupdate sets a flag once r.r <= rtol^2 b.b and every kernel of
     // the later iterations returns at once, so a fixed number of iterations can be enqueued without a host round trip.
     // The first solve after a (re)assembly finds that number the slow way (a look every coarse_check iterations);
-    // later solves enqueue 1.5 x the largest count seen + 16 (the count moves by 10-20 % from one right-hand side to
-    // the next; a no-op iteration costs ~3 us of launches), leave a probe (flag, count, r.r) behind in pinned
+    // later solves enqueue the budget coarse_budget_for() gives, leave a probe (flag, count, r.r) behind in pinned
     // memory and return; the probe is checked at the next solve (or when the iteration count is asked for).
     hmg_ctx *c = g->ctx;
     const Launch &L = c->L;
@@ -1884,16 +1898,16 @@ void coarse_solve(hmg_grid *g, hmg_vec *b1, hmg_vec *x1)
 
 // Down leg of one level of the V-cycle (src/multigrid.jl:100-106): pre-smoother, local residual, restriction,
 // zero initial guess on the coarser level.  Inside the library the pre-smoother's dead tail is dropped and its pending
-// x-update(s) ride in the load phase of the local residual (see smooth()); x, the local residual in r and the
+// x-update(s) ride in the load phase of the local residual (Role::Pre); x, the local residual in r and the
 // coarse right-hand side are what the reference leaves, p and Ap are scratch.
 // Can level k be entered with a zero initial guess that is never written to memory?  Level 1: the scatter of the coarse
-// solution overwrites every entry of x.  Levels above: with the default two CG steps and the lazy dead tail the pre-smoother
-// never touches x, and the local residual that carries both pending x-updates writes it (flags bit 7: x is not read).
+// solution overwrites every entry of x.  Levels above: with two CG steps and the tail DeadDefer2 the pre-smoother never
+// touches x, and the local residual that carries both pending x-updates writes it (flags bit 7: x is not read).
 bool zero_entry_ok(const hmg_grid *g, int k, int steps)
 {
     if (!g->ctx->zero_entry) return false;
     if (k == 1) return true;
-    if (!(g->fuse_cg && g->ctx->fold_x && g->ctx->lazy_dead && steps == 2)) return false;
+    if (steps != 2 || smooth_form(g, k, steps, Role::Pre).tail != Tail::DeadDefer2) return false;
     // (register-blocked levels take that residual through the instantiation that also restricts in its epilogue -- the only one
     //  of theirs the zero-input form is compiled into)
     const LevelDev &lv = g->ld[k - 1];
@@ -1911,11 +1925,10 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
     const Launch &L = g->ctx->L;
-    // (an odd number of pointer exchanges would leave r and p swapped: both smoother calls take the same `steps`)
-    const bool swap_rp = g->ctx->swap_rp && g->fuse_cg && steps > 0;
-    const DeferredX dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], /*live_tail=*/false,
-                                /*defer_x=*/g->ctx->fold_x, swap_rp, nullptr, /*lazy=*/g->ctx->lazy_dead, false, x_zero);
-    need(!x_zero || (dx.rs >= 0 && dx.two_updates), "zero initial guess: the pre-smoother did not defer both x-updates");
+    SmoothForm form = smooth_form(g, k, steps, Role::Pre);
+    need(!x_zero || form.tail == Tail::DeadDefer2, "zero initial guess: the pre-smoother does not defer both x-updates");
+    form.x_zero = x_zero;
+    const DeferredX dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form);
     const bool skip_fill = inside && steps_next >= 0 && zero_entry_ok(g, k - 1, steps_next);
     if (dx.rs >= 0) {
         // local residual with the pre-smoother's pending x-update(s) folded into its load phase (x written back),
@@ -1958,26 +1971,19 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
     if (!skip_fill) launch_fill(L, nxt[0]->d, vec_len(nxt[0]), 0.0);
 }
 
-// Up leg (src/multigrid.jl:112-115): coarse-grid correction x_k += P x_{k-1}, post-smoother.
-// Inside hmg_vcycle (option lean_post) the post-smoother's dead tail is dropped as the pre-smoother's is: on the finest
-// level the caller can read x and r, so only the last p-update and the face sums of the last Ap go (scratch_p); on the
-// levels below nothing but x is read before the next visit overwrites r, p and Ap (local residual, p <- r, Ap <- 0:
-// src/multigrid.jl:46-50,104), so of the last CG step only alpha and x += alpha p are done.  x (and r on the finest
-// level) are bit-identical with the full sequence.
-void vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, int lean = 0)
+// Up leg (src/multigrid.jl:112-115): coarse-grid correction x_k += P x_{k-1}, post-smoother (role PostTop on the finest
+// level, PostBelow below it).
+void vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role)
 {
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
     const Launch &L = g->ctx->L;
-    const bool swap_rp = g->ctx->swap_rp && g->fuse_cg && steps > 0;
     // coarse-grid correction: folded into the post-smoother's first residual where the fused kernel can hold the
     // coarse column in LDS next to the lattice image (two workgroups per CU must still fit), else a separate pass
     const bool fold_p = g->ctx->fold_prolong && g->fuse_cg && apply_lds_bytes(lev(g, k)) <= 160 * 1024 &&
                         apply_lds_bytes(lev(g, k)) + sizeof(double) * (size_t)lev(g, k - 1).nf <= 80 * 1024;
     if (!fold_p) launch_prolong_add(L, lev(g, k), lev(g, k - 1), g->md.ncells, nxt[0]->d, cur[0]->d);
-    const bool x_only = lean == 2 && steps > 0;
-    smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], /*live_tail=*/!x_only, false, swap_rp, fold_p ? nxt[0] : nullptr,
-           false, /*scratch_p=*/lean == 1);
+    smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], smooth_form(g, k, steps, role), fold_p ? nxt[0] : nullptr);
 }
 
 void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top = true)
@@ -1992,7 +1998,7 @@ void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool 
     vcycle_down(g, k, steps, st, /*inside=*/true, /*x_zero=*/!top && zero_entry_ok(g, k, steps), steps_coarse);
     vcycle(g, k - 1, steps_coarse, steps_coarse, st, false);
     if (top) g->ctx->last_top_form = 0;
-    vcycle_up(g, k, steps, st, g->ctx->lean_post ? (top ? 1 : 2) : 0);
+    vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow);
 }
 
 // ---- multi-GPU cut exchange -------------------------------------------------------------------
@@ -2389,8 +2395,6 @@ static int ctx_create(int device, void *stream, bool use_given, hmg_ctx **out)
     c->L.num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     c->L.apply_threads = 0;
     c->L.apply_mass_only = 0;
-    c->L.apply_unblocked = 0;
-    c->L.persistent_waves = 32 * (int64_t)c->L.num_cu;
     c->L.cell_order = 1;
     c->L.weight_cache = 1;  // level 6: class weight rows from the class-weight cache (k_apply<.., WC>)
     c->L.apply_wave = 1;    // level 5: one wave per cell where the class-weight cache exists (hmg_apply_wave.hip)
@@ -2459,9 +2463,6 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
     std::string n(name);
     if (n == "apply_threads")
         ctx->L.apply_threads = (int)value;
-
-    else if (n == "apply_unblocked")
-        ctx->L.apply_unblocked = value != 0;
     else if (n == "apply_wg512")
         ctx->L.apply_wg512 = value != 0;
     else if (n == "apply_pack")            // 1 = default; 0: level 2 one cell per wave like levels 3-4 (A/B knob)
@@ -2486,8 +2487,6 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         ctx->L.wave_grid = std::max<int64_t>(1, value);
     else if (n == "cell_order")            // 1 = default: XCD-aware cell order of the register-blocked full-grid apply launches
         ctx->L.cell_order = value != 0;
-    else if (n == "persistent_waves")        // per CU; 0 = one workgroup per cell (dev / A-B knob)
-        ctx->L.persistent_waves = value > 0 ? value * (int64_t)ctx->L.num_cu : (int64_t)1 << 40;
     else if (n == "coarse_poly")           // Chebyshev iterates per preconditioner application of the level-1 PCG (1 = Jacobi)
         ctx->coarse_poly = std::max<int>(1, std::min<int>(16, (int)value));
     else if (n == "coarse_maxit")
@@ -2518,7 +2517,7 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         ctx->lazy_post = value != 0;
     else if (n == "lazy_top")
         ctx->lazy_top = (int)value;
-    else if (n == "prolong_in_image" || n == "prolong_gather")   // (prolong_gather: the option's name in round 2)
+    else if (n == "prolong_in_image")
         ctx->prolong_in_image = value != 0;
     else if (n == "overlap_min_doubles")
         ctx->overlap_min_doubles = value;
@@ -3345,7 +3344,7 @@ int hmg_smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_ve
     check_vec(g, level, r, "r");
     check_vec(g, level, p, "p");
     check_vec(g, level, Ap, "Ap");
-    smooth(g, level, steps, x, b, r, p, Ap);
+    smooth(g, level, steps, x, b, r, p, Ap, smooth_form(g, level, steps, Role::Plain));
     HMG_END
 }
 
@@ -3425,7 +3424,7 @@ int hmg_level_tune_placement(hmg_grid *g, int level, int steps, hmg_vec **states
             // as hmg_vcycle runs them on its top level (each half exchanges the r and p pointers: restored by the pair; the
             // coarse x stays the zero it is)
             vcycle_down(g, level, steps, states, /*inside=*/true, /*x_zero=*/false, /*steps_next=*/2);
-            vcycle_up(g, level, steps, states, c->lean_post ? 1 : 0);
+            vcycle_up(g, level, steps, states, Role::PostTop);
             HIPCHK(hipEventRecord(e1, c->stream));
             HIPCHK(hipEventSynchronize(e1));
             float ms = 0.f;
@@ -3543,7 +3542,7 @@ int hmg_vcycle_up(hmg_grid *g, int level, int steps, hmg_vec **states)
 {
     HMG_TRY
     check_two_levels(g, level, states);
-    vcycle_up(g, level, steps, states, g->ctx->lean_post ? 1 : 0);   // as the finest level of hmg_vcycle
+    vcycle_up(g, level, steps, states, Role::PostTop);   // as the finest level of hmg_vcycle
     HMG_END
 }
 

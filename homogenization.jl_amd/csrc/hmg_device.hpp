@@ -158,7 +158,6 @@ struct Launch {
     int num_cu;
     int apply_threads;    // 0 = auto
     int apply_mass_only;  // 1: only the mass term (next_rhs!), set around a single launch
-    int apply_unblocked;  // 1: node-per-thread interior sweep instead of the register-blocked one (dev / A-B knob)
     int apply_wg512;      // 1 (default): cells that would take the 1024-thread register-blocked instantiation take the 512-thread one:
                           // three workgroups (three columns in flight) per CU instead of two
     int cell_order;       // 1 (default): full-grid register-blocked apply launches walk the cells XCD by XCD (MeshDev::cell_perm)
@@ -174,8 +173,6 @@ struct Launch {
     int64_t slab2_grid;   // its grid (0: one workgroup per CU)
     int restrict_slab2;   // 1 (default): the stand-alone restriction of levels with slab tables goes through it too (eight loader waves)
     int slab2_force;      // 1 (experiment): every 3D level with slab tables of two slabs or more takes it (level 6 with HMG_SLAB_LDS_KB <= 30)
-    int64_t persistent_waves;   // grid of the one-wave apply instantiations (default 32 per CU: what is resident at once); they
-                          // loop over the cells.  Larger than the number of cells = one workgroup per cell
 };
 
 // out = (src ? src : 0) + alpha * A x, then (use_mask) zero Dirichlet DOFs.  src may alias out.

@@ -1003,7 +1003,7 @@ size_t apply_lds_bytes(const LevelDev &lv)
 bool apply_restricts(const Launch &L, const LevelDev &lv)
 {
     // the conditions under which launch_apply_dim reaches the 512-thread register-blocked instantiations (level 6)
-    if (!(lv.dim == 3 && apply_lds_bytes(lv) <= 160 * 1024 && L.apply_threads == 0 && !L.apply_unblocked && lv.rs_word &&
+    if (!(lv.dim == 3 && apply_lds_bytes(lv) <= 160 * 1024 && L.apply_threads == 0 && lv.rs_word &&
           lv.rs_w && lv.nf_coarse > 0 && lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4))
         return false;
     if (lv.nf > 2048)       // level 6: the 512-thread shape
@@ -1063,7 +1063,7 @@ static void launch_apply_generic(const Launch &L, const LevelDev &lv, const Mesh
         b.ncell_list = nblocks;
     }
     // (NT == 64: persistent one-wave workgroups, see the kernel -- 32 waves per CU are resident)
-    const int64_t grid = NT == 64 ? std::min<int64_t>(nblocks, (int64_t)L.persistent_waves) : nblocks;
+    const int64_t grid = NT == 64 ? std::min<int64_t>(nblocks, 32 * (int64_t)L.num_cu) : nblocks;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, L.stream, lv, mesh.coef, mesh.dmask, b);
     check_launch();
 }
@@ -1138,8 +1138,7 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
     else if (nt <= 192 && nf <= 192)
         launch_apply_generic<DIM, 192, 1, FUSED, 0, WD>(L, lv, mesh, a, lds);
     else if (nt <= 256 && nf <= 1024) {
-        if (DIM == 3 && lv.blk_R == 4 && lv.nblk <= 192 && lv.nfi <= 128 && lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4 &&
-            !L.apply_unblocked) {
+        if (DIM == 3 && lv.blk_R == 4 && lv.nblk <= 192 && lv.nfi <= 128 && lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4) {
             if constexpr (!WD) {
                 if (FUSED && DIM == 3 && a.rcoarse && lv.rs_word && lv.rs_w && !a.xcoarse) {
                     launch_apply_generic<DIM, 256, 4, FUSED, DIM == 3 ? 4 : 0, false, false, FUSED && DIM == 3>(
@@ -1158,14 +1157,14 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
         if constexpr (!WD) {
             if (nt <= 512) {
                 if (DIM == 3 && lv.blk_R == 6 && lv.nblk <= 1024 && lv.nfi <= 512 && lv.nei <= 64 && lv.nedge == 6 &&
-                    lv.ncorner == 4 && !L.apply_unblocked)
+                    lv.ncorner == 4)
                     launch_apply_generic<DIM, 512, 13, FUSED, DIM == 3 ? 6 : 0>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                 else
                     launch_apply_generic<DIM, 512, 13, FUSED>(L, lv, mesh, a, lds);
             } else
                 launch_apply_generic<DIM, 640, 11, FUSED>(L, lv, mesh, a, lds);
         }
-    } else if (DIM == 3 && lv.blk_R == 6 && lv.nblk <= 960 && lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4 && !L.apply_unblocked) {
+    } else if (DIM == 3 && lv.blk_R == 6 && lv.nblk <= 960 && lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4) {
         if constexpr (!WD) {
             if (L.apply_wg512 && lv.nfi <= 512) {
                 // (own instantiation: the in-image staging of the coarse column costs the others registers; it handles the

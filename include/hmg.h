@@ -50,49 +50,56 @@ int hmg_ctx_sync(hmg_ctx *ctx);
 /* Hands the blocks of destroyed level vectors that the context keeps for reuse (option "vec_pool") back to the device;
  * done automatically when an allocation of a level vector fails and when the context goes. */
 int hmg_ctx_release_memory(hmg_ctx *ctx);
-/* option names: "apply_threads" (workgroup size of the apply kernel, 0 = auto), "apply_wg512" (1 = default: level-6
- * cells -- 6545 nodes, 52 KB of LDS -- are applied by 512-thread workgroups, three resident per CU; 0 = by 1024-thread
- * workgroups, two per CU; same arithmetic per node), "fuse_cg" (1 = fused CG pass,
- * default; read when a grid is created), "fold_x" / "lazy_dead" / "swap_rp" / "fold_prolong" (1 = default: hmg_vcycle
- * folds the pre-smoother's last x-update into the local residual / lets the pre-smoother's last step write nothing
- * and folds both pending x-updates / lets CG step 0 take r itself as p by exchanging the two handles' device
- * pointers / folds the prolongation into the post-smoother's first residual -- exact savings, results unchanged;
- * 0 = the plain sequence), "lean_post" (1 = default: hmg_vcycle also drops the post-smoothers' dead tails -- the last
- * p-update and, below the top level, everything of the last CG step but x += alpha p; x of every level and r of the
- * top level are unchanged bit for bit, p / Ap (and r below the top level) are scratch on return, as they are for the
- * reference's own callers: the next smoothing_steps! overwrites them before reading, src/multigrid.jl:46-50;
- * 0 = they hold what the reference leaves), "lazy_post" (1 = default: below the top level the post-smoother's dead last step
- * writes nothing -- its direction is formed in LDS for the apply and again on the fly by the one pass that does both pending
- * x-updates; x unchanged bit for bit), "lazy_top" (the same on the top level, where r is live as well: 1 = the last
- * step's apply writes Ap alone and its r-update carries both x-updates; 2 = default: with three steps or more the step before
- * writes its direction into a spare vector of the top level's size -- reserved when the first vector of the finest level is
- * created or wrapped, or by hmg_grid_reserve_spare; never inside a V-cycle -- and leaves its x-update to
- * that pass too; x and r unchanged bit for bit), "apply_wave" (1 = default: cells of 969 nodes -- 3D level 5 -- are applied by one WAVE
- * per cell with the class weights taken from a cache that hmg_grid_set_operator fills, hmg_apply_wave.hip; 0 = the 256-thread
- * workgroup kernel; taken only where the mesh has at most 1024 distinct coefficient rows and |alpha| = 1; "wave_grid": its
- * persistent waves per CU, default 16 = what the LDS holds, "wave_grid_total": the same as an absolute number -- tests), "prolong_in_image" (1 = default: on level 6 the folded prolongation stages the
- * coarse column at the even nodes of the LDS lattice image itself instead of in LDS of its own behind it, which would cost
- * the third resident workgroup; "prolong_gather", the option's round-2 name, is still accepted), "fold_restrict" (1 = default:
- * inside hmg_vcycle the local residual of levels 6 and 5 restricts itself in its kernel's epilogue and is not stored; the
- * coarse right-hand side is the stand-alone restriction's to the last bit), "zero_entry" (1 = default: inside hmg_vcycle a
- * coarse level's zero initial guess is never written -- its first residual is the constrained copy of b and the local
- * residual that carries both pending x-updates does not read x), "fold_faces" (1 = default: the face part of A p's
- * interface sum rides in the CG r-update), "cell_order" (1 = default: the full-grid apply launches of cells of >= 969 nodes
- * walk the cells XCD by XCD -- workgroups are dispatched round-robin over the eight XCDs, XCD x takes the x-th contiguous eighth
- * of the cells; a performance hint, results unchanged), "persistent_waves" (one-wave apply workgroups per CU that walk the
- * cells of the small levels; default 32, 0 = one workgroup per cell), "overlap_min_doubles" / "comm_rehearsal" (multi-GPU, below),
- * "vec_pool" (1 = default: hmg_vec_destroy keeps the block for the next
- * hmg_vec_create of the same size -- re-allocating freed device memory costs ~35 ms per GB here; 0 = free at once and
- * release what is held; hmg_ctx_destroy releases it too), "coarse_maxit", "coarse_check", "coarse_poly" (4 = default: the
- * level-1 PCG is preconditioned by that many Chebyshev iterates of the Jacobi-scaled operator -- k - 1 sparse products without a
- * reduction per outer iteration --; 1 = plain Jacobi), "weight_cache" / "apply_small" / "apply_pack" (1 = default: class weights of levels 2-6
- * from the class-weight cache; levels 2-4 by the pipelined one-wave kernel, level 2 four cells to a wave, hmg_apply_small.hip),
- * "apply_slab2" (1 = default: cells larger than the LDS -- 3D level 7 -- are applied by ONE persistent 1024-thread workgroup per CU
- * whose waves have roles, hmg_apply_slab.hip: loader waves stream the next k-plane window from HBM while evaluator waves work on the
- * current one; 0 = the rolling-window kernel of rounds 1-4, same arithmetic per node; "slab2_grid": its workgroups, 0 = one per CU; "restrict_slab2": 1 = default, the stand-alone restriction of such a level goes
- * through it too; "slab2_force": experiment, level 6 through it -- needs HMG_SLAB_LDS_KB <= 30 when the grid is created),
- * "time_apply"; "coarse_rtol" and "coarse_poly_ratio" (20: the interval [lmax / ratio, lmax]) via hmg_ctx_set_option_f64.  Environment: HMG_SLAB_LDS_KB (LDS window of the slab
- * kernel for cells larger than the LDS, default 70). */
+/* Options of hmg_ctx_set_option: name, default, what the other value changes.
+ *
+ * Operator apply -- performance only, the same arithmetic per node:
+ *   "apply_threads" 0: workgroup size of the apply kernel chosen per level; n: n threads.
+ *   "apply_wg512" 1: level-6 cells (6545 nodes, 52 KB of LDS) by 512-thread workgroups, three per CU; 0: 1024 threads, two per CU.
+ *   "apply_pack" 1: 3D level-2 cells four to a wave (hmg_apply_small.hip); 0: one cell per wave, as on levels 3-4.
+ *   "apply_small" 1: levels 2-4 by the pipelined one-wave kernel where the class-weight cache exists; 0: the generic kernel.
+ *   "weight_cache" 1: level 6 takes its class weights from the cache hmg_grid_set_operator fills; 0: combines them per cell.
+ *   "apply_wave" 1: level 5 (969 nodes) by one wave per cell where the cache exists and |alpha| = 1 (hmg_apply_wave.hip);
+ *       0: the 256-thread kernel.  "wave_grid" 16: its persistent waves per CU; "wave_grid_total": as an absolute number.
+ *   "apply_slab2" 1: cells larger than the LDS (level 7) by one persistent 1024-thread workgroup per CU, loader waves
+ *       streaming the next k-plane window while evaluator waves work on the current one (hmg_apply_slab.hip); 0: the
+ *       rolling-window kernel.  "slab2_grid" 0: one workgroup per CU; n: n workgroups.
+ *   "restrict_slab2" 1: the stand-alone restriction of such a level goes through that kernel too; 0: the rolling-window kernel.
+ *   "slab2_force" 0; 1 (experiment): level 6 through it as well -- needs HMG_SLAB_LDS_KB <= 30 when the grid is created.
+ *   "cell_order" 1: full-grid apply launches of cells of >= 969 nodes walk the cells XCD by XCD; 0: in storage order.
+ *
+ * CG smoother and V-cycle.  The exact savings (every option below but fuse_cg) drop or fold work whose results the
+ * reference's own control flow overwrites before anybody reads them: x, and r of the top level, are the same to the last
+ * bit; 0 takes the plain sequence of src/multigrid.jl:46-119.
+ *   "fuse_cg" 1: the p-update and both reductions ride in the apply pass; 0: one kernel per statement.  Read when a grid
+ *       is created.
+ *   "fold_x" 1: the pre-smoother's last x-update rides in the local residual.
+ *   "lazy_dead" 1: the pre-smoother's dead last step writes nothing and both pending x-updates ride in the local residual.
+ *   "swap_rp" 1: CG step 0 takes r itself as p by exchanging the two handles' device pointers (an even number of times).
+ *   "fold_faces" 1: the face part of A p's interface sum rides in the CG r-update.
+ *   "lean_post" 1: the post-smoothers' dead tails go too: p and Ap, and r below the top level, are scratch on return (the
+ *       next smoothing_steps! overwrites them before reading, src/multigrid.jl:46-50); 0: they hold what the reference leaves.
+ *   "lazy_post" 1: below the top level the post-smoother's dead last step writes nothing; one pass does both x-updates.
+ *   "lazy_top" 2: on the top level the last r-update carries the pending x-updates of the last two steps (three steps or
+ *       more; the direction of the step before goes to a spare vector of the top level's size, reserved when the first
+ *       vector of the finest level is created or wrapped, or by hmg_grid_reserve_spare); 1: of the last step; 0: neither.
+ *   "fold_prolong" 1: the prolongation rides in the post-smoother's first residual.
+ *   "prolong_in_image" 1: on level 6 that residual stages the coarse column at the even nodes of the LDS lattice image
+ *       (three workgroups per CU stay resident); 0: in LDS of its own behind it.
+ *   "fold_restrict" 1: levels 5 and 6 restrict the local residual in the kernel's epilogue and do not store it.
+ *   "zero_entry" 1: a coarse level's zero initial guess is never written; its first residual is the constrained copy of b.
+ *
+ * Level-1 solve (hmg_coarse_last_iterations):
+ *   "coarse_poly" 4: the PCG is preconditioned by that many Chebyshev iterates of the Jacobi-scaled operator; 1: plain Jacobi.
+ *   "coarse_maxit" 5000, "coarse_check" 25: the checked solve's limit and the iterations between its looks at the residual.
+ *   "coarse_probe" 1: a budgeted solve leaves a probe behind; 0: none (stream-capture experiments).
+ *   hmg_ctx_set_option_f64: "coarse_rtol" 1e-13; "coarse_poly_ratio" 20: the preconditioner's interval is [lmax / ratio, lmax].
+ *
+ * Other:
+ *   "vec_pool" 1: hmg_vec_destroy keeps the block for the next hmg_vec_create of the same size (re-allocating freed device
+ *       memory costs ~35 ms per GB here); 0: free at once, and release what is held.
+ *   "time_apply" 0: off; n: HIP-event timing of the apply launches of levels >= n (hmg_ctx_apply_timing).
+ *   "overlap_min_doubles", "comm_rehearsal": multi-GPU, below.
+ * Environment: HMG_SLAB_LDS_KB, the LDS window of the slab kernel for cells larger than the LDS (default 70). */
 int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value);
 int hmg_ctx_set_option_f64(hmg_ctx *ctx, const char *name, double value);
 /* HIP-event timing of the operator-apply launches of levels >= the value given to option "time_apply"
@@ -218,9 +225,9 @@ int hmg_coarse_solve(hmg_grid *grid, hmg_vec *b1, hmg_vec *x1);
 /* Iterations of the last level-1 solve; blocks until its probe has landed.  -1 (hmg_last_error set): that solve did not
  * reach coarse_rtol.  How a solve is policed: the first solve on a new matrix (operator, lambda or domain changed) looks at
  * its residual every "coarse_check" iterations and fails with an error after "coarse_maxit"; later solves enqueue
- * 1.5 x the largest count seen + 16 iterations without a host round trip and leave a probe behind, which is judged by the
- * next call that synchronises the stream anyway (hmg_vec_norm_unique, hmg_vec_dot, hmg_integrate, hmg_ctx_sync, this
- * function) or by the next solve: an unconverged solve is an ERROR of that call (the V-cycle that used it was inexact),
+ * 1.25 x the largest count seen + 4 iterations (plain Jacobi, "coarse_poly" = 1: 1.5 x + 16) without a host round trip
+ * and leave a probe behind, which is judged by the next call that synchronises the stream anyway (hmg_vec_norm_unique,
+ * hmg_vec_dot, hmg_integrate, hmg_ctx_sync, this function) or by the next solve: an unconverged solve is an ERROR of that call (the V-cycle that used it was inexact),
  * the budget is dropped, and repeating the V-cycle solves the slow, checked way.  The reference's CHOLMOD solve
  * (src/multigrid.jl:84) cannot fail this way; the error keeps that contract visible. */
 int hmg_coarse_last_iterations(const hmg_grid *grid);

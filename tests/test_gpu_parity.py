@@ -779,13 +779,21 @@ EXACT_OPTIONS = ("lean_post", "lazy_post", "lazy_top", "lazy_dead", "fold_x", "s
                  "zero_entry", "cell_order")
 
 
-@pytest.mark.parametrize("steps", [1, 2, 4, 5])
+@pytest.mark.parametrize("steps", [1, 2, 4, 5, "3/1", "unfused"])
 def test_exact_savings_are_exact_for_other_step_counts(ctx, steps):
     """The same with 1, 2, 4 and 5 smoothing steps on the finest level (the deferred x-updates of its post-smoother take another
-    form for each: none, two updates in the last r-update, three with the spare direction vector behind a regular step)."""
+    form for each: none, two updates in the last r-update, three with the spare direction vector behind a regular step), with
+    one step below the finest level ("3/1": the pre-smoother defers one x-update, the post-smoother's dead step writes x), and
+    on a grid without the fused CG pass ("unfused": dead and scratch-p tails of the one-kernel-per-statement smoother)."""
     from homogenization_jl_amd import driver
     levels = 4
-    base, cond, g, op = driver.checkerboard_problem(ctx, hmg.Tet64, 4, levels, seed=12)
+    fused = steps != "unfused"
+    steps, steps_coarse = {"3/1": (3, 1), "unfused": (3, 2)}.get(steps, (steps, 2))
+    ctx.set_option("fuse_cg", int(fused))                      # (read when a grid is created)
+    try:
+        base, cond, g, op = driver.checkerboard_problem(ctx, hmg.Tet64, 4, levels, seed=12)
+    finally:
+        ctx.set_option("fuse_cg", 1)
     res = []
     try:
         for on in (1, 0, "lazy_top=1"):
@@ -798,7 +806,7 @@ def test_exact_savings_are_exact_for_other_step_counts(ctx, steps):
             hmg.apply_constraint(st[-1].x, levels, g)
             bl = hmg.BaseLevel(g)
             for _ in range(2):
-                hmg.vcycle(g, bl, [op] * levels, st, levels, steps)
+                hmg.vcycle(g, bl, [op] * levels, st, levels, steps, steps_coarse)
             res.append((st[-1].x.to_host(), st[-1].r.to_host()))
             for s in st:
                 s.close()
