@@ -219,6 +219,7 @@ struct hmg_ctx {
     int64_t small_launches = 0;              // launches of the pipelined small-level apply
     int64_t wave_launches = 0;               // launches of the one-wave-per-cell apply (hmg_ctx_counter)
     int64_t slab2_launches = 0;              // launches of the role-split slab apply (hmg_apply_slab.hip)
+    int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
     int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
@@ -578,8 +579,9 @@ static void upload_levels(hmg_grid *g)
                 for (size_t q = 0; q < lp.size(); ++q) lp[q] = (uint16_t)(T.meta[q] & 0xffffu);
                 B.lpos.upload(lp, s);
             }
-            {
+            if (!T.meta.empty()) {
                 // compact / wide addressing words (decode32 / decode32w in hmg_kernels.hip)
+                // (2D levels 9..11 have no packed words: none of these tables is built there, see build_level_tables)
                 std::vector<int32_t> slot_of_L(T.nf, -1);
                 for (int q = 0; q < T.nf; ++q) slot_of_L[(size_t)(T.meta[q] & 0xffffu)] = q;
                 const bool compact_ok = T.dim == 3 ? T.m <= 63 : T.m <= 255;
@@ -604,6 +606,13 @@ static void upload_levels(hmg_grid *g)
                 B.pos32.upload(p32, s);
                 B.pos32w.upload(p32w, s);
                 B.sweep32.upload(s32, s);
+            } else {
+                // 2D levels 9..11: the row-band kernels (hmg_apply_rows.hip) derive slot and class from (i,j) -- check that rule here
+                for (int q = 0; q < T.nf; ++q) {
+                    int cls = -1;
+                    const int sl = rows_slot(T.m, T.slot_ijk[3 * q], T.slot_ijk[3 * q + 1], T.nei, T.off_int, cls);
+                    if (T.dim != 2 || sl != q || cls != (int)T.slot_cls[q]) throw std::runtime_error("row-band apply: slot rule broken");
+                }
             }
             // register-blocked interior of k_apply (interior_block in hmg_kernels.hip): every R-th interior k-plane,
             // all its interior (i,j) in lattice order; R = 6 makes the 4495 interior nodes of level 6 945 entries,
@@ -825,7 +834,8 @@ static void upload_levels(hmg_grid *g)
             B.ctab.upload(T.ctab, s);
             B.hier2slot.upload(T.hier2slot, s);
             B.par_a.upload(T.par_a, s);
-            {
+            if (l == 0 || g->lt[l - 1].nf <= 0x10000) {
+                // (16-bit parents: not built where the coarse cell has more slots -- 2D level 11; its prolongation reads par_a / par_b)
                 std::vector<uint32_t> pp(T.par_a.size());
                 for (size_t q = 0; q < pp.size(); ++q) {
                     if ((uint32_t)T.par_a[q] > 0xffffu || (uint32_t)T.par_b[q] > 0xffffu)
@@ -2402,6 +2412,7 @@ static int ctx_create(int device, void *stream, bool use_given, hmg_ctx **out)
     c->L.n_wave_launches = &c->wave_launches;
     c->L.apply_slab2 = 1;   // level 7: one persistent workgroup per CU, loader and evaluator waves (hmg_apply_slab.hip)
     c->L.n_slab2_launches = &c->slab2_launches;
+    c->L.n_rows_launches = &c->rows_launches;
     c->L.slab2_grid = 0;
     c->L.slab2_force = 0;
     c->L.restrict_slab2 = 1;
@@ -2439,6 +2450,7 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     const std::string n(name);
     if (n == "wave_launches") return ctx->wave_launches;
     if (n == "slab2_launches") return ctx->slab2_launches;
+    if (n == "rows_launches") return ctx->rows_launches;
     if (n == "small_launches") return ctx->small_launches;
     if (n == "comm_calls") return ctx->comm_calls;
     if (n == "device_allocs") return device_allocs().load();

@@ -10,6 +10,28 @@ namespace hmg {
 // its addressing words two iterations (<= 2 x 1024 threads) ahead of a trip count rounded up to the block size
 constexpr int TABLE_PAD = 3 * 1024;
 
+// Storage slot and entity class of lattice node (i,j) of a 2D level with m intervals per edge (storage order of
+// build_level_tables: corners (0,0), (m,0), (0,m); edges j = 0, i = 0, i + j = m, each in ascending lattice order; the interior
+// in lattice order, j then i).  The row-band kernels of 2D levels without packed addressing words derive slots with it;
+// upload_levels checks it against the host tables of every such level.
+__host__ __device__ inline int rows_slot(int m, int i, int j, int nei, int off_int, int &cls)
+{
+    if (j == 0) {
+        cls = i == 0 ? 4 : i == m ? 5 : 1;
+        return i == 0 ? 0 : i == m ? 1 : 3 + i - 1;
+    }
+    if (i == 0) {
+        cls = j == m ? 6 : 2;
+        return j == m ? 2 : 3 + nei + j - 1;
+    }
+    if (i + j == m) {
+        cls = 3;
+        return 3 + 2 * nei + j - 1;
+    }
+    cls = 0;
+    return off_int + (j - 1) * (m - 1) - (((j - 1) * j) >> 1) + i - 1;
+}
+
 struct LevelDev {
     int dim, level, m;
     int nf, ld;
@@ -173,6 +195,7 @@ struct Launch {
     int64_t slab2_grid;   // its grid (0: one workgroup per CU)
     int restrict_slab2;   // 1 (default): the stand-alone restriction of levels with slab tables goes through it too (eight loader waves)
     int slab2_force;      // 1 (experiment): every 3D level with slab tables of two slabs or more takes it (level 6 with HMG_SLAB_LDS_KB <= 30)
+    int64_t *n_rows_launches;   // launches of the row-band apply of 2D cells larger than the LDS (hmg_ctx_counter "rows_launches")
 };
 
 // out = (src ? src : 0) + alpha * A x, then (use_mask) zero Dirichlet DOFs.  src may alias out.
@@ -193,6 +216,14 @@ void launch_apply_wave(const Launch &L, const LevelDev &lv, const MeshDev &mesh,
 // cells larger than the LDS (hmg_apply_slab.hip): one persistent workgroup per CU, loader and evaluator waves
 bool apply_slab2_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a);
 void launch_apply_slab2(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused);
+// 2D cells larger than the LDS (hmg_apply_rows.hip, levels 9..11): the cell walks through LDS in bands of lattice rows.  Throws for
+// the forms it does not have (folded prolongation, epilogue restriction, restriction weights).
+void launch_apply_rows(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused, bool wd);
+// prolongation where the coarse cell exceeds the LDS (2D levels 10, 11): 32-bit parents, coarse values gathered through L2
+void launch_prolong_add_wide(const Launch &L, const LevelDev &fine, const LevelDev &coarse, int64_t ncells, const double *xc,
+                             double *xf);
+// sum over first copies of x*x on levels without packed addressing words (entity class from the slot ranges): partials[0..nb)
+int64_t launch_norm2_unique_wide(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *x);
 // small 3D levels (hmg_apply_small.hip): one persistent, software-pipelined wave per cell
 bool apply_small_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused);
 void launch_apply_small(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused);

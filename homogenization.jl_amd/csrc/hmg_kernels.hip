@@ -1088,6 +1088,11 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
     //  VERDICT r4 item 4's "cell as two half-images, the second half's loads in flight while the first is evaluated")
     const bool force_slab2 = DIM == 3 && !WD && L.slab2_force && mesh.slab.head && mesh.slab.nslab >= 2 && lv.nf > 2048 &&
                              !a.xcoarse && !a.rcoarse && !(a.flags & (4 | 8));
+    if (DIM == 2 && lds > 160 * 1024) {
+        // 2D levels 9..11: the cell walks through LDS in bands of lattice rows (hmg_apply_rows.hip)
+        launch_apply_rows(L, lv, mesh, a, FUSED, WD);
+        return;
+    }
     if (lds > 160 * 1024 || force_slab2) {
         if (DIM != 3 || !mesh.slab.head) throw std::runtime_error("operator apply: cell does not fit the LDS");
         if constexpr (DIM == 3 && !WD) {
@@ -1554,6 +1559,10 @@ void launch_prolong_add(const Launch &L, const LevelDev &fine, const LevelDev &c
                         const double *xc, double *xf)
 {
     size_t lds = sizeof(double) * coarse.nf;
+    if (lds > 160 * 1024 && fine.dim == 2) {   // 2D levels 10 and 11: coarse values gathered through L2 (hmg_apply_rows.hip)
+        launch_prolong_add_wide(L, fine, coarse, ncells, xc, xf);
+        return;
+    }
     if (lds > 160 * 1024) throw std::runtime_error("prolongation: coarse cell does not fit LDS");
     if (fine.nf <= 256) {
         auto k = k_prolong_add<64>;
@@ -2135,6 +2144,15 @@ k_norm2_unique(LevelDev lv, int64_t ncells, const uint16_t *__restrict__ dupmask
 
 void launch_norm2_unique(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *x, int slot)
 {
+    if (!lv.meta) {   // 2D levels 9..11 have no packed words: entity classes from the slot ranges (hmg_apply_rows.hip)
+        const int64_t nbw = launch_norm2_unique_wide(L, lv, mesh, x);
+        if (nbw == 0) {
+            launch_fill(L, L.scal + slot, 1, 0.0);
+            return;
+        }
+        finalize(L, (int)nbw, slot);
+        return;
+    }
     int64_t nb = mesh.ncells;
     if (nb > (int64_t)L.num_cu * 8) nb = (int64_t)L.num_cu * 8;
     hipLaunchKernelGGL(k_norm2_unique, dim3((unsigned)nb), dim3(256), 0, L.stream, lv, mesh.ncells, mesh.dupmask, x,

@@ -104,9 +104,11 @@ int dir_index(int dim, int di, int dj, int dk)
 std::vector<LevelTables> build_level_tables(int dim, int nlevels)
 {
     if (dim != 2 && dim != 3) throw std::runtime_error("dim must be 2 or 3");
-    // 16-bit lattice addresses and 6/8-bit row indices in the packed tables: m <= 64 (3D), m <= 128 (2D)
-    if (nlevels < 1 || nlevels > (dim == 3 ? 7 : 8))
-        throw std::runtime_error(dim == 3 ? "nlevels must be in 1..7 for tetrahedra" : "nlevels must be in 1..8 for triangles");
+    // 16-bit lattice addresses and 6/8-bit row indices in the packed tables: m <= 64 (3D), m <= 128 (2D).  2D levels 9..11
+    // (m = 256..1024) build no packed addressing tables at all (meta, interior sweep): their kernels (hmg_apply_rows.hip) derive
+    // lattice positions and storage slots from (i,j) themselves.  Level 12 (2.1 M nodes per cell) is not offered.
+    if (nlevels < 1 || nlevels > (dim == 3 ? 7 : 11))
+        throw std::runtime_error(dim == 3 ? "nlevels must be in 1..7 for tetrahedra" : "nlevels must be in 1..11 for triangles");
     const int ndir = dim == 3 ? 15 : 7;
     const int ndiff = dim == 3 ? 6 : 3;
     const int nterm = ndiff + 1;
@@ -283,7 +285,8 @@ std::vector<LevelTables> build_level_tables(int dim, int nlevels)
             int n = m - k;
             return PO[k] + j * (n + 1) - j * (j - 1) / 2 + i;
         };
-        T.meta.assign(nf, 0);
+        const bool packed = dim == 3 || m <= 128;   // the packed words (pack_meta, sweep) hold this level's values
+        T.meta.assign(packed ? nf : 0, 0);
         int amin = 0, amax = nf - 1, amin_interior = 0;
         for (int s = 0; s < nf; ++s) {
             int i = T.slot_ijk[3 * s], j = T.slot_ijk[3 * s + 1], k = T.slot_ijk[3 * s + 2];
@@ -294,7 +297,7 @@ std::vector<LevelTables> build_level_tables(int dim, int nlevels)
                 A = tri(m - k) - j;
                 B = tri(m - k + 1) - j;
             }
-            T.meta[s] = pack_meta((uint32_t)L, (uint32_t)len, T.slot_cls[s], (uint32_t)A, (uint32_t)B);
+            if (packed) T.meta[s] = pack_meta((uint32_t)L, (uint32_t)len, T.slot_cls[s], (uint32_t)A, (uint32_t)B);
             int addr[15] = {L,           L + 1,           L - 1,       L + len - 1, L - len,
                             L + len,     L - len - 1,     L + A - len, L - B + len + 1,
                             L + A - 1,   L - B + 1,       L + A,       L - B,
@@ -318,7 +321,7 @@ std::vector<LevelTables> build_level_tables(int dim, int nlevels)
         // interior sweep: rows (j,k) that contain cell-interior nodes, all positions i = 0..len-1
         T.sweep_meta.clear();
         T.sweep_slot.clear();
-        if (T.nint > 0) {
+        if (T.nint > 0 && packed) {
             std::vector<int32_t> slot_of_L(nf, -1);
             for (int s2 = 0; s2 < nf; ++s2) slot_of_L[(int)(T.meta[s2] & 0xffffu)] = s2;
             const int kmax = dim == 3 ? m : 0;

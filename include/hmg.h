@@ -118,7 +118,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name);
 
 /* ---- grid: ImplicitFineGrid(base, levels)  (src/implicit_fine_grid.jl:13-18) ------------------ */
 /* Also derives ZeroDirichletConstraint(list_boundary_nodes_edges_faces(base)...)
- * (src/interface.jl:207-284, src/implicit_fine_grid.jl:80-84). */
+ * (src/interface.jl:207-284, src/implicit_fine_grid.jl:80-84).
+ * nlevels: 1..7 for tetrahedra, 1..11 for triangles (2D levels 9..11: cells larger than the LDS, row-band kernels). */
 int hmg_grid_create(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords /* dim*nnodes */,
                     int64_t ncells, const int64_t *cells /* (dim+1)*ncells, 1-based */, hmg_grid **out);
 int hmg_grid_destroy(hmg_grid *grid);
