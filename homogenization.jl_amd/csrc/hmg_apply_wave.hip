@@ -37,12 +37,6 @@ namespace hmg {
 
 namespace {
 
-// geometry this kernel is compiled for (checked by apply_wave_ok against the level's tables)
-constexpr int WM = 16, WNF = 969, WNFI = 105, WNEI = 15, WNCORNER = 4, WNBLK = 152, WNFC = 165, WR = 4;
-constexpr int WOFF_EDGE = 4, WOFF_FACE = 94, WNEC = 94;
-constexpr int WNQ = 16;            // slots per lane: 15 full rounds of 64 + 9
-constexpr int WVZ = 168;           // doubles in front of the lattice image: class rows 5..14 (edges, corners) x 16 + 8 spare (lanes without a slot write to the last one)
-
 // a zero the backend cannot see through: OR-ed into a loop-invariant table word it makes everything DECODED from the word
 // belong to the current cell -- otherwise the backend hoists dozens of decoded addresses out of the cell loop and spills them
 // (lessons of the round-2 pipelined kernel) -- while the word itself stays an ordinary loop-invariant value

@@ -134,7 +134,6 @@ struct LevelBufs {
     DevBuf<double> rs_w;
     DevBuf<uint16_t> rs_lp;
     DevBuf<uint16_t> blk_slot;
-    int nblk = 0, blk_R = 0;
     // one-wave-per-cell apply of level 5 (k_apply_wave): per-lane tables + the class-weight cache of the current operator
     DevBuf<uint32_t> wave_tab, wave_lpos, wave_par, wave_cl, wave_rs;
     DevBuf<double> wcache;
@@ -463,34 +462,19 @@ void ensure_reduce_scratch(hmg_ctx *c, int64_t nentries)
 void upload_mesh(hmg_grid *g)
 {
     const MeshTables &M = g->cur();
-    MeshDev &d0 = g->md;
-    d0.dim = M.dim;
-    d0.ncells = M.ncells;
-    d0.nnodes = M.nnodes;
+    const char *xcd_env = std::getenv("HMG_XCD_LISTS");      // (dev knob: 0 = the cut / inner lists as the partition analysis made them)
+    const MeshKernelTables K = build_mesh_kernel_tables(M, !(xcd_env && xcd_env[0] == '0'));
     DryUploads dry_scope(!g->ctx, &g->upload_hash);   // host-only grid: the tables are built and checksummed, nothing is uploaded
     hipStream_t s = g->ctx ? g->ctx->stream : nullptr;
     g->d_cells.upload(M.cells, s);
     g->d_face_pairs.upload(M.face_pairs, s);
-    {
-        std::vector<int32_t> fp((size_t)M.ncells * 4, -1);
-        for (size_t q = 3 * (size_t)M.ncut_face_pairs; q + 2 < M.face_pairs.size(); q += 3) {   // (cut pairs never ride in the r-update)
-            const int32_t ca = M.face_pairs[q], cb = M.face_pairs[q + 1], la = M.face_pairs[q + 2] & 15, lb = M.face_pairs[q + 2] >> 4;
-            fp[(size_t)ca * 4 + la] = (cb << 2) | lb;
-            fp[(size_t)cb * 4 + lb] = (ca << 2) | la;
-        }
-        g->d_face_partner.upload(fp, s);
-    }
+    g->d_face_partner.upload(K.face_partner, s);
     g->d_edge_ptr.upload(M.edge_ptr, s);
     g->d_edge_ent.upload(M.edge_ent, s);
     g->d_node_ptr.upload(M.node_ptr, s);
     g->d_node_ent.upload(M.node_ent, s);
     g->d_node_first.upload(M.node_first, s);
-    {   // the class-weight-cache kernels read the masks of two neighbouring cells as ONE 32-bit word (HMG_KP(uint32_t, dmask)[cell >> 1]
-        // in hmg_kernels.hip / hmg_apply_wave.hip / hmg_apply_small.hip): an even number of entries, whatever the cell count
-        std::vector<uint16_t> dm(M.dmask);
-        if (dm.size() & 1) dm.push_back((uint16_t)0);
-        g->d_dmask.upload(dm, s);
-    }
+    g->d_dmask.upload(K.dmask, s);
     g->d_dupmask.upload(M.dupmask, s);
     g->d_mult.upload(M.mult, s);
 #ifdef HMG_PHASE_TIMING
@@ -499,6 +483,9 @@ void upload_mesh(hmg_grid *g)
     constexpr size_t BP = 2;
 #endif
     if (g->d_blockpart.n < (size_t)M.ncells * BP) g->d_blockpart.alloc((size_t)M.ncells * BP);
+    g->d_cells_cut.upload(K.cells_cut, s);
+    g->d_cells_inner.upload(K.cells_inner, s);
+    g->d_cell_perm.upload(K.cell_perm, s);
     MeshDev &d = g->md;
     d.dim = M.dim;
     d.ncells = M.ncells;
@@ -518,42 +505,11 @@ void upload_mesh(hmg_grid *g)
     d.dupmask = g->d_dupmask.p;
     d.mult = g->d_mult.p;
     d.blockpart = g->d_blockpart.p;
-    {   // (the cell lists of the overlapped exchange in the XCD-aware order too: workgroup b -> XCD b % 8 walks the
-        //  (b % 8)-th contiguous eighth of the list, see cell_perm below)
-        const char *env = std::getenv("HMG_XCD_LISTS");          // (dev knob: 0 = the lists as the partition analysis made them)
-        const bool on = !(env && env[0] == '0');
-        auto xcd_order = [on](const std::vector<int32_t> &v) {
-            if (!on) return v;
-            const int64_t n = (int64_t)v.size(), len = (n + 7) / 8;
-            std::vector<int32_t> o((size_t)n);
-            int64_t k = 0;
-            for (int64_t b = 0; k < n; ++b) {
-                const int64_t pos = b / 8, c = (b % 8) * len + pos;
-                if (pos < len && c < n) o[(size_t)k++] = v[(size_t)c];
-            }
-            return o;
-        };
-        g->d_cells_cut.upload(xcd_order(M.cells_cut), s);
-        g->d_cells_inner.upload(xcd_order(M.cells_inner), s);
-    }
     d.cells_cut = g->d_cells_cut.p;
     d.cells_inner = g->d_cells_inner.p;
     d.ncells_cut = (int64_t)M.cells_cut.size();
     d.ncells_inner = (int64_t)M.cells_inner.size();
-    {   // XCD-aware cell order of the full-grid apply launches (option cell_order): workgroups are dispatched round-robin over
-        // the 8 XCDs (workgroup b -> XCD b % 8), so with cell = b every XCD's L2 sees every eighth column of every vector.  Here
-        // XCD x walks the x-th contiguous eighth of the cells instead: -0.7 ... -1.3 ms per V-cycle (2, 4, 16 regions: -0.1 ... -0.4;
-        // 64 regions or runs of 8 cells per XCD: slower; profiles/r03_experiments.txt).  A performance hint only: any mapping is correct.
-        const int64_t n = M.ncells, len = (n + 7) / 8;
-        std::vector<int32_t> perm((size_t)n);
-        int64_t k = 0;
-        for (int64_t b = 0; k < n; ++b) {
-            const int64_t pos = b / 8, c = (b % 8) * len + pos;
-            if (pos < len && c < n) perm[(size_t)k++] = (int32_t)c;
-        }
-        g->d_cell_perm.upload(perm, s);
-        d.cell_perm = g->d_cell_perm.p;
-    }
+    d.cell_perm = g->d_cell_perm.p;          // (XCD x walks the x-th eighth of the cells, see build_mesh_kernel_tables)
     d.ncut_edge_groups = M.ncut_edge_groups;
     d.ncut_node_groups = M.ncut_node_groups;
     d.ncut_face_pairs = M.ncut_face_pairs;
@@ -565,420 +521,61 @@ static void upload_levels(hmg_grid *g)
 {
     DryUploads dry_scope(!g->ctx, &g->upload_hash);
     hipStream_t s = g->ctx ? g->ctx->stream : nullptr;
+    // LDS of a slab window: half of the CU's, so that two workgroups are resident (HMG_SLAB_LDS_KB overrides, dev knob)
+    const char *kb_env = std::getenv("HMG_SLAB_LDS_KB");
+    const int slab_kb = kb_env ? std::max(16, std::min(158, std::atoi(kb_env))) : 70;
     g->ld.resize(g->nlevels);
     for (int l = 0; l < g->nlevels; ++l) {
         const LevelTables &T = g->lt[l];
+        const LevelTables *C = l > 0 ? &g->lt[l - 1] : nullptr;
+        const AddressTables A = build_address_tables(T);
+        const BlockedInterior blk = build_blocked_interior(T);
+        const SlabWindows sw = build_slab_windows(T, C, slab_kb);
+        const TransferTables X = build_transfer_tables(T, C, blk);
+        const WaveTables W = build_wave_tables(T, C, blk, X.clpos);
         g->lb.emplace_back(new LevelBufs);
         LevelBufs &B = *g->lb.back();
-        std::vector<uint32_t> B_blk_word_host;     // host copies for the tables of k_apply_wave (below)
-        std::vector<uint16_t> B_blk_slot_host, wave_cl_host;
-        {
-            B.meta.upload(T.meta, s);
-            {
-                std::vector<uint16_t> lp(T.meta.size());
-                for (size_t q = 0; q < lp.size(); ++q) lp[q] = (uint16_t)(T.meta[q] & 0xffffu);
-                B.lpos.upload(lp, s);
-            }
-            if (!T.meta.empty()) {
-                // compact / wide addressing words (decode32 / decode32w in hmg_kernels.hip)
-                // (2D levels 9..11 have no packed words: none of these tables is built there, see build_level_tables)
-                std::vector<int32_t> slot_of_L(T.nf, -1);
-                for (int q = 0; q < T.nf; ++q) slot_of_L[(size_t)(T.meta[q] & 0xffffu)] = q;
-                const bool compact_ok = T.dim == 3 ? T.m <= 63 : T.m <= 255;
-                auto pack32 = [&](uint64_t mt, int cls) -> uint32_t {
-                    if (!compact_ok) return 0u;
-                    const int sl = slot_of_L[(size_t)(mt & 0xffffu)];
-                    const uint32_t j = T.slot_ijk[3 * sl + 1], k = T.slot_ijk[3 * sl + 2];
-                    return (uint32_t)(mt & 0xffffu) | (j << 16) | (T.dim == 3 ? (k << 22) : 0u) | ((uint32_t)cls << 28);
-                };
-                std::vector<uint32_t> p32(T.meta.size()), s32(T.sweep_meta.size()), p32w(T.meta.size());
-                for (size_t q = 0; q < p32.size(); ++q) {
-                    p32[q] = pack32(T.meta[q], T.slot_cls[q]);
-                    const uint32_t i = T.slot_ijk[3 * q], j = T.slot_ijk[3 * q + 1], k = T.slot_ijk[3 * q + 2];
-                    if (T.dim == 3 && (i > 127 || j > 127 || k > 127))
-                        throw std::runtime_error("lattice coordinate exceeds 127");
-                    p32w[q] = (i & 127u) | ((j & 127u) << 7) | ((k & 127u) << 14) | ((uint32_t)T.slot_cls[q] << 21);
-                }
-                for (size_t q = 0; q < s32.size(); ++q) s32[q] = pack32(T.sweep_meta[q], 0);
-                // padding read (never used) by k_apply's two-ahead table prefetch: see TABLE_PAD there
-                p32.resize(p32.size() + TABLE_PAD, 0u);
-                s32.resize(s32.size() + TABLE_PAD, 0u);
-                B.pos32.upload(p32, s);
-                B.pos32w.upload(p32w, s);
-                B.sweep32.upload(s32, s);
-            } else {
-                // 2D levels 9..11: the row-band kernels (hmg_apply_rows.hip) derive slot and class from (i,j) -- check that rule here
-                for (int q = 0; q < T.nf; ++q) {
-                    int cls = -1;
-                    const int sl = rows_slot(T.m, T.slot_ijk[3 * q], T.slot_ijk[3 * q + 1], T.nei, T.off_int, cls);
-                    if (T.dim != 2 || sl != q || cls != (int)T.slot_cls[q]) throw std::runtime_error("row-band apply: slot rule broken");
-                }
-            }
-            // register-blocked interior of k_apply (interior_block in hmg_kernels.hip): every R-th interior k-plane,
-            // all its interior (i,j) in lattice order; R = 6 makes the 4495 interior nodes of level 6 945 entries,
-            // one pass of a 1024-thread workgroup
-            // (level 5: R = 4, 152 entries for its 256-thread workgroup)
-            if (T.dim == 3 && T.nint > 0 && T.m <= 63 && (T.nf > 2048 || (T.nf > 256 && T.nf <= 1024)) &&
-                sizeof(double) * (size_t)(T.nf + 512) <= 160 * 1024) {
-                const int R = T.nf > 2048 ? 6 : 4, m = T.m;
-                std::vector<int32_t> slot_of_L(T.nf, -1);
-                for (int q = 0; q < T.nf; ++q) slot_of_L[(size_t)(T.meta[q] & 0xffffu)] = q;
-                auto tri = [](int n) { return (n + 1) * (n + 2) / 2; };
-                std::vector<int> PO(m + 2, 0);
-                for (int k = 0; k <= m; ++k) PO[k + 1] = PO[k] + tri(m - k);
-                auto lin = [&](int i, int j, int k) { return PO[k] + j * (m - k + 1) - j * (j - 1) / 2 + i; };
-                std::vector<uint32_t> bw;
-                std::vector<uint16_t> bs;
-                size_t covered = 0;
-                for (int k0 = 1; k0 <= m - 3; k0 += R)
-                    for (int j = 1; j + k0 <= m - 2; ++j)
-                        for (int i = 1; i + j + k0 <= m - 1; ++i) {
-                            const int nv = std::min(R, m - i - j - k0);
-                            const int L = lin(i, j, k0), sl = slot_of_L[L];
-                            if (sl < T.off_int || T.slot_cls[sl] != 0) throw std::runtime_error("blocked interior: not an interior node");
-                            // the kernel derives the slots of the R nodes from the first: check that rule here
-                            int ds = tri(m - k0 - 3) - (j - 1), cur = sl;
-                            for (int r = 1; r < nv; ++r) {
-                                cur += ds;
-                                ds -= (m - k0) - 1 - r;
-                                if (cur != slot_of_L[lin(i, j, k0 + r)]) throw std::runtime_error("blocked interior: slot rule broken");
-                            }
-                            bw.push_back((uint32_t)L | ((uint32_t)j << 16) | ((uint32_t)k0 << 22) | ((uint32_t)nv << 28));
-                            bs.push_back((uint16_t)sl);
-                            covered += nv;
-                        }
-                if ((int)covered != T.nint) throw std::runtime_error("blocked interior: tables do not cover the interior");
-                // the same instantiation evaluates the faces one class per wave and skips the taps that leave the cell
-                // (face_tap_mask in hmg_kernels.hip: f0 k = 0, f1 j = 0, f2 i = 0, f3 i+j+k = m): check them against
-                // the class table, and the run counts the kernel is compiled for (4 waves x 2 runs of 64 per face,
-                // 3 runs of 64 for corners + edges)
-                static const uint32_t absent[4] = {1u << 8 | 1u << 10 | 1u << 12 | 1u << 14, 1u << 4 | 1u << 6 | 1u << 7 | 1u << 13,
-                                                   1u << 2 | 1u << 3 | 1u << 9 | 1u << 14, 1u << 1 | 1u << 5 | 1u << 11 | 1u << 13};
-                const int nw = T.nf > 2048 ? 16 : 4;     // waves of the workgroup that runs this level
-                bool ok = T.nface == 4 && T.nfi <= 128 * std::max(nw / 4, 1) && T.nei <= 64 && (int)bw.size() <= (nw - 1) * 64;
-                for (int f = 0; ok && f < 4; ++f)
-                    for (int d = 0; d < T.ndir; ++d) {
-                        bool zero = true;
-                        for (int t = 0; t < T.nterm; ++t) zero = zero && T.ctab[((size_t)(1 + f) * T.ndir + d) * T.nterm + t] == 0.0;
-                        if (((absent[f] >> d) & 1u) && !zero) ok = false;   // a tap the kernel skips carries weight
-                    }
-                // edges: an edge node keeps the taps both of its faces keep (edge_tap_mask)
-                static const int ef[6][2] = {{0, 1}, {0, 2}, {1, 2}, {0, 3}, {1, 3}, {2, 3}};
-                for (int e = 0; ok && e < T.nedge && T.nedge == 6; ++e)
-                    for (int d = 0; d < T.ndir; ++d) {
-                        bool zero = true;
-                        for (int t = 0; t < T.nterm; ++t) zero = zero && T.ctab[((size_t)(1 + T.nface + e) * T.ndir + d) * T.nterm + t] == 0.0;
-                        if ((((absent[ef[e][0]] | absent[ef[e][1]]) >> d) & 1u) && !zero) ok = false;
-                    }
-                if (!ok) throw std::runtime_error("blocked apply: the class table does not match the kernel's face / edge tap masks");
-                B.nblk = (int)bw.size();
-                B.blk_R = R;
-                B_blk_word_host = bw;
-                B_blk_slot_host = bs;
-                bw.resize(bw.size() + TABLE_PAD, 0u);
-                bs.resize(bs.size() + TABLE_PAD, (uint16_t)0);
-                B.blk_word.upload(bw, s);
-                B.blk_slot.upload(bs, s);
-            }
-            // slab tables: needed by the apply of levels whose cell exceeds the LDS (level 7), and used by the
-            // restriction of every large 3D level (level 6: the whole cell is one slab)
-            if (T.dim == 3 && T.nf > 2048) {
-                // greedy slabs of k-planes: the rolling window [k0-1, k1] (+ zero guard) of k_apply_slab must fit
-                // half of the CU's LDS, so that two workgroups are resident (HMG_SLAB_LDS_KB overrides, dev knob)
-                int kb = 70;
-                if (const char *e = std::getenv("HMG_SLAB_LDS_KB")) kb = std::max(16, std::min(158, std::atoi(e)));
-                const int cap = (kb * 1024) / 8 - 232;
-                const int slab_g0 = 0;
-                auto po = [&](int k) {
-                    long long n1 = T.m + 1, n2 = T.m + 1 - std::min(std::max(k, 0), T.m + 1);
-                    return (int)((n1 * (n1 + 1) * (n1 + 2) - n2 * (n2 + 1) * (n2 + 2)) / 6);
-                };
-                std::vector<int> sk{0};
-                int maxn = 0;
-                while (sk.back() <= T.m) {
-                    int k0 = sk.back(), k1 = k0 + 1;
-                    while (k1 <= T.m && slab_g0 + T.lds_g1 + po(k1 + 2) - po(k0 - 1) <= cap) ++k1;
-                    int nn = slab_g0 + T.lds_g1 + po(k1 + 1) - po(k0 - 1);
-                    if (nn > cap) throw std::runtime_error("apply slabs: a single plane does not fit the LDS");
-                    maxn = std::max(maxn, nn);
-                    sk.push_back(k1);
-                }
-                B.nslab = (int)sk.size() - 1;
-                B.slab_lds_nodes = maxn;
-                // Inside every entity segment the slots are ordered by plane k, so the slots of planes [ka, kb) are
-                // one contiguous run.  15 segments: 4 corners, 6 edges, 4 faces, interior.
-                std::vector<std::pair<int, int>> seg;
-                for (int c = 0; c < T.ncorner; ++c) seg.push_back({c, c + 1});
-                for (int e = 0; e < T.nedge; ++e) seg.push_back({T.off_edge + e * T.nei, T.off_edge + (e + 1) * T.nei});
-                for (int f = 0; f < T.nface; ++f) seg.push_back({T.off_face + f * T.nfi, T.off_face + (f + 1) * T.nfi});
-                seg.push_back({T.off_int, T.nf});                    // interior last: the kernel's fast path
-                auto run = [&](std::pair<int, int> sg, int ka, int kb) {   // slots of the segment with ka <= k < kb
-                    int b = sg.second, e = sg.first;
-                    for (int t = sg.first; t < sg.second; ++t) {
-                        int k = T.slot_ijk[3 * t + 2];
-                        if (k >= ka && k < kb) {
-                            b = std::min(b, t);
-                            e = std::max(e, t + 1);
-                        }
-                    }
-                    if (b >= e) return std::pair<int, int>{0, 0};
-                    for (int t = b; t < e; ++t) {
-                        int k = T.slot_ijk[3 * t + 2];
-                        if (k < ka || k >= kb) throw std::runtime_error("apply slabs: plane range is not contiguous");
-                    }
-                    return std::pair<int, int>{b, e};
-                };
-                // flat lists per slab (k_apply_slab): slots new in the rolling window (planes k0-1 and k0 come
-                // from the previous slab's LDS image) and slots evaluated (surface entities first)
-                std::vector<int> head((size_t)B.nslab * 8, 0);
-                std::vector<uint32_t> ldw, cpw;
-                std::vector<uint16_t> cps;
-                for (int sl = 0; sl < B.nslab; ++sl) {
-                    head[sl * 8 + 0] = sk[sl];
-                    head[sl * 8 + 1] = (int)ldw.size();
-                    head[sl * 8 + 3] = (int)cpw.size();
-                    for (size_t si = 0; si < seg.size(); ++si) {
-                        const auto &sg = seg[si];
-                        if (si + 1 == seg.size()) head[sl * 8 + 5] = (int)cpw.size() - head[sl * 8 + 3];   // surface entries
-                        auto ld = run(sg, sl == 0 ? 0 : sk[sl] + 1, sk[sl + 1] + 1);
-                        for (int t = ld.first; t < ld.second; ++t)
-                            ldw.push_back((uint32_t)(T.meta[t] & 0xffffu) | ((uint32_t)t << 16));
-                        auto cp = run(sg, sk[sl], sk[sl + 1]);
-                        const bool interior = si + 1 == seg.size();
-                        for (int t = cp.first; t < cp.second; ++t) {
-                            // surface entries: i | j << 7 | k << 14 | cls << 21 (decode32w); cell interior (round 4): the lattice
-                            // position itself, L | j << 16 | k << 23 (decode_lattice: no tetrahedral-number arithmetic per node)
-                            if (interior)
-                                cpw.push_back((uint32_t)(T.meta[t] & 0xffffu) | (((uint32_t)T.slot_ijk[3 * t + 1] & 127u) << 16) |
-                                              (((uint32_t)T.slot_ijk[3 * t + 2] & 127u) << 23));
-                            else
-                            cpw.push_back(((uint32_t)T.slot_ijk[3 * t] & 127u) | (((uint32_t)T.slot_ijk[3 * t + 1] & 127u) << 7) |
-                                          (((uint32_t)T.slot_ijk[3 * t + 2] & 127u) << 14) | ((uint32_t)T.slot_cls[t] << 21));
-                            cps.push_back((uint16_t)t);
-                        }
-                    }
-                    head[sl * 8 + 2] = (int)ldw.size() - head[sl * 8 + 1];
-                    head[sl * 8 + 4] = (int)cpw.size() - head[sl * 8 + 3];
-                }
-                if ((int)ldw.size() != T.nf || (int)cpw.size() != T.nf)
-                    throw std::runtime_error("apply slabs: the slab lists do not cover the cell exactly once");
-                // k_apply_slab2 (hmg_apply_slab.hip) takes the interior slots of a slab as one run of consecutive slots
-                for (int sl = 0; sl < B.nslab; ++sl) {
-                    const int b0 = head[sl * 8 + 3] + head[sl * 8 + 5], e0 = head[sl * 8 + 3] + head[sl * 8 + 4];
-                    for (int q = b0 + 1; q < e0; ++q)
-                        if (cps[(size_t)q] != cps[(size_t)q - 1] + 1) throw std::runtime_error("apply slabs: interior slots of a slab are not consecutive");
-                    B.slab_max_surf = std::max(B.slab_max_surf, head[sl * 8 + 5]);
-                    B.slab_max_int = std::max(B.slab_max_int, head[sl * 8 + 4] - head[sl * 8 + 5]);
-                }
-                ldw.resize(ldw.size() + TABLE_PAD, 0u);
-                cpw.resize(cpw.size() + TABLE_PAD, 0u);
-                cps.resize(cps.size() + TABLE_PAD, (uint16_t)0);
-                B.slab_head.upload(head, s);
-                B.slab_ld_word.upload(ldw, s);
-                B.slab_cp_word.upload(cpw, s);
-                B.slab_cp_slot.upload(cps, s);
-                if (l > 0) {
-                    // restriction through the same window (launch_restrict_slab): evaluated nodes = the even
-                    // lattice nodes (= nodes of the coarser level), output slot = their COARSE storage slot;
-                    // weights 1 / 0.5 on the taps that exist (nonzero mass entry of the class table)
-                    const LevelTables &C = g->lt[l - 1];
-                    const int mc = C.m;
-                    std::vector<int32_t> cslot((size_t)(mc + 1) * (mc + 1) * (mc + 1), -1);
-                    auto cidx = [&](int i, int j, int k) { return ((size_t)k * (mc + 1) + j) * (mc + 1) + i; };
-                    for (int q = 0; q < C.nf; ++q) cslot[cidx(C.slot_ijk[3 * q], C.slot_ijk[3 * q + 1], C.slot_ijk[3 * q + 2])] = q;
-                    std::vector<int> rhead(head);
-                    std::vector<uint32_t> rsw;
-                    std::vector<uint16_t> rss;
-                    for (int sl = 0; sl < B.nslab; ++sl) {
-                        rhead[sl * 8 + 3] = (int)rsw.size();
-                        for (size_t si = 0; si < seg.size(); ++si) {
-                            if (si + 1 == seg.size()) rhead[sl * 8 + 5] = (int)rsw.size() - rhead[sl * 8 + 3];
-                            auto cp = run(seg[si], sk[sl], sk[sl + 1]);
-                            for (int t = cp.first; t < cp.second; ++t) {
-                                const int i = T.slot_ijk[3 * t], j = T.slot_ijk[3 * t + 1], k = T.slot_ijk[3 * t + 2];
-                                if ((i | j | k) & 1) continue;
-                                const int cs = cslot[cidx(i / 2, j / 2, k / 2)];
-                                if (cs < 0) throw std::runtime_error("slab restriction: even node without a coarse slot");
-                                if (si + 1 == seg.size())     // (cell interior: lattice-position form, as above)
-                                    rsw.push_back((uint32_t)(T.meta[t] & 0xffffu) | (((uint32_t)j & 127u) << 16) | (((uint32_t)k & 127u) << 23));
-                                else
-                                rsw.push_back(((uint32_t)i & 127u) | (((uint32_t)j & 127u) << 7) | (((uint32_t)k & 127u) << 14) |
-                                              ((uint32_t)T.slot_cls[t] << 21));
-                                rss.push_back((uint16_t)cs);
-                            }
-                        }
-                        rhead[sl * 8 + 4] = (int)rsw.size() - rhead[sl * 8 + 3];
-                        B.slab_rs_max_surf = std::max(B.slab_rs_max_surf, rhead[sl * 8 + 5]);
-                        B.slab_rs_max_int = std::max(B.slab_rs_max_int, rhead[sl * 8 + 4] - rhead[sl * 8 + 5]);
-                    }
-                    if ((int)rsw.size() != C.nf) throw std::runtime_error("slab restriction: lists do not cover the coarse cell");
-                    rsw.resize(rsw.size() + TABLE_PAD, 0u);
-                    rss.resize(rss.size() + TABLE_PAD, (uint16_t)0);
-                    std::vector<double> rt(T.ctab.size(), 0.0);
-                    for (int c = 0; c < T.ncls; ++c)
-                        for (int d = 0; d < T.ndir; ++d) {
-                            const size_t e = ((size_t)c * T.ndir + d) * T.nterm + T.nterm - 1;
-                            rt[e] = T.ctab[e] != 0.0 ? (d == 0 ? 1.0 : 0.5) : 0.0;
-                        }
-                    B.slab_rs_head.upload(rhead, s);
-                    B.slab_rs_word.upload(rsw, s);
-                    B.slab_rs_slot.upload(rss, s);
-                    B.rtab.upload(rt, s);
-                }
-            }
-            {
-                std::vector<uint16_t> ss(T.sweep_slot);
-                ss.resize(ss.size() + TABLE_PAD, (uint16_t)0xffff);
-                B.sweep_slot.upload(ss, s);
-            }
-            B.ctab.upload(T.ctab, s);
-            B.hier2slot.upload(T.hier2slot, s);
-            B.par_a.upload(T.par_a, s);
-            if (l == 0 || g->lt[l - 1].nf <= 0x10000) {
-                // (16-bit parents: not built where the coarse cell has more slots -- 2D level 11; its prolongation reads par_a / par_b)
-                std::vector<uint32_t> pp(T.par_a.size());
-                for (size_t q = 0; q < pp.size(); ++q) {
-                    if ((uint32_t)T.par_a[q] > 0xffffu || (uint32_t)T.par_b[q] > 0xffffu)
-                        throw std::runtime_error("coarse slot exceeds 16 bits");
-                    pp[q] = (uint32_t)T.par_a[q] | ((uint32_t)T.par_b[q] << 16);
-                }
-                B.par32.upload(pp, s);
-            }
-            B.par_b.upload(T.par_b, s);
-            if (l > 0 && T.dim == 3 && B.nblk > 0 && T.nf <= 0xffff) {
-                // folded prolongation, coarse column staged in the image itself (k_apply<.., CG>): coarse slot c = lattice
-                // node (ci,cj,ck) of the coarser level sits at the fine lattice node (2ci,2cj,2ck)
-                const LevelTables &C = g->lt[l - 1];
-                const int m = T.m;
-                std::vector<int32_t> lat((size_t)(m + 1) * (m + 1) * (m + 1), -1);
-                auto at = [&](int i, int j, int k) -> int32_t & { return lat[((size_t)k * (m + 1) + j) * (m + 1) + i]; };
-                for (int q = 0; q < T.nf; ++q)
-                    at(T.slot_ijk[3 * q], T.slot_ijk[3 * q + 1], T.slot_ijk[3 * q + 2]) = (int32_t)(T.meta[q] & 0xffffu);
-                std::vector<uint16_t> cl((size_t)C.nf);
-                for (int c = 0; c < C.nf; ++c) {
-                    const int32_t Lp = at(2 * C.slot_ijk[3 * c], 2 * C.slot_ijk[3 * c + 1], 2 * C.slot_ijk[3 * c + 2]);
-                    if (Lp < 0) throw std::runtime_error("prolongation tables: coarse node without a fine lattice node");
-                    cl[c] = (uint16_t)Lp;
-                }
-                std::vector<uint64_t> p64((size_t)T.nf);
-                for (int q = 0; q < T.nf; ++q) {
-                    const uint64_t a = cl[(size_t)T.par_a[q]], b = cl[(size_t)T.par_b[q]], self = T.meta[q] & 0xffffu;
-                    // (an identity row is its own parent: the coarse value sits where the slot's own value will go)
-                    if (T.par_a[q] == T.par_b[q] && a != self) throw std::runtime_error("prolongation tables: identity row off its node");
-                    p64[q] = a | (b << 16) | (self << 32);
-                }
-                B.clpos.upload(cl, s);
-                B.par64.upload(p64, s);
-                wave_cl_host = cl;
-                // restriction in the epilogue of the local residual (k_apply<.., RS>): addressing word of every coarse slot's
-                // fine node and the weights 1 / 0.5 on the taps that exist (nonzero mass entry of the class table) -- the
-                // weights of the stand-alone restriction (rtab above / launch_restrict_slab)
-                std::vector<int32_t> fslot((size_t)(m + 1) * (m + 1) * (m + 1), -1);
-                for (int q = 0; q < T.nf; ++q)
-                    fslot[((size_t)T.slot_ijk[3 * q + 2] * (m + 1) + T.slot_ijk[3 * q + 1]) * (m + 1) + T.slot_ijk[3 * q]] = q;
-                std::vector<uint32_t> rw((size_t)C.nf);
-                for (int c = 0; c < C.nf; ++c) {
-                    const int i = 2 * C.slot_ijk[3 * c], j = 2 * C.slot_ijk[3 * c + 1], k = 2 * C.slot_ijk[3 * c + 2];
-                    const int fs = fslot[((size_t)k * (m + 1) + j) * (m + 1) + i];
-                    if (fs < 0 || i > 127 || j > 127 || k > 127) throw std::runtime_error("restriction tables: bad coarse node");
-                    rw[c] = ((uint32_t)i & 127u) | (((uint32_t)j & 127u) << 7) | (((uint32_t)k & 127u) << 14) |
-                            ((uint32_t)T.slot_cls[fs] << 21);
-                }
-                std::vector<double> wts((size_t)T.ncls * T.ndir, 0.0);
-                for (int c = 0; c < T.ncls; ++c)
-                    for (int d = 0; d < T.ndir; ++d)
-                        wts[(size_t)c * T.ndir + d] =
-                            T.ctab[((size_t)c * T.ndir + d) * T.nterm + T.nterm - 1] != 0.0 ? (d == 0 ? 1.0 : 0.5) : 0.0;
-                B.rs_word.upload(rw, s);
-                B.rs_w.upload(wts, s);
-                if (T.nf <= 2048) {
-                    // levels whose stand-alone restriction is k_restrict: the epilogue sums in ITS order (the reference's:
-                    // identity row first, then the midpoints in ascending fine hierarchical id) -- same bits on both paths
-                    std::vector<uint16_t> lp(T.ridx.size());
-                    for (size_t e = 0; e < lp.size(); ++e) lp[e] = (uint16_t)(T.meta[(size_t)T.ridx[e]] & 0xffffu);
-                    B.rs_lp.upload(lp, s);
-                }
-            }
-            if (T.dim == 3 && T.m == 16 && T.nf == 969 && B.nblk == 152 && B.blk_R == 4 && T.lds_g0 == 0 && T.nfi == 105 && T.nei == 15 &&
-                T.ncorner == 4 && T.nedge == 6 && T.nface == 4 && T.off_edge == 4 && T.off_face == 94) {
-                // Tables of k_apply_wave (hmg_apply_wave.hip): what lane l of the one wave that owns a cell needs, row by row.
-                //   wave_tab rows 0..7   faces: run r = 2 f + h covers nodes h * 64 + l of face f
-                //            rows 8..9   corners and edges: slot r * 64 + l (< 94)
-                //            rows 10..12 interior blocks u = r * 64 + l (< 152): the block word of the blocked tables
-                //            row 13      storage slot of block l | of block 64 + l << 16
-                //            row 14      storage slot of block 128 + l | class of slot l << 16 | class of slot 64 + l << 24
-                //   surface words: L | len << 10 | A << 15 | B << 23 | valid << 31 (rows have len = m+1-j-k nodes, A / B = offsets
-                //   to the same (i,j) in the plane above / below, as decode32 derives them)
-                const int m = T.m, WVZ = 168, WDUMMY = 167;
-                auto surf_word = [&](int t, bool valid) -> uint32_t {
-                    const uint32_t L = (uint32_t)(T.meta[(size_t)t] & 0xffffu);
-                    const int j = T.slot_ijk[3 * t + 1], k = T.slot_ijk[3 * t + 2];
-                    const int len = m + 1 - j - k, n = m - k, Tk = (n + 1) * (n + 2) / 2;
-                    const int A = Tk - j, Bo = Tk + n + 2 - j;
-                    if (L > 1023u || len < 0 || len > 31 || A < 0 || A > 255 || Bo < 0 || Bo > 255)
-                        throw std::runtime_error("wave tables: addressing word out of range");
-                    return L | ((uint32_t)len << 10) | ((uint32_t)A << 15) | ((uint32_t)Bo << 23) | (valid ? 1u << 31 : 0u);
-                };
-                std::vector<uint32_t> wt((size_t)WAVE_TAB_ROWS * 64, 0u), wl(8 * 64, 0u);
-                std::vector<uint32_t> bwv(B_blk_word_host.begin(), B_blk_word_host.begin() + B.nblk);
-                for (int l = 0; l < 64; ++l) {
-                    for (int r = 0; r < 8; ++r) {
-                        const int f = r >> 1, ti = (r & 1) * 64 + l;
-                        const bool valid = ti < T.nfi;
-                        wt[(size_t)r * 64 + l] = surf_word(T.off_face + f * T.nfi + (valid ? ti : 0), valid);
-                    }
-                    uint32_t cls[2];
-                    for (int r = 0; r < 2; ++r) {
-                        const int t = r * 64 + l;
-                        const bool valid = t < T.off_face;
-                        wt[(size_t)(8 + r) * 64 + l] = surf_word(valid ? t : 0, valid);
-                        cls[r] = T.slot_cls[(size_t)(valid ? t : T.off_edge)];
-                        if (cls[r] < 5 || cls[r] > 14) throw std::runtime_error("wave tables: edge / corner class out of range");
-                    }
-                    uint32_t bsl[3];
-                    for (int r = 0; r < 3; ++r) {
-                        const int u = r * 64 + l;
-                        const bool valid = u < B.nblk;
-                        // (no block: block 0's addresses with no valid node -- nothing is stored)
-                        wt[(size_t)(10 + r) * 64 + l] = valid ? bwv[(size_t)u] : (bwv[0] & 0x0fffffffu);
-                        bsl[r] = valid ? B_blk_slot_host[(size_t)u] : B_blk_slot_host[0];
-                    }
-                    wt[(size_t)13 * 64 + l] = bsl[0] | (bsl[1] << 16);
-                    wt[(size_t)14 * 64 + l] = bsl[2] | (cls[0] << 16) | (cls[1] << 24);
-                    for (int i = 0; i < 8; ++i) {
-                        uint32_t off[2];
-                        for (int h = 0; h < 2; ++h) {
-                            const int t = l + 64 * (2 * i + h);
-                            off[h] = 8u * (uint32_t)(t < T.nf ? WVZ + (int)(T.meta[(size_t)t] & 0xffffu) : WDUMMY);
-                        }
-                        wl[(size_t)i * 64 + l] = off[0] | (off[1] << 16);
-                    }
-                }
-                B.wave_tab.upload(wt, s);
-                B.wave_lpos.upload(wl, s);
-                if (l > 0 && !wave_cl_host.empty() && g->lt[l - 1].nf == 165) {
-                    const LevelTables &C = g->lt[l - 1];
-                    std::vector<uint32_t> wp(16 * 64, 0u), wc(3 * 64, 8u * (uint32_t)WDUMMY), wr((size_t)192 * 8, 0u);
-                    for (int t = 0; t < T.nf; ++t)
-                        wp[(size_t)(t / 64) * 64 + t % 64] = (uint32_t)wave_cl_host[(size_t)T.par_a[t]] | ((uint32_t)wave_cl_host[(size_t)T.par_b[t]] << 16);
-                    for (int c = 0; c < C.nf; ++c) wc[(size_t)(c / 64) * 64 + c % 64] = 8u * (uint32_t)(WVZ + wave_cl_host[(size_t)c]);
-                    for (int c = 0; c < C.nf; ++c) {
-                        const int b = T.rptr[c], n = T.rptr[c + 1] - b;
-                        if (n < 1 || n > 15) throw std::runtime_error("wave tables: restriction row longer than 15");
-                        uint16_t e[16] = {0};
-                        for (int q = 0; q < n; ++q) e[q] = (uint16_t)(T.meta[(size_t)T.ridx[b + q]] & 0xffffu);
-                        e[15] = (uint16_t)n;
-                        for (int q = 0; q < 8; ++q) wr[(size_t)c * 8 + q] = (uint32_t)e[2 * q] | ((uint32_t)e[2 * q + 1] << 16);
-                    }
-                    B.wave_par.upload(wp, s);
-                    B.wave_cl.upload(wc, s);
-                    B.wave_rs.upload(wr, s);
-                }
-            }
-            B.rptr.upload(T.rptr, s);
-            B.ridx.upload(T.ridx, s);
-            B.dphi.upload(T.dphi, s);
-        }
+        // (in this order: a host-only grid's checksum folds in the uploads one after another; an empty table uploads nothing)
+        B.meta.upload(T.meta, s);
+        B.lpos.upload(A.lpos, s);
+        B.pos32.upload(A.pos32, s);
+        B.pos32w.upload(A.pos32w, s);
+        B.sweep32.upload(A.sweep32, s);
+        B.blk_word.upload(blk.word, s);
+        B.blk_slot.upload(blk.slot, s);
+        B.slab_head.upload(sw.head, s);
+        B.slab_ld_word.upload(sw.ld_word, s);
+        B.slab_cp_word.upload(sw.cp_word, s);
+        B.slab_cp_slot.upload(sw.cp_slot, s);
+        B.slab_rs_head.upload(sw.rs_head, s);
+        B.slab_rs_word.upload(sw.rs_word, s);
+        B.slab_rs_slot.upload(sw.rs_slot, s);
+        B.rtab.upload(sw.rtab, s);
+        B.sweep_slot.upload(A.sweep_slot, s);
+        B.ctab.upload(T.ctab, s);
+        B.hier2slot.upload(T.hier2slot, s);
+        B.par_a.upload(T.par_a, s);
+        B.par32.upload(X.par32, s);
+        B.par_b.upload(T.par_b, s);
+        B.clpos.upload(X.clpos, s);
+        B.par64.upload(X.par64, s);
+        B.rs_word.upload(X.rs_word, s);
+        B.rs_w.upload(X.rs_w, s);
+        B.rs_lp.upload(X.rs_lp, s);
+        B.wave_tab.upload(W.tab, s);
+        B.wave_lpos.upload(W.lpos, s);
+        B.wave_par.upload(W.par, s);
+        B.wave_cl.upload(W.cl, s);
+        B.wave_rs.upload(W.rs, s);
+        B.rptr.upload(T.rptr, s);
+        B.ridx.upload(T.ridx, s);
+        B.dphi.upload(T.dphi, s);
+        B.nslab = sw.nslab;
+        B.slab_lds_nodes = sw.lds_nodes;
+        B.slab_max_surf = sw.max_surf;
+        B.slab_max_int = sw.max_int;
+        B.slab_rs_max_surf = sw.rs_max_surf;
+        B.slab_rs_max_int = sw.rs_max_int;
         LevelDev &D = g->ld[l];
         D.dim = T.dim;
         D.level = T.level;
@@ -999,7 +596,7 @@ static void upload_levels(hmg_grid *g)
         D.nterm = T.nterm;
         D.lds_g0 = T.lds_g0;
         D.lds_g1 = T.lds_g1;
-        D.nf_coarse = l > 0 ? g->lt[l - 1].nf : 0;
+        D.nf_coarse = C ? C->nf : 0;
         D.meta = B.meta.p;
         D.lpos = B.lpos.p;
         D.sweep_slot = B.sweep_slot.p;
@@ -1009,8 +606,8 @@ static void upload_levels(hmg_grid *g)
         D.nsweep = (int)T.sweep_meta.size();
         D.blk_word = B.blk_word.p;
         D.blk_slot = B.blk_slot.p;
-        D.nblk = B.nblk;
-        D.blk_R = B.blk_R;
+        D.nblk = blk.nblk;
+        D.blk_R = blk.R;
         D.ctab = B.ctab.p;
         D.hier2slot = B.hier2slot.p;
         D.par_a = B.par_a.p;

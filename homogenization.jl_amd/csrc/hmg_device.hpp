@@ -79,6 +79,12 @@ struct LevelDev {
     const double *wcache;          // null: not available on this level
 };
 
+// level-5 geometry k_apply_wave is compiled for (apply_wave_ok checks it against the level's tables, build_wave_tables lays
+// out the wave tables by it)
+constexpr int WM = 16, WNF = 969, WNFI = 105, WNEI = 15, WNCORNER = 4, WNBLK = 152, WNFC = 165, WR = 4;
+constexpr int WOFF_EDGE = 4, WOFF_FACE = 94, WNEC = 94;
+constexpr int WNQ = 16;            // slots per lane: 15 full rounds of 64 + 9
+constexpr int WVZ = 168;           // doubles in front of the lattice image: class rows 5..14 (edges, corners) x 16 + 8 spare (lanes without a slot write to the last one)
 constexpr int WAVE_TAB_ROWS = 15;
 constexpr int WAVE_ROW = 16;                  // doubles per class row of the weight cache (15 taps + 1 pad: 128-B rows)
 constexpr int WAVE_WSTRIDE = 15 * WAVE_ROW;   // doubles per (cell class, sign)

@@ -195,6 +195,76 @@ void assemble_coarse_matrix(const MeshTables &mesh, const double *sigma, double 
                             CoarseMatrix &out);
 
 // ---------------------------------------------------------------------------------------------
+// Addressing tables of the kernels, derived from LevelTables / MeshTables (hmg_kernel_tables.cpp).  Each builder decides
+// whether its kernels run on the level (a table that is not built stays empty) and checks the rules the kernels rely on.
+// Tables marked (+ pad) end in TABLE_PAD padding entries: they are uploaded as they are.
+// ---------------------------------------------------------------------------------------------
+
+// Addressing words of k_apply, every level but the 2D levels 9..11 (their row-band kernels derive slot and class from (i,j):
+// rows_slot is checked there instead).
+struct AddressTables {
+    std::vector<uint16_t> lpos;          // lattice position of every slot (every level with packed words)
+    std::vector<uint32_t> pos32;         // L | j<<16 | k<<22 | cls<<28 (decode32), 0 where m is too large    (+ pad)
+    std::vector<uint32_t> pos32w;        // i | j<<7 | k<<14 | cls<<21 (decode32w)
+    std::vector<uint32_t> sweep32;       // sweep_meta in the pos32 form, cls = 0                            (+ pad)
+    std::vector<uint16_t> sweep_slot;    // LevelTables::sweep_slot, every level                     (+ pad of 0xffff)
+};
+AddressTables build_address_tables(const LevelTables &T);
+
+// Register-blocked interior of k_apply (interior_block): 3D levels whose cell fits the LDS, run by a 256- or 1024-thread workgroup.
+struct BlockedInterior {
+    int nblk = 0, R = 0;                 // blocks, nodes per block (0: not blocked)
+    std::vector<uint32_t> word;          // L | j<<16 | k0<<22 | nv<<28 of the block's first node (i,j,k0)  (+ pad)
+    std::vector<uint16_t> slot;          // storage slot of that node                                        (+ pad)
+};
+BlockedInterior build_blocked_interior(const LevelTables &T);
+
+// Rolling-window tables of k_apply_slab (SlabTables) and of the slab restriction, 3D levels of more than 2048 slots.
+struct SlabWindows {
+    int nslab = 0, lds_nodes = 0, max_surf = 0, max_int = 0;
+    std::vector<int> head;               // per slab: k0, ld_off, ld_cnt, cp_off, cp_cnt, cp_surf, 0, 0
+    std::vector<uint32_t> ld_word;       // slots new in the window: L | slot<<16                            (+ pad)
+    std::vector<uint32_t> cp_word;       // evaluated slots: surface decode32w, interior L | j<<16 | k<<23    (+ pad)
+    std::vector<uint16_t> cp_slot;       // evaluated slots: storage slot                                    (+ pad)
+    // restriction through the same window (a coarser level exists): the even lattice nodes, their COARSE slots
+    int rs_max_surf = 0, rs_max_int = 0;
+    std::vector<int> rs_head;
+    std::vector<uint32_t> rs_word;       // (+ pad)
+    std::vector<uint16_t> rs_slot;       // (+ pad)
+    std::vector<double> rtab;            // restriction weights in class-table layout
+};
+// coarse: the next coarser level (nullptr on level 1); lds_kb: LDS per window, in KB
+SlabWindows build_slab_windows(const LevelTables &T, const LevelTables *coarse, int lds_kb);
+
+// Transfer tables read inside the lattice image: 16-bit parent pairs, and on blocked 3D levels the prolongation folded into
+// k_apply (coarse column staged at the even nodes of the image) and the restriction in its epilogue.
+struct TransferTables {
+    std::vector<uint32_t> par32;         // par_a | par_b<<16
+    std::vector<uint16_t> clpos;         // lattice position of every coarse slot's fine node
+    std::vector<uint64_t> par64;         // clpos of par_a | of par_b<<16 | own lattice position<<32
+    std::vector<uint32_t> rs_word;       // decode32w word of every coarse slot's fine node
+    std::vector<double> rs_w;            // restriction weights per (class, tap)
+    std::vector<uint16_t> rs_lp;         // ridx as lattice positions (levels restricted by k_restrict)
+};
+TransferTables build_transfer_tables(const LevelTables &T, const LevelTables *coarse, const BlockedInterior &blk);
+
+// Per-lane tables of the one-wave-per-cell apply of level 5 (k_apply_wave; LevelDev::wave_*).
+struct WaveTables {
+    std::vector<uint32_t> tab, lpos, par, cl, rs;
+};
+WaveTables build_wave_tables(const LevelTables &T, const LevelTables *coarse, const BlockedInterior &blk,
+                             const std::vector<uint16_t> &clpos);
+
+// Mesh-level tables of the kernels.
+struct MeshKernelTables {
+    std::vector<int32_t> face_partner;   // per cell and local face: partner cell<<2 | its local face, -1 (none, or cut)
+    std::vector<uint16_t> dmask;         // MeshTables::dmask, padded to an even count
+    std::vector<int32_t> cell_perm;      // XCD-aware order of the cells
+    std::vector<int32_t> cells_cut, cells_inner;   // in XCD-aware order too (xcd_lists), else as the partition made them
+};
+MeshKernelTables build_mesh_kernel_tables(const MeshTables &M, bool xcd_lists);
+
+// ---------------------------------------------------------------------------------------------
 // Partition by coarse-cell ownership (one rank per GPU).
 // ---------------------------------------------------------------------------------------------
 struct Partition {

@@ -454,3 +454,71 @@ print(h.hexdigest())
         env = dict(os.environ, HMG_SETUP_THREADS=t)
         out.append(subprocess.check_output([sys.executable, "-c", code], env=env).decode().strip().splitlines()[-1])
     assert out[0] == out[1]
+
+
+def upload_hash(g):
+    v = g.table_i32("upload_hash", 1).astype(np.uint32)
+    return (int(v[1]) << 32) | int(v[0])
+
+
+def _octant_mesh():
+    from homogenization_jl_amd import dist as hdist, driver
+    w = 4
+    base = driver.checkerboard_mesh(hmg.Tet64, (w, w, w), origin=(-w / 2.0,) * 3, transposed_lookup=False)
+    return base, hdist.block_owner(base, (2, 2, 2), w // 2, (-w / 2.0,) * 3)
+
+
+def _hashes_cube(levels):
+    return lambda oracle: [upload_hash(host_grid(oracle.hypercube(3, 2), levels))]
+
+
+def _hashes_octants(oracle):
+    from homogenization_jl_amd import dist as hdist
+    base, octant = _octant_mesh()
+    return [upload_hash(hdist.PartitionedGrid(None, base, 4, octant, r, 8)) for r in range(8)]
+
+
+def _hashes_rehearsal(oracle):
+    from homogenization_jl_amd import dist as hdist
+    base, octant = _octant_mesh()
+    return [upload_hash(hdist.PartitionedGrid(None, base, 4, np.zeros_like(octant), 0, 1, cut_owner=octant))]
+
+
+def _hashes_tri_ranks(oracle):
+    from homogenization_jl_amd import dist as hdist, driver
+    world, dim, width = 4, 2, 8
+    origin = (-width / 2.0,) * dim
+    base = driver.order_nodes_and_elements_by_magnitude(driver.hypercube(hmg.Tri64, width, origin=origin))
+    owner = hdist.block_owner(base, hdist.block_shape(world, dim), width / 2.0, origin)
+    return [upload_hash(hdist.PartitionedGrid(None, base, 4, owner, r, world)) for r in range(world)]
+
+
+def _hashes_shrunk(oracle):
+    O = oracle
+    m = O.order_nodes_and_elements_by_magnitude(O.hypercube(3, 6, origin=(-3.0, -3.0, -3.0)))
+    g = host_grid(m, 4)
+    g.shrink(O.find_elements_in_radius(m, 2), O.find_nodes_in_radius(m, 2))
+    return [upload_hash(g)]
+
+
+# checksums of every table a device grid would upload (DryUploads), for what the pins of test_tri_deep_tables.py do not reach:
+# multi-slab levels at other LDS windows, the cut-first cell lists and cut face pairs of partitioned grids, a shrunk mesh
+UPLOAD_PINS = {
+    "slab28_l6": (_hashes_cube(6), {"HMG_SLAB_LDS_KB": "28"}, [0xf420547325d3b042]),
+    "slab56_l7": (_hashes_cube(7), {"HMG_SLAB_LDS_KB": "56"}, [0xfecc5a1b20e26075]),
+    "octant_ranks": (_hashes_octants, {}, [0x6d9e2cb391083a52, 0x6cb52f9907b43f27, 0x87e105afe034930b, 0x699e4ce4fd2f5d08,
+                                           0x16aa77ae147b3e80, 0x64bad483f5398cf8, 0x1d91710a5334b2f7, 0xf4a987dd176c5c04]),
+    "octant_rehearsal": (_hashes_rehearsal, {}, [0x97a73ded884fc831]),
+    "tri_ranks": (_hashes_tri_ranks, {}, [0x6bf0310b8d784a03, 0x4a3c0d79bc526a46, 0xf31f8a570585b362, 0xd52d815be7f40e0e]),
+    "shrunk": (_hashes_shrunk, {}, [0x6612f68d0d3ccd2c]),
+}
+
+
+@pytest.mark.parametrize("case", sorted(UPLOAD_PINS))
+def test_upload_hashes_pinned(oracle, monkeypatch, case):
+    make, env, want = UPLOAD_PINS[case]
+    for name in ("HMG_SLAB_LDS_KB", "HMG_XCD_LISTS", "HMG_PARTITION_ANALYSIS", "HMG_EXCHANGE"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    assert [hex(h) for h in make(oracle)] == [hex(h) for h in want]
