@@ -153,7 +153,7 @@ def test_transfer_interfaces_duplicates(cases, levels):
 
 @pytest.mark.parametrize("fused", [1, 0])
 def test_smoothing_steps(oracle, ctx, cases, fused):
-    """smoothing_steps! on level 10, fused CG pass and one kernel per statement: x, r, p <= 1e-10."""
+    """smoothing_steps! on level 10, fused CG pass and one kernel per statement: x, r, p, Ap <= 1e-10."""
     if fused:
         c = cases[10]
     else:
@@ -171,6 +171,7 @@ def test_smoothing_steps(oracle, ctx, cases, fused):
     assert relerr(dst.x.to_host(), st.x) <= 1e-10
     assert relerr(dst.r.to_host(), st.r) <= 1e-10
     assert relerr(dst.p.to_host(), st.p) <= 1e-10
+    assert relerr(dst.Ap.to_host(), st.Ap) <= 1e-10
 
 
 @pytest.mark.parametrize("levels", [9, 10, 11])
