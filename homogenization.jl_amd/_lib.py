@@ -84,6 +84,13 @@ SIGNATURES = {
     "hmg_vcycle": (c_int, [vp, c_int, c_int, c_int, pp]),
     "hmg_vcycle_down": (c_int, [vp, c_int, c_int, pp]),
     "hmg_vcycle_up": (c_int, [vp, c_int, c_int, pp]),
+    "hmg_fcg_create": (c_int, [vp, c_int, c_int, c_int, pp]),
+    "hmg_fcg_destroy": (c_int, [vp]),
+    "hmg_fcg_start": (c_int, [vp, vp, vp, pp]),
+    "hmg_fcg_step": (c_int, [vp, vp, pp]),
+    "hmg_fcg_residual_norm": (c_int, [vp, pp, p_f64]),
+    "hmg_fcg_scalars": (c_int, [vp, p_f64]),
+    "hmg_fcg_vec": (vp, [vp, c_int]),
     "hmg_grid_set_cut": (c_int, [vp, c_i64, c_i64, c_i64, c_i64, p_i64, p_i32, c_i64, p_i64, p_i32, c_i64, p_i64, p_i32]),
     "hmg_grid_set_exchange": (c_int, [vp, EXCHANGE_FN, EXCHANGE_FN, vp, vp, c_i64]),
     "hmg_grid_cut_buffer_doubles": (c_i64, [vp, c_int]),

@@ -531,6 +531,71 @@ def vcycle_tolerant(implicit: ImplicitFineGrid, base: BaseLevel, ops, levels, k:
     return True
 
 
+class FlexibleCG:
+    """Flexible CG with one retained direction, preconditioned by one vcycle! per iteration (include/hmg.h, hmg_fcg_*): the
+    Krylov counterpart of repeating `vcycle`.  Owns p, q and R -- three vectors of level k's size, allocated here.  The iterate
+    is a vector of the caller's that is none of levels[k-1]'s five; levels[k-1].x receives the preconditioned residual and
+    levels[k-1].b is left alone.  `start` once per operator / domain / right-hand side (after a shrink or a change of lam a
+    `step` without it raises), then one `step` per iteration; nothing in a step waits for the device."""
+
+    def __init__(self, implicit: ImplicitFineGrid, base: BaseLevel, ops, levels, k: int, steps: int = 3, steps_coarse: int = 2):
+        self._lib = L.load()
+        self.implicit, self.ops, self.levels, self.k = implicit, ops, levels, k
+        self.x = None
+        ops[k - 1]._bind()
+        h = ctypes.c_void_p()
+        L.check(self._lib.hmg_fcg_create(implicit.h, k, int(steps), int(steps_coarse), ctypes.byref(h)))
+        self.h = h
+        self._fin = weakref.finalize(self, self._lib.hmg_fcg_destroy, h)
+
+    def start(self, x: DeviceMatrix, b: DeviceMatrix):
+        """R = b - A_loc x; x must be consistent and constrained (broadcast_interfaces / apply_constraint)."""
+        self.ops[self.k - 1]._bind()
+        L.check(self._lib.hmg_fcg_start(self.h, x.h, b.h, _state_handles(self.levels)))
+        self.x = x
+        return self
+
+    def step(self):
+        L.check(self._lib.hmg_fcg_step(self.h, self.x.h, _state_handles(self.levels)))
+
+    def step_tolerant(self) -> bool:
+        """`step` for driver loops, as `vcycle_tolerant`: False if the V-cycle inside used an inexact level-1 solve (the step is
+        then a weaker but valid iterate: flexible CG tolerates a preconditioner that varies)."""
+        self.step()
+        try:
+            self.implicit.ctx.sync()
+        except L.HmgError as e:
+            if "did not reach coarse_rtol" not in str(e):
+                raise
+            return False
+        return True
+
+    def residual_norm(self) -> float:
+        """Norm of the true residual (interface-summed R, every node once); waits for the device."""
+        out = ctypes.c_double()
+        L.check(self._lib.hmg_fcg_residual_norm(self.h, _state_handles(self.levels), ctypes.byref(out)))
+        return out.value
+
+    def scalars(self):
+        """(alpha, beta, p.q, p.R) of the last step; waits for the device."""
+        out = (ctypes.c_double * 4)()
+        L.check(self._lib.hmg_fcg_scalars(self.h, out))
+        return tuple(out)
+
+    def vec(self, which: str) -> np.ndarray:
+        """Host copy of "p", "q" or "R" (Nf x Ne, hierarchical order)."""
+        h = self._lib.hmg_fcg_vec(self.h, "pqR".index(which))
+        shape = (self.implicit.nf(self.k), self.implicit.ncells())
+        out = np.zeros(shape, dtype=np.float64, order="F")
+        L.check(self._lib.hmg_vec_download(ctypes.c_void_p(h), out.ctypes.data_as(L.p_f64)))
+        return out
+
+    def close(self):
+        if self.h:
+            self._fin()
+            self.h = None
+
+
 def _state_handles(levels):
     arr = (ctypes.c_void_p * (5 * len(levels)))()
     for i, st in enumerate(levels):

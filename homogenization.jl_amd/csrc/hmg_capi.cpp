@@ -2,6 +2,7 @@
 // orchestration on one HIP stream with device-resident CG scalars.
 #include "../../include/hmg.h"
 #include "hmg_device.hpp"
+#include "hmg_fcg.hpp"
 #include "hmg_host.hpp"
 
 #include <dlfcn.h>
@@ -220,6 +221,7 @@ struct hmg_ctx {
     int64_t slab2_launches = 0;              // launches of the role-split slab apply (hmg_apply_slab.hip)
     int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
     int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
+    int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
     // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB
@@ -341,6 +343,8 @@ struct hmg_grid {
     bool wc_ready = false;
     double lambda = 0.0;
     bool has_op = false;
+    uint64_t op_epoch = 0;                       // operators this grid has had (new sigma, new lambda, domain shrink): what an
+                                                 // hmg_fcg object compares its residual's operator with
     // coarse system
     CoarseMatrix cm;
     CoarseDev cd{};
@@ -1613,6 +1617,79 @@ void exchange_cut(hmg_grid *g, const LevelDev &lv, double *x);
 
 }  // namespace
 
+// ---- what hmg_fcg.cpp needs from in here (hmg_fcg.hpp) --------------------------------------------
+namespace hmg {
+
+hmg_ctx *fcg_hook_ctx(hmg_grid *g)
+{
+    need(g != nullptr, "null grid");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    return g->ctx;
+}
+
+double *fcg_hook_vec(const hmg_grid *g, int level, const hmg_vec *v, const char *name)
+{
+    check_vec(g, level, v, name);
+    return v->d;
+}
+
+int64_t fcg_hook_len(const hmg_grid *g, int level) { return (int64_t)lev(g, level).ld * g->md.ncells; }
+
+uint64_t fcg_hook_epoch(const hmg_grid *g) { return g->op_epoch; }
+
+void fcg_hook_vcycle_zero(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st)
+{
+    need(g && g->has_op && st, "null argument or operator not set");
+    if (k == 1) {                                  // (the scatter of the level-1 solution overwrites every entry of x)
+        vcycle(g, 1, steps, steps_coarse, st);
+        return;
+    }
+    const bool x_zero = zero_entry_ok(g, k, steps);
+    if (!x_zero) launch_fill(g->ctx->L, st[5 * (k - 1)]->d, vec_len(st[5 * (k - 1)]), 0.0);
+    vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
+    vcycle(g, k - 1, steps_coarse, steps_coarse, st, false);
+    g->ctx->last_top_form = 0;
+    vcycle_up(g, k, steps, st, Role::PostTop);
+}
+
+void fcg_hook_scalar_sum(hmg_grid *g, int slot, int count) { scalar_sum(g, slot, count); }
+
+double *fcg_hook_alloc(hmg_ctx *c, size_t count)
+{
+    HIPCHK(hipSetDevice(c->device));
+    void *p = nullptr;
+    if (hipMalloc(&p, count * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        release_pooled_memory();
+        hipError_t e = hipMalloc(&p, count * sizeof(double));
+        if (e != hipSuccess)
+            throw std::runtime_error(std::string("hipMalloc of the reduction scratch (") + std::to_string((count * sizeof(double)) >> 10) +
+                                     " KiB) failed: " + hipGetErrorString(e));
+    }
+    device_allocs() += 1;
+    hipError_t e = hipMemsetAsync(p, 0, count * sizeof(double), c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e));
+    }
+    return (double *)p;
+}
+
+void fcg_hook_free(hmg_ctx *c, double *p)
+{
+    LifetimeLock lock(lifetime_mutex());
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(p);
+}
+
+void fcg_hook_account(hmg_ctx *c, int64_t fcg_bytes_delta)
+{
+    LifetimeLock lock(lifetime_mutex());
+    c->fcg_bytes += fcg_bytes_delta;
+}
+
+}  // namespace hmg
+
 namespace {
 
 // Buffer layout of one level (see CutLevel), built at the first exchange on that level and after every re-partition.
@@ -2052,6 +2129,7 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "comm_calls") return ctx->comm_calls;
     if (n == "device_allocs") return device_allocs().load();
     if (n == "spare_bytes") return ctx->spare_bytes;
+    if (n == "fcg_bytes") return ctx->fcg_bytes;
     if (n == "lazy_top_form") return ctx->last_top_form;
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
     return -1;
@@ -2331,6 +2409,7 @@ int hmg_grid_set_operator(hmg_grid *g, const double *sigma, double lambda)
         g->sigma.assign(sigma, sigma + (size_t)g->mesh_full.ncells * g->dim);
     g->lambda = lambda;
     g->has_op = true;
+    g->op_epoch += 1;
     upload_operator(g);
     HMG_END
 }
@@ -2340,6 +2419,7 @@ int hmg_grid_set_lambda(hmg_grid *g, double lambda)
     HMG_TRY
     need(g != nullptr, "null grid");
     g->lambda = lambda;
+    g->op_epoch += 1;
     g->coarse_ready = false;
     if (g->ctx && g->has_op) ensure_weight_cache(g);
     HMG_END
@@ -2363,6 +2443,7 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    g->op_epoch += 1;
     if (g->part) {
         // prefix of the GLOBAL mesh: this rank keeps its cells with a global id below the prefix length (local
         // cells are in ascending global order, so that is a prefix of every local level vector as well); cut

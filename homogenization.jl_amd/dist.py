@@ -357,13 +357,15 @@ def partitioned_checkerboard(ctx, width: int, levels: int, world: int, rank: int
 def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, rank: int, refinements: int = 2,
                                             smoothing_steps: int = 3, tolerance: float = 1e-4, xi=None, seed: int = 0,
                                             values=(1.0, 9.0), sigma_grid=None, x0=None, max_cycles: int = 1000,
-                                            group=None, log=None, backend=None, stats: dict | None = None):
+                                            group=None, log=None, backend=None, stats: dict | None = None,
+                                            accelerate: bool = False):
     """driver.checkerboard_homogenization over `world` ranks (one GPU each): the base mesh is split into blocks about
     the origin (halves / quadrants / octants for 2, 4, 8 ranks), so that the centred sub-domains the outer loop
     shrinks to stay balanced.  Every rank runs the same host loop; the per-cycle integrals are local sums
     added over the ranks, everything else goes through the partitioned V-cycle.  Returns (sigma, history) like the
     single-GPU driver, identical on every rank.  `stats` (a dict) receives "inexact_vcycles": V-cycles whose budgeted level-1 solve
-    missed coarse_rtol (every rank sees the same replicated solve, hence the same count)."""
+    missed coarse_rtol (every rank sees the same replicated solve, hence the same count).  `accelerate`: as in the single-GPU
+    driver (api.FlexibleCG; per iteration two small sums over the ranks are all it adds to the V-cycle's communication)."""
     dim = api._dim_of(eltype)
     # the blocks are halves per axis about the origin: 1, 2, 4 (and 8 in 3D) ranks.  Checked on every rank before any
     # collective, so that an unsupported size fails everywhere instead of hanging the ranks that do own cells
@@ -392,9 +394,11 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
     nf = grid.nf(total_grids)
     if x0 is None:
         x0 = api.host_random((nf, base.elements.shape[0]), seed + 1)       # hashed by GLOBAL cell id
-    top.x.from_host(np.asfortranarray(x0[:, grid.local_cells]))
-    api.broadcast_interfaces(top.x, grid, total_grids)
-    api.apply_constraint(top.x, total_grids, grid)
+    xv = api.DeviceMatrix(grid, total_grids) if accelerate else top.x      # the iterate
+    fcg = api.FlexibleCG(grid, None, [op] * total_grids, states, total_grids, smoothing_steps) if accelerate else None
+    xv.from_host(np.asfortranarray(x0[:, grid.local_cells]))
+    api.broadcast_interfaces(xv, grid, total_grids)
+    api.apply_constraint(xv, total_grids, grid)
     api.rhs_axi_grad_v(top.b, grid, xi)
     v_prev = None                                        # allocated at the first domain shrink
     rank_sum = ex.rank_sum
@@ -404,21 +408,24 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
     for k in range(n + 1):
         base_level = api.BaseLevel(grid)
         dsig, dsig_prev = 0.0, 0.0
+        if accelerate:
+            fcg.start(xv, top.b)
         for i in range(1, max_cycles + 1):
-            if not api.vcycle_tolerant(grid, base_level, [op] * total_grids, states, total_grids, smoothing_steps):
+            if not (fcg.step_tolerant() if accelerate else
+                    api.vcycle_tolerant(grid, base_level, [op] * total_grids, states, total_grids, smoothing_steps)):
                 inexact += 1                             # (as in driver.checkerboard_homogenization: counted and said)
                 if rank == 0:
                     warnings.warn(f"partitioned_checkerboard_homogenization: V-cycle {i} of outer step {k} used an inexact "
                                   f"level-1 solve ({inexact} so far)")
             nint = grid.local_count_below(driver.find_elements_in_radius(cur, box_radius))
-            area = api.integrate_area(top.x, grid, nint)
+            area = api.integrate_area(xv, grid, nint)
             if k == 0:
-                integral = api.integrate_first_term(top.x, grid, nint, xi, b=top.b)
+                integral = api.integrate_first_term(xv, grid, nint, xi, b=top.b)
             else:
-                integral = api.integrate_terms(top.x, v_prev, grid, nint)
+                integral = api.integrate_terms(xv, v_prev, grid, nint)
             area, integral = rank_sum(area, integral)
             dsig = 2.0 ** k * integral / area
-            rnorm = api.norm_unique(top.r)
+            rnorm = fcg.residual_norm() if accelerate else api.norm_unique(top.r)
             history.append((k, i, rnorm, sigma + dsig, abs(dsig - dsig_prev)))
             if log and rank == 0:
                 log(history[-1])
@@ -436,12 +443,15 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
         ne_keep = driver.find_elements_in_radius(cur, total_radius)
         cur = api.Mesh(cur.nodes[:nn_keep], np.ascontiguousarray(cur.elements[:ne_keep]))
         grid.shrink(ne_keep, nn_keep)
-        api.apply_constraint(top.x, total_grids, grid)
+        api.apply_constraint(xv, total_grids, grid)
         if v_prev is None:
             v_prev = api.DeviceMatrix(top.x.implicit, total_grids)
-        v_prev.copyto(top.x)
+        v_prev.copyto(xv)
         op.lam = lam
-        api.next_rhs(top.b, top.x, grid)
+        api.next_rhs(top.b, xv, grid)
     if stats is not None:
         stats["inexact_vcycles"] = inexact
+    if accelerate:
+        fcg.close()
+        xv.close()
     return sigma, history

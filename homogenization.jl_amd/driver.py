@@ -182,7 +182,7 @@ def checkerboard_problem(ctx, eltype, width: int, levels: int, seed: int = 0, va
 def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, smoothing_steps: int = 3,
                                 tolerance: float = 1e-4, xi=None, save=None, *, ctx=None, seed: int = 0,
                                 values=(1.0, 9.0), sigma_grid=None, x0=None, max_cycles: int = 1000, log=None,
-                                timings: dict | None = None, tune_placement: int = 0):
+                                timings: dict | None = None, tune_placement: int = 0, accelerate: bool = False):
     """checkerboard_homogenization(n, type; refinements, smoothing_steps, tolerance, xi, save) -> sigma
     (src/examples/homogenized_coefficients.jl:174-343) with every level-vector operation on the device.
 
@@ -196,7 +196,12 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
     the first V-cycle), "solve_s" (everything after), "vcycles", "outer_steps", "cells", and "inexact_vcycles": V-cycles whose
     level-1 solve ran out of its iteration budget (each also raises a warning; 0 in every recorded run).
     `tune_placement` = T > 0: the finest level's five memory blocks are assigned to their roles by measurement
-    (api.tune_placement, T candidates; pays off for long runs only -- about 0.1 s per candidate at config 3)."""
+    (api.tune_placement, T candidates; pays off for long runs only -- about 0.1 s per candidate at config 3).
+    `accelerate` = True: the V-cycle preconditions a flexible CG iteration (api.FlexibleCG) instead of being repeated as it is: one
+    `start` per outer step, one `step` per cycle; the same integrals, stopping rule and history (entry 2 is the norm of the true
+    residual), "vcycles" counts the iterations.  Four more vectors of the finest level's size: the iterate (the finest level's own
+    x holds the preconditioned residual; its b keeps the right-hand side, which `integrate_first_term` reads at k = 0) and the
+    method's p, q, R.  At tolerances far above rounding the two forms stop at iterates that differ by about the tolerance."""
     import time
     t_start = time.perf_counter()
     save_dir = "."
@@ -232,14 +237,16 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
         tuned = api.tune_placement(implicit, ops, states, total_grids, smoothing_steps, trials=int(tune_placement))
         if timings is not None:
             timings["tune_ms"] = tuned
+    xv = api.DeviceMatrix(implicit, total_grids) if accelerate else top.x      # the iterate
+    fcg = api.FlexibleCG(implicit, None, ops, states, total_grids, smoothing_steps) if accelerate else None
     ctx.sync()
     t_alloc = time.perf_counter()
     if x0 is None:
-        top.x.rand(seed + 1)
+        xv.rand(seed + 1)
     else:
-        top.x.from_host(x0)
-    api.broadcast_interfaces(top.x, implicit, total_grids)
-    api.apply_constraint(top.x, total_grids, implicit)
+        xv.from_host(x0)
+    api.broadcast_interfaces(xv, implicit, total_grids)
+    api.apply_constraint(xv, total_grids, implicit)
     api.rhs_axi_grad_v(top.b, implicit, xi)
     v_prev = None                                        # allocated at the first domain shrink (10 GB at config 3)
     cur = base
@@ -250,21 +257,24 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
     for k in range(n + 1):
         base_level = api.BaseLevel(implicit)             # level-1 operator for the current lam / domain
         dsig, dsig_prev = 0.0, 0.0
+        if accelerate:
+            fcg.start(xv, top.b)                         # new boundary, new lam, new right-hand side: a new residual
         for i in range(1, max_cycles + 1):
-            if not api.vcycle_tolerant(implicit, base_level, ops, states, total_grids, smoothing_steps):
+            if not (fcg.step_tolerant() if accelerate else
+                    api.vcycle_tolerant(implicit, base_level, ops, states, total_grids, smoothing_steps)):
                 # the level-1 solve ran out of its blind iteration budget: this cycle's coarse-grid correction was inexact (a weaker
                 # but valid iterate; the library counts the next solve again).  The reference's CHOLMOD solve cannot miss -- say so.
                 inexact += 1
                 warnings.warn(f"checkerboard_homogenization: V-cycle {i} of outer step {k} used an inexact level-1 solve "
                               f"({inexact} so far)")
             nint = find_elements_in_radius(cur, box_radius)
-            area = api.integrate_area(top.x, implicit, nint)
+            area = api.integrate_area(xv, implicit, nint)
             if k == 0:
-                integral = api.integrate_first_term(top.x, implicit, nint, xi, b=top.b)   # b = rhs_a.xi.grad(v) at k = 0
+                integral = api.integrate_first_term(xv, implicit, nint, xi, b=top.b)   # b = rhs_a.xi.grad(v) at k = 0
             else:
-                integral = api.integrate_terms(top.x, v_prev, implicit, nint)
+                integral = api.integrate_terms(xv, v_prev, implicit, nint)
             dsig = 2.0 ** k * integral / area
-            rnorm = api.norm_unique(top.r)
+            rnorm = fcg.residual_norm() if accelerate else api.norm_unique(top.r)
             history.append((k, i, rnorm, sigma + dsig, abs(dsig - dsig_prev)))
             if log:
                 log(history[-1])
@@ -273,7 +283,7 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
             dsig_prev = dsig
         sigma += dsig
         if save is not None:                             # ref: ...homogenized_coefficients.jl:303
-            vtk.export_unknown(implicit, top.x, k, save, os.path.join(save_dir, f"ahom_{k}"))
+            vtk.export_unknown(implicit, xv, k, save, os.path.join(save_dir, f"ahom_{k}"))
         lam /= 2
         box_radius = compute_box_radius(k + 1, n)
         boundary_layer = compute_boundary_layer(lam, n)
@@ -284,12 +294,12 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
         ne_keep = find_elements_in_radius(cur, total_radius)
         cur = Mesh(cur.nodes[:nn_keep], np.ascontiguousarray(cur.elements[:ne_keep]))
         implicit.shrink(ne_keep, nn_keep)                # new boundary; level vectors keep their storage
-        api.apply_constraint(top.x, total_grids, implicit)
+        api.apply_constraint(xv, total_grids, implicit)
         if v_prev is None:
             v_prev = api.DeviceMatrix(top.x.implicit, total_grids)
-        v_prev.copyto(top.x)
+        v_prev.copyto(xv)
         op.lam = lam
-        api.next_rhs(top.b, top.x, implicit)
+        api.next_rhs(top.b, xv, implicit)
     ctx.sync()
     if timings is not None:
         timings.update(setup_s=t_setup - t_start, setup_mesh_s=t_mesh - t_start, setup_tables_s=t_grid - t_mesh,
@@ -298,6 +308,9 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
                        outer_steps=len({h[0] for h in history}), cells=int(base.elements.shape[0]), width=int(width),
                        inexact_vcycles=inexact)
     # the level vectors go back now, not whenever the collector gets to them (71 GB at BASELINE config 3)
+    if accelerate:
+        fcg.close()
+        xv.close()
     for st in states:
         st.close()
     if v_prev is not None:

@@ -112,7 +112,8 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    one), "device_allocs" (device / pinned allocations the library has made in this process: constant across hmg_vcycle once the
    grid, its operator, its level-1 system and the level vectors exist), "spare_bytes" (spare direction vectors held by this
    context's grids, see hmg_grid_reserve_spare), "lazy_top_form" (the form the last finest-level post-smoother inside hmg_vcycle
-   took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain); -1 for an unknown name.  No counterpart in
+   took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "fcg_bytes" (p, q and R of this context's
+   hmg_fcg objects); -1 for an unknown name.  No counterpart in
    the reference. */
 int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name);
 
@@ -248,6 +249,43 @@ int hmg_vcycle(hmg_grid *grid, int top_level, int steps, int steps_coarse, hmg_v
  * r / p wrap caller-owned memory. */
 int hmg_vcycle_down(hmg_grid *grid, int level, int steps, hmg_vec **states);
 int hmg_vcycle_up(hmg_grid *grid, int level, int steps, hmg_vec **states);
+
+/* ---- V-cycle-preconditioned flexible CG --------------------------------------------------------------
+ * Repeating hmg_vcycle is a stationary iteration.  These calls use the same V-cycle as the preconditioner of a flexible
+ * conjugate gradient iteration with one retained direction (Notay's FCG(1): the CG smoother makes the V-cycle a slightly
+ * non-linear operator, for which the plain PCG recurrence is the wrong one).  No counterpart in the reference.
+ *
+ *   start   R = b - A_loc x, Dirichlet rows zeroed
+ *   step    z = hmg_vcycle on the top level with right-hand side R and a zero initial guess
+ *           first step p = z; later beta = -(z.q) / (p.q)_prev, p = z + beta p
+ *           q = A_loc p, Dirichlet rows zeroed;  alpha = (p.R) / (p.q);  x += alpha p;  R -= alpha q
+ *
+ * x, z, p are consistent vectors (all copies of a shared node equal), b, R, q are loads (the copies add up to the global
+ * value; A_loc is hmg_apply_ex with constrain = 1, which does no interface sum), so the plain dot products over the
+ * storage are the global inner products: the outer iteration has no interface sum and no cut exchange of its own.  On a
+ * partitioned grid a step adds two sums over the ranks (z.q; p.q and p.R together) through the grid's scalar_sum hook / the
+ * in-library communicator.  alpha and beta are formed on the device: a step enqueues work and returns.
+ *
+ * The object (an opaque handle, passed as void *) is bound to a grid and a top level and owns p, q and R: three vectors of
+ * the top level's size from the context's pool of level-vector memory, allocated by hmg_fcg_create -- setup memory,
+ * hmg_ctx_counter "device_allocs" does not move in start / step; their size is counter "fcg_bytes".  A create that does not
+ * get the memory fails.  `states` as for hmg_vcycle; the top level's x receives z, its r, p, Ap are scratch, its b is not
+ * touched (R takes its place inside the V-cycle, by handle).  x is a vector of the caller's that is none of the top level's
+ * five; x must be consistent and constrained (hmg_interface_sum / hmg_constraint) when hmg_fcg_start is called.
+ * After hmg_grid_shrink, hmg_grid_set_lambda or hmg_grid_set_operator the residual belongs to the old operator:
+ * hmg_fcg_start must be called again, hmg_fcg_step and hmg_fcg_residual_norm fail until it has been.
+ * A budgeted level-1 solve that misses its tolerance is reported as for hmg_vcycle (hmg_coarse_last_iterations): by the
+ * next synchronising call; the step remains a valid, weaker iterate. */
+int hmg_fcg_create(hmg_grid *grid, int top_level, int steps, int steps_coarse, void **out);
+int hmg_fcg_destroy(void *fcg);
+int hmg_fcg_start(void *fcg, hmg_vec *x, hmg_vec *b, hmg_vec **states);
+int hmg_fcg_step(void *fcg, hmg_vec *x, hmg_vec **states);
+/* first-copy norm of the interface-summed R (the true residual norm), through the top level's r.  Synchronises. */
+int hmg_fcg_residual_norm(void *fcg, hmg_vec **states, double *norm);
+/* out[0..4) = alpha, beta, p.q, p.R of the last step (beta = 0 in the first step after a start).  Synchronises. */
+int hmg_fcg_scalars(void *fcg, double *out);
+/* which: 0 p, 1 q, 2 R -- owned by the object, valid until hmg_fcg_destroy; NULL for anything else */
+hmg_vec *hmg_fcg_vec(void *fcg, int which);
 
 /* ---- multi-GPU hooks (one process per GPU; the host layer owns the communicator) ------------------
  * The grid of a rank holds the cells that rank owns.  Entities shared with other ranks are listed by

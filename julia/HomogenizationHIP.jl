@@ -220,6 +220,44 @@ function vcycle!(implicit, base::HipBaseLevel, ops::Vector, levels::Vector{HipSt
     nothing
 end
 
+# V-cycle-preconditioned flexible CG with one retained direction (include/hmg.h, hmg_fcg_*; api.FlexibleCG): owns p, q and R
+# (three vectors of level k's size).  start!(f, x, b) once per operator / domain / right-hand side, then step!(f) per
+# iteration; x is a HipMatrix of the caller's that is none of levels[k]'s five.
+mutable struct HipFlexibleCG
+    h::Ptr{Cvoid}
+    levels::Vector{HipState}
+    ops::Vector
+    k::Int
+    x::Union{HipMatrix,Nothing}
+end
+function HipFlexibleCG(base::HipBaseLevel, ops::Vector, levels::Vector{HipState}, k::Int, steps = 3, steps_coarse = 2)
+    h = Ref{Ptr{Cvoid}}()
+    bind!(base.grid, ops, k)
+    check(ccall((:hmg_fcg_create, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Ref{Ptr{Cvoid}}), base.grid.h, k, steps, steps_coarse, h))
+    finalizer(f -> ccall((:hmg_fcg_destroy, LIB), Cint, (Ptr{Cvoid},), f.h), HipFlexibleCG(h[], levels, ops, k, nothing))
+end
+function start!(f::HipFlexibleCG, x::HipMatrix, b::HipMatrix)
+    bind!(x.grid, f.ops, f.k)
+    check(ccall((:hmg_fcg_start, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), f.h, x.h, b.h, handles(f.levels)))
+    f.x = x
+    f
+end
+step!(f::HipFlexibleCG) =
+    check(ccall((:hmg_fcg_step, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), f.h, f.x.h, handles(f.levels)))
+function residual_norm(f::HipFlexibleCG)
+    o = Ref{Float64}(0.0)
+    check(ccall((:hmg_fcg_residual_norm, LIB), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ref{Float64}), f.h, handles(f.levels), o))
+    o[]
+end
+function scalars(f::HipFlexibleCG)                                        # (alpha, beta, p.q, p.R) of the last step
+    o = zeros(Float64, 4)
+    check(ccall((:hmg_fcg_scalars, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), f.h, o))
+    (o[1], o[2], o[3], o[4])
+end
+# p, q, R as HipMatrix views of the object's own memory (which = 0, 1, 2; valid while f lives, never destroyed through the view)
+fcg_vec(f::HipFlexibleCG, which::Integer) =
+    HipMatrix(ccall((:hmg_fcg_vec, LIB), Ptr{Cvoid}, (Ptr{Cvoid}, Cint), f.h, which), f.levels[f.k].x.grid, f.k)
+
 # Optional, once after the level states exist and before they hold data: which memory block plays x, b, r, p, Ap of
 # level k is chosen by timing that level's share of a V-cycle (include/hmg.h, hmg_level_tune_placement).
 function tune_placement!(ops::Vector, levels::Vector{HipState}, k::Int, steps = 3; trials = 8, extra = 2)
