@@ -481,6 +481,20 @@ def integrate_area(v: DeviceMatrix, implicit: ImplicitFineGrid, nsubset: int) ->
     return _integrate(implicit, 2, v, None, nsubset, None)
 
 
+def integrate_pair_mass(v: DeviceMatrix, w: DeviceMatrix, implicit: ImplicitFineGrid, nsubset: int) -> float:
+    """Mq(v; w) = sum |J| * w.(M v) over the first `nsubset` cells: the bilinear form of two correctors behind the off-diagonal
+    entries of the homogenized tensor (hmg_integrate mode 3).  w may be v; nothing is written.  With the two functions above:
+    integrate_terms(v, w) = Mq(v; v) + Mq(v; w), integrate_first_term(v, b) = integrate_pair_load(v, b) + Mq(v; v).
+    No counterpart in the reference."""
+    return _integrate(implicit, 3, v, w, nsubset, None)
+
+
+def integrate_pair_load(v: DeviceMatrix, s: DeviceMatrix, implicit: ImplicitFineGrid, nsubset: int) -> float:
+    """Lq(v; s) = sum |J| * v.s over the first `nsubset` cells, s a load vector such as rhs_axi_grad_v's (hmg_integrate mode 4:
+    a streaming pass of 16 B/DOF, the same bits in every run).  No counterpart in the reference."""
+    return _integrate(implicit, 4, v, s, nsubset, None)
+
+
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))

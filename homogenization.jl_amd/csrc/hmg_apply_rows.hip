@@ -97,6 +97,7 @@ k_apply_rows(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
         for (int q = 0; q < 4; ++q) mq[q] = a.mult ? __builtin_amdgcn_readfirstlane(mp[q]) : 0x01010101u;
     }
     const bool wdot = WD && FUSED && (a.flags & 8);   // src multiplies: out = alpha A x, pap += mult (x + src) out
+    const double wself = (wdot && (a.flags & 256)) ? 0.0 : 1.0;   // ... pair form: x itself enters with weight 0, pap += mult src out
     double rr = 0.0, pap = 0.0;
     __syncthreads();                                                // W complete
     double w0[NDIR];                                                // interior weight row, SGPR-resident
@@ -207,7 +208,7 @@ k_apply_rows(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
                     o = stencil_eval_v<2>(w0, xs + L, len, 0, 0, ctr);
                     if (!wdot) o = sv[q] + o;
                     if (!FUSED || oc) oc[t] = o;
-                    if (FUSED) pap += (wdot ? ctr + sv[q] : ctr) * o;
+                    if (FUSED) pap += (wdot ? fma(wself, ctr, sv[q]) : ctr) * o;
                 } else {
                     o = stencil_eval_c<2>(W + cls * NDIR, xs, L, len, 0, 0, ctr);
                     if (!wdot) o = sv[q] + o;
@@ -217,7 +218,7 @@ k_apply_rows(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
                         const int en = cls - 1;
                         const uint32_t word = en < 4 ? mq[0] : en < 8 ? mq[1] : en < 12 ? mq[2] : mq[3];
                         const uint32_t mu = (word >> (8 * (en & 3))) & 0xffu;
-                        pap += (double)mu * ((wdot ? ctr + sv[q] : ctr) * o);
+                        pap += (double)mu * ((wdot ? fma(wself, ctr, sv[q]) : ctr) * o);
                     }
                 }
             }

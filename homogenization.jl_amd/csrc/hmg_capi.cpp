@@ -2988,18 +2988,28 @@ int hmg_integrate(hmg_grid *g, int mode, hmg_vec *v, hmg_vec *vprev, int64_t nce
         *out = area;
         return 0;
     }
-    need(mode == 0 || mode == 1, "mode must be 0 (first term), 1 (terms) or 2 (area)");
+    need(mode == 0 || mode == 1 || mode == 3 || mode == 4,
+         "mode must be 0 (first term), 1 (terms), 2 (area), 3 (mass pairing) or 4 (load pairing)");
     if (ncells_subset == 0) {
         *out = 0.0;
         return 0;
     }
-    need(vprev != nullptr, mode == 0 ? "mode 0 needs the right-hand side rhs_a.xi.grad(v) (hmg_rhs_axi_grad) as second vector"
-                                     : "mode 1 needs the previous iterate as second vector");
+    static const char *const need_second[5] = {
+        "mode 0 needs the right-hand side rhs_a.xi.grad(v) (hmg_rhs_axi_grad) as second vector",
+        "mode 1 needs the previous iterate as second vector", "",
+        "mode 3 needs the second corrector as second vector (it may be v itself)",
+        "mode 4 needs a load vector (such as hmg_rhs_axi_grad's) as second vector"};
+    need(vprev != nullptr, need_second[mode]);
     check_vec(g, v->level, vprev, "second vector");
-    need(v->d != vprev->d, "the two vectors must not alias");
+    // (modes 0 and 1 run with the second vector as the pass's source next to its input; 3 and 4 write nothing and read both)
+    need(mode >= 3 || v->d != vprev->d, "the two vectors must not alias");
     (void)xi;   // (mode 0: the direction already sits in the right-hand side the caller passes)
-    set_slab(g, lev(g, v->level));
-    launch_integrate(g->ctx->L, lev(g, v->level), g->md, mode, ncells_subset, v->d, vprev->d, S_TMP);
+    if (mode == 4) {
+        launch_integrate_load(g->ctx->L, lev(g, v->level), g->md, ncells_subset, v->d, vprev->d, S_TMP);
+    } else {
+        set_slab(g, lev(g, v->level));
+        launch_integrate(g->ctx->L, lev(g, v->level), g->md, mode, ncells_subset, v->d, vprev->d, S_TMP);
+    }
     *out = read_scalar(g->ctx, S_TMP);
     HMG_END
 }

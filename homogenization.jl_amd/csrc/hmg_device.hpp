@@ -152,7 +152,8 @@ struct ApplyArgs {
                            // last term of the class table, no per-cell scaling (restriction); bit 3 (fused): src
                            // multiplies instead of being added, sum mult (x + src) out; bit 4: mass term not scaled
                            // by |J|; bit 5 (fused): unit multiplicities; bit 6 (fused, xcoarse): the coarse column is staged
-                           // in the lattice image; bit 7 (fused, x3 mode): x is zero and is not read
+                           // in the lattice image; bit 7 (fused, x3 mode): x is zero and is not read; bit 8 (with bit 3,
+                           // read by the driver-integral instantiations only): src alone multiplies, sum mult src out
     int64_t ncells_prefix; // > 0: only the first ncells_prefix cells
     int64_t out_ld;        // column stride of out if it differs from the level's (slab restriction), else 0
     const int32_t *cell_list;   // optional: workgroup b works on cell cell_list[b] (ncell_list of them)
@@ -318,6 +319,9 @@ void launch_rhs_dphi(const Launch &L, const LevelDev &lv, int64_t ncells, const 
 // scal[slot] = integral over the first nsub cells; second = b (mode 0, first term) / the previous iterate (mode 1)
 void launch_integrate(const Launch &L, const LevelDev &lv, const MeshDev &mesh, int mode, int64_t nsub, const double *v,
                       const double *second, int slot);
+// sum over the first nsub cells of |J_c| sum_i v_i load_i: a streaming pass, 16 B/DOF, deterministic
+void launch_integrate_load(const Launch &L, const LevelDev &lv, const MeshDev &mesh, int64_t nsub, const double *v,
+                           const double *load, int slot);
 
 // multi-GPU cut exchange, all three kinds (faces, edges, nodes) at once: unpack = 0 packs buf[pos[e] + k] <- x (first
 // local copy), 1 writes x <- buf[pos[e] + k]; pos[e] = first buffer position of the run of local cut copy e (layout:

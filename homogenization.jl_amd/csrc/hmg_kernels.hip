@@ -503,6 +503,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
     const int nsurf = lv.off_int;
     const int nsw = RB ? lv.nblk : lv.nsweep;
     const bool wdot = WD && FUSED && (a.flags & 8);   // src multiplies: out = alpha A x, pap += mult (x + src) out
+    const double wself = (wdot && (a.flags & 256)) ? 0.0 : 1.0;   // ... pair form: x itself enters with weight 0, pap += mult src out
     HMG_STAMP(2);   // tables requested, before the barrier
     __syncthreads();
     HMG_STAMP(3);
@@ -522,7 +523,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
             const int e = cls - 1;
             const uint32_t word = e < 4 ? mq[0] : e < 8 ? mq[1] : e < 12 ? mq[2] : mq[3];
             const uint32_t mu = (word >> (8 * (e & 3))) & 0xffu;
-            pap += (double)mu * ((wdot ? ctr + sv : ctr) * o);
+            pap += (double)mu * ((wdot ? fma(wself, ctr, sv) : ctr) * o);
         }
         return o;
     };
@@ -549,13 +550,13 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
             if (face >= 4)
                 ;
             else if (face == 0)
-                face_items<0, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr);
+                face_items<0, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr, wself);
             else if (face == 1)
-                face_items<1, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr);
+                face_items<1, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr, wself);
             else if (face == 2)
-                face_items<2, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr);
+                face_items<2, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr, wself);
             else
-                face_items<3, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr);
+                face_items<3, FI, FUSED, FUSED && !RS>(wv, 16, xs, m, lv.nfi, fbase, ft0, fw, fdir, fmult, sc, oc, pap, lane, nopre, false, wdot, RS ? kf : nullptr, wself);
 #pragma unroll
             for (int q = 0; q < NE; ++q) {
                 if (edge[q] < 0) continue;
@@ -565,12 +566,12 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                 const double nop1[1] = {0.0};
                 const int wl = 32 + 16 * q;
                 switch (edge[q]) {
-                case 0: class_items<edge_tap_mask(0), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
-                case 1: class_items<edge_tap_mask(1), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
-                case 2: class_items<edge_tap_mask(2), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
-                case 3: class_items<edge_tap_mask(3), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
-                case 4: class_items<edge_tap_mask(4), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
-                default: class_items<edge_tap_mask(5), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr); break;
+                case 0: class_items<edge_tap_mask(0), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
+                case 1: class_items<edge_tap_mask(1), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
+                case 2: class_items<edge_tap_mask(2), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
+                case 3: class_items<edge_tap_mask(3), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
+                case 4: class_items<edge_tap_mask(4), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
+                default: class_items<edge_tap_mask(5), 1, FUSED, FUSED && !RS>(wv, wl, xs, m, lv.nei, ebase[q], 0, ew[q], edir, emult, sc, oc, pap, lane, nop1, false, wdot, RS ? &ke[q] : nullptr, wself); break;
                 }
             }
             if (wave == NW - 1 && lane < lv.ncorner) kc = surface_node(lane, cw);
@@ -596,13 +597,13 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         if constexpr (!RS) {
         if (DIM == 3 && tid < nsw) {
             if (sc)
-                interior_block<RB ? RB : 1, FUSED, true>(w0, xs, m, nf >> 1, q0, s0, sc, oc, pap, wdot);
+                interior_block<RB ? RB : 1, FUSED, true>(w0, xs, m, nf >> 1, q0, s0, sc, oc, pap, wdot, wself);
             else
                 interior_block<RB ? RB : 1, FUSED, false>(w0, xs, m, nf >> 1, q0, s0, sc, oc, pap);
         }
         if (DIM == 3 && NPASS > 1 && tid + NT < nsw) {      // second pass (the host selects NT >= nblk / 2)
             if (sc)
-                interior_block<RB ? RB : 1, FUSED, true>(w0, xs, m, nf >> 1, q1, s1, sc, oc, pap, wdot);
+                interior_block<RB ? RB : 1, FUSED, true>(w0, xs, m, nf >> 1, q1, s1, sc, oc, pap, wdot, wself);
             else
                 interior_block<RB ? RB : 1, FUSED, false>(w0, xs, m, nf >> 1, q1, s1, sc, oc, pap);
         }
@@ -625,7 +626,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                 double o = stencil_eval_v<DIM>(w0, xs + L, len, A, B, ctr);
                 if (!wdot) o = sv + o;
                 if (!FUSED || oc) oc[t] = o;
-                if (FUSED) pap += (wdot ? ctr + sv : ctr) * o;
+                if (FUSED) pap += (wdot ? fma(wself, ctr, sv) : ctr) * o;
             }
         }
     }
@@ -795,6 +796,7 @@ k_apply_slab(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
         for (int q = 0; q < 4; ++q) mq[q] = a.mult ? __builtin_amdgcn_readfirstlane(mp[q]) : 0x01010101u;
     }
     const bool wdot = WD && FUSED && (a.flags & 8);   // src multiplies: out = alpha A x, pap += mult (x + src) out
+    const double wself = (wdot && (a.flags & 256)) ? 0.0 : 1.0;   // ... pair form: x itself enters with weight 0, pap += mult src out
     double rr = 0.0, pap = 0.0;
     auto plane_off = [&](int k) {   // PO(k) = number of lattice nodes in planes < k
         if (k <= 0) return 0;
@@ -924,7 +926,7 @@ k_apply_slab(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
                     const int en = cls - 1;
                     const uint32_t word = en < 4 ? mq[0] : en < 8 ? mq[1] : en < 12 ? mq[2] : mq[3];
                     const uint32_t mu = (word >> (8 * (en & 3))) & 0xffu;
-                    pap += (double)mu * ((wdot ? ctr + sv : ctr) * o);
+                    pap += (double)mu * ((wdot ? fma(wself, ctr, sv) : ctr) * o);
                 }
             }
         }
@@ -947,7 +949,7 @@ k_apply_slab(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
                 double o = stencil_eval_v<DIM>(w0, xs + L, len, A, B, ctr);
                 if (!wdot) o = sv + o;
                 if (!FUSED || oc) oc[t] = o;
-                if (FUSED) pap += (wdot ? ctr + sv : ctr) * o;
+                if (FUSED) pap += (wdot ? fma(wself, ctr, sv) : ctr) * o;
             }
         }
         lo_prev = lo;
@@ -2589,9 +2591,10 @@ void launch_coarse_residual_norm(const Launch &L, const CoarseDev &A)
 // driver integrals over a prefix of cells (ref: src/examples/homogenized_coefficients.jl:592-667)
 //   mode 0: sum_cells |J| sum_i v_i (b_i + (M v)_i), b = dphi . P = the right-hand side of outer step 0   integrate_first_term
 //   mode 1: sum_cells |J| sum_i (v_i + w_i) (M v)_i                                                        integrate_terms
+//   mode 3: sum_cells |J| sum_i w_i (M v)_i                      the bilinear form of two correctors (w may be v)
 // M = reference-element mass matrix of the level.  One pass of the FUSED operator apply in "reductions only" form
 // (no output vector): mass term only and unscaled, unit multiplicities, no constraint; the per-cell sum it leaves
-// in blockpart is sum_i x_i (src_i + (M x)_i) resp. sum_i (x_i + src_i) (M x)_i, scaled by |J_c| in the reduction.
+// in blockpart is sum_i x_i (src_i + (M x)_i), sum_i (x_i + src_i) (M x)_i resp. sum_i src_i (M x)_i, scaled by |J_c| in the reduction.
 // Works for every level the apply works for (the slab kernel included) and moves 16 B per DOF.
 // ---------------------------------------------------------------------------------------------
 void launch_integrate(const Launch &L, const LevelDev &lv, const MeshDev &mesh, int mode, int64_t nsub, const double *v,
@@ -2602,13 +2605,59 @@ void launch_integrate(const Launch &L, const LevelDev &lv, const MeshDev &mesh, 
     a.lambda = 1.0;
     a.x = v;
     a.src = second;
-    a.flags = 2 | 16 | 32 | (mode == 1 ? 8 : 0);
+    a.flags = 2 | 16 | 32 | (mode == 1 ? 8 : mode == 3 ? 8 | 256 : 0);
     a.ncells_prefix = nsub;
     launch_apply_fused_kernel(L, lv, mesh, a);
     hipLaunchKernelGGL(k_reduce_weighted, dim3(256), dim3(256), 0, L.stream, mesh.blockpart, mesh.coef, lv.nterm - 1, nsub,
                        L.partials);
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, L.stream, L.partials, 256, L.scal, slot);
     check_launch();
+}
+
+// Load pairing of the driver integrals: sum over the first nsub cells of |J_c| sum_i v_i s_i (s a load vector such as
+// rhs_a.xi.grad(v)).  A streaming kernel in the launch shape of the others (one double2 per thread by FLAT index over the
+// prefix's nsub * ld doubles, one block per 512 doubles, no loop): the pairs are aligned whatever ld is, a pair may straddle
+// two columns, so each element finds its own cell.  The block's first cell comes from one 64-bit division per block, the
+// thread's from a 32-bit one.  One partial per block, folded in block order: the same bits in every run.
+__global__ void __launch_bounds__(SB)
+k_dot_cellweighted(const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ coef, int jterm,
+                   int nf, int ld, int64_t n, double *partials)
+{
+    __shared__ double red[4];
+    const int64_t e0 = (int64_t)blockIdx.x * (2 * SB);          // first element of this block
+    const int64_t cb = e0 / ld;
+    const uint32_t off = (uint32_t)(e0 - cb * ld) + 2u * threadIdx.x;   // < ld + 2 SB
+    const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
+    double acc = 0.0;
+    if (i < (n >> 1)) {
+        const double2 xv = reinterpret_cast<const double2 *>(x)[i], yv = reinterpret_cast<const double2 *>(y)[i];
+        const uint32_t dc = off / (uint32_t)ld;
+        int64_t c = cb + dc;
+        int t = (int)(off - dc * (uint32_t)ld);
+        if (t < nf) acc += coef[c * 8 + jterm] * (xv.x * yv.x);
+        if (++t == ld) {
+            t = 0;
+            ++c;
+        }
+        if (t < nf) acc += coef[c * 8 + jterm] * (xv.y * yv.y);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0 && (int)((n - 1) % ld) < nf)
+        acc += coef[((n - 1) / ld) * 8 + jterm] * (x[n - 1] * y[n - 1]);
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+void launch_integrate_load(const Launch &L, const LevelDev &lv, const MeshDev &mesh, int64_t nsub, const double *v,
+                           const double *load, int slot)
+{
+    const int64_t n = nsub * lv.ld;
+    const int64_t nb = stream_blocks(n);
+    check_grid(nb);
+    if (!v || !load || !mesh.coef) throw std::runtime_error("load pairing: null vector or no operator coefficients on the device");
+    hipLaunchKernelGGL(k_dot_cellweighted, dim3((unsigned)nb), dim3(SB), 0, L.stream, v, load, mesh.coef, lv.nterm - 1, lv.nf,
+                       (int)lv.ld, n, reduce_target(L, nb));
+    check_launch();
+    reduce_finish(L, nb, slot);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -282,10 +282,11 @@ template <uint32_t M, int NITEM, bool FUSED, bool PAP = FUSED>
 __device__ __forceinline__ void class_items(double wv, int wlane0, const double *xs, int m, int nfi, int slot_base, int t0,
                                             const uint32_t (&fw)[NITEM], bool dirichlet, double mult, const double *sc,
                                             double *oc, double &pap, int lane, const double (&pre)[NITEM], bool use_pre,
-                                            bool wdot = false, double *keep = nullptr)
+                                            bool wdot = false, double *keep = nullptr, double wself = 1.0)
 {
     // keep (optional, NITEM entries): the results are handed back as well (restriction in the epilogue)
-    // wdot: the source value multiplies instead of being added: out = alpha A x, pap += mult (x + src) out
+    // wdot: the source value multiplies instead of being added: out = alpha A x, pap += mult (wself x + src) out; wself = 1, or
+    // 0 for the pair form, in which src alone multiplies (1 x + src is x + src to the last bit)
     // wv: the class weight row, spread over the lanes wlane0 .. wlane0 + 14 of this wave; M: the taps that exist
     double w[15];
 #pragma unroll
@@ -319,7 +320,7 @@ __device__ __forceinline__ void class_items(double wv, int wlane0, const double 
                 if ((M >> 13) & 1u) acc += w[13] * lds_ld(pu + 1 - len);
                 if ((M >> 14) & 1u) acc += w[14] * lds_ld(pd + len);
                 o = wdot ? acc : sv + acc;
-                if (PAP) pap += mult * ((wdot ? ctr + sv : ctr) * o);
+                if (PAP) pap += mult * ((wdot ? fma(wself, ctr, sv) : ctr) * o);
             }
             if (!FUSED || oc) oc[t] = o;
             if (keep) keep[q] = o;
@@ -331,10 +332,10 @@ template <int F, int NITEM, bool FUSED, bool PAP = FUSED>
 __device__ __forceinline__ void face_items(double wv, int wlane0, const double *xs, int m, int nfi, int slot_base, int t0,
                                            const uint32_t (&fw)[NITEM], bool dirichlet, double mult, const double *sc,
                                            double *oc, double &pap, int lane, const double (&pre)[NITEM], bool use_pre,
-                                           bool wdot = false, double *keep = nullptr)
+                                           bool wdot = false, double *keep = nullptr, double wself = 1.0)
 {
     class_items<face_tap_mask(F), NITEM, FUSED, PAP>(wv, wlane0, xs, m, nfi, slot_base, t0, fw, dirichlet, mult, sc, oc, pap, lane,
-                                                     pre, use_pre, wdot, keep);
+                                                     pre, use_pre, wdot, keep, wself);
 }
 
 // Edge e of the reference simplex lies on two faces (edge order of the reference: (1,2) (1,3) (1,4) (2,3) (2,4) (3,4) =
@@ -370,11 +371,12 @@ __device__ __forceinline__ void block_slots(int m, uint32_t word, int slot0, int
 }
 
 // acc[r] holds the value the sum of node r starts from (0, or the source value for out = src + alpha A x).
-// WDOT: wsv[r] is added to the node's own value in the p.Ap-type sum (driver integrals: (v + w) . M v).
+// WDOT: wsv[r] is added to wself times the node's own value in the p.Ap-type sum (driver integrals: (v + w) . M v with
+// wself = 1, w . M v with wself = 0).
 template <int R, bool FUSED, bool WDOT = false, bool KEEP = false>
 __device__ __forceinline__ void interior_block_core(const double (&w)[15], const double *xs, int m, int safe, uint32_t word,
                                                     int slot0, double *oc, double &pap, double (&acc)[R],
-                                                    const double *wsv = nullptr)
+                                                    const double *wsv = nullptr, double wself = 1.0)
 {
     // KEEP: the finished sums stay in acc[] for the caller (restriction in the epilogue) and p.Ap is not formed
     const int L = (int)(word & 0xffffu), j = (int)((word >> 16) & 63u), k0 = (int)((word >> 22) & 63u);
@@ -411,7 +413,7 @@ __device__ __forceinline__ void interior_block_core(const double (&w)[15], const
             if (KEEP) acc[s - 2] = t;
             if (s - 2 < nv) {
                 if (!FUSED || oc) oc[slot] = t;
-                if (FUSED && !KEEP) pap += (WDOT ? ctr[s - 2] + wsv[s - 2] : ctr[s - 2]) * t;   // (the CG passes have no src)
+                if (FUSED && !KEEP) pap += (WDOT ? fma(wself, ctr[s - 2], wsv[s - 2]) : ctr[s - 2]) * t;   // (the CG passes have no src)
             }
             slot += ds;
             ds -= n0 - s;                   // n0 - 2 - r, r = s - 2
@@ -482,7 +484,8 @@ __device__ __forceinline__ void interior_block_keep(const double (&w)[15], const
 
 template <int R, bool FUSED, bool SRC>
 __device__ __forceinline__ void interior_block(const double (&w)[15], const double *xs, int m, int safe, uint32_t word,
-                                               int slot0, const double *sc, double *oc, double &pap, bool wdot = false)
+                                               int slot0, const double *sc, double *oc, double &pap, bool wdot = false,
+                                               double wself = 1.0)
 {
     double acc[R];
     if (SRC) {
@@ -498,7 +501,7 @@ __device__ __forceinline__ void interior_block(const double (&w)[15], const doub
                 wsv[r] = acc[r];
                 acc[r] = 0.0;
             }
-            interior_block_core<R, FUSED, true>(w, xs, m, safe, word, slot0, oc, pap, acc, wsv);
+            interior_block_core<R, FUSED, true>(w, xs, m, safe, word, slot0, oc, pap, acc, wsv, wself);
             return;
         }
     } else {

@@ -455,3 +455,111 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
         fcg.close()
         xv.close()
     return sigma, history
+
+
+def partitioned_checkerboard_homogenization_tensor(ctx, n: int, eltype, world: int, rank: int, refinements: int = 2,
+                                                   smoothing_steps: int = 3, tolerance: float = 1e-4, seed: int = 0,
+                                                   values=(1.0, 9.0), sigma_grid=None, x0=None, max_cycles: int = 1000,
+                                                   group=None, log=None, backend=None, stats: dict | None = None,
+                                                   accelerate: bool = False):
+    """driver.checkerboard_homogenization_tensor over `world` ranks, partitioned like partitioned_checkerboard_homogenization:
+    the same loop (d corrector solves per outer step on one grid, then the off-diagonal increments from the pair integrals),
+    with every integral a local sum added over the ranks -- the shares of all pairs of a step in one call.  Returns
+    (Sigma, history) like the single-GPU driver, identical on every rank."""
+    dim = api._dim_of(eltype)
+    if world not in ((1, 2, 4) if dim == 2 else (1, 2, 4, 8)):
+        raise ValueError(f"partitioned_checkerboard_homogenization_tensor: {world} ranks are not supported in {dim}D "
+                         "(blocks are halves per axis: 1, 2, 4" + (", 8" if dim == 3 else "") + ")")
+    lam = 1.0
+    Sigma = np.zeros((dim, dim))
+    box_radius = driver.compute_box_radius(0, n)
+    boundary_layer = driver.compute_boundary_layer(lam, n)
+    total_radius = box_radius + boundary_layer
+    width = 2 * total_radius
+    origin = (-float(total_radius),) * dim
+    base = driver.checkerboard_mesh(eltype, width, origin=origin, transposed_lookup=True)
+    if sigma_grid is None:
+        sigma_grid = driver.generate_conductivity(dim, width, seed, values)
+    cond = driver.conductivity_per_element(base, sigma_grid, (total_radius + 1.0,) * dim)
+    owner = block_owner(base, block_shape(world, dim), width / 2.0, origin)
+    total_grids = refinements + 1
+    grid = PartitionedGrid(ctx, base, total_grids, owner, rank, world)
+    ex = Exchange(ctx, grid, group, backend)
+    op = api.L2PlusDivAGrad(grid, lam, cond)
+    ops = [op] * total_grids
+    states = [api.LevelState(grid, i + 1) for i in range(total_grids)]
+    top = states[-1]
+    if x0 is None:
+        x0 = api.host_random((grid.nf(total_grids), base.elements.shape[0]), seed + 1)       # hashed by GLOBAL cell id
+    x0_local = np.asfortranarray(x0[:, grid.local_cells])
+    xv = api.DeviceMatrix(grid, total_grids) if accelerate else top.x      # the iterate
+    fcg = api.FlexibleCG(grid, None, ops, states, total_grids, smoothing_steps) if accelerate else None
+    V = [api.DeviceMatrix(grid, total_grids) for _ in range(dim)]          # v_k^i
+    Vprev = None                                         # v_{k-1}^i: allocated at the first domain shrink
+    rank_sum = ex.rank_sum
+    cur = base
+    history = []
+    inexact = 0
+    for k in range(n + 1):
+        base_level = api.BaseLevel(grid)
+        nint = grid.local_count_below(driver.find_elements_in_radius(cur, box_radius))
+        area = rank_sum(api.integrate_area(xv, grid, nint))[0]
+        for d in range(dim):
+            if k == 0:
+                xv.from_host(x0_local)
+                api.broadcast_interfaces(xv, grid, total_grids)
+                api.apply_constraint(xv, total_grids, grid)
+                api.rhs_axi_grad_v(top.b, grid, np.eye(dim)[d])
+            else:
+                xv.copyto(Vprev[d])
+                api.next_rhs(top.b, xv, grid)
+            dsig, dsig_prev = 0.0, 0.0
+            if accelerate:
+                fcg.start(xv, top.b)
+            for i in range(1, max_cycles + 1):
+                if not (fcg.step_tolerant() if accelerate else
+                        api.vcycle_tolerant(grid, base_level, ops, states, total_grids, smoothing_steps)):
+                    inexact += 1
+                    if rank == 0:
+                        warnings.warn(f"partitioned_checkerboard_homogenization_tensor: V-cycle {i} of outer step {k}, direction "
+                                      f"{d}, used an inexact level-1 solve ({inexact} so far)")
+                if k == 0:
+                    integral = api.integrate_first_term(xv, grid, nint, np.eye(dim)[d], b=top.b)
+                else:
+                    integral = api.integrate_terms(xv, Vprev[d], grid, nint)
+                integral = rank_sum(integral)[0]
+                dsig = 2.0 ** k * integral / area
+                rnorm = fcg.residual_norm() if accelerate else api.norm_unique(top.r)
+                history.append((k, d, i, rnorm, Sigma[d, d] + dsig, abs(dsig - dsig_prev)))
+                if log and rank == 0:
+                    log(history[-1])
+                if abs(dsig - dsig_prev) < tolerance:
+                    break
+                dsig_prev = dsig
+            Sigma[d, d] += dsig
+            V[d].copyto(xv)
+        Sigma += driver.pair_increments(V, Vprev, k, nint, area, grid, top.b, rank_sum=rank_sum)
+        lam /= 2
+        box_radius = driver.compute_box_radius(k + 1, n)
+        boundary_layer = driver.compute_boundary_layer(lam, n)
+        if box_radius + boundary_layer > total_radius:
+            break
+        total_radius = box_radius + boundary_layer
+        nn_keep = driver.find_nodes_in_radius(cur, total_radius)
+        ne_keep = driver.find_elements_in_radius(cur, total_radius)
+        cur = api.Mesh(cur.nodes[:nn_keep], np.ascontiguousarray(cur.elements[:ne_keep]))
+        grid.shrink(ne_keep, nn_keep)
+        for v in V:
+            api.apply_constraint(v, total_grids, grid)
+        if Vprev is None:
+            Vprev = [api.DeviceMatrix(grid, total_grids) for _ in range(dim)]
+        V, Vprev = Vprev, V
+        op.lam = lam
+    if stats is not None:
+        stats["inexact_vcycles"] = inexact
+    if accelerate:
+        fcg.close()
+        xv.close()
+    for v in V + (Vprev or []):
+        v.close()
+    return Sigma, history

@@ -321,6 +321,189 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
     return sigma, history
 
 
+def pair_increments(V, Vprev, k, nint, area, implicit, scratch, rank_sum=None):
+    """The off-diagonal increments 2^k I_k^{ij} / area of the homogenized tensor from the correctors V[i] = v_k^i of one outer
+    step (Vprev[i] = v_{k-1}^i under the step's constraint; unused at k = 0), as a symmetric matrix with a zero diagonal:
+
+        k = 0    I^{ij} = 1/2 [Lq(v^i; b^j) + Lq(v^j; b^i)] + Mq(v^i; v^j),    b^j = rhs_a.e_j.grad(v), regenerated into `scratch`
+        k >= 1   I^{ij} = Mq(v_k^i; v_k^j) + 1/2 [Mq(v_k^j; v_{k-1}^i) + Mq(v_k^i; v_{k-1}^j)]
+
+    (Mq = api.integrate_pair_mass, Lq = api.integrate_pair_load; for i = j these are integrate_first_term / integrate_terms, which
+    the cycle loops have formed already).  rank_sum: the sum over the ranks of a partitioned grid (one call for all pairs)."""
+    dim = len(V)
+    pairs = [(i, j) for i in range(dim) for j in range(i + 1, dim)]
+    val = dict.fromkeys(pairs, 0.0)
+    if k == 0:
+        for j in range(dim):
+            api.rhs_axi_grad_v(scratch, implicit, np.eye(dim)[j])
+            for i in range(dim):
+                if i != j:
+                    val[min(i, j), max(i, j)] += 0.5 * api.integrate_pair_load(V[i], scratch, implicit, nint)
+    for i, j in pairs:
+        val[i, j] += api.integrate_pair_mass(V[i], V[j], implicit, nint)
+        if k > 0:
+            val[i, j] += 0.5 * (api.integrate_pair_mass(V[j], Vprev[i], implicit, nint) +
+                                api.integrate_pair_mass(V[i], Vprev[j], implicit, nint))
+    if rank_sum is not None and pairs:
+        val = dict(zip(pairs, rank_sum(*[val[p] for p in pairs])))
+    out = np.zeros((dim, dim))
+    for (i, j), v in val.items():
+        out[i, j] = out[j, i] = 2.0 ** k * v / area
+    return out
+
+
+def checkerboard_homogenization_tensor(n: int = 4, eltype=Tri64, refinements: int = 2, smoothing_steps: int = 3,
+                                       tolerance: float = 1e-4, save=None, *, ctx=None, seed: int = 0, values=(1.0, 9.0),
+                                       sigma_grid=None, x0=None, max_cycles: int = 1000, log=None,
+                                       timings: dict | None = None, tune_placement: int = 0, accelerate: bool = False):
+    """The full homogenized tensor from ONE run: -> (Sigma, history), Sigma a symmetric (dim, dim) array with
+    xi' Sigma xi = what `checkerboard_homogenization(xi=xi)` returns once both have converged.  The keywords are those of
+    `checkerboard_homogenization` without `xi`.
+
+    The correctors are linear in the direction, so d corrector solves (e_1 .. e_d) are enough where polarising by hand takes
+    d (d + 1) / 2 complete runs; the off-diagonal entries follow from cross integrals of the correctors (`pair_increments`:
+    api.integrate_pair_mass / integrate_pair_load).  The radii and the shrink schedule do not depend on the direction, so all
+    directions share the outer loop: base mesh, grid, operator, level states, the optional flexible-CG object and the BaseLevel
+    of an outer step are built once.  Within outer step k, direction by direction: the right-hand side is rhs_a.e_i.grad(v) at
+    k = 0 and next_rhs of v_{k-1}^i afterwards, the start vector the seeded x0 at k = 0 (the same for every direction) and
+    v_{k-1}^i under the new constraint afterwards; cycle loop, stopping rule on the diagonal increment, the handling of an inexact
+    level-1 solve and the residual norm are those of the scalar driver, and Sigma_ii accumulates exactly the increments that loop
+    forms.  After the last direction the off-diagonal increments are formed, then the domain shrinks, the handles of v_k and
+    v_{k-1} are exchanged and lam is halved.
+
+    history rows: (k, direction, cycle, norm(r), Sigma_ii so far, |change of the increment|).  `timings` receives the scalar
+    driver's entries plus "directions" and "pair_integrals_s"; `save` writes one ahom_<k>_<i>.vtu per step and direction.
+
+    Memory beyond the scalar driver, in vectors of the finest level's size: d always (v_k^i), d more from the first shrink on
+    (v_{k-1}^i; the scalar driver's v_prev is among them), none for b^j (the finest level's own b is free once the last direction
+    of a step has converged).  At BASELINE config 3 (d = 3; outer step 0 is its only step) that is about 31 GB next to 61 GB of
+    level vectors."""
+    import time
+    t_start = time.perf_counter()
+    save_dir = "."
+    if isinstance(save, tuple):
+        save, save_dir = save
+    dim = api._dim_of(eltype)
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = api.Context(0)
+    lam = 1.0
+    Sigma = np.zeros((dim, dim))
+    box_radius = compute_box_radius(0, n)
+    boundary_layer = compute_boundary_layer(lam, n)
+    total_radius = box_radius + boundary_layer
+    width = 2 * total_radius
+    base = checkerboard_mesh(eltype, width, origin=(-float(total_radius),) * dim, transposed_lookup=True)
+    if sigma_grid is None:
+        sigma_grid = generate_conductivity(dim, width, seed, values)
+    cond = conductivity_per_element(base, sigma_grid, (total_radius + 1.0,) * dim)
+    t_mesh = time.perf_counter()
+    total_grids = refinements + 1
+    if save is not None:
+        if not 1 <= save <= total_grids:
+            raise ValueError("save must be a level in 1..refinements+1")
+        vtk.export_domain(base, cond, os.path.join(save_dir, "checkerboard"))
+    implicit = api.ImplicitFineGrid(ctx, base, total_grids)
+    op = api.L2PlusDivAGrad(implicit, lam, cond)
+    ops = [op] * total_grids
+    t_grid = time.perf_counter()
+    states = [api.LevelState(implicit, i + 1) for i in range(total_grids)]
+    top = states[-1]
+    if tune_placement:
+        tuned = api.tune_placement(implicit, ops, states, total_grids, smoothing_steps, trials=int(tune_placement))
+        if timings is not None:
+            timings["tune_ms"] = tuned
+    xv = api.DeviceMatrix(implicit, total_grids) if accelerate else top.x      # the iterate
+    fcg = api.FlexibleCG(implicit, None, ops, states, total_grids, smoothing_steps) if accelerate else None
+    V = [api.DeviceMatrix(implicit, total_grids) for _ in range(dim)]          # v_k^i
+    Vprev = None                                         # v_{k-1}^i: allocated at the first domain shrink
+    ctx.sync()
+    t_alloc = time.perf_counter()
+    cur = base
+    history = []
+    inexact = 0                                          # V-cycles whose budgeted level-1 solve missed coarse_rtol
+    t_pairs = 0.0
+    t_setup = t_alloc                                    # (x0 and the right-hand sides belong to the directions' solves)
+    for k in range(n + 1):
+        base_level = api.BaseLevel(implicit)             # level-1 operator for the current lam / domain: one per outer step
+        nint = find_elements_in_radius(cur, box_radius)
+        for d in range(dim):
+            if k == 0:
+                if x0 is None:
+                    xv.rand(seed + 1)
+                else:
+                    xv.from_host(x0)
+                api.broadcast_interfaces(xv, implicit, total_grids)
+                api.apply_constraint(xv, total_grids, implicit)
+                api.rhs_axi_grad_v(top.b, implicit, np.eye(dim)[d])
+            else:
+                xv.copyto(Vprev[d])                      # v_{k-1}^i, the new constraint applied at the shrink
+                api.next_rhs(top.b, xv, implicit)
+            dsig, dsig_prev = 0.0, 0.0
+            if accelerate:
+                fcg.start(xv, top.b)
+            for i in range(1, max_cycles + 1):
+                if not (fcg.step_tolerant() if accelerate else
+                        api.vcycle_tolerant(implicit, base_level, ops, states, total_grids, smoothing_steps)):
+                    inexact += 1                         # (as in checkerboard_homogenization: counted and said)
+                    warnings.warn(f"checkerboard_homogenization_tensor: V-cycle {i} of outer step {k}, direction {d}, used an "
+                                  f"inexact level-1 solve ({inexact} so far)")
+                area = api.integrate_area(xv, implicit, nint)
+                if k == 0:
+                    integral = api.integrate_first_term(xv, implicit, nint, np.eye(dim)[d], b=top.b)
+                else:
+                    integral = api.integrate_terms(xv, Vprev[d], implicit, nint)
+                dsig = 2.0 ** k * integral / area
+                rnorm = fcg.residual_norm() if accelerate else api.norm_unique(top.r)
+                history.append((k, d, i, rnorm, Sigma[d, d] + dsig, abs(dsig - dsig_prev)))
+                if log:
+                    log(history[-1])
+                if abs(dsig - dsig_prev) < tolerance:
+                    break
+                dsig_prev = dsig
+            Sigma[d, d] += dsig
+            V[d].copyto(xv)
+            if save is not None:
+                vtk.export_unknown(implicit, xv, k, save, os.path.join(save_dir, f"ahom_{k}_{d}"))
+        t0 = time.perf_counter()
+        Sigma += pair_increments(V, Vprev, k, nint, api.integrate_area(xv, implicit, nint), implicit, top.b)
+        t_pairs += time.perf_counter() - t0
+        lam /= 2
+        box_radius = compute_box_radius(k + 1, n)
+        boundary_layer = compute_boundary_layer(lam, n)
+        if box_radius + boundary_layer > total_radius:
+            break
+        total_radius = box_radius + boundary_layer
+        nn_keep = find_nodes_in_radius(cur, total_radius)
+        ne_keep = find_elements_in_radius(cur, total_radius)
+        cur = Mesh(cur.nodes[:nn_keep], np.ascontiguousarray(cur.elements[:ne_keep]))
+        implicit.shrink(ne_keep, nn_keep)                # new boundary; level vectors keep their storage
+        for v in V:
+            api.apply_constraint(v, total_grids, implicit)
+        if Vprev is None:
+            Vprev = [api.DeviceMatrix(implicit, total_grids) for _ in range(dim)]
+        V, Vprev = Vprev, V                              # the handles change places: nothing is copied
+        op.lam = lam
+    ctx.sync()
+    if timings is not None:
+        timings.update(setup_s=t_setup - t_start, setup_mesh_s=t_mesh - t_start, setup_tables_s=t_grid - t_mesh,
+                       setup_alloc_s=t_alloc - t_grid, setup_init_s=t_setup - t_alloc,
+                       solve_s=time.perf_counter() - t_setup, vcycles=len(history),
+                       outer_steps=len({h[0] for h in history}), cells=int(base.elements.shape[0]), width=int(width),
+                       inexact_vcycles=inexact, directions=dim, pair_integrals_s=t_pairs)
+    if accelerate:
+        fcg.close()
+        xv.close()
+    for st in states:
+        st.close()
+    for v in V + (Vprev or []):
+        v.close()
+    implicit.close()
+    if own_ctx:
+        ctx.close()
+    return Sigma, history
+
+
 def checkerboard_hypercube_multigrid(n: int, eltype=Tet64, refinements: int = 2, max_cycles: int = 5, save=None, *,
                                      ctx=None, seed: int = 1, sigma_grid=None, x0=None):
     """checkerboard_hypercube_multigrid(n, elementtype, refinements, max_cycles, save) -> residual norms

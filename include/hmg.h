@@ -193,11 +193,23 @@ int hmg_rhs_axi_grad(hmg_grid *grid, const double *xi /* dim */, hmg_vec *b);
 /* local_rhs!(b, implicit): b[:, e] = |det J_e| * int phi over the refined reference cell (unit load;
  * src/implicit_fine_grid.jl:391-409, used by checkerboard_hypercube_multigrid, ...homogenized_coefficients.jl:543) */
 int hmg_local_rhs(hmg_grid *grid, hmg_vec *b);
-/* integrate_first_term (mode 0), integrate_terms (mode 1), integrate_area (mode 2) over the first ncells_subset cells
- * (src/examples/homogenized_coefficients.jl:592-689).  `second` is, for mode 0, the vector rhs_a xi grad v! produced for
- * the same xi (hmg_rhs_axi_grad: the reference recomputes dot(dphi_i, P) per node, :621 -- it is that vector entry);
- * for mode 1 the previous iterate v_{k-1}.  One 16 B/DOF pass of the operator-apply kernel in reductions-only form, on
- * every level the apply supports.  Partitioned grid: local cells, this rank's share (the host adds the shares). */
+/* The driver integrals over the first ncells_subset cells (src/examples/homogenized_coefficients.jl:592-689); M is the level's
+ * reference mass matrix, |J_c| the cell's Jacobian determinant, all sums run over the cells c < ncells_subset and the nodes i:
+ *
+ *   mode  value                                  second                                          reference
+ *   0     sum |J_c| v_i (second_i + (M v)_i)     rhs_a xi grad v! for the same xi (*)            integrate_first_term
+ *   1     sum |J_c| (v_i + second_i) (M v)_i     the previous iterate v_{k-1}                    integrate_terms
+ *   2     sum |J_c| 1' M 1                       unused (v names the level)                      integrate_area
+ *   3     sum |J_c| second_i (M v)_i             another corrector; may be v itself              none: mass pairing Mq(v; second)
+ *   4     sum |J_c| v_i second_i                 a load vector such as hmg_rhs_axi_grad's        none: load pairing Lq(v; second)
+ *
+ * (*) hmg_rhs_axi_grad: the reference recomputes dot(dphi_i, P) per node, :621 -- it is that vector entry.
+ * So mode 0 = mode 4 + mode 3 with second = v, and mode 1 = mode 3 (v, v) + mode 3 (v, second); modes 3 and 4 are the bilinear
+ * forms in two different correctors that the off-diagonal entries of the homogenized tensor need.  Modes 0 and 1 refuse
+ * second = v; modes 3 and 4 write nothing and accept it.  Modes 0, 1 and 3 are one 16 B/DOF pass of the operator-apply kernel in
+ * reductions-only form, on every level the apply supports; mode 4 is one streaming pass of 16 B/DOF.  None allocates, and the
+ * partial sums are folded in a fixed order: the same bits in every run.  ncells_subset = 0 gives 0; any other mode is an error.
+ * Partitioned grid: local cells, this rank's share (the host adds the shares). */
 int hmg_integrate(hmg_grid *grid, int mode, hmg_vec *v, hmg_vec *second, int64_t ncells_subset, const double *xi,
                   double *out);
 /* next_rhs!(b, x, implicit, ops): b = lambda*|J|*M*x  (src/examples/homogenized_coefficients.jl:695-713) */

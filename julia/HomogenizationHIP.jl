@@ -288,6 +288,12 @@ integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, o
 integrate_terms(vₖ::HipMatrix, vₖ₋₁::HipMatrix, implicit, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
     (bind!(vₖ.grid, ops); integrate(vₖ.grid, 1, vₖ, vₖ₋₁, length(subset)))
 integrate_area(g::HipGrid, v::HipMatrix, subset::AbstractUnitRange) = integrate(g, 2, v, nothing, length(subset))
+# The two pair forms behind the off-diagonal entries of the homogenized tensor (no counterpart in the reference; api.py has
+# the same two): Mq(v; w) = Σ |J| w⋅(M v), w may be v; Lq(v; s) = Σ |J| v⋅s with a load vector s such as rhs_aξ∇v!'s.
+integrate_pair_mass(v::HipMatrix, w::HipMatrix, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+    (bind!(v.grid, ops); integrate(v.grid, 3, v, w, length(subset)))
+integrate_pair_load(v::HipMatrix, s::HipMatrix, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+    (bind!(v.grid, ops); integrate(v.grid, 4, v, s, length(subset)))
 
 # ---- checkerboard_homogenization(n, ElT; refinements, smoothing_steps, tolerance, ξ, save, backend = :hip) -----------
 # The reference's loop (src/examples/homogenized_coefficients.jl:174-343) with HipMatrix states; mirrors driver.py.

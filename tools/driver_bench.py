@@ -2,7 +2,12 @@
 """Wall-clock of the whole driver to a tolerance: device path vs the CPU oracle, identical inputs.
   python tools/driver_bench.py --n 1 --dim 3 --refinements 4 --tolerance 1e-5 [--no-cpu] [--accelerate] [--contrast 100]
 --accelerate: the V-cycle preconditions a flexible CG iteration (driver.checkerboard_homogenization(accelerate=True)); the CPU
-oracle has the stationary iteration only, so --accelerate implies --no-cpu."""
+oracle has the stationary iteration only, so --accelerate implies --no-cpu.
+--tensor [--repeats R] [--warmup W]: the full homogenized tensor.  One run of driver.checkerboard_homogenization_tensor (d corrector
+solves, one setup) against the d (d + 1) / 2 runs of the scalar driver that polarising by hand takes (xi = e_i and
+(e_i + e_j) / sqrt 2), same field, same seed, in one process: W untimed rounds of both first (code objects, the pool of
+level-vector memory), then R timed rounds that alternate the two; wall clock around whole runs, each of which ends in a device
+synchronise.  Prints the times of every round, their medians, the ratio and the largest difference of the two tensors."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,11 +23,58 @@ ap.add_argument("--tolerance", type=float, default=1e-5)
 ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--accelerate", action="store_true")
 ap.add_argument("--contrast", type=float, default=9.0, help="sigma takes the values 1 and this")
+ap.add_argument("--tensor", action="store_true", help="one tensor run against d (d + 1) / 2 scalar runs")
+ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
 width = 2 * (driver.compute_box_radius(0, a.n) + driver.compute_boundary_layer(1.0, a.n))
 sgrid = driver.generate_conductivity(a.dim, width, 5, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
+if a.tensor:
+    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, seed=7, accelerate=a.accelerate)
+    E = np.eye(a.dim)
+    pairs = [(i, j) for i in range(a.dim) for j in range(i + 1, a.dim)]
+
+    def tensor_run():
+        tm = {}
+        t0 = time.perf_counter()
+        S, hist = driver.checkerboard_homogenization_tensor(a.n, tag, timings=tm, **kw)
+        ctx.sync()
+        return time.perf_counter() - t0, S, len(hist), tm
+
+    def scalar_runs():
+        S, cycles = np.zeros((a.dim, a.dim)), 0
+        t0 = time.perf_counter()
+        for i in range(a.dim):
+            S[i, i], h = driver.checkerboard_homogenization(a.n, tag, xi=E[i], **kw)
+            cycles += len(h)
+        for i, j in pairs:
+            q, h = driver.checkerboard_homogenization(a.n, tag, xi=(E[i] + E[j]) / np.sqrt(2.0), **kw)
+            S[i, j] = S[j, i] = q - 0.5 * (S[i, i] + S[j, j])
+            cycles += len(h)
+        ctx.sync()
+        return time.perf_counter() - t0, S, cycles
+
+    for _ in range(a.warmup):
+        tensor_run()
+        scalar_runs()
+    tt, ts = [], []
+    for _ in range(a.repeats):
+        t, S_t, cyc_t, tm = tensor_run()
+        tt.append(t)
+        t, S_s, cyc_s = scalar_runs()
+        ts.append(t)
+    print(json.dumps({"config": f"checkerboard_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, "
+                                f"tolerance={a.tolerance})", "width": width, "accelerate": a.accelerate, "contrast": a.contrast,
+                      "warmup": a.warmup, "repeats": a.repeats, "scalar_runs_per_round": a.dim + len(pairs),
+                      "wall_s_tensor": tt, "wall_s_scalar_runs": ts, "median_s_tensor": float(np.median(tt)),
+                      "median_s_scalar_runs": float(np.median(ts)), "ratio_scalar_over_tensor": float(np.median(ts) / np.median(tt)),
+                      "vcycles_tensor": cyc_t, "vcycles_scalar_runs": cyc_s, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
+                      "pair_integrals_s": tm["pair_integrals_s"], "outer_steps": tm["outer_steps"],
+                      "inexact_vcycles": tm["inexact_vcycles"], "Sigma": S_t.tolist(),
+                      "max_abs_diff_to_polarised": float(np.abs(S_t - S_s).max())}))
+    sys.exit(0)
 tm = {}
 t0 = time.perf_counter()
 sig, hist = driver.checkerboard_homogenization(a.n, tag, refinements=a.refinements, tolerance=a.tolerance, ctx=ctx,
