@@ -13,12 +13,7 @@
 // Everything a step does is enqueued on the context's stream; alpha and beta are formed on the device.
 #include "../../include/hmg.h"
 #include "hmg_fcg.hpp"
-#include "hmg_host.hpp"
-
-#include <stdexcept>
-#include <string>
-
-using namespace hmg;
+#include "hmg_objects.hpp"
 
 // (the handle crosses the C ABI as void *)
 struct hmg_fcg {
@@ -36,31 +31,6 @@ struct hmg_fcg {
 
 namespace {
 
-int fail(const std::exception &e)
-{
-    last_error() = e.what();
-    return 1;
-}
-
-#define FCG_TRY try {
-#define FCG_END                         \
-    }                                   \
-    catch (const std::exception &e)     \
-    {                                   \
-        return fail(e);                 \
-    }                                   \
-    catch (...)                         \
-    {                                   \
-        last_error() = "unknown error"; \
-        return 1;                       \
-    }                                   \
-    return 0;
-
-void need(bool c, const char *msg)
-{
-    if (!c) throw std::runtime_error(msg);
-}
-
 // a call of the C ABI from inside: its message is already in hmg_last_error
 void ok(int rc)
 {
@@ -70,11 +40,11 @@ void ok(int rc)
 FcgLaunch launch_of(hmg_fcg *f)
 {
     FcgLaunch F{};
-    F.stream = (hipStream_t)hmg_ctx_stream(f->ctx);
+    F.stream = f->ctx->stream;
     F.fs = f->scratch;
     F.fold = f->scratch + F_COUNT;
     F.part = f->scratch + F_COUNT + 512;
-    F.bank = (double *)hmg_ctx_scalar_bank(f->ctx);      // (asked for per call: hmg_ctx_set_scalar_bank may have moved it)
+    F.bank = f->ctx->L.scal;                             // (read per call: hmg_ctx_set_scalar_bank may have moved it)
     need(F.bank != nullptr, "the context has no scalar bank");
     return F;
 }
@@ -84,8 +54,12 @@ void release(hmg_fcg *f)
     if (f->p) (void)hmg_vec_destroy(f->p);
     if (f->q) (void)hmg_vec_destroy(f->q);
     if (f->R) (void)hmg_vec_destroy(f->R);
-    if (f->scratch) fcg_hook_free(f->ctx, f->scratch);
-    if (f->vec_bytes) fcg_hook_account(f->ctx, -3 * f->vec_bytes);
+    if (f->scratch) {                                    // (set after the context, as vec_bytes is)
+        LifetimeLock lock(lifetime_mutex());
+        (void)hipStreamSynchronize(f->ctx->stream);
+        (void)hipFree(f->scratch);
+        f->ctx->fcg_bytes -= 3 * f->vec_bytes;
+    }
     delete f;
 }
 
@@ -93,13 +67,13 @@ void check_states(hmg_fcg *f, hmg_vec **states)
 {
     need(states != nullptr, "null states");
     for (int l = 1; l <= f->level; ++l)
-        for (int k = 0; k < 5; ++k) (void)fcg_hook_vec(f->g, l, states[5 * (l - 1) + k], "states[]");
+        for (int k = 0; k < 5; ++k) check_vec(f->g, l, states[5 * (l - 1) + k], "states[]");
 }
 
 void need_current(hmg_fcg *f, const char *what)
 {
     if (!f->started) throw std::runtime_error(std::string(what) + ": hmg_fcg_start has not been called");
-    if (f->epoch != fcg_hook_epoch(f->g))
+    if (f->epoch != f->g->op_epoch)
         throw std::runtime_error(std::string(what) + ": the grid was shrunk or its operator or lambda changed since hmg_fcg_start; "
                                  "the residual and the direction belong to the old operator -- call hmg_fcg_start again");
 }
@@ -110,7 +84,7 @@ extern "C" {
 
 int hmg_fcg_create(hmg_grid *grid, int top_level, int steps, int steps_coarse, void **out)
 {
-    FCG_TRY
+    HMG_TRY
     need(grid && out, "null argument");
     need(top_level >= 1 && top_level <= hmg_grid_nlevels(grid), "top_level out of range");
     need(steps >= 0 && steps_coarse >= 0, "negative number of smoothing steps");
@@ -120,41 +94,48 @@ int hmg_fcg_create(hmg_grid *grid, int top_level, int steps, int steps_coarse, v
     f->steps = steps;
     f->steps_coarse = steps_coarse;
     try {
-        f->ctx = fcg_hook_ctx(grid);
-        const int64_t n = fcg_hook_len(grid, top_level);
+        const int64_t n = (int64_t)lev(grid, top_level).ld * grid->md.ncells;     // (lev: a host-only grid has no compute path)
+        f->ctx = grid->ctx;
         // p, q, R: from the context's pool of level-vector memory; a vector that does not fit is an error, there is no
         // form of the iteration without them
         ok(hmg_vec_create(grid, top_level, &f->p));
         ok(hmg_vec_create(grid, top_level, &f->q));
         ok(hmg_vec_create(grid, top_level, &f->R));
         f->nb_cap = fcg_blocks(n);
-        f->scratch = fcg_hook_alloc(f->ctx, (size_t)(F_COUNT + 512 + 2 * f->nb_cap));
+        const size_t sbytes = sizeof(double) * (size_t)(F_COUNT + 512 + 2 * f->nb_cap);
+        HIPCHK(hipSetDevice(f->ctx->device));
+        hipError_t e = device_malloc((void **)&f->scratch, sbytes);
+        if (e != hipSuccess)
+            throw std::runtime_error(std::string("hipMalloc of the reduction scratch (") + std::to_string(sbytes >> 10) +
+                                     " KiB) failed: " + hipGetErrorString(e));
+        HIPCHK(hipMemsetAsync(f->scratch, 0, sbytes, f->ctx->stream));
         f->vec_bytes = (int64_t)sizeof(double) * n;
-        fcg_hook_account(f->ctx, 3 * f->vec_bytes);
+        LifetimeLock lock(lifetime_mutex());
+        f->ctx->fcg_bytes += 3 * f->vec_bytes;
     } catch (const std::exception &e) {
         const std::string why = e.what();
         release(f);
         throw std::runtime_error("hmg_fcg_create: " + why);
     }
     *out = f;
-    FCG_END
+    HMG_END
 }
 
 int hmg_fcg_destroy(void *handle)
 {
-    FCG_TRY
+    HMG_TRY
     hmg_fcg *fcg = (hmg_fcg *)handle;
     if (fcg && --fcg->refs <= 0) release(fcg);
-    FCG_END
+    HMG_END
 }
 
 int hmg_fcg_start(void *handle, hmg_vec *x, hmg_vec *b, hmg_vec **states)
 {
-    FCG_TRY
+    HMG_TRY
     hmg_fcg *f = (hmg_fcg *)handle;
     need(f && x && b, "null argument");
     check_states(f, states);
-    const int64_t n = fcg_hook_len(f->g, f->level);
+    const int64_t n = vec_len(f->R);
     need(fcg_blocks(n) <= f->nb_cap, "the grid has grown since hmg_fcg_create");
     hmg_vec **top = states + 5 * (f->level - 1);
     for (int k = 0; k < 5; ++k)
@@ -162,52 +143,54 @@ int hmg_fcg_start(void *handle, hmg_vec *x, hmg_vec *b, hmg_vec **states)
     f->started = false;
     ok(hmg_apply_ex(f->g, f->level, -1.0, x, b, f->R, 1));      // R = b - A_loc x, Dirichlet rows zeroed
     f->have_dir = false;
-    f->epoch = fcg_hook_epoch(f->g);
+    f->epoch = f->g->op_epoch;
     f->started = true;
-    FCG_END
+    HMG_END
 }
 
 int hmg_fcg_step(void *handle, hmg_vec *x, hmg_vec **states)
 {
-    FCG_TRY
+    HMG_TRY
     hmg_fcg *f = (hmg_fcg *)handle;
     need(f && x, "null argument");
     need_current(f, "hmg_fcg_step");
     check_states(f, states);
-    const int64_t n = fcg_hook_len(f->g, f->level);
-    double *xd = fcg_hook_vec(f->g, f->level, x, "x");
+    const int64_t n = vec_len(f->R);
+    check_vec(f->g, f->level, x, "x");
     hmg_vec **top = states + 5 * (f->level - 1);
     for (int k = 0; k < 5; ++k) need(x != top[k], "x must not be one of the top level's state vectors");
-    double *pd = fcg_hook_vec(f->g, f->level, f->p, "p"), *qd = fcg_hook_vec(f->g, f->level, f->q, "q"),
-           *Rd = fcg_hook_vec(f->g, f->level, f->R, "R");
+    check_vec(f->g, f->level, f->p, "p");
+    check_vec(f->g, f->level, f->q, "q");
+    check_vec(f->g, f->level, f->R, "R");
+    double *xd = x->d, *pd = f->p->d, *qd = f->q->d, *Rd = f->R->d;
     // z = V(0, R): the V-cycle takes R where the top level's b stands (the handle, not a copy) and leaves z in the top level's x
     hmg_vec *b_keep = top[1];
     top[1] = f->R;
     try {
-        fcg_hook_vcycle_zero(f->g, f->level, f->steps, f->steps_coarse, states);
+        vcycle(f->g, f->level, f->steps, f->steps_coarse, states, /*top=*/true, /*zero_guess=*/true);
     } catch (...) {
         top[1] = b_keep;
         throw;
     }
     top[1] = b_keep;
-    const double *zd = fcg_hook_vec(f->g, f->level, top[0], "states[]");   // (after the V-cycle: it may exchange r and p)
+    const double *zd = top[0]->d;                        // (read after the V-cycle, which exchanges device pointers of handles)
     const FcgLaunch F = launch_of(f);
     if (f->have_dir) {
         launch_fcg_dot_zq(F, zd, qd, n);
-        fcg_hook_scalar_sum(f->g, FB_ZQ, 1);
+        scalar_sum(f->g, FB_ZQ, 1);
     }
     launch_fcg_direction(F, pd, zd, n, f->have_dir ? 0 : 1);
     f->have_dir = true;
     ok(hmg_apply_ex(f->g, f->level, 1.0, f->p, nullptr, f->q, 1));          // q = A_loc p, Dirichlet rows zeroed
     launch_fcg_dots_pq_pr(F, pd, qd, Rd, n);
-    fcg_hook_scalar_sum(f->g, FB_PQ, 2);
+    scalar_sum(f->g, FB_PQ, 2);
     launch_fcg_update(F, xd, Rd, pd, qd, n);
-    FCG_END
+    HMG_END
 }
 
 int hmg_fcg_residual_norm(void *handle, hmg_vec **states, double *norm)
 {
-    FCG_TRY
+    HMG_TRY
     hmg_fcg *f = (hmg_fcg *)handle;
     need(f && norm, "null argument");
     need_current(f, "hmg_fcg_residual_norm");
@@ -216,23 +199,23 @@ int hmg_fcg_residual_norm(void *handle, hmg_vec **states, double *norm)
     ok(hmg_vec_copy(r, f->R));
     ok(hmg_interface_sum(f->g, f->level, r));
     ok(hmg_vec_norm_unique(r, norm));
-    FCG_END
+    HMG_END
 }
 
 int hmg_fcg_scalars(void *handle, double *out)
 {
-    FCG_TRY
+    HMG_TRY
     hmg_fcg *f = (hmg_fcg *)handle;
     need(f && out, "null argument");
     double h[F_COUNT];
-    if (hipMemcpyAsync(h, f->scratch, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)hmg_ctx_stream(f->ctx)) != hipSuccess)
+    if (hipMemcpyAsync(h, f->scratch, sizeof(h), hipMemcpyDeviceToHost, f->ctx->stream) != hipSuccess)
         throw std::runtime_error("hmg_fcg_scalars: copy from the device failed");
     ok(hmg_ctx_sync(f->ctx));
     out[0] = h[F_ALPHA];
     out[1] = h[F_BETA];
     out[2] = h[F_PQ];
     out[3] = h[F_PR];
-    FCG_END
+    HMG_END
 }
 
 hmg_vec *hmg_fcg_vec(void *handle, int which)

@@ -1,14 +1,10 @@
 // Flexible CG with one retained direction, preconditioned by the V-cycle (include/hmg.h: hmg_fcg_*): what its host module
-// (hmg_fcg.cpp), its kernels (hmg_fcg.hip) and the hooks it needs inside hmg_capi.cpp share.
+// (hmg_fcg.cpp) and its kernels (hmg_fcg.hip) share.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-
-struct hmg_ctx;
-struct hmg_grid;
-struct hmg_vec;
 
 namespace hmg {
 
@@ -37,22 +33,5 @@ void launch_fcg_direction(const FcgLaunch &F, double *p, const double *z, int64_
 void launch_fcg_dots_pq_pr(const FcgLaunch &F, const double *p, const double *q, const double *R, int64_t n);
 // alpha = bank[FB_PR] / bank[FB_PQ]; x += alpha p; R -= alpha q; fs[F_ALPHA, F_PQ, F_PR] = alpha, p.q, p.R
 void launch_fcg_update(const FcgLaunch &F, double *x, double *R, const double *p, const double *q, int64_t n);
-
-// ---- hooks into hmg_capi.cpp (they throw std::runtime_error) ---------------------------------------------------------
-hmg_ctx *fcg_hook_ctx(hmg_grid *g);
-// v is a level vector of this grid and level that holds the grid's current cells; returns its device pointer
-double *fcg_hook_vec(const hmg_grid *g, int level, const hmg_vec *v, const char *name);
-int64_t fcg_hook_len(const hmg_grid *g, int level);          // ld * current cells
-// counts the operators this grid has had: hmg_grid_set_operator, hmg_grid_set_lambda and hmg_grid_shrink each add one
-uint64_t fcg_hook_epoch(const hmg_grid *g);
-// hmg_vcycle on a zero initial guess: where the smoother's form lets the top level be entered with a zero that is never written
-// (zero_entry_ok) it is, otherwise x is filled first -- the same bits either way
-void fcg_hook_vcycle_zero(hmg_grid *g, int top_level, int steps, int steps_coarse, hmg_vec **states);
-// sum over the ranks of bank[slot .. slot + count) through the grid's scalar_sum hook (nothing on an unpartitioned grid)
-void fcg_hook_scalar_sum(hmg_grid *g, int slot, int count);
-// device memory of count doubles, zero-filled on the context's stream (counted by "device_allocs"); throws if it is not there
-double *fcg_hook_alloc(hmg_ctx *c, size_t count);
-void fcg_hook_free(hmg_ctx *c, double *p);
-void fcg_hook_account(hmg_ctx *c, int64_t fcg_bytes_delta);   // hmg_ctx_counter "fcg_bytes"
 
 }  // namespace hmg

@@ -1,5 +1,5 @@
 // Addressing tables of the apply and transfer kernels, derived on the host from the reference tables (LevelTables) and the
-// base mesh (MeshTables).  No device here: hmg_capi.cpp uploads what these builders return, as it is.
+// base mesh (MeshTables).  No device here: hmg_upload.cpp uploads what these builders return, as it is.
 #include "hmg_device.hpp"
 #include "hmg_host.hpp"
 

@@ -1,0 +1,419 @@
+// What the host modules of libhmg_hip.so share: the objects behind the handles of include/hmg.h and the functions that cross
+// a module boundary, each declared once.  Internal: only .cpp files include it (no kernel file does).
+//
+//   hmg_context.cpp  lifetimes of contexts, grids and vectors, device memory and the level-vector pool, options, counters
+//   hmg_upload.cpp   grid creation: kernel tables to the device (or, on a host-only grid, into the checksum), operator, queries
+//   hmg_smooth.cpp   operator apply with its sums, CG smoother, V-cycle, placement tuner
+//   hmg_coarse.cpp   level-1 system, its PCG and the probes budgeted solves leave behind
+//   hmg_comm.cpp     cut exchange, the RCCL communicator and the exchange settings of a grid
+//   hmg_fcg.cpp      flexible CG around the V-cycle
+//   hmg_capi.cpp     vector operations, primitives, right-hand sides, integrals: argument checks and one call each
+//
+// Every extern "C" entry point lives in the module it fronts; hmg_capi.cpp keeps those that front none.
+#pragma once
+
+#include "../../include/hmg.h"
+#include "hmg_device.hpp"
+#include "hmg_host.hpp"
+
+#include <atomic>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+struct ncclComm;        // (<rccl/rccl.h> is hmg_comm.cpp's alone)
+
+using namespace hmg;    // (as every host module does)
+
+#define HIPCHK(expr)                                                                            \
+    do {                                                                                        \
+        hipError_t _e = (expr);                                                                 \
+        if (_e != hipSuccess)                                                                   \
+            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(_e) + " (" #expr ")"); \
+    } while (0)
+
+namespace hmg {
+
+// Handles may be destroyed from another thread than the one that computes (finalizers of a garbage-collected host: Julia
+// runs them where it likes, Python's weakref.finalize on the collecting thread): reference counts, the registry of live
+// contexts and the pooled level-vector blocks are guarded by this lock.  (Recursive: a failed allocation inside a guarded
+// region hands the pools back.)  Everything else on one context is for one host thread at a time (include/hmg.h).
+std::recursive_mutex &lifetime_mutex();
+using LifetimeLock = std::lock_guard<std::recursive_mutex>;
+
+// Device / pinned allocations the library has made so far (hmg_ctx_counter "device_allocs"): after setup -- grid, operator, level-1
+// system, level vectors -- a V-cycle makes none (tests/test_gpu_parity.py::test_no_allocation_inside_a_vcycle).
+std::atomic<int64_t> &device_allocs();
+
+// hipMalloc; when it fails, every live context hands its pooled level-vector blocks back (they may be what is in the way) and
+// it is tried once more.  Counts the allocation; on failure *p stays null and the second attempt's error is returned -- the
+// caller says what could not be had.
+hipError_t device_malloc(void **p, size_t bytes);
+
+// Host-only grids (hmg_grid_create with a NULL context: table queries, and the CPU sanitizer job of tests/test_sanitizers.py)
+// run every table builder as a device grid does; inside a DryUploads scope the uploads keep a running checksum of what WOULD have
+// gone to the device instead of touching the HIP runtime (hmg_grid_table_i32 "upload_hash": the same mesh must give the same
+// tables whatever the allocator hands out -- an uninitialised read shows up as a checksum that moves with ASan's malloc fill).
+struct DryUploads {
+    static DryUploads *&current()
+    {
+        static thread_local DryUploads *c = nullptr;
+        return c;
+    }
+    bool dry;
+    uint64_t *hash;
+    DryUploads *prev;
+    DryUploads(bool dry_, uint64_t *hash_) : dry(dry_), hash(hash_), prev(current()) { current() = this; }
+    ~DryUploads() { current() = prev; }
+    DryUploads(const DryUploads &) = delete;
+    DryUploads &operator=(const DryUploads &) = delete;
+    static bool active() { return current() && current()->dry; }
+    static void note(const void *data, size_t bytes)
+    {
+        uint64_t h = *current()->hash ^ (bytes * 0x9e3779b97f4a7c15ull);
+        const unsigned char *b = (const unsigned char *)data;
+        for (size_t i = 0; i < bytes; ++i) h = (h ^ b[i]) * 1099511628211ull;
+        *current()->hash = h;
+    }
+};
+
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    void alloc(size_t count)
+    {
+        release();
+        n = count;
+        if (!count || DryUploads::active()) return;
+        HIPCHK(device_malloc((void **)&p, count * sizeof(T)));
+    }
+    void upload(const std::vector<T> &h, hipStream_t s)
+    {
+        alloc(h.size());
+        if (DryUploads::active()) {
+            DryUploads::note(h.data(), h.size() * sizeof(T));
+            return;
+        }
+        if (!h.empty()) {
+            HIPCHK(hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    }
+};
+
+struct LevelBufs {
+    DevBuf<uint64_t> meta;
+    DevBuf<uint16_t> lpos, sweep_slot;
+    DevBuf<int> slab_head, slab_rs_head;
+    DevBuf<uint32_t> slab_ld_word, slab_cp_word, slab_rs_word;
+    DevBuf<uint16_t> slab_cp_slot, slab_rs_slot;
+    DevBuf<double> rtab;   // restriction weights in class-table layout (slab levels)
+    int nslab = 0, slab_lds_nodes = 0, slab_max_surf = 0, slab_rs_max_surf = 0, slab_max_int = 0, slab_rs_max_int = 0;
+    DevBuf<uint32_t> pos32, pos32w, sweep32, par32, blk_word;
+    DevBuf<uint64_t> par64;
+    DevBuf<uint16_t> clpos;
+    DevBuf<uint32_t> rs_word;
+    DevBuf<double> rs_w;
+    DevBuf<uint16_t> rs_lp;
+    DevBuf<uint16_t> blk_slot;
+    // one-wave-per-cell apply of level 5 (k_apply_wave): per-lane tables + the class-weight cache of the current operator
+    DevBuf<uint32_t> wave_tab, wave_lpos, wave_par, wave_cl, wave_rs;
+    DevBuf<double> wcache;
+    DevBuf<double> ctab;
+    DevBuf<int32_t> hier2slot, par_a, par_b, rptr, ridx;
+    DevBuf<double> dphi;
+};
+
+struct CutKind {
+    int64_t nglobal = 0;
+    int64_t nentries = 0;
+    std::vector<int64_t> gid;                    // host: global cut id of every local copy
+    std::vector<int32_t> seg;                    // host: segment / index inside it (sharers-only exchange), may be empty
+    std::vector<int64_t> sidx;
+    DevBuf<int32_t> cell_lid;
+    DevBuf<uint8_t> first;
+};
+
+// Exchange-buffer layout of one level (built at the first exchange on that level).
+//   global layout (all-reduce over every rank): [faces | edges | nodes], a run per GLOBAL cut id -- identical on all ranks;
+//   segment layout (exchange among the sharers only): this rank's segments one after the other, inside a segment faces,
+//   edges, nodes -- a segment has the same length and order on each of its members.
+struct CutLevel {
+    bool ready = false;
+    DevBuf<int64_t> pos[3];                      // per local cut copy: first buffer position of its run
+    int64_t ndoubles = 0;                        // buffer positions used on this level
+    // segment layout only:
+    std::vector<int64_t> ops;                    // messages, 4 numbers each: peer rank, buffer offset, count, stage offset
+    int64_t nstage = 0;                          // staging doubles (the peers' partial segments land there)
+    DevBuf<int64_t> plan;                        // k_seg_sum: nseg, then per segment off, size, nmembers, mtab offset; then mtab
+};
+
+struct ApplyTimer {
+    bool on = false;
+    int min_level = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    std::vector<int> ev_level;          // per used event pair: the level of the launch and its algorithmic bytes
+    std::vector<double> ev_bytes;
+    size_t used = 0;
+};
+
+// state of the last coarse solve, copied to pinned host memory behind the solve and read when somebody asks
+struct CoarseProbe {
+    double *h = nullptr;            // pinned: S_DONE, S_ITER, S_CRR, b.b
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    int budget = 0;                 // iterations launched by the solve the probe belongs to
+    int generation = 0;             // the level-1 matrix (hmg_grid::coarse_generation) that solve used
+};
+
+}  // namespace hmg
+
+// Lifetimes: a vector keeps its grid alive, a grid its context (reference counts, single host thread): hmg_*_destroy
+// hands the caller's reference back, the object goes when the last dependant has gone -- the order in which a host
+// (finalizers of a garbage-collected language in particular) destroys handles does not matter.
+struct hmg_ctx {
+    int refs = 1;
+    ApplyTimer timer;
+    bool fuse_cg_default = true;
+    bool fold_x = true;   // V-cycle: pre-smoother's last x-update rides with the local residual
+    bool swap_rp = true;  // V-cycle: step 0 of a smoother takes r itself as p (pointer exchange), see smooth_form()
+    bool fold_prolong = true;   // V-cycle: prolongation folded into the post-smoother's first residual
+    bool lazy_dead = true;      // V-cycle: the pre-smoother's dead last step writes nothing (see smooth_form())
+    bool fold_faces = true;     // fused CG: the face part of Ap's interface sum rides in the r-update (all steps but a live last one)
+    bool lean_post = true;      // V-cycle: the post-smoother's dead tail is dropped too (see smooth_form())
+    bool lazy_post = true;      // ... and below the finest level its dead last step writes nothing: both x-updates in one pass
+    int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
+    bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
+    bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
+    bool prolong_in_image = true;  // folded prolongation, level 6: the coarse column is staged at the even nodes of the lattice image
+                                   // instead of in LDS of its own behind it (three workgroups per CU stay resident)
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    DevBuf<double> partials, scal, rpart;
+    Launch L{};
+    int coarse_maxit = 5000;
+    int coarse_check = 25;
+    bool coarse_probe = true;   // budgeted level-1 solves leave a probe behind (off: stream-capture experiments)
+    double coarse_rtol = 1e-13;
+    int coarse_poly = 4;            // level-1 PCG: Chebyshev iterates per preconditioner application (1 = plain Jacobi)
+    double coarse_poly_ratio = 20.0;   // ... on the interval [lmax / ratio, lmax] of D^-1 A, lmax = its Gershgorin bound
+    // in-library communicator (one rank per GPU, RCCL over xGMI): hmg_comm_init
+    ncclComm *comm = nullptr;
+    int comm_nranks = 1, comm_rank = 0;
+    hipStream_t comm_stream = nullptr;       // the overlapped cut exchange runs here
+    hipEvent_t ev_packed = nullptr, ev_summed = nullptr;
+    int64_t comm_calls = 0, comm_doubles = 0;
+    int64_t small_launches = 0;              // launches of the pipelined small-level apply
+    int64_t wave_launches = 0;               // launches of the one-wave-per-cell apply (hmg_ctx_counter)
+    int64_t slab2_launches = 0;              // launches of the role-split slab apply (hmg_apply_slab.hip)
+    int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
+    int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
+    int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
+    int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
+    // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
+    // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB
+    // 0.001 s fresh, 2.05 s after a hipFree), i.e. 1.9 s of the 71 GB a second driver call allocates.
+    bool vec_pool_on = true;
+    std::vector<std::pair<size_t, void *>> vec_pool;
+    // rehearsal on fewer GPUs than the partition is meant for: a grid that holds rank r's share of an N-rank partition
+    // may use a communicator of another size (the neighbours' contributions are then simply missing from the sums --
+    // the work per rank, the message sizes and the stream choreography are the real ones, the numbers are not)
+    bool comm_rehearsal = false;
+    int64_t overlap_min_doubles = 524288;   // levels whose GLOBAL cut is below 4 MiB (about 1 MiB per rank at octants) are
+                                            // exchanged in the plain form (see apply_then_sum)
+    // grids of this context whose last budgeted level-1 solve still has its probe in flight: judged at the next call that
+    // synchronises the stream anyway (norms, dot products, integrals, hmg_ctx_sync, downloads)
+    std::vector<struct hmg_grid *> probe_grids;
+};
+
+struct hmg_grid {
+    int refs = 1;
+    hmg_ctx *ctx = nullptr;
+    int dim = 0, nlevels = 0;
+    std::vector<LevelTables> lt;
+    std::vector<std::unique_ptr<LevelBufs>> lb;
+    std::vector<LevelDev> ld;
+    MeshTables mesh_full, mesh;
+    bool shrunk = false;
+    MeshDev md{};
+    DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
+    DevBuf<uint16_t> d_dmask, d_dupmask;
+    DevBuf<uint8_t> d_mult;
+    DevBuf<double> d_blockpart;
+    bool fuse_cg = true;
+    DevBuf<double> d_coef;
+    std::vector<double> sigma, coef;
+    // class-weight cache (k_apply_wave): cells with bitwise equal coefficient rows share a class
+    DevBuf<int32_t> d_cell_class;
+    DevBuf<double> d_coef_rep;
+    int nclasses = 0;
+    double wc_lambda = 0.0;
+    bool wc_ready = false;
+    double lambda = 0.0;
+    bool has_op = false;
+    uint64_t op_epoch = 0;                       // operators this grid has had (new sigma, new lambda, domain shrink): what an
+                                                 // hmg_fcg object compares its residual's operator with
+    // coarse system
+    CoarseMatrix cm;
+    CoarseDev cd{};
+    bool coarse_ready = false;
+    DevBuf<int32_t> c_rowptr, c_colidx, c_interior;
+    DevBuf<double> c_val, c_diag, c_b, c_x, c_r, c_z, c_p, c_q, c_u, c_z2, c_d;   // (c_z2, c_d: Chebyshev preconditioner)
+    DevBuf<double> top_spare;           // second direction vector of the finest level's post-smoother (smooth(), lazy_top = 2)
+    bool top_spare_refused = false;
+    double c_lmax = 2.0;                         // Gershgorin bound of D^-1 A of the level-1 matrix
+    int coarse_last_it = 0;
+    int coarse_budget = 0;                       // iterations a solve enqueues blindly (0: not known yet)
+    int coarse_generation = 0;                   // counts the level-1 matrices assembled for this grid
+    int64_t coarse_misses = 0;                   // budgeted solves that ran out of iterations (each one was reported or, with a
+                                                 // new matrix in between, only counted)
+    std::unique_ptr<CoarseProbe> probe{new CoarseProbe};
+    // multi-GPU
+    std::unique_ptr<Partition> part;
+    std::vector<double> sigma_global;
+    // inputs of the partition analysis, kept for a domain shrink (re-analysis of the prefix mesh)
+    std::vector<double> part_coords;
+    std::vector<int64_t> part_cells;
+    std::vector<int32_t> part_owner, part_cut_owner;     // (part_cut_owner: rehearsal partitions only, else empty)
+    bool part_halo = true;                               // partition analysis on this rank's cells + one-cell halo (see create_grid)
+    int64_t part_nnodes = 0, part_ncells = 0;
+    DevBuf<int32_t> d_nodes_g, d_owned, d_cells_gnode;
+    CutKind cut[3];   // faces, edges, nodes
+    // Number of cut entities per kind OVER ALL RANKS, agreed once per partition analysis (agree_on_cut): what the overlap
+    // decision of apply_then_sum looks at.  (CutKind::nglobal is rank-local after a halo-only analysis.)  -1: no agreement
+    // possible (no scalar_sum callback) -- the plain form everywhere.
+    int64_t cut_agreed[3] = {0, 0, 0};
+    bool cut_agreed_ready = false;
+    std::vector<std::unique_ptr<CutLevel>> cutlv;   // [nlevels]
+    bool sharers = false;                        // exchange among the sharers of each cut entity (segments) instead of one
+                                                 // all-reduce over the global cut buffer; needs a p2p transport (below)
+    hmg_exchange_fn exchange = nullptr, scalar_sum = nullptr;
+    hmg_exchange_fn ex_begin = nullptr;          // asynchronous form: begin issues the sum, end waits for it
+    int (*ex_end)(void *) = nullptr;
+    hmg_p2p_fn p2p = nullptr, p2p_begin = nullptr;   // segment layout: the messages of one exchange (sync / begin; ex_end ends it)
+    double *stage = nullptr;
+    int64_t stage_cap = 0;
+    DevBuf<double> own_stage;
+    bool overlap = true;
+    DevBuf<int32_t> d_cells_cut, d_cells_inner, d_cell_perm;
+    void *ex_user = nullptr;
+    double *ex_buf = nullptr;
+    int64_t ex_cap = 0;
+    DevBuf<double> own_exbuf;                    // hmg_grid_use_comm: library-owned exchange buffer
+
+    uint64_t upload_hash = 1469598103934665603ull;   // host-only grids: checksum of every table a device grid would upload (DryUploads)
+
+    const MeshTables &cur() const { return shrunk ? mesh : mesh_full; }
+};
+
+struct hmg_vec {
+    hmg_grid *g = nullptr;
+    int level = 0;
+    double *d = nullptr;
+    bool own = false;
+    int64_t alloc_cells = 0;
+    size_t bytes = 0;        // own: size of the allocation behind d
+};
+
+namespace hmg {
+
+inline int fail(const std::exception &e)
+{
+    last_error() = e.what();
+    return 1;
+}
+
+#define HMG_TRY try {
+#define HMG_END                      \
+    }                                \
+    catch (const std::exception &e)  \
+    {                                \
+        return fail(e);              \
+    }                                \
+    catch (...)                      \
+    {                                \
+        last_error() = "unknown error"; \
+        return 1;                    \
+    }                                \
+    return 0;
+
+inline void need(bool c, const char *msg)
+{
+    if (!c) throw std::runtime_error(msg);
+}
+
+inline const LevelDev &lev(const hmg_grid *g, int level)
+{
+    need(g != nullptr, "null grid");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    need(level >= 1 && level <= g->nlevels, "level out of range");
+    return g->ld[level - 1];
+}
+
+inline void check_vec(const hmg_grid *g, int level, const hmg_vec *v, const char *name)
+{
+    if (!v) throw std::runtime_error(std::string("null vector: ") + name);
+    if (v->g != g) throw std::runtime_error(std::string("vector belongs to another grid: ") + name);
+    if (v->level != level) throw std::runtime_error(std::string("vector has the wrong level: ") + name);
+    if (v->alloc_cells < g->md.ncells) throw std::runtime_error(std::string("vector too small: ") + name);
+}
+
+inline int64_t vec_len(const hmg_vec *v) { return (int64_t)v->g->ld[v->level - 1].ld * v->g->md.ncells; }
+
+inline bool has_exchange(const hmg_grid *g) { return g->exchange || g->ex_begin || g->p2p || g->p2p_begin; }
+
+// ---- hmg_context.cpp ----
+// zero-filled device memory for one level vector, from the context's pool where it has a block of that size
+double *vec_alloc(hmg_ctx *c, size_t bytes);
+void grid_unref(hmg_grid *grid);
+// scal[slot] on the host: synchronises the stream, so the pending probes are judged as well
+double read_scalar(hmg_ctx *c, int slot);
+
+// ---- hmg_upload.cpp ----
+// (re)forms the class-weight cache when the operator or lambda has changed; called in front of every apply
+void ensure_weight_cache(hmg_grid *g);
+
+// ---- hmg_smooth.cpp ----
+void set_slab(hmg_grid *g, const LevelDev &lv);
+// out = (src ? src : 0) + alpha * A x, cell-local (no interface sum); mask: the Dirichlet constraint
+void apply(hmg_grid *g, const LevelDev &lv, double alpha, const double *x, const double *src, double *out, int mask);
+void restrict_level(hmg_grid *g, int level_fine, const double *rf, double *bc);
+void interface_sum(hmg_grid *g, const LevelDev &lv, double *x, bool faces = true);
+// sum over the ranks of scal[slot .. slot + count) through the grid's scalar_sum callback (nothing on an unpartitioned grid)
+void scalar_sum(hmg_grid *g, int slot, int count);
+bool reserve_top_spare(hmg_grid *g, bool must);
+void release_top_spare(hmg_grid *g);
+bool wants_top_spare(const hmg_grid *g, int level);
+// zero_guess (top level only; below it always holds): x is to be taken as zero whatever it holds -- never written where the
+// smoother's form allows that (zero_entry_ok), filled first otherwise: the same bits either way
+void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top = true, bool zero_guess = false);
+
+// ---- hmg_coarse.cpp ----
+void coarse_solve(hmg_grid *g, hmg_vec *b1, hmg_vec *x1);
+void probe_unlist(hmg_grid *g);
+void judge_probes(hmg_ctx *c);
+
+// ---- hmg_comm.cpp ----
+void exchange_cut(hmg_grid *g, const LevelDev &lv, double *x);
+void cut_pack(hmg_grid *g, const LevelDev &lv, double *x, int unpack);
+void exchange_prepare(hmg_grid *g, const LevelDev &lv);
+void exchange_run(hmg_grid *g, const LevelDev &lv, bool async);
+void exchange_finish(hmg_grid *g, const LevelDev &lv, bool async);
+// communicator, second stream and events of a context go (errors ignored: the context is on its way out, or they were checked)
+void comm_drop(hmg_ctx *c);
+
+}  // namespace hmg

@@ -5,7 +5,7 @@ The HOST code of every source file is instrumented (`make asan tsan` in csrc: Ad
 ThreadSanitizer; the device code is compiled as always), and tools/sanitize/host_tables.c drives everything that runs on the host
 before and between kernel launches -- mesh synthesis, the table builders of hmg_grid_create, operator coefficients and cell
 classes, the level-1 assembly, the domain shrink, the partition analysis of every rank -- through the C ABI with a NULL context:
-the uploads are checksummed instead of sent (DryUploads, csrc/hmg_capi.cpp).  No GPU is touched: sanitizers are for the CPU
+the uploads are checksummed instead of sent (DryUploads, csrc/hmg_objects.hpp).  No GPU is touched: sanitizers are for the CPU
 build box only.
 
 Checked: no sanitizer report, and the checksums of the would-be device tables are the same for 1 / 3 / 16 setup threads and for

@@ -2,7 +2,7 @@
 # Per-launch durations, algorithmic bytes and TB/s of the level-7 operator-apply launches of the last V-cycle of a bench run at
 # BASELINE config 5's per-GPU share (rocprofv3 kernel trace; 24 576 cells x 47 905 nodes = 1.177e9 DOFs, sigma in {1, 100}).
 # $1 = output tag under gpurun_out/, EXTRA_OPTIONS = context options of the run ("apply_slab2=0": k_apply_slab of rounds 3-4).
-# Launch order inside hmg_vcycle on the finest level (three CG steps, every exact saving on; csrc/hmg_capi.cpp smooth()):
+# Launch order inside hmg_vcycle on the finest level (three CG steps, every exact saving on; csrc/hmg_smooth.cpp smooth()):
 #   pre-smoother : residual (x, b in; r out: 24 B/DOF) | step 0 (r is p: r in, Ap out: 16) | step 1 (r, p, x in; p, x, Ap out: 48) |
 #                  dead last step (r, p in: 16) | local residual with both pending x-updates (x, p, r, b in; x, r out: 48)
 #   [restriction through the window: its own pass, k_apply_slab<3,1024,false>: 8 + 1.1]  [prolongation: k_prolong_add_big: 17.1]

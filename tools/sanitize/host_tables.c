@@ -1,7 +1,7 @@
 /*
  * host_tables.c -- every HOST code path behind the C ABI that runs before (and between) the first kernel launches, driven without a
  * GPU: mesh synthesis, the table builders of hmg_grid_create (NULL context: the uploads are checksummed instead of sent, see
- * DryUploads in csrc/hmg_capi.cpp), operator coefficients + cell classes, level-1 assembly, the domain shrink, and the partition
+ * DryUploads in csrc/hmg_objects.hpp), operator coefficients + cell classes, level-1 assembly, the domain shrink, and the partition
  * analysis (halo and global form) of every rank.  Built against the AddressSanitizer / UBSan / ThreadSanitizer builds of the
  * library by tests/test_sanitizers.py (`make -C homogenization.jl_amd/csrc asan tsan`), run with HMG_SETUP_THREADS = 1 / 3 / 16.
  *
