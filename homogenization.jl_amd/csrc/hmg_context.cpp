@@ -249,6 +249,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "spare_bytes") return ctx->spare_bytes;
     if (n == "fcg_bytes") return ctx->fcg_bytes;
     if (n == "lazy_top_form") return ctx->last_top_form;
+    if (n == "lazy_pre_form") return ctx->last_pre_form;
+    if (n == "coarse_x_folds") return ctx->coarse_x_folds;
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
     return -1;
 }
@@ -270,7 +272,7 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
     static const std::pair<const char *, bool hmg_ctx::*> flags[] = {
         {"coarse_probe", &hmg_ctx::coarse_probe}, {"fuse_cg", &hmg_ctx::fuse_cg_default}, {"fold_x", &hmg_ctx::fold_x},
         {"swap_rp", &hmg_ctx::swap_rp}, {"fold_prolong", &hmg_ctx::fold_prolong}, {"zero_entry", &hmg_ctx::zero_entry},
-        {"fold_restrict", &hmg_ctx::fold_restrict}, {"lazy_dead", &hmg_ctx::lazy_dead}, {"fold_faces", &hmg_ctx::fold_faces},
+        {"fold_restrict", &hmg_ctx::fold_restrict}, {"lazy_dead", &hmg_ctx::lazy_dead}, {"lazy_pre", &hmg_ctx::lazy_pre}, {"fold_coarse_x", &hmg_ctx::fold_coarse_x}, {"fold_faces", &hmg_ctx::fold_faces},
         {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
         {"comm_rehearsal", &hmg_ctx::comm_rehearsal}};
     for (const auto &f : flags)

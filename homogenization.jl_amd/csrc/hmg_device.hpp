@@ -138,8 +138,14 @@ struct ApplyArgs {
     int a_num, a_den;
     const double *x3;      // optional (k_apply FUSED, with x2, without xacc): xin = (x + ax*x2) + c*(x3 + beta*x2),
     int c_num, c_den;      //   ax = scal[a_num]/scal[a_den], c = scal[c_num]/scal[c_den]: two CG x-updates at once
+    const double *x4;      // optional (x3 mode of the register-blocked k_apply that restricts in its epilogue -- apply_defers3() -- only):
+    int d_num, d_den;      //   x + (scal[d_num]/scal[d_den]) * x4 takes the place of x, a third x-update in front of the two.  Every
+                           //   other kernel family (k_apply_wave, k_apply_small, k_apply_slab / _slab2, k_apply_rows) refuses it
     const double *xcoarse; // optional (fused kernel, not the slab one): xin = x + P xcoarse first (prolongation of the
     int64_t ldc;           //   coarse-grid correction; column stride ldc), written back through xout
+    const double *xc_p, *xc_r;   // optional (with xcoarse and flags bit 6, register-blocked k_apply -- apply_folds_coarse_x() -- only): the
+                           //   coarse column is (xcoarse + (scal[a_num]/scal[a_den]) xc_p) + (scal[c_num]/scal[c_den]) (xc_r +
+                           //   (scal[s_num]/scal[s_den]) xc_p), the coarser level's last two CG x-updates; every other family refuses them
     const double *src;     // optional: out = src + alpha * A * xin
     double *out;
     double *rcoarse;       // optional (k_apply RS instantiation): restrict_to!(rcoarse, P, out) in the epilogue -- column stride
@@ -211,6 +217,10 @@ void launch_apply(const Launch &L, const LevelDev &lv, const MeshDev &mesh, doub
 size_t apply_lds_bytes(const LevelDev &lv);
 // can the fused apply of this level restrict its output in its epilogue (ApplyArgs::rcoarse)?
 bool apply_restricts(const Launch &L, const LevelDev &lv);
+// can the residual with the folded prolongation finish the coarse x on the way (ApplyArgs::xc_p, xc_r)?  Level 6's in-image form only.
+bool apply_folds_coarse_x(const Launch &L, const LevelDev &lv);
+// ... and can that residual carry three pending x-updates (ApplyArgs::x4)?  Level 6's 512-thread shape only.
+bool apply_defers3(const Launch &L, const LevelDev &lv);
 // Fused CG pass, see k_apply<.., FUSED>: the kernel (possibly over a cell list, several launches) leaves
 // per-cell partial sums in mesh.blockpart; the reduce step turns them into scal[slot_pap] = sum mult*xin*out and
 // scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.scal / a.mult / a.blockpart are filled in here.

@@ -69,7 +69,10 @@ __global__ void __launch_bounds__(256) k_finalize(const double *__restrict__ par
 // from the class table and the cell's seven scales by every wave: ONE load per lane, requested in front of the column loads, no
 // table terms held across the load phase, no products -- the same weights to the last bit (same products, same order, formed once)
 // LF (fused WC instantiations): the form of the load phase is known at compile time -- 1: one stream in one batch (CG step 0),
-// 2: two streams in one batch, nothing stored (a dead step), 3: the batched general form; 0: decided at run time.  One form per
+// 2: two streams in one batch, nothing stored (a dead step), 3: the batched general form; 0: decided at run time;
+// 4 (RS): the local residual that carries THREE pending x-updates (ApplyArgs::x4: a fourth stream, batches of a third);
+// 5 (CG): the coarse column is (x + a p) + c (r + b p) of three coarse columns (ApplyArgs::xc_p, xc_r: the coarser level's post-smoother
+// left both its x-updates to this pass).  One form per
 // instantiation: the other forms' values do not compete for the 80 registers, and the dead step can take its rows behind the
 // column loads (two whole columns in one batch are 65 registers in flight: with the rows in front it lost 0.5 ms) while the
 // others take them in front.
@@ -268,7 +271,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
     };
     // (measured, profiles/r04_experiments.txt: the dead step with its rows in front as well, step 0 with the words of its interior
     //  blocks in front, the dead step through the general instantiation -- no difference beyond +-0.05 ms per launch)
-    constexpr bool rows_late = WC && LF == 2;
+    constexpr bool rows_late = WC && (LF == 2 || LF == 5);   // (LF == 5: behind the coarse columns, whose three streams need the registers first)
     // (the one-form instantiations have registers to spare -- 70 of 80 --: their addressing words are requested in front of the
     //  column as well, so that nothing but the barrier stands between the column's arrival and the evaluation)
     constexpr bool WEARLY = false;       // (measured: LF == 1 with its words in front goes from 70 to 80 registers + 16 B of scratch)
@@ -289,6 +292,11 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         const double beta = x2c ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
         const double ax = xac || x3c ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
         const double c2 = x3c ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
+        // x4 (own instantiation, LF == 4): a third pending x-update in front of the two, x + dx4*p0 in the place of x -- the
+        // roundings of x += a0*p0; x += ax*p1; p2 = r2 + beta*p1; x += c2*p2 done one after the other
+        constexpr bool X4 = FUSED && RS && LF == 4;
+        const double *x4c = X4 && a.x4 ? a.x4 + cell * lv.ld : nullptr;
+        const double dx4 = x4c ? a.scal[a.d_num] / a.scal[a.d_den] : 0.0;
         // FUSED, optional: the prolongation of the coarse-grid correction, xin = x + P xcoarse (interpolate_and_sum_to!,
         // src/interpolation.jl:64-74: identity rows += 1.0 c[a], midpoints += 0.5 c[a], += 0.5 c[b] in the CSC
         // column order), from the cell's coarse column staged in LDS behind the lattice image
@@ -314,15 +322,33 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         // 4.2 TB/s), the whole column in one batch of loads like the light passes.  Same roundings as the staged form.
         if (cgather && ccol) {
             constexpr int NC = 2;                                   // coarse slots per thread (host: nf_coarse <= NC * NT)
-            double cv2[NC];
+            // CX: the coarse x is not in memory yet -- its last two CG x-updates are done here, per coarse entry, before it is staged:
+            // (x + cxa*p) + cxc*(r + cxb*p), the three roundings of k_cg_x2_update
+            constexpr bool CX = cgather && LF == 5;
+            const double *cpc = CX ? a.xc_p + cell * a.ldc : nullptr, *crc = CX ? a.xc_r + cell * a.ldc : nullptr;
+            const double cxa = CX ? to_sgpr(a.scal[a.a_num] / a.scal[a.a_den]) : 0.0;
+            const double cxb = CX ? to_sgpr(a.scal[a.s_num] / a.scal[a.s_den]) : 0.0;
+            const double cxc = CX ? to_sgpr(a.scal[a.c_num] / a.scal[a.c_den]) : 0.0;
+            double cv2[NC], cp2[CX ? NC : 1], cr2[CX ? NC : 1];
             int cl2[NC];
 #pragma unroll
             for (int q = 0; q < NC; ++q) {
                 const int c = tid + q * NT;
                 if (c < lv.nf_coarse) {
                     cv2[q] = ccol[c];
+                    if (CX) {
+                        cp2[q] = cpc[c];
+                        cr2[q] = crc[c];
+                    }
                     cl2[q] = lv.clpos[c];
                 }
+            }
+            if (CX) {      // (before the fine column's loads: its 13 values and words need the registers)
+#pragma unroll
+                for (int q = 0; q < NC; ++q)
+                    if (tid + q * NT < lv.nf_coarse) cv2[q] = axpy1(cxc, axpy1(cxb, cp2[q], cr2[q]), axpy1(cxa, cp2[q], cv2[q]));
+                __builtin_amdgcn_sched_barrier(0);
+                if (EARLY && rows_late) issue_rows();
             }
             double xv[SPT];
             uint64_t pw[SPT];
@@ -420,7 +446,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                 }
             }
         }
-        constexpr int HB = FUSED ? (SPT + 1) / 2 : SPT;
+        constexpr int HB = X4 ? (SPT + 2) / 3 : FUSED ? (SPT + 1) / 2 : SPT;   // (four streams: three batches hold what two of three streams do)
         // flags bit 7 (fused passes through the batch path below): x is known to be zero -- a coarse level entered with the zero
         // initial guess of src/multigrid.jl:106 -- and is not read (its memory need not even hold the zeros yet)
         // (compiled into the instantiations that can meet it only -- the local residual of a register-blocked level is the RS
@@ -429,7 +455,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         if (!light && !light2 && !(cgather && ccol)) {
 #pragma unroll
         for (int q0 = 0; q0 < SPT; q0 += HB) {
-            double xv[HB], x2v[HB], xav[HB];
+            double xv[HB], x2v[HB], xav[HB], x4v[X4 ? HB : 1];
             int lp[HB];
             uint32_t pw[HB];
 #pragma unroll
@@ -437,6 +463,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                 const int t = tid + (q0 + q) * NT;
                 if (q0 + q < SPT && t < nf) {
                     xv[q] = xzero ? 0.0 : xc[t];
+                    if (X4) x4v[q] = x4c ? x4c[t] : 0.0;
                     x2v[q] = x2c ? x2c[t] : 0.0;
                     xav[q] = xac ? xac[t] : x3c ? x3c[t] : 0.0;
                     lp[q] = lv.lpos[t];
@@ -457,6 +484,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                         if (!cgather && ccol) v = prolong(v, pw[q]);
                         if (xac) xac[t] = axpy1(ax, x2v[q], xav[q]);
                         if (x3c) {
+                            if (X4 && x4c) v = axpy1(dx4, x4v[q], v);
                             const double t1 = axpy1(ax, x2v[q], v);
                             const double p2 = axpy1(beta, x2v[q], xav[q]);
                             v = axpy1(c2, p2, t1);
@@ -477,6 +505,7 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
                 if (!cgather && ccol) v = prolong(v, lv.par32[t]);
                 if (xac) xac[t] = axpy1(ax, pv, xac[t]);
                 if (x3c) {
+                    if (X4 && x4c) v = axpy1(dx4, x4c[t], v);
                     const double t1 = axpy1(ax, pv, v);
                     const double p2 = axpy1(beta, pv, x3c[t]);
                     v = axpy1(c2, p2, t1);
@@ -1014,6 +1043,21 @@ bool apply_restricts(const Launch &L, const LevelDev &lv)
     return lv.nf > 192 && lv.nf <= 1024 && lv.blk_R == 4 && lv.nblk <= 192 && lv.nfi <= 128 && lv.rs_lp != nullptr;
 }
 
+bool apply_defers3(const Launch &L, const LevelDev &lv)
+{
+    // level 6's 512-thread shape, the whole column in the batched load phase: the only instantiation with the fourth stream
+    return apply_restricts(L, lv) && lv.nf > 2048 && lv.nf <= 13 * 512;
+}
+
+bool apply_folds_coarse_x(const Launch &L, const LevelDev &lv)
+{
+    // the conditions under which launch_apply_dim takes the residual with the folded prolongation (flags bit 6) through the
+    // 512-thread register-blocked instantiation that stages the coarse column in the lattice image: level 6
+    return lv.dim == 3 && apply_lds_bytes(lv) <= 160 * 1024 && L.apply_threads == 0 && L.apply_wg512 && lv.blk_R == 6 && lv.nblk <= 960 &&
+           lv.nei <= 64 && lv.nedge == 6 && lv.ncorner == 4 && lv.nfi <= 512 && lv.par64 && lv.clpos && lv.nf > 2048 &&
+           lv.nf <= 13 * 512 && lv.nf_coarse > 0 && lv.nf_coarse <= 2 * 512;
+}
+
 static size_t apply_lds_bytes_rb(const LevelDev &lv)   // register-blocked instantiations: only the corners' weight rows in LDS
 {
     return sizeof(double) * (size_t)(WSZ_RB + lv.lds_g0 + lv.nf + lv.lds_g1);
@@ -1048,6 +1092,8 @@ static void launch_apply_generic(const Launch &L, const LevelDev &lv, const Mesh
 {
     auto kern = k_apply<DIM, NT, SPT, FUSED, RB, WD, CG, RS, WC, LF>;
     if (a.rcoarse && !RS) throw std::runtime_error("operator apply: this instantiation cannot restrict in its epilogue");
+    if (a.xc_p && !(CG && LF == 5)) throw std::runtime_error("operator apply: this instantiation cannot finish the coarse x");
+    if (a.x4 && LF != 4) throw std::runtime_error("operator apply: this instantiation cannot carry a third pending x-update");
     if ((a.flags & 128) && !(FUSED && (RS || RB == 0)))
         throw std::runtime_error("operator apply: this instantiation cannot take a zero input that is not in memory");
     if (FUSED && a.xcoarse && !CG) lds += sizeof(double) * (size_t)lv.nf_coarse;   // coarse column behind the lattice image
@@ -1074,6 +1120,14 @@ template <int DIM, bool FUSED, bool WD = false>
 static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a)
 {
     const size_t lds = apply_lds_bytes(lv);
+    // a third pending x-update: the register-blocked local residual of level 6 alone has the stream (no other family is reached with it)
+    if (a.x4 && !(FUSED && DIM == 3 && !WD && a.x3 && a.x2 && a.xout && a.rcoarse && !a.xcoarse && !a.xacc && !(a.flags & 128) &&
+                  apply_defers3(L, lv)))
+        throw std::runtime_error("operator apply: a third pending x-update (x4) where no kernel carries it");
+    // the coarse x with its last two updates pending: the in-image prolongation of level 6 alone combines the three coarse columns
+    if ((a.xc_p || a.xc_r) && !(FUSED && DIM == 3 && !WD && a.xc_p && a.xc_r && a.xcoarse && (a.flags & 64) && !a.x2 && !a.xacc && !a.x3 &&
+                                !a.rcoarse && apply_folds_coarse_x(L, lv)))
+        throw std::runtime_error("operator apply: pending coarse x-updates (xc_p, xc_r) where no kernel carries them");
     if constexpr (DIM == 3 && !WD) {
         // level 5: one wave per cell, class weights from the cache (hmg_apply_wave.hip)
         if (apply_wave_ok(L, lv, mesh, a, FUSED)) {
@@ -1182,8 +1236,12 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
                 constexpr int R6 = DIM == 3 ? 6 : 0;
                 constexpr bool F3 = FUSED && DIM == 3;
                 if (DIM == 3 && weight_cache_ok(L, lv, mesh, a)) {      // class weights from the cache (WC), else combined per cell
-                    if (cg)
+                    if (cg && a.xc_p)
+                        launch_apply_generic<DIM, 512, 13, FUSED, R6, false, F3, false, DIM == 3, F3 ? 5 : 0>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
+                    else if (cg)
                         launch_apply_generic<DIM, 512, 13, FUSED, R6, false, F3, false, DIM == 3>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
+                    else if (rs && a.x4)
+                        launch_apply_generic<DIM, 512, 13, FUSED, R6, false, false, F3, DIM == 3, F3 ? 4 : 0>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                     else if (rs)
                         launch_apply_generic<DIM, 512, 13, FUSED, R6, false, false, F3, DIM == 3>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                     else if (FUSED && !a.x2 && !a.xacc && !a.x3 && !a.xcoarse && !a.rcoarse)                 // CG step 0
@@ -1194,8 +1252,12 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
                         launch_apply_generic<DIM, 512, 13, FUSED, R6, false, false, false, DIM == 3>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                     return;
                 }
-                if (cg)
+                if (cg && a.xc_p)
+                    launch_apply_generic<DIM, 512, 13, FUSED, R6, false, F3, false, false, F3 ? 5 : 0>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
+                else if (cg)
                     launch_apply_generic<DIM, 512, 13, FUSED, R6, false, F3>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
+                else if (rs && a.x4)
+                    launch_apply_generic<DIM, 512, 13, FUSED, R6, false, false, F3, false, F3 ? 4 : 0>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                 else if (rs)
                     launch_apply_generic<DIM, 512, 13, FUSED, R6, false, false, F3>(L, lv, mesh, a, apply_lds_bytes_rb(lv));
                 else

@@ -192,9 +192,11 @@ struct hmg_ctx {
     bool swap_rp = true;  // V-cycle: step 0 of a smoother takes r itself as p (pointer exchange), see smooth_form()
     bool fold_prolong = true;   // V-cycle: prolongation folded into the post-smoother's first residual
     bool lazy_dead = true;      // V-cycle: the pre-smoother's dead last step writes nothing (see smooth_form())
+    bool lazy_pre = true;       // ... and with three steps or more the step before it leaves its x-update too, its direction in the spare vector (see smooth_form())
     bool fold_faces = true;     // fused CG: the face part of Ap's interface sum rides in the r-update (all steps but a live last one)
     bool lean_post = true;      // V-cycle: the post-smoother's dead tail is dropped too (see smooth_form())
     bool lazy_post = true;      // ... and below the finest level its dead last step writes nothing: both x-updates in one pass
+    bool fold_coarse_x = true;  // ... and the level below the finest leaves them to the finest level's first residual, which reads that x anyway (see coarse_x_folds())
     int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
     bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
     bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
@@ -223,6 +225,8 @@ struct hmg_ctx {
     int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
     int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
     int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
+    int64_t coarse_x_folds = 0;              // residuals that finished the coarser level's x on the way (option fold_coarse_x)
+    int last_pre_form = 0;                   // x-updates the last pre-smoother of a V-cycle's down leg left to its local residual: 0 .. 3
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
     // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB

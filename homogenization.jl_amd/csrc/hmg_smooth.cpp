@@ -150,8 +150,8 @@ void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, in
     // algorithmic HBM streams of this launch: x in, out, + src, + x2 (p_old), + xout (p), + xacc (x read and write)
     // (flags bit 7: x is a zero that is not read)
     const double streams = ((a.flags & 128) ? 0.0 : 1.0) + (a.out ? 1.0 : 0.0) + (a.src ? 1.0 : 0.0) + (a.x2 ? 1.0 : 0.0) + (a.xout ? 1.0 : 0.0) +
-                           (a.xacc ? 2.0 : 0.0) + (a.x3 ? 1.0 : 0.0) + (a.xcoarse ? (double)lv.nf_coarse / (double)lv.nf : 0.0) +
-                           (a.rcoarse ? (double)lv.nf_coarse / (double)lv.nf : 0.0);
+                           (a.xacc ? 2.0 : 0.0) + (a.x3 ? 1.0 : 0.0) + (a.x4 ? 1.0 : 0.0) + (a.xcoarse ? (double)lv.nf_coarse / (double)lv.nf : 0.0) +
+                           (a.rcoarse ? (double)lv.nf_coarse / (double)lv.nf : 0.0) + (a.xc_p ? 2.0 * (double)lv.nf_coarse / (double)lv.nf : 0.0);
     TimedRegion tr(g, lv, 8.0 * (double)lv.nf * (double)g->md.ncells * streams);
     // (overlapping costs launches -- the apply in two parts, the interface sums in two parts: worth it where the exchange
     //  moves real data; on the small levels, launch-bound as they are, it only adds to the chain.  Rehearsal on one rank,
@@ -247,6 +247,7 @@ enum class Tail {
     DeadXp,      // dead step, then x += alpha p
     DeadDefer,   // dead step, x += alpha p left to the caller's local residual (fold_x)
     DeadDefer2,  // dead step that writes nothing (p formed in LDS only), both pending x-updates left to the caller (lazy_dead)
+    DeadDefer3,  // ... and step steps - 2 writes its direction into the spare vector and leaves its x-update too: three pending (lazy_pre)
     DeadX2,      // dead step that writes nothing, then one pass does both x-updates (lazy_post)
 };
 
@@ -255,11 +256,13 @@ struct SmoothForm {
                             // times per V-cycle: wrapped buffers end up holding what their names say)
     bool ride = false;      // the face part of Ap's interface sum rides in the r-update (every step but a live last one)
     Tail tail = Tail::Full;
+    bool hand_up = false;   // (set by the caller, tail DeadX2) both x-updates are left to the finer level's first residual (coarse_x_folds())
     bool x_zero = false;    // (set by the caller) x is a coarse level's zero initial guess that is not in memory
                             // (zero_entry_ok): the first residual is the constrained copy of b, b - A 0 to the last bit
 };
 
-// What a pre-smoother leaves to its caller (tails DeadDefer and DeadDefer2).
+// What a pre-smoother leaves to its caller (tails DeadDefer, DeadDefer2 and DeadDefer3), or a post-smoother below the finest level
+// to the level above (tail DeadX2 with hand_up: the two-update form, with the vectors that hold p1 and r2).
 struct DeferredX {
     int rs = -1;         // >= 0: x += (scal[rs] / scal[pap]) * p_last is still to be done
     int pap = S_PAP;
@@ -267,6 +270,11 @@ struct DeferredX {
     //   x += (scal[a_num]/scal[a_den]) p1;  p2 = r2 + (scal[b_num]/scal[b_den]) p1;  x += (scal[rs]/scal[pap]) p2
     bool two_updates = false;
     int a_num = -1, a_den = -1, b_num = -1, b_den = -1;
+    // three updates (Tail::DeadDefer3): in front of those two x += (scal[d_num]/scal[d_den]) p0, p0 = the p handle; p1 is then
+    // the grid's spare vector
+    bool three_updates = false;
+    int d_num = -1, d_den = -1;
+    const double *p = nullptr, *r = nullptr;   // (hand_up)
 };
 
 // Every context option that shapes the smoother is read here, before the first launch.
@@ -284,8 +292,13 @@ SmoothForm smooth_form(const hmg_grid *g, int level, int steps, Role role)
     const bool faces = c->fold_faces && lv.dim == 3 && lv.nfi > 0;
     f.swap_rp = role != Role::Plain && c->swap_rp && steps > 0;
     f.ride = faces;
-    if (role == Role::Pre && c->fold_x)
+    if (role == Role::Pre && c->fold_x) {
         f.tail = steps >= 2 && c->lazy_dead ? Tail::DeadDefer2 : Tail::DeadDefer;
+        // (the local residual must be the launch that has the fourth stream: vcycle_down takes it under the same conditions)
+        if (f.tail == Tail::DeadDefer2 && steps >= 3 && c->lazy_pre && faces && c->fold_restrict && apply_defers3(c->L, lv) &&
+            g->top_spare.n >= (size_t)lv.ld * (size_t)g->md.ncells)
+            f.tail = Tail::DeadDefer3;
+    }
     else if (dead)
         f.tail = steps >= 2 && c->lazy_post ? Tail::DeadX2 : Tail::DeadXp;
     else if (lean && steps >= 2 && c->lazy_top > 0 && faces)
@@ -345,7 +358,7 @@ bool wants_top_spare(const hmg_grid *g, int level)
 namespace {
 
 DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
-                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr)
+                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
 {
     // ref: src/multigrid.jl:46-71
     const LevelDev &lv = lev(g, level);
@@ -371,6 +384,20 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
             a.xout = x->d;
             // (cells that fill a third of the LDS: no room for the coarse column next to three resident images)
             if (g->ctx->prolong_in_image && apply_lds_bytes(lv) > 48 * 1024) a.flags |= 64;
+            if (cx && cx->rs >= 0) {
+                // the coarse x still lacks its last two CG updates: done per coarse entry where the column is staged (24 instead of
+                // 32 + 8 B per coarse DOF, one launch fewer)
+                need(cx->two_updates && cx->p && cx->r && (a.flags & 64), "pending coarse x-updates where the residual cannot carry them");
+                a.xc_p = cx->p;
+                a.xc_r = cx->r;
+                a.a_num = cx->a_num;
+                a.a_den = cx->a_den;
+                a.s_num = cx->b_num;
+                a.s_den = cx->b_den;
+                a.c_num = cx->rs;
+                a.c_den = cx->pap;
+                g->ctx->coarse_x_folds += 1;
+            }
             apply_then_sum(g, lv, a, true, -1, -1);
         } else {
             apply_then_sum(g, lv, a, false, -1, -1);
@@ -442,7 +469,7 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
     };
     const int last = steps - 1;
     for (int i = 0; i < last; ++i) {
-        if (f.tail == Tail::Top3 && i == last - 1) {
+        if ((f.tail == Tail::Top3 || f.tail == Tail::DeadDefer3) && i == last - 1) {
             // slots: rs_{i-1} in `other`, p.Ap_{i-1} in S_PAP (both kept for the deferred x-update), rs_i in `cur`;
             // this step's p.Ap goes to S_PAP2 and its r.r to S_RS3
             ApplyArgs a = args(i);
@@ -479,11 +506,32 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         // step goes to its own slot: S_PAP still holds the previous step's, which the first of the two x-updates needs.
         a.out = a.xout = a.xacc = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP2, -1);
+        if (f.tail == Tail::DeadX2 && f.hand_up) {
+            DeferredX d{cur, S_PAP2, true, other, S_PAP, cur, other};
+            d.p = p->d;
+            d.r = r->d;
+            return d;
+        }
         if (f.tail == Tail::DeadX2) {
             launch_cg_x2_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, cur, S_PAP2);
             return {};
         }
         return DeferredX{cur, S_PAP2, true, other, S_PAP, cur, other};   // alpha_i; alpha_{i-1} = rs_{i-1} / p.Ap_{i-1}, beta_i
+    case Tail::DeadDefer3:
+        // the dead step after a step that wrote its direction into the spare vector (slots as for Top3): reads r and the spare,
+        // writes nothing; x += alpha_{i-2} p_{i-2}, x += alpha_{i-1} p_{i-1} and x += alpha_i (r_i + beta_i p_{i-1}) are the caller's
+        a.x2 = g->top_spare.p;
+        a.out = a.xout = a.xacc = nullptr;
+        a.s_num = S_RS3;
+        a.s_den = cur;
+        apply_then_sum(g, lv, a, true, S_PAP3, -1);
+        {
+            DeferredX d{S_RS3, S_PAP3, true, cur, S_PAP2, S_RS3, cur};
+            d.three_updates = true;
+            d.d_num = other;
+            d.d_den = S_PAP;
+            return d;
+        }
     case Tail::Top2:
         // (p.Ap of this step to its own slot: S_PAP keeps the previous step's for the first of the two x-updates)
         a.xout = a.xacc = nullptr;
@@ -526,7 +574,8 @@ bool zero_entry_ok(const hmg_grid *g, int k, int steps)
     return true;
 }
 
-void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false, bool x_zero = false, int steps_next = -1)
+// Returns the number of x-updates the pre-smoother left to the local residual (hmg_ctx_counter "lazy_pre_form").
+int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false, bool x_zero = false, int steps_next = -1)
 {
     // x_zero: this level's x is a zero nobody has written (see zero_entry_ok); steps_next: the CG steps the next coarser
     // level will take (inside hmg_vcycle; decides whether ITS zero initial guess has to be written)
@@ -540,6 +589,7 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
     need(!x_zero || form.tail == Tail::DeadDefer2, "zero initial guess: the pre-smoother does not defer both x-updates");
     form.x_zero = x_zero;
     const DeferredX dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form);
+    const int deferred = dx.rs < 0 ? 0 : dx.three_updates ? 3 : dx.two_updates ? 2 : 1;
     const bool skip_fill = inside && steps_next >= 0 && zero_entry_ok(g, k - 1, steps_next);
     if (dx.rs >= 0) {
         // local residual with the pre-smoother's pending x-update(s) folded into its load phase (x written back),
@@ -549,8 +599,14 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
         a.alpha = -1.0;
         a.lambda = g->lambda;
         a.x = cur[0]->d;
-        a.x2 = cur[3]->d;
+        a.x2 = dx.three_updates ? g->top_spare.p : cur[3]->d;
         a.xout = cur[0]->d;
+        if (dx.three_updates) {        // (49 B/DOF: x, p0, p1, r and b in, x and the restricted column out)
+            need(g->ctx->fold_restrict && apply_defers3(L, lev(g, k)), "three pending x-updates where the local residual cannot carry them");
+            a.x4 = cur[3]->d;
+            a.d_num = dx.d_num;
+            a.d_den = dx.d_den;
+        }
         if (dx.two_updates) {
             a.x3 = cur[2]->d;
             a.a_num = dx.a_num;
@@ -572,7 +628,7 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
             a.ldrc = lev(g, k - 1).ld;
             apply_then_sum(g, lev(g, k), a, true, -1, -1, /*sum_out=*/false);
             if (!skip_fill) launch_fill(L, nxt[0]->d, vec_len(nxt[0]), 0.0);
-            return;
+            return deferred;
         }
         apply_then_sum(g, lev(g, k), a, true, -1, -1, /*sum_out=*/false);
     } else {
@@ -580,11 +636,13 @@ void vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = fals
     }
     restrict_level(g, k, cur[2]->d, nxt[1]->d);
     if (!skip_fill) launch_fill(L, nxt[0]->d, vec_len(nxt[0]), 0.0);
+    return deferred;
 }
 
 // Up leg (src/multigrid.jl:112-115): coarse-grid correction x_k += P x_{k-1}, post-smoother (role PostTop on the finest
 // level, PostBelow below it).
-void vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role)
+// cx: what level k - 1's post-smoother left of its x (hand_up); hand_up: may this level's post-smoother leave its own in turn?
+DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const DeferredX *cx = nullptr, bool hand_up = false)
 {
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
@@ -593,28 +651,53 @@ void vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role)
     // coarse column in LDS next to the lattice image (two workgroups per CU must still fit), else a separate pass
     const bool fold_p = g->ctx->fold_prolong && g->fuse_cg && apply_lds_bytes(lev(g, k)) <= 160 * 1024 &&
                         apply_lds_bytes(lev(g, k)) + sizeof(double) * (size_t)lev(g, k - 1).nf <= 80 * 1024;
+    need(!(cx && cx->rs >= 0) || fold_p, "pending coarse x-updates without the folded prolongation");
     if (!fold_p) launch_prolong_add(L, lev(g, k), lev(g, k - 1), g->md.ncells, nxt[0]->d, cur[0]->d);
-    smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], smooth_form(g, k, steps, role), fold_p ? nxt[0] : nullptr);
+    SmoothForm form = smooth_form(g, k, steps, role);
+    form.hand_up = hand_up && form.tail == Tail::DeadX2;
+    return smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form, fold_p ? nxt[0] : nullptr, cx);
+}
+
+// Does level k's post-smoother take the coarse x with its last two updates pending?  Its first residual must be the launch that
+// stages the coarse column in the lattice image (the conditions of vcycle_up() and smooth(), and the kernel's own), and the level
+// below must end in the one-pass form (DeadX2) that is handed up instead.  Nothing else reads that x: the next V-cycle's down leg
+// enters the level with a zero guess (src/multigrid.jl:106).  Inside hmg_vcycle only -- hmg_vcycle_up takes a caller's coarse x.
+bool coarse_x_folds(const hmg_grid *g, int k, int steps_below)
+{
+    const hmg_ctx *c = g->ctx;
+    if (k < 3 || !c->fold_coarse_x || !c->lazy_post || !c->fold_prolong || !c->lean_post || !g->fuse_cg || !c->prolong_in_image) return false;
+    const LevelDev &lv = g->ld[(size_t)k - 1];
+    if (!(apply_lds_bytes(lv) > 48 * 1024 && apply_lds_bytes(lv) <= 160 * 1024 &&
+          apply_lds_bytes(lv) + sizeof(double) * (size_t)g->ld[(size_t)k - 2].nf <= 80 * 1024))
+        return false;
+    return apply_folds_coarse_x(c->L, lv) && smooth_form(g, k - 1, steps_below, Role::PostBelow).tail == Tail::DeadX2;
+}
+
+// hand_up: the level above finishes this level's x in its first residual (coarse_x_folds()); returns what is left to it
+DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool hand_up)
+{
+    // ref: src/multigrid.jl:73-119
+    if (k == 1) {                                  // (the scatter of the level-1 solution overwrites every entry of x)
+        hmg_vec **cur = st;
+        coarse_solve(g, cur[1], cur[0]);
+        return {};
+    }
+    // (below the top level x is the zero initial guess the level above left -- written only if this level needs it in memory;
+    //  a zero guess on the top level (hmg_fcg_step) is written here on the same condition)
+    const bool x_zero = (zero_guess || !top) && zero_entry_ok(g, k, steps);
+    if (top && zero_guess && !x_zero) launch_fill(g->ctx->L, st[5 * (k - 1)]->d, vec_len(st[5 * (k - 1)]), 0.0);
+    const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
+    if (top) g->ctx->last_pre_form = deferred;
+    const DeferredX cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
+    if (top) g->ctx->last_top_form = 0;
+    return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up);
 }
 
 }  // namespace
 
 void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess)
 {
-    // ref: src/multigrid.jl:73-119
-    if (k == 1) {                                  // (the scatter of the level-1 solution overwrites every entry of x)
-        hmg_vec **cur = st;
-        coarse_solve(g, cur[1], cur[0]);
-        return;
-    }
-    // (below the top level x is the zero initial guess the level above left -- written only if this level needs it in memory;
-    //  a zero guess on the top level (hmg_fcg_step) is written here on the same condition)
-    const bool x_zero = (zero_guess || !top) && zero_entry_ok(g, k, steps);
-    if (top && zero_guess && !x_zero) launch_fill(g->ctx->L, st[5 * (k - 1)]->d, vec_len(st[5 * (k - 1)]), 0.0);
-    vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
-    vcycle(g, k - 1, steps_coarse, steps_coarse, st, false);
-    if (top) g->ctx->last_top_form = 0;
-    vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow);
+    (void)vcycle_level(g, k, steps, steps_coarse, st, top, zero_guess, /*hand_up=*/false);
 }
 
 }  // namespace hmg
@@ -724,8 +807,8 @@ int hmg_level_tune_placement(hmg_grid *g, int level, int steps, hmg_vec **states
             HIPCHK(hipEventRecord(e0, c->stream));
             // as hmg_vcycle runs them on its top level (each half exchanges the r and p pointers: restored by the pair; the
             // coarse x stays the zero it is)
-            vcycle_down(g, level, steps, states, /*inside=*/true, /*x_zero=*/false, /*steps_next=*/2);
-            vcycle_up(g, level, steps, states, Role::PostTop);
+            (void)vcycle_down(g, level, steps, states, /*inside=*/true, /*x_zero=*/false, /*steps_next=*/2);
+            (void)vcycle_up(g, level, steps, states, Role::PostTop);
             HIPCHK(hipEventRecord(e1, c->stream));
             HIPCHK(hipEventSynchronize(e1));
             float ms = 0.f;
@@ -803,7 +886,7 @@ int hmg_vcycle_down(hmg_grid *g, int level, int steps, hmg_vec **states)
 {
     HMG_TRY
     check_two_levels(g, level, states);
-    vcycle_down(g, level, steps, states);
+    g->ctx->last_pre_form = vcycle_down(g, level, steps, states);
     HMG_END
 }
 
@@ -811,7 +894,7 @@ int hmg_vcycle_up(hmg_grid *g, int level, int steps, hmg_vec **states)
 {
     HMG_TRY
     check_two_levels(g, level, states);
-    vcycle_up(g, level, steps, states, Role::PostTop);   // as the finest level of hmg_vcycle
+    (void)vcycle_up(g, level, steps, states, Role::PostTop);   // as the finest level of hmg_vcycle
     HMG_END
 }
 

@@ -74,11 +74,21 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *       is created.
  *   "fold_x" 1: the pre-smoother's last x-update rides in the local residual.
  *   "lazy_dead" 1: the pre-smoother's dead last step writes nothing and both pending x-updates ride in the local residual.
+ *   "lazy_pre" 1: with three steps or more the step before the dead one leaves its x-update to the local residual as well and
+ *       writes its direction into the spare vector of "lazy_top" = 2 (unused during the pre-smoother): three pending updates.
+ *       Taken on level 6 where that residual is the register-blocked kernel that restricts in its epilogue ("fold_restrict"),
+ *       with "fold_x", "lazy_dead" and "fold_faces" on and the spare vector present; everywhere else -- level 7 (k_apply_slab2),
+ *       level 5 and below (k_apply_wave, k_apply_small), 2D -- the two-update form stays.  hmg_ctx_counter "lazy_pre_form".
  *   "swap_rp" 1: CG step 0 takes r itself as p by exchanging the two handles' device pointers (an even number of times).
  *   "fold_faces" 1: the face part of A p's interface sum rides in the CG r-update.
  *   "lean_post" 1: the post-smoothers' dead tails go too: p and Ap, and r below the top level, are scratch on return (the
  *       next smoothing_steps! overwrites them before reading, src/multigrid.jl:46-50); 0: they hold what the reference leaves.
  *   "lazy_post" 1: below the top level the post-smoother's dead last step writes nothing; one pass does both x-updates.
+ *   "fold_coarse_x" 1: inside hmg_vcycle the level below a level-6 top level goes further: that pass is dropped and the top level's
+ *       first post-smoothing residual, which reads that x as its coarse column anyway, combines the coarse x, p and r columns where
+ *       it stages them (the same three roundings per entry).  Needs "lazy_post", "fold_prolong", "prolong_in_image" and "lean_post";
+ *       x of that level is then scratch on return from hmg_vcycle, like its r (nothing reads it: the next V-cycle enters the level
+ *       with a zero guess).  hmg_vcycle_up takes the caller's coarse x as it is.  hmg_ctx_counter "coarse_x_folds".
  *   "lazy_top" 2: on the top level the last r-update carries the pending x-updates of the last two steps (three steps or
  *       more; the direction of the step before goes to a spare vector of the top level's size, reserved when the first
  *       vector of the finest level is created or wrapped, or by hmg_grid_reserve_spare); 1: of the last step; 0: neither.
@@ -112,7 +122,9 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    one), "device_allocs" (device / pinned allocations the library has made in this process: constant across hmg_vcycle once the
    grid, its operator, its level-1 system and the level vectors exist), "spare_bytes" (spare direction vectors held by this
    context's grids, see hmg_grid_reserve_spare), "lazy_top_form" (the form the last finest-level post-smoother inside hmg_vcycle
-   took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "fcg_bytes" (p, q and R of this context's
+   took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "lazy_pre_form" (the x-updates the
+   last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "coarse_x_folds" (residuals
+   that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
    hmg_fcg objects); -1 for an unknown name.  No counterpart in
    the reference. */
 int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name);

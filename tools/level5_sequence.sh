@@ -7,6 +7,8 @@
 #   restriction in the epilogue (b, r, p in; x, coarse b out: 32 + 1.4) | C residual with the coarse-grid correction
 #   (x, coarse x, b in; x, r out: 32 + 1.4) | F step 0 (16) | F last step (option lazy_post: reads r, p: 16; LAST_B=40 for runs
 #   with lazy_post=0 or builds before round 4, where it also reads x and writes p, x)
+# (option fold_coarse_x, level 6 on top: the k_cg_x2_update pass that followed the last step -- 32 B/DOF, not an apply launch -- is
+#  gone; the six apply launches and their bytes are what they were)
 set -e
 T=${1:-l5seq}
 cd /tmp; export TMPDIR=/tmp
