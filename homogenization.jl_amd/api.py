@@ -31,6 +31,8 @@ from . import _lib as L
 Tri64 = "Tri64"   # element-type tags (src/grid.jl:29-37)
 Tet64 = "Tet64"
 
+SMOOTHERS = {"cg": 0, "jacobi": 1}   # hmg_grid_set_smoother
+
 
 def _dim_of(tag):
     return {Tri64: 2, Tet64: 3, 2: 2, 3: 3}[tag]
@@ -205,6 +207,18 @@ class ImplicitFineGrid:
         """The sixth finest-level vector of the default V-cycle form (include/hmg.h: hmg_grid_reserve_spare): True reserves it now
         and raises if the memory is not there, False releases it (the reference's five vectors per level)."""
         L.check(self._lib.hmg_grid_reserve_spare(self.h, 1 if enable else 0))
+
+    def set_smoother(self, kind="cg"):
+        """The smoother of smoothing_steps / vcycle / FlexibleCG on this grid (include/hmg.h: hmg_grid_set_smoother): "cg" is the
+        reference's (default), "jacobi" is CG preconditioned by the inverse diagonal of the assembled operator.  "jacobi" reserves
+        one vector per level >= 2 and raises if the memory is not there; set it before the level vectors are created."""
+        if kind not in SMOOTHERS:
+            raise ValueError(f"smoother must be one of {sorted(SMOOTHERS)}, not {kind!r}")
+        L.check(self._lib.hmg_grid_set_smoother(self.h, SMOOTHERS[kind]))
+
+    def smoother(self) -> str:
+        k = int(self._lib.hmg_grid_smoother(self.h))
+        return {v: n for n, v in SMOOTHERS.items()}[k]
 
     def coarse_setup(self):
         L.check(self._lib.hmg_coarse_setup(self.h))
@@ -498,6 +512,18 @@ def integrate_pair_load(v: DeviceMatrix, s: DeviceMatrix, implicit: ImplicitFine
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))
+
+
+def set_smoother(implicit: ImplicitFineGrid, kind: str = "cg"):
+    """"cg" (the reference's smoother, default) or "jacobi" (CG preconditioned by the inverse diagonal)."""
+    implicit.set_smoother(kind)
+
+
+def smoother_diag(implicit: ImplicitFineGrid, level: int, out: DeviceMatrix = None) -> DeviceMatrix:
+    """The level's inverse diagonal as the "jacobi" smoother uses it (0 on constrained nodes), formed first if it is stale."""
+    out = DeviceMatrix(implicit, level) if out is None else out
+    L.check(implicit._lib.hmg_grid_smoother_diag(implicit.h, level, out.h))
+    return out
 
 
 class BaseLevel:

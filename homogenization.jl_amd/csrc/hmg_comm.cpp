@@ -328,6 +328,7 @@ int hmg_grid_set_exchange(hmg_grid *g, hmg_exchange_fn exchange, hmg_exchange_fn
     g->exchange = exchange;
     g->scalar_sum = scalar_sum_fn;
     g->cut_agreed_ready = false;
+    g->dinv_ready = false;                       // (the smoother's diagonal is summed through the exchange)
     g->ex_user = user;
     g->ex_buf = (double *)device_exchange_buf;
     g->ex_cap = exchange_buf_doubles;
@@ -340,6 +341,7 @@ int hmg_grid_set_exchange_async(hmg_grid *g, hmg_exchange_fn begin, int (*end)(v
     need(g != nullptr, "null grid");
     g->ex_begin = begin;
     g->ex_end = end;
+    g->dinv_ready = false;
     HMG_END
 }
 
@@ -475,6 +477,7 @@ int hmg_grid_use_comm(hmg_grid *g)
     g->exchange = comm_exchange;             // (the level-1 gather stays an all-reduce of the global nodal vector)
     g->scalar_sum = comm_exchange;           // (the same in-place sum, on the scalar bank)
     g->cut_agreed_ready = false;
+    g->dinv_ready = false;
     g->ex_begin = comm_exchange_begin;
     g->ex_end = comm_exchange_end;
     g->p2p = comm_p2p_sync;
@@ -490,6 +493,7 @@ int hmg_grid_set_exchange_p2p(hmg_grid *g, int enabled, hmg_p2p_fn p2p, hmg_p2p_
     need(!enabled || g->part != nullptr, "the sharers-only exchange needs a grid made by hmg_grid_create_partition");
     g->sharers = enabled != 0;
     g->cutlv.clear();
+    g->dinv_ready = false;
     g->p2p = p2p;
     g->p2p_begin = p2p_begin;
     g->stage = (double *)device_stage_buf;

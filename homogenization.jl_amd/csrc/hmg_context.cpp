@@ -140,6 +140,7 @@ void grid_unref(hmg_grid *grid)
     }
     probe_unlist(grid);
     release_top_spare(grid);
+    release_smoother_diag(grid);
     if (grid->probe && grid->probe->h) (void)hipHostFree(grid->probe->h);
     if (grid->probe && grid->probe->ev) (void)hipEventDestroy(grid->probe->ev);
     delete grid;
@@ -248,6 +249,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "device_allocs") return device_allocs().load();
     if (n == "spare_bytes") return ctx->spare_bytes;
     if (n == "fcg_bytes") return ctx->fcg_bytes;
+    if (n == "smoother_diag_bytes") return ctx->smoother_diag_bytes;
+    if (n == "smoother_diag_builds") return ctx->smoother_diag_builds;
     if (n == "lazy_top_form") return ctx->last_top_form;
     if (n == "lazy_pre_form") return ctx->last_pre_form;
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;

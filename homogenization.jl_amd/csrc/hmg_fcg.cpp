@@ -74,7 +74,7 @@ void need_current(hmg_fcg *f, const char *what)
 {
     if (!f->started) throw std::runtime_error(std::string(what) + ": hmg_fcg_start has not been called");
     if (f->epoch != f->g->op_epoch)
-        throw std::runtime_error(std::string(what) + ": the grid was shrunk or its operator or lambda changed since hmg_fcg_start; "
+        throw std::runtime_error(std::string(what) + ": the grid was shrunk or its operator, lambda or smoother changed since hmg_fcg_start; "
                                  "the residual and the direction belong to the old operator -- call hmg_fcg_start again");
 }
 
@@ -141,6 +141,7 @@ int hmg_fcg_start(void *handle, hmg_vec *x, hmg_vec *b, hmg_vec **states)
     for (int k = 0; k < 5; ++k)
         need(x != top[k], "x must not be one of the top level's state vectors: the V-cycle inside a step overwrites them");
     f->started = false;
+    ensure_smoother_diag(f->g, f->level, states);
     ok(hmg_apply_ex(f->g, f->level, -1.0, x, b, f->R, 1));      // R = b - A_loc x, Dirichlet rows zeroed
     f->have_dir = false;
     f->epoch = f->g->op_epoch;
@@ -162,6 +163,7 @@ int hmg_fcg_step(void *handle, hmg_vec *x, hmg_vec **states)
     check_vec(f->g, f->level, f->p, "p");
     check_vec(f->g, f->level, f->q, "q");
     check_vec(f->g, f->level, f->R, "R");
+    ensure_smoother_diag(f->g, f->level, states);
     double *xd = x->d, *pd = f->p->d, *qd = f->q->d, *Rd = f->R->d;
     // z = V(0, R): the V-cycle takes R where the top level's b stands (the handle, not a copy) and leaves z in the top level's x
     hmg_vec *b_keep = top[1];

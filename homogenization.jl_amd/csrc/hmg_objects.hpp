@@ -225,6 +225,8 @@ struct hmg_ctx {
     int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
     int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
     int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
+    int64_t smoother_diag_bytes = 0;         // inverse diagonals held by this context's grids (hmg_grid_set_smoother)
+    int64_t smoother_diag_builds = 0;        // times a grid of this context formed them (ensure_smoother_diag)
     int64_t coarse_x_folds = 0;              // residuals that finished the coarser level's x on the way (option fold_coarse_x)
     int last_pre_form = 0;                   // x-updates the last pre-smoother of a V-cycle's down leg left to its local residual: 0 .. 3
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
@@ -279,6 +281,13 @@ struct hmg_grid {
     DevBuf<double> c_val, c_diag, c_b, c_x, c_r, c_z, c_p, c_q, c_u, c_z2, c_d;   // (c_z2, c_d: Chebyshev preconditioner)
     DevBuf<double> top_spare;           // second direction vector of the finest level's post-smoother (smooth(), lazy_top = 2)
     bool top_spare_refused = false;
+    // Jacobi-preconditioned CG smoother (hmg_grid_set_smoother): per level >= 2 the inverse of the assembled operator's diagonal,
+    // 0 on constrained nodes -- a consistent level vector, reserved by the call (setup memory), formed by ensure_smoother_diag()
+    int smoother = 0;                            // 0: CG (src/multigrid.jl:46-71), 1: Jacobi-preconditioned CG
+    std::vector<std::unique_ptr<DevBuf<double>>> dinv;   // [nlevels], empty with smoother 0
+    bool dinv_ready = false;                     // false: operator, lambda, domain, cut or exchange changed since they were formed
+    std::vector<char> dinv_level_ready;          // [nlevels] formed since then (a level is formed where a call first smooths on it)
+    bool dinv_build_counted = false;             // ... and "smoother_diag_builds" has counted this generation
     double c_lmax = 2.0;                         // Gershgorin bound of D^-1 A of the level-1 matrix
     int coarse_last_it = 0;
     int coarse_budget = 0;                       // iterations a solve enqueues blindly (0: not known yet)
@@ -402,6 +411,13 @@ void scalar_sum(hmg_grid *g, int slot, int count);
 bool reserve_top_spare(hmg_grid *g, bool must);
 void release_top_spare(hmg_grid *g);
 bool wants_top_spare(const hmg_grid *g, int level);
+// forms the stale inverse diagonal of one level of a grid with smoother 1 (kernels and the interface sum's exchange only, no
+// allocation): at the entry of every call that smooths on that level, before its first launch.  scratch: a vector of the level
+// that the call overwrites anyway (its Ap; the output of hmg_grid_smoother_diag) -- the fixed-point sum needs a second array
+void ensure_smoother_diag(hmg_grid *g, int level, double *scratch);
+// ... of levels 2 .. top, the scratch of a level being the Ap of its state (states: five handles per level)
+void ensure_smoother_diag(hmg_grid *g, int top, hmg_vec **states);
+void release_smoother_diag(hmg_grid *g);
 // zero_guess (top level only; below it always holds): x is to be taken as zero whatever it holds -- never written where the
 // smoother's form allows that (zero_entry_ok), filled first otherwise: the same bits either way
 void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top = true, bool zero_guess = false);

@@ -3,6 +3,7 @@
 // (hmg_smooth, hmg_vcycle*, hmg_level_tune_placement, hmg_grid_reserve_spare).
 #include "../../include/hmg.h"
 #include "hmg_objects.hpp"
+#include "hmg_pcg.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -285,7 +286,9 @@ SmoothForm smooth_form(const hmg_grid *g, int level, int steps, Role role)
     const bool lean = c->lean_post && (role == Role::PostTop || role == Role::PostBelow);
     const bool dead = role == Role::Pre || (lean && role == Role::PostBelow);
     SmoothForm f;
-    if (!g->fuse_cg) {
+    // (the Jacobi-preconditioned smoother has the tails of the unfused path and nothing else: no pointer exchange, no riding face
+    //  sums, no deferred x-updates)
+    if (!g->fuse_cg || g->smoother == 1) {
         f.tail = dead ? Tail::DeadXp : lean ? Tail::ScratchP : Tail::Full;
         return f;
     }
@@ -352,20 +355,71 @@ void release_top_spare(hmg_grid *g)
 // the three-update form applies to: 3D grids whose finest level has face interiors (smooth_form(): Top3)
 bool wants_top_spare(const hmg_grid *g, int level)
 {
-    return g->ctx && g->ctx->lazy_top > 1 && level == g->nlevels && g->dim == 3 && g->ld[(size_t)level - 1].nfi > 0;
+    return g->ctx && g->smoother == 0 && g->ctx->lazy_top > 1 && level == g->nlevels && g->dim == 3 && g->ld[(size_t)level - 1].nfi > 0;
+}
+
+// The inverse diagonals of the Jacobi-preconditioned smoother, level by level: the cell-local diagonal, its interface sum (on a
+// partitioned grid with the cut exchange -- every rank gets here in the same call), then the inversion off the constrained nodes.
+void ensure_smoother_diag(hmg_grid *g, int level, double *scratch)
+{
+    if (g->smoother != 1 || level < 2) return;
+    need(g->has_op, "operator not set");
+    need(g->dinv.size() == (size_t)g->nlevels && level <= g->nlevels, "Jacobi-preconditioned smoother: the inverse diagonals were not reserved");
+    if (!g->dinv_ready) {                        // a new generation: nothing formed, nothing counted
+        g->dinv_level_ready.assign((size_t)g->nlevels, 0);
+        g->dinv_build_counted = false;
+        g->dinv_ready = true;
+    }
+    if (g->dinv_level_ready[(size_t)level - 1]) return;
+    const LevelDev &lv = lev(g, level);
+    double *d = g->dinv[(size_t)level - 1]->p;
+    need(scratch != nullptr && scratch != d, "Jacobi-preconditioned smoother: no scratch vector to form the diagonal with");
+    // (a rank without cells launches nothing and still takes part in the exchanges)
+    for (int limb = diag_limbs() - 1; limb >= 0; --limb) {
+        launch_operator_diag(g->ctx->L, lv, g->md, g->lambda, limb, scratch);
+        interface_sum(g, lv, scratch);
+        launch_diag_accum(g->ctx->L, lv, g->md, scratch, d, limb);
+    }
+    launch_dinv_finish(g->ctx->L, lv, g->md, d);
+    g->dinv_level_ready[(size_t)level - 1] = 1;
+    if (!g->dinv_build_counted) {
+        g->ctx->smoother_diag_builds += 1;
+        g->dinv_build_counted = true;
+    }
+}
+
+void ensure_smoother_diag(hmg_grid *g, int top, hmg_vec **states)
+{
+    if (g->smoother != 1) return;
+    for (int level = 2; level <= top; ++level) ensure_smoother_diag(g, level, states[5 * (level - 1) + 4]->d);
+}
+
+void release_smoother_diag(hmg_grid *g)
+{
+    int64_t bytes = 0;
+    for (const auto &d : g->dinv)
+        if (d) bytes += (int64_t)(d->n * sizeof(double));
+    if (g->ctx) {
+        if (bytes > 0) (void)hipStreamSynchronize(g->ctx->stream);
+        g->ctx->smoother_diag_bytes -= bytes;
+    }
+    g->dinv.clear();
+    g->dinv_level_ready.clear();
+    g->dinv_ready = false;
 }
 
 namespace {
 
-DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
-                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
+// r = b - A x, constraint, interface sum (src/multigrid.jl:50): the first residual of both smoothers, with the forms its caller
+// may ask for -- x a zero that is not in memory (f.x_zero), the coarse-grid correction riding in the load phase (xcoarse, cx)
+void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, const SmoothForm &f, const hmg_vec *xcoarse,
+                    const DeferredX *cx)
 {
-    // ref: src/multigrid.jl:46-71
     const LevelDev &lv = lev(g, level);
     const Launch &L = g->ctx->L;
     const int64_t n = vec_len(x);
     {
-        ApplyArgs a{};                                                    // r = b - A x, constraint, interface sum
+        ApplyArgs a{};
         a.alpha = -1.0;
         a.lambda = g->lambda;
         a.x = x->d;
@@ -402,6 +456,71 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         } else {
             apply_then_sum(g, lv, a, false, -1, -1);
         }
+    }
+}
+
+// CG preconditioned by the inverse diagonal of the assembled operator (hmg_grid_set_smoother(grid, 1)), after first_residual():
+//   z = dinv o r;  p = z;  rz = r.z
+//   steps x { Ap = A p, constraint, interface sum;  alpha = rz / p.Ap;  x += alpha p;  r -= alpha Ap;
+//             rz' = r.(dinv o r);  p = dinv o r + (rz'/rz) p;  rz = rz' }
+// z is never stored; rz / rz' alternate between S_RS and S_RS2 as r.r does in smooth(), p.Ap is in S_PAP.  With fuse_cg the apply is
+// the fused step-0 launch (no x2, no xout: 16 B/DOF, p.Ap formed in its epilogue), else the plain apply and a dot product.  Tails:
+// those of the unfused path of smooth() (smooth_form()).
+void smooth_pcg(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_vec *p, hmg_vec *Ap, const SmoothForm &f)
+{
+    const LevelDev &lv = lev(g, level);
+    const Launch &L = g->ctx->L;
+    const int64_t n = vec_len(x);
+    need(g->dinv_ready && g->dinv.size() == (size_t)g->nlevels && g->dinv_level_ready[(size_t)level - 1] && g->dinv[(size_t)level - 1] &&
+             (g->dinv[(size_t)level - 1]->p || n == 0),
+         "Jacobi-preconditioned smoother: no inverse diagonal for this level");
+    need(f.tail == Tail::Full || f.tail == Tail::ScratchP || f.tail == Tail::DeadXp, "Jacobi-preconditioned smoother: unknown tail");
+    const double *dinv = g->dinv[(size_t)level - 1]->p;
+    int cur = S_RS, other = S_RS2;
+    launch_pcg_start(L, p->d, r->d, dinv, n, cur);                          // p = dinv o r; rz = r.p
+    scalar_sum(g, cur, 1);
+    for (int i = 0; i < steps; ++i) {
+        if (g->fuse_cg) {
+            ApplyArgs a{};                                                    // Ap = A p, constraint, interface sum; p.Ap
+            a.alpha = 1.0;
+            a.lambda = g->lambda;
+            a.x = p->d;
+            a.out = Ap->d;
+            a.flags = 1;
+            apply_then_sum(g, lv, a, true, S_PAP, -1);
+        } else {
+            apply(g, lv, 1.0, p->d, nullptr, Ap->d, 1);
+            interface_sum(g, lv, Ap->d);
+            launch_dot(L, p->d, Ap->d, n, S_PAP);
+            scalar_sum(g, S_PAP, 1);
+        }
+        const bool last = i == steps - 1;
+        if (last && f.tail != Tail::Full) {
+            if (f.tail == Tail::ScratchP) {
+                launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, cur, S_PAP, other);   // alpha = rz / p.Ap
+                scalar_sum(g, other, 1);
+            }
+            launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rz / p.Ap) p
+            return;
+        }
+        launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, cur, S_PAP, other);       // alpha = rz / p.Ap; rz'
+        scalar_sum(g, other, 1);
+        launch_pcg_xp(L, x->d, p->d, r->d, dinv, n, cur, S_PAP, other, cur);  // beta = rz' / rz
+        std::swap(cur, other);
+    }
+}
+
+DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
+                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
+{
+    // ref: src/multigrid.jl:46-71
+    const LevelDev &lv = lev(g, level);
+    const Launch &L = g->ctx->L;
+    const int64_t n = vec_len(x);
+    first_residual(g, level, x, b, r, f, xcoarse, cx);
+    if (g->smoother == 1) {
+        smooth_pcg(g, level, steps, x, r, p, Ap, f);
+        return {};
     }
     int cur = S_RS, other = S_RS2;
     if (!g->fuse_cg || steps <= 0) {
@@ -566,6 +685,7 @@ bool zero_entry_ok(const hmg_grid *g, int k, int steps)
 {
     if (!g->ctx->zero_entry) return false;
     if (k == 1) return true;
+    if (g->smoother == 1) return false;          // (its zero guesses are written)
     if (steps != 2 || smooth_form(g, k, steps, Role::Pre).tail != Tail::DeadDefer2) return false;
     // (register-blocked levels take that residual through the instantiation that also restricts in its epilogue -- the only one
     //  of theirs the zero-input form is compiled into)
@@ -665,7 +785,7 @@ DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, cons
 bool coarse_x_folds(const hmg_grid *g, int k, int steps_below)
 {
     const hmg_ctx *c = g->ctx;
-    if (k < 3 || !c->fold_coarse_x || !c->lazy_post || !c->fold_prolong || !c->lean_post || !g->fuse_cg || !c->prolong_in_image) return false;
+    if (k < 3 || g->smoother == 1 || !c->fold_coarse_x || !c->lazy_post || !c->fold_prolong || !c->lean_post || !g->fuse_cg || !c->prolong_in_image) return false;
     const LevelDev &lv = g->ld[(size_t)k - 1];
     if (!(apply_lds_bytes(lv) > 48 * 1024 && apply_lds_bytes(lv) <= 160 * 1024 &&
           apply_lds_bytes(lv) + sizeof(double) * (size_t)g->ld[(size_t)k - 2].nf <= 80 * 1024))
@@ -718,6 +838,58 @@ int hmg_grid_reserve_spare(hmg_grid *g, int enable)
     HMG_END
 }
 
+// The smoother of a grid: 0 = the reference's CG (default), 1 = CG preconditioned by the inverse diagonal of the assembled operator.
+// Kind 1 reserves one vector per level >= 2 here (setup memory; formed at the next call that smooths); kind 0 hands them back.
+int hmg_grid_set_smoother(hmg_grid *g, int kind)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only)");
+    need(kind == 0 || kind == 1, "smoother kind must be 0 (CG) or 1 (Jacobi-preconditioned CG)");
+    HIPCHK(hipSetDevice(g->ctx->device));
+    if (kind == 1 && g->dinv.size() != (size_t)g->nlevels) {
+        release_smoother_diag(g);
+        std::vector<std::unique_ptr<DevBuf<double>>> bufs((size_t)g->nlevels);
+        int64_t bytes = 0;
+        for (int level = 2; level <= g->nlevels; ++level) {
+            const size_t n = (size_t)g->ld[(size_t)level - 1].ld * (size_t)g->mesh_full.ncells;
+            bufs[(size_t)level - 1].reset(new DevBuf<double>);
+            try {
+                bufs[(size_t)level - 1]->alloc(n);
+            } catch (const std::exception &) {
+                (void)hipGetLastError();
+                throw std::runtime_error("hmg_grid_set_smoother: the inverse diagonal of level " + std::to_string(level) + " (" +
+                                         std::to_string((n * sizeof(double)) >> 20) + " MiB) does not fit the device memory; the smoother is unchanged");
+            }
+            bytes += (int64_t)(n * sizeof(double));
+        }
+        g->dinv = std::move(bufs);
+        g->ctx->smoother_diag_bytes += bytes;
+    }
+    if (kind == 0) {
+        release_smoother_diag(g);
+        // (a vector of the finest level created from now on brings the spare direction vector of the CG forms as it always did)
+    }
+    g->smoother = kind;
+    g->dinv_ready = false;
+    g->op_epoch += 1;                            // an hmg_fcg object's direction belongs to the old preconditioner
+    HMG_END
+}
+
+int hmg_grid_smoother(const hmg_grid *g) { return g ? g->smoother : -1; }
+
+int hmg_grid_smoother_diag(hmg_grid *g, int level, hmg_vec *out)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(g->smoother == 1, "hmg_grid_smoother_diag: the grid's smoother has no diagonal (hmg_grid_set_smoother(grid, 1))");
+    need(level >= 2 && level <= g->nlevels, "level out of range (2..nlevels: level 1 has no smoother)");
+    check_vec(g, level, out, "out");
+    ensure_smoother_diag(g, level, out->d);
+    launch_copy(g->ctx->L, out->d, g->dinv[(size_t)level - 1]->p, vec_len(out));
+    HMG_END
+}
+
 // ---- fused fast path ----------------------------------------------------------------------------
 int hmg_smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap)
 {
@@ -728,6 +900,7 @@ int hmg_smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_ve
     check_vec(g, level, r, "r");
     check_vec(g, level, p, "p");
     check_vec(g, level, Ap, "Ap");
+    ensure_smoother_diag(g, level, Ap->d);
     smooth(g, level, steps, x, b, r, p, Ap, smooth_form(g, level, steps, Role::Plain));
     HMG_END
 }
@@ -758,6 +931,7 @@ int hmg_level_tune_placement(hmg_grid *g, int level, int steps, hmg_vec **states
     }
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
+    ensure_smoother_diag(g, level, state[4]->d);
     const size_t bytes = state[0]->bytes;
     const int64_t n = vec_len(state[0]);
     std::vector<double *> blk;
@@ -870,6 +1044,7 @@ int hmg_vcycle(hmg_grid *g, int top_level, int steps, int steps_coarse, hmg_vec 
     need(top_level >= 1 && top_level <= g->nlevels, "top_level out of range");
     for (int l = 1; l <= top_level; ++l)
         for (int q = 0; q < 5; ++q) check_vec(g, l, states[5 * (l - 1) + q], "states[]");
+    ensure_smoother_diag(g, top_level, states);
     vcycle(g, top_level, steps, steps_coarse, states);
     HMG_END
 }
@@ -886,6 +1061,7 @@ int hmg_vcycle_down(hmg_grid *g, int level, int steps, hmg_vec **states)
 {
     HMG_TRY
     check_two_levels(g, level, states);
+    ensure_smoother_diag(g, level, states[5 * (level - 1) + 4]->d);
     g->ctx->last_pre_form = vcycle_down(g, level, steps, states);
     HMG_END
 }
@@ -894,6 +1070,7 @@ int hmg_vcycle_up(hmg_grid *g, int level, int steps, hmg_vec **states)
 {
     HMG_TRY
     check_two_levels(g, level, states);
+    ensure_smoother_diag(g, level, states[5 * (level - 1) + 4]->d);
     (void)vcycle_up(g, level, steps, states, Role::PostTop);   // as the finest level of hmg_vcycle
     HMG_END
 }

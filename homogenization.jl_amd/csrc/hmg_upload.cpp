@@ -301,6 +301,7 @@ void set_cut_kind(hmg_grid *g, int k, int64_t nglobal, int64_t n, const int64_t 
     }
     g->cutlv.clear();                            // buffer layouts are rebuilt at the next exchange
     g->cut_agreed_ready = false;                 // ... and the ranks agree on the size of the new cut at the next apply
+    g->dinv_ready = false;                       // ... and the smoother's diagonal is summed across the new cut
     DryUploads dry_scope(!g->ctx, &g->upload_hash);
     c.cell_lid.upload(hc, g->ctx ? g->ctx->stream : nullptr);
     c.first.upload(first, g->ctx ? g->ctx->stream : nullptr);
@@ -400,6 +401,7 @@ int hmg_grid_set_operator(hmg_grid *g, const double *sigma, double lambda)
     g->lambda = lambda;
     g->has_op = true;
     g->op_epoch += 1;
+    g->dinv_ready = false;
     upload_operator(g);
     HMG_END
 }
@@ -410,6 +412,7 @@ int hmg_grid_set_lambda(hmg_grid *g, double lambda)
     need(g != nullptr, "null grid");
     g->lambda = lambda;
     g->op_epoch += 1;
+    g->dinv_ready = false;
     g->coarse_ready = false;
     if (g->ctx && g->has_op) ensure_weight_cache(g);
     HMG_END
@@ -420,6 +423,7 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
     HMG_TRY
     need(g != nullptr, "null grid");
     g->op_epoch += 1;
+    g->dinv_ready = false;
     if (g->part) {
         // prefix of the GLOBAL mesh: this rank keeps its cells with a global id below the prefix length (local
         // cells are in ascending global order, so that is a prefix of every local level vector as well); cut

@@ -358,14 +358,16 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
                                             smoothing_steps: int = 3, tolerance: float = 1e-4, xi=None, seed: int = 0,
                                             values=(1.0, 9.0), sigma_grid=None, x0=None, max_cycles: int = 1000,
                                             group=None, log=None, backend=None, stats: dict | None = None,
-                                            accelerate: bool = False):
+                                            accelerate: bool = False, smoother: str = "cg"):
     """driver.checkerboard_homogenization over `world` ranks (one GPU each): the base mesh is split into blocks about
     the origin (halves / quadrants / octants for 2, 4, 8 ranks), so that the centred sub-domains the outer loop
     shrinks to stay balanced.  Every rank runs the same host loop; the per-cycle integrals are local sums
     added over the ranks, everything else goes through the partitioned V-cycle.  Returns (sigma, history) like the
     single-GPU driver, identical on every rank.  `stats` (a dict) receives "inexact_vcycles": V-cycles whose budgeted level-1 solve
     missed coarse_rtol (every rank sees the same replicated solve, hence the same count).  `accelerate`: as in the single-GPU
-    driver (api.FlexibleCG; per iteration two small sums over the ranks are all it adds to the V-cycle's communication)."""
+    driver (api.FlexibleCG; per iteration two small sums over the ranks are all it adds to the V-cycle's communication).
+    `smoother`: as in the single-GPU driver ("cg" or "jacobi"; the inverse diagonals are summed across the cut once per operator,
+    on every rank in the same call); reported in stats["smoother"]."""
     dim = api._dim_of(eltype)
     # the blocks are halves per axis about the origin: 1, 2, 4 (and 8 in 3D) ranks.  Checked on every rank before any
     # collective, so that an unsupported size fails everywhere instead of hanging the ranks that do own cells
@@ -387,6 +389,7 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
     owner = block_owner(base, blocks, width / 2.0, origin)          # halves per axis; axes with one block clamp to 0
     total_grids = refinements + 1
     grid = PartitionedGrid(ctx, base, total_grids, owner, rank, world)
+    grid.set_smoother(smoother)                          # (before the level vectors)
     ex = Exchange(ctx, grid, group, backend)
     op = api.L2PlusDivAGrad(grid, lam, cond)
     states = [api.LevelState(grid, i + 1) for i in range(total_grids)]
@@ -451,6 +454,7 @@ def partitioned_checkerboard_homogenization(ctx, n: int, eltype, world: int, ran
         api.next_rhs(top.b, xv, grid)
     if stats is not None:
         stats["inexact_vcycles"] = inexact
+        stats["smoother"] = smoother
     if accelerate:
         fcg.close()
         xv.close()
@@ -461,11 +465,11 @@ def partitioned_checkerboard_homogenization_tensor(ctx, n: int, eltype, world: i
                                                    smoothing_steps: int = 3, tolerance: float = 1e-4, seed: int = 0,
                                                    values=(1.0, 9.0), sigma_grid=None, x0=None, max_cycles: int = 1000,
                                                    group=None, log=None, backend=None, stats: dict | None = None,
-                                                   accelerate: bool = False):
+                                                   accelerate: bool = False, smoother: str = "cg"):
     """driver.checkerboard_homogenization_tensor over `world` ranks, partitioned like partitioned_checkerboard_homogenization:
     the same loop (d corrector solves per outer step on one grid, then the off-diagonal increments from the pair integrals),
     with every integral a local sum added over the ranks -- the shares of all pairs of a step in one call.  Returns
-    (Sigma, history) like the single-GPU driver, identical on every rank."""
+    (Sigma, history) like the single-GPU driver, identical on every rank.  `accelerate`, `smoother`, `stats`: as there."""
     dim = api._dim_of(eltype)
     if world not in ((1, 2, 4) if dim == 2 else (1, 2, 4, 8)):
         raise ValueError(f"partitioned_checkerboard_homogenization_tensor: {world} ranks are not supported in {dim}D "
@@ -484,6 +488,7 @@ def partitioned_checkerboard_homogenization_tensor(ctx, n: int, eltype, world: i
     owner = block_owner(base, block_shape(world, dim), width / 2.0, origin)
     total_grids = refinements + 1
     grid = PartitionedGrid(ctx, base, total_grids, owner, rank, world)
+    grid.set_smoother(smoother)                          # (before the level vectors)
     ex = Exchange(ctx, grid, group, backend)
     op = api.L2PlusDivAGrad(grid, lam, cond)
     ops = [op] * total_grids
@@ -557,6 +562,7 @@ def partitioned_checkerboard_homogenization_tensor(ctx, n: int, eltype, world: i
         op.lam = lam
     if stats is not None:
         stats["inexact_vcycles"] = inexact
+        stats["smoother"] = smoother
     if accelerate:
         fcg.close()
         xv.close()

@@ -125,7 +125,8 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "lazy_pre_form" (the x-updates the
    last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
-   hmg_fcg objects); -1 for an unknown name.  No counterpart in
+   hmg_fcg objects), "smoother_diag_bytes" (inverse diagonals held by this context's grids, see hmg_grid_set_smoother) and
+   "smoother_diag_builds" (times a grid of this context formed them); -1 for an unknown name.  No counterpart in
    the reference. */
 int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name);
 
@@ -151,6 +152,25 @@ int hmg_grid_shrink(hmg_grid *grid, int64_t ncells_prefix, int64_t nnodes_prefix
  * two-update form: hmg_ctx_counter "lazy_top_form" / "spare_bytes"), or explicitly here: enable = 1 reserves it now and FAILS if
  * the memory is not there; enable = 0 releases it and keeps it released (the five-vector footprint of the reference). */
 int hmg_grid_reserve_spare(hmg_grid *grid, int enable);
+/* The smoother of hmg_smooth, hmg_vcycle*, hmg_fcg_*: kind 0 = the reference's CG (src/multigrid.jl:46-71, the default), kind 1 = CG
+ * preconditioned by the inverse of the assembled operator's diagonal (no counterpart in the reference):
+ *     dinv = 0 on constrained nodes, else 1 / (interface sum of the cell-local diagonal of lambda M + K_sigma)
+ *     r = b - A x, constraint, interface sum;  z = dinv o r;  p = z;  rz = dot(r, z)
+ *     steps x { Ap = A p, constraint, interface sum;  alpha = rz / dot(p, Ap);  x += alpha p;  r -= alpha Ap;
+ *               rz' = dot(r, dinv o r);  p = dinv o r + (rz'/rz) p;  rz = rz' }
+ * (dot over the raw storage, copies counted, as hmg_vec_dot).  The V-cycle around it is unchanged.  On a checkerboard of contrast
+ * 100 it needs a fraction of the cycles of kind 0 at about 1.5 times the traffic per cycle.
+ * Kind 1 reserves one vector per level >= 2 (setup memory, hmg_ctx_counter "smoother_diag_bytes") and FAILS if the memory is not
+ * there; kind 0 releases them.  The diagonals go stale with hmg_grid_set_operator, hmg_grid_set_lambda, hmg_grid_shrink,
+ * hmg_grid_set_smoother and a change of cut or exchange, and are formed again (kernels only, no allocation) at the next
+ * hmg_smooth / hmg_vcycle* / hmg_fcg_start / hmg_fcg_step / hmg_grid_smoother_diag, before that call's first launch -- on a
+ * partitioned grid with five cut exchanges per level (the diagonal is summed in fixed point, limb by limb: the same bits whatever the
+ * partition), so all ranks make that call together; a level is formed by the first such call that smooths on it.  Changing the smoother counts as a new
+ * operator for an hmg_fcg object (hmg_fcg_step then asks for hmg_fcg_start).  A grid without a device context is refused. */
+int hmg_grid_set_smoother(hmg_grid *grid, int kind);
+int hmg_grid_smoother(const hmg_grid *grid);           /* the kind; -1 for a null grid */
+/* out = dinv of the level (2..nlevels), formed first if it is stale; kind 1 only */
+int hmg_grid_smoother_diag(hmg_grid *grid, int level, hmg_vec *out);
 int64_t hmg_grid_ncells(const hmg_grid *grid);
 int64_t hmg_grid_nnodes(const hmg_grid *grid);
 int hmg_grid_nlevels(const hmg_grid *grid);

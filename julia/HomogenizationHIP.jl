@@ -148,6 +148,16 @@ Base.Array(v::HipMatrix) =
     (a = Matrix{Float64}(undef, size(v)...); check(ccall((:hmg_vec_download, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), v.h, a)); a)
 Base.fill!(v::HipMatrix, x) = (check(ccall((:hmg_vec_fill, LIB), Cint, (Ptr{Cvoid}, Float64), v.h, x)); v)
 Base.copyto!(d::HipMatrix, s::HipMatrix) = (check(ccall((:hmg_vec_copy, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), d.h, s.h)); d)
+# The smoother of smoothing_steps! / vcycle! / the flexible CG on this grid (include/hmg.h: hmg_grid_set_smoother): :cg is the
+# reference's (default), :jacobi is CG preconditioned by the inverse diagonal of the assembled operator.  :jacobi reserves one vector
+# per level >= 2 (an error if the device memory is not there): set it before the level vectors are created.
+const SMOOTHERS = Dict(:cg => 0, :jacobi => 1)
+set_smoother!(g::HipGrid, kind::Symbol = :cg) =
+    check(ccall((:hmg_grid_set_smoother, LIB), Cint, (Ptr{Cvoid}, Cint), g.h, SMOOTHERS[kind]))
+smoother(g::HipGrid) = (k = ccall((:hmg_grid_smoother, LIB), Cint, (Ptr{Cvoid},), g.h); k == 1 ? :jacobi : :cg)
+# the level's inverse diagonal as the :jacobi smoother uses it (0 on constrained nodes), formed first if it is stale
+smoother_diag!(out::HipMatrix, g::HipGrid, level::Integer) =
+    (check(ccall((:hmg_grid_smoother_diag, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), g.h, level, out.h)); out)
 # rand!(x) (src/examples/homogenized_coefficients.jl:246): seeded and layout independent on the device
 rand!(v::HipMatrix; seed::Integer = 1, cell_offset::Integer = 0) =
     (check(ccall((:hmg_vec_fill_random, LIB), Cint, (Ptr{Cvoid}, UInt64, Int64), v.h, seed, cell_offset)); v)

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Wall-clock of the whole driver to a tolerance: device path vs the CPU oracle, identical inputs.
-  python tools/driver_bench.py --n 1 --dim 3 --refinements 4 --tolerance 1e-5 [--no-cpu] [--accelerate] [--contrast 100]
+  python tools/driver_bench.py --n 1 --dim 3 --refinements 4 --tolerance 1e-5 [--no-cpu] [--accelerate] [--contrast 100] [--smoother jacobi]
 --accelerate: the V-cycle preconditions a flexible CG iteration (driver.checkerboard_homogenization(accelerate=True)); the CPU
 oracle has the stationary iteration only, so --accelerate implies --no-cpu.
+--smoother jacobi: the V-cycle's smoother is the Jacobi-preconditioned CG (driver keyword smoother="jacobi"); the CPU oracle has the
+reference's smoother only, so it implies --no-cpu as well.
 --tensor [--repeats R] [--warmup W]: the full homogenized tensor.  One run of driver.checkerboard_homogenization_tensor (d corrector
 solves, one setup) against the d (d + 1) / 2 runs of the scalar driver that polarising by hand takes (xi = e_i and
 (e_i + e_j) / sqrt 2), same field, same seed, in one process: W untimed rounds of both first (code objects, the pool of
@@ -22,6 +24,7 @@ ap.add_argument("--refinements", type=int, default=4)
 ap.add_argument("--tolerance", type=float, default=1e-5)
 ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--accelerate", action="store_true")
+ap.add_argument("--smoother", choices=("cg", "jacobi"), default="cg")
 ap.add_argument("--contrast", type=float, default=9.0, help="sigma takes the values 1 and this")
 ap.add_argument("--tensor", action="store_true", help="one tensor run against d (d + 1) / 2 scalar runs")
 ap.add_argument("--repeats", type=int, default=3)
@@ -32,7 +35,8 @@ sgrid = driver.generate_conductivity(a.dim, width, 5, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
 if a.tensor:
-    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, seed=7, accelerate=a.accelerate)
+    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, seed=7, accelerate=a.accelerate,
+              smoother=a.smoother)
     E = np.eye(a.dim)
     pairs = [(i, j) for i in range(a.dim) for j in range(i + 1, a.dim)]
 
@@ -66,8 +70,8 @@ if a.tensor:
         t, S_s, cyc_s = scalar_runs()
         ts.append(t)
     print(json.dumps({"config": f"checkerboard_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, "
-                                f"tolerance={a.tolerance})", "width": width, "accelerate": a.accelerate, "contrast": a.contrast,
-                      "warmup": a.warmup, "repeats": a.repeats, "scalar_runs_per_round": a.dim + len(pairs),
+                                f"tolerance={a.tolerance})", "width": width, "accelerate": a.accelerate, "smoother": a.smoother,
+                      "contrast": a.contrast, "warmup": a.warmup, "repeats": a.repeats, "scalar_runs_per_round": a.dim + len(pairs),
                       "wall_s_tensor": tt, "wall_s_scalar_runs": ts, "median_s_tensor": float(np.median(tt)),
                       "median_s_scalar_runs": float(np.median(ts)), "ratio_scalar_over_tensor": float(np.median(ts) / np.median(tt)),
                       "vcycles_tensor": cyc_t, "vcycles_scalar_runs": cyc_s, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
@@ -78,14 +82,15 @@ if a.tensor:
 tm = {}
 t0 = time.perf_counter()
 sig, hist = driver.checkerboard_homogenization(a.n, tag, refinements=a.refinements, tolerance=a.tolerance, ctx=ctx,
-                                               sigma_grid=sgrid, seed=7, timings=tm, accelerate=a.accelerate)
+                                               sigma_grid=sgrid, seed=7, timings=tm, accelerate=a.accelerate,
+                                               smoother=a.smoother)
 ctx.sync()
 t_gpu = time.perf_counter() - t0
 out = {"config": f"checkerboard_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
        "width": width, "sigma_gpu": sig, "vcycles": len(hist), "wall_s_gpu_incl_setup": t_gpu,
-       "accelerate": a.accelerate, "contrast": a.contrast, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
+       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
        "outer_steps": tm["outer_steps"], "inexact_vcycles": tm["inexact_vcycles"]}
-if not (a.no_cpu or a.accelerate):
+if not (a.no_cpu or a.accelerate or a.smoother != "cg"):
     from oracle import oracle as O
     nf = hist and None
     impl_nf = {2: [3, 6, 15, 45, 153, 561], 3: [4, 10, 35, 165, 969, 6545]}[a.dim][a.refinements]
