@@ -42,6 +42,7 @@ SIGNATURES = {
     "hmg_grid_create": (c_int, [vp, c_int, c_int, c_i64, p_f64, c_i64, p_i64, pp]),
     "hmg_grid_destroy": (c_int, [vp]),
     "hmg_grid_set_operator": (c_int, [vp, p_f64, c_f64]),
+    "hmg_grid_set_operator_tensor": (c_int, [vp, p_f64, c_f64]),
     "hmg_grid_set_lambda": (c_int, [vp, c_f64]),
     "hmg_grid_shrink": (c_int, [vp, c_i64, c_i64]),
     "hmg_grid_reserve_spare": (c_int, [vp, c_int]),

@@ -50,6 +50,23 @@ class Mesh:
         return self.nodes.shape[1]
 
 
+def pack_sigmas(sigmas, ncells, dim):
+    """Per-cell conductivities as the library takes them: (ncells, dim) -- diagonal tensors -- stays as it is; (ncells, dim, dim)
+    must be symmetric (ValueError otherwise) and is packed to the upper triangle by rows, (ncells, dim (dim + 1) / 2): 3D 11, 12, 13,
+    22, 23, 33; 2D 11, 12, 22 (hmg_grid_set_operator_tensor).  Returns (array, is_tensor)."""
+    s = np.asarray(sigmas, dtype=np.float64)
+    if s.shape == (ncells, dim):
+        return np.ascontiguousarray(s), False
+    if s.shape != (ncells, dim, dim):
+        raise ValueError(f"sigmas must have shape ({ncells}, {dim}) or ({ncells}, {dim}, {dim}), not {s.shape}")
+    st = np.swapaxes(s, 1, 2)
+    asym = (s != st) & ~(np.isnan(s) & np.isnan(st))       # (what is not finite is the library's to refuse)
+    if asym.any():
+        raise ValueError(f"the tensor of cell {int(np.argwhere(asym)[0][0])} is not symmetric")
+    iu = np.triu_indices(dim)
+    return np.ascontiguousarray(s[:, iu[0], iu[1]]), True
+
+
 class Context:
     """One GPU + one HIP stream. stream: a raw hipStream_t (int) such as
     torch.cuda.current_stream().cuda_stream, or None for a library-owned stream."""
@@ -193,9 +210,10 @@ class ImplicitFineGrid:
 
     # -- operator / domain -------------------------------------------------------------------
     def set_operator(self, sigmas, lam):
-        s = np.ascontiguousarray(sigmas, dtype=np.float64)
-        assert s.shape == (self.base.elements.shape[0], self.base.dim)
-        L.check(self._lib.hmg_grid_set_operator(self.h, s.ctypes.data_as(L.p_f64), float(lam)))
+        """sigmas: (ncells, dim) diagonal tensors, or (ncells, dim, dim) full symmetric ones (pack_sigmas)."""
+        s, tensor = pack_sigmas(sigmas, self.base.elements.shape[0], self.base.dim)
+        entry = self._lib.hmg_grid_set_operator_tensor if tensor else self._lib.hmg_grid_set_operator
+        L.check(entry(self.h, s.ctypes.data_as(L.p_f64), float(lam)))
 
     def set_lambda(self, lam):
         L.check(self._lib.hmg_grid_set_lambda(self.h, float(lam)))
@@ -344,13 +362,15 @@ class _Operator:
 
 class L2PlusDivAGrad(_Operator):
     """lam*I - div(sigma grad), sigma constant per coarse cell; carries the Dirichlet constraint
-    (held by the grid).  Mutable lam like the reference's struct.  ref: src/build_local_operators.jl:26-32"""
+    (held by the grid).  Mutable lam like the reference's struct.  ref: src/build_local_operators.jl:26-32
+    sigmas: (ncells, dim), the diagonals of diagonal tensors as in the reference, or (ncells, dim, dim), full symmetric
+    tensors (ValueError if one is not symmetric; the library refuses one that is not positive definite)."""
 
     def __init__(self, implicit: ImplicitFineGrid, lam: float, sigmas):
         self.implicit = implicit
         self._lam = float(lam)
         self.sigmas = np.ascontiguousarray(sigmas, dtype=np.float64)
-        self._bind()
+        self._bind()                 # (set_operator packs, and checks symmetry, before the library is called)
 
     @property
     def lam(self):

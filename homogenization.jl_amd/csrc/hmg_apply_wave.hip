@@ -450,22 +450,25 @@ k_apply_wave(LevelDev lv, const uint16_t *__restrict__ dmask, const int32_t *__r
 // W[class][sign][entity class][16]: the weights k_apply forms per cell (cell_scales + the seven-term sums, same order --
 // bit-identical), once per distinct coefficient row
 __global__ void __launch_bounds__(256)
-k_weight_cache(LevelDev lv, const double *__restrict__ coef_rep, double lambda, double *__restrict__ wcache)
+k_weight_cache(LevelDev lv, const double *__restrict__ coef_rep, int64_t nsets, double lambda, double *__restrict__ wcache)
 {
-    const int cls = blockIdx.x >> 1;
-    const double alpha = (blockIdx.x & 1) ? -1.0 : 1.0;
-    double s[7];
-    cell_scales<3>(coef_rep + (size_t)cls * 8, alpha, lambda, s, 0);
-    double *out = wcache + (size_t)blockIdx.x * WAVE_WSTRIDE;
-    for (int idx = threadIdx.x; idx < 15 * WAVE_ROW; idx += 256) {
-        const int c = idx / WAVE_ROW, d = idx % WAVE_ROW;
-        double w = 0.0;
-        if (c < lv.ncls && d < 15) {
-            const double *ct = lv.ctab + ((size_t)c * 15 + d) * 7;
+    // (a bounded grid walks the 2 x classes weight sets: the launch holds at any number of classes)
+    for (int64_t set = blockIdx.x; set < nsets; set += gridDim.x) {
+        const int64_t cls = set >> 1;
+        const double alpha = (set & 1) ? -1.0 : 1.0;
+        double s[7];
+        cell_scales<3>(coef_rep + (size_t)cls * 8, alpha, lambda, s, 0);
+        double *out = wcache + (size_t)set * WAVE_WSTRIDE;
+        for (int idx = threadIdx.x; idx < 15 * WAVE_ROW; idx += 256) {
+            const int c = idx / WAVE_ROW, d = idx % WAVE_ROW;
+            double w = 0.0;
+            if (c < lv.ncls && d < 15) {
+                const double *ct = lv.ctab + ((size_t)c * 15 + d) * 7;
 #pragma unroll
-            for (int t = 0; t < 7; ++t) w += ct[t] * s[t];
+                for (int t = 0; t < 7; ++t) w += ct[t] * s[t];
+            }
+            out[idx] = w;
         }
-        out[idx] = w;
     }
 }
 
@@ -473,7 +476,9 @@ void launch_weight_cache(const Launch &L, const LevelDev &lv, const double *coef
 {
     if (nclasses <= 0) return;
     if (lv.dim != 3 || lv.ncls != 15 || lv.ndir != 15 || lv.nterm != 7) throw std::runtime_error("weight cache: not a 3D level");
-    hipLaunchKernelGGL(k_weight_cache, dim3((unsigned)(2 * nclasses)), dim3(256), 0, L.stream, lv, coef_rep, lambda, wcache);
+    const int64_t nsets = 2 * (int64_t)nclasses;
+    const int64_t grid = std::min<int64_t>(nsets, (int64_t)1 << 20);       // (2^20 blocks x 256 threads: inside every launch limit)
+    hipLaunchKernelGGL(k_weight_cache, dim3((unsigned)grid), dim3(256), 0, L.stream, lv, coef_rep, nsets, lambda, wcache);
     check_launch();
 }
 

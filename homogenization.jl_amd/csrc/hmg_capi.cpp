@@ -228,14 +228,19 @@ int hmg_rhs_axi_grad(hmg_grid *g, const double *xi, hmg_vec *b)
     check_vec(g, b->level, b, "b");
     const MeshTables &M = g->cur();
     const int dim = g->dim;
-    // P = -detJ * (Jinv' * (sigma .* xi))   (ref: ...homogenized_coefficients.jl:468)
+    // P = -detJ * (Jinv' * (sigma .* xi))   (ref: ...homogenized_coefficients.jl:468); a full tensor: sigma * xi
+    const int sn = g->sig_n;
     std::vector<double> pv((size_t)M.ncells * 3, 0.0);
     for (int64_t c = 0; c < M.ncells; ++c) {
         const double *Ji = &M.jinv[(size_t)c * dim * dim];
-        const double *sg = &g->sigma[(size_t)c * dim];
+        const double *sg = &g->sigma[(size_t)c * sn];
+        double sx[3] = {0.0, 0.0, 0.0};
+        if (sn != dim)
+            for (int k = 0; k < dim; ++k)
+                for (int l = 0; l < dim; ++l) sx[k] += sg[sym_index(dim, k, l)] * xi[l];
         for (int a = 0; a < dim; ++a) {
             double s = 0.0;
-            for (int k = 0; k < dim; ++k) s += Ji[k + dim * a] * (sg[k] * xi[k]);
+            for (int k = 0; k < dim; ++k) s += Ji[k + dim * a] * (sn != dim ? sx[k] : sg[k] * xi[k]);
             pv[(size_t)c * 3 + a] = -M.detj[c] * s;
         }
     }

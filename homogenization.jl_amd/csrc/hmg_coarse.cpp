@@ -66,7 +66,7 @@ void coarse_setup(hmg_grid *g)
 {
     need(g->has_op, "hmg_grid_set_operator must be called first");
     const MeshTables &M = g->part ? g->part->global : g->cur();
-    assemble_coarse_matrix(M, g->part ? g->sigma_global.data() : g->sigma.data(), g->lambda, g->cm);
+    assemble_coarse_matrix(M, g->part ? g->sigma_global.data() : g->sigma.data(), g->sig_n, g->lambda, g->cm);
     DryUploads dry_scope(!g->ctx, &g->upload_hash);
     hipStream_t s = g->ctx ? g->ctx->stream : nullptr;
     g->c_rowptr.upload(g->cm.rowptr, s);

@@ -140,6 +140,7 @@ void grid_unref(hmg_grid *grid)
     }
     probe_unlist(grid);
     release_top_spare(grid);
+    release_weight_cache(grid);
     release_smoother_diag(grid);
     if (grid->probe && grid->probe->h) (void)hipHostFree(grid->probe->h);
     if (grid->probe && grid->probe->ev) (void)hipEventDestroy(grid->probe->ev);
@@ -208,6 +209,7 @@ static int ctx_create(int device, void *stream, bool use_given, hmg_ctx **out)
     c->L.apply_pack = 1;    // level 2: four cells per wave
     c->L.apply_small = 1;   // levels 2-4: pipelined one-wave kernel (hmg_apply_small.hip)
     c->L.n_small_launches = &c->small_launches;
+    c->L.n_wc_launches = &c->wc_launches;
     c->L.apply_wg512 = 1;   // level 6: three 512-thread workgroups per CU (measured: V-cycle 149.5 -> 141 ms; 3 x 640 threads do not fit the wave slots: 174 ms)
     {
         LifetimeLock lock(lifetime_mutex());
@@ -245,9 +247,13 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "slab2_launches") return ctx->slab2_launches;
     if (n == "rows_launches") return ctx->rows_launches;
     if (n == "small_launches") return ctx->small_launches;
+    if (n == "weight_cache_launches") return ctx->wc_launches;
     if (n == "comm_calls") return ctx->comm_calls;
     if (n == "device_allocs") return device_allocs().load();
     if (n == "spare_bytes") return ctx->spare_bytes;
+    if (n == "weight_cache_classes") return ctx->wc_classes;
+    if (n == "weight_cache_bytes") return ctx->wc_bytes;
+    if (n == "weight_cache_refusals") return ctx->wc_refusals;
     if (n == "fcg_bytes") return ctx->fcg_bytes;
     if (n == "smoother_diag_bytes") return ctx->smoother_diag_bytes;
     if (n == "smoother_diag_builds") return ctx->smoother_diag_builds;
@@ -293,6 +299,8 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         ctx->L.apply_small = value != 0;
     else if (n == "weight_cache")          // 1 = default; 0: level 6 combines its class weights per cell (A/B knob)
         ctx->L.weight_cache = value != 0;
+    else if (n == "weight_cache_classes")  // most distinct coefficient rows that still get a cache at the next operator (0 = default: no limit)
+        ctx->wc_max_classes = std::max<int64_t>(0, value);
     else if (n == "apply_slab2")           // 1 = default; 0: cells larger than the LDS keep k_apply_slab (A/B knob)
         ctx->L.apply_slab2 = value != 0;
     else if (n == "restrict_slab2")        // 1 = default; 0: the stand-alone restriction keeps k_apply_slab (A/B knob)

@@ -200,6 +200,7 @@ struct Launch {
     int apply_pack;       // 1 (default): cells of at most 16 nodes (3D level 2) four to a wave (k_apply_pack)
     int apply_small;      // 1 (default): levels 2-4 (3D, <= 192 nodes per cell) take the pipelined one-wave kernel where the cache exists
     int64_t *n_small_launches;
+    int64_t *n_wc_launches;
     int apply_wave;       // 1 (default): level 5 takes the one-wave-per-cell kernel where the class-weight cache exists
     int64_t wave_grid;    // its grid: waves resident at once (16 per CU)
     int64_t *n_wave_launches;   // counts its launches (hmg_ctx_counter "wave_launches"; tests check that the path is taken)

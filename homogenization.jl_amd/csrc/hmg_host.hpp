@@ -178,9 +178,18 @@ void restrict_mesh_tables(const MeshTables &full, int64_t ncells_prefix, int64_t
                           MeshTables &out);
 
 // Per-cell operator coefficients: coef[cell*8 + t] = |J| * P_t for the unique entries of
-// P = J^-1 diag(sigma) J^-T (3D: 11,12,13,22,23,33; 2D: 11,12,22), then |J| at t = nterm-1.
+// P = J^-1 sigma J^-T (3D: 11,12,13,22,23,33; 2D: 11,12,22), then |J| at t = nterm-1.
+// sigma holds `sn` numbers per cell: dim (the diagonal of a diagonal tensor; the reference's arithmetic, to the bit) or
+// sym_ncomp(dim) (a full symmetric tensor in the order of the row above).
 // ref: src/apply_local_operators.jl:101-118.
-void build_cell_coefficients(const MeshTables &mesh, const double *sigma, std::vector<double> &coef);
+inline int sym_ncomp(int dim) { return dim * (dim + 1) / 2; }
+// position of entry (a, b) of a symmetric dim x dim tensor in that order
+inline int sym_index(int dim, int a, int b)
+{
+    if (a > b) std::swap(a, b);
+    return a * dim - a * (a - 1) / 2 + (b - a);
+}
+void build_cell_coefficients(const MeshTables &mesh, const double *sigma, int sn, std::vector<double> &coef);
 
 // Coarse (level-1) operator lambda*M + K_sigma on the base mesh, interior rows/cols only, CSR.
 // ref: src/examples/homogenized_coefficients.jl:358-402 (assemble_checkerboard), src/grid.jl:176-202.
@@ -191,7 +200,7 @@ struct CoarseMatrix {
     std::vector<int32_t> rowptr, colidx;
     std::vector<double> val, diag;
 };
-void assemble_coarse_matrix(const MeshTables &mesh, const double *sigma, double lambda,
+void assemble_coarse_matrix(const MeshTables &mesh, const double *sigma, int sn, double lambda,
                             CoarseMatrix &out);
 
 // ---------------------------------------------------------------------------------------------

@@ -1114,6 +1114,7 @@ static void launch_apply_generic(const Launch &L, const LevelDev &lv, const Mesh
     const int64_t grid = NT == 64 ? std::min<int64_t>(nblocks, 32 * (int64_t)L.num_cu) : nblocks;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, L.stream, lv, mesh.coef, mesh.dmask, b);
     check_launch();
+    if (WC && L.n_wc_launches) *L.n_wc_launches += 1;
 }
 
 template <int DIM, bool FUSED, bool WD = false>

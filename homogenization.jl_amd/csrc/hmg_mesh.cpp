@@ -584,30 +584,41 @@ void build_partition(int dim, int64_t nnodes, const double *coords, int64_t ncel
         (is_cut_cell[q] ? local.cells_cut : local.cells_inner).push_back((int32_t)q);
 }
 
-void build_cell_coefficients(const MeshTables &M, const double *sigma, std::vector<double> &coef)
+void build_cell_coefficients(const MeshTables &M, const double *sigma, int sn, std::vector<double> &coef)
 {
     const int dim = M.dim;
     const int nterm = dim == 3 ? 7 : 4;
+    const bool full = sn != dim;
     coef.assign((size_t)M.ncells * 8, 0.0);
     for (int64_t c = 0; c < M.ncells; ++c) {
         const double *Ji = &M.jinv[(size_t)c * dim * dim];   // column-major inv(J')
-        const double *sg = &sigma[(size_t)c * dim];
+        const double *sg = &sigma[(size_t)c * sn];
         double det = M.detj[c];
         int t = 0;
         for (int a = 0; a < dim; ++a)
             for (int b = a; b < dim; ++b, ++t) {
-                // P = Jinv' * (sigma .* Jinv)   (src/apply_local_operators.jl:105)
                 double s = 0.0;
-                for (int k = 0; k < dim; ++k) s += Ji[k + dim * a] * (sg[k] * Ji[k + dim * b]);
+                if (full) {
+                    // P = Jinv' * (sigma * Jinv), sigma a full symmetric tensor
+                    for (int k = 0; k < dim; ++k) {
+                        double sj = 0.0;
+                        for (int l = 0; l < dim; ++l) sj += sg[sym_index(dim, k, l)] * Ji[l + dim * b];
+                        s += Ji[k + dim * a] * sj;
+                    }
+                } else {
+                    // P = Jinv' * (sigma .* Jinv)   (src/apply_local_operators.jl:105)
+                    for (int k = 0; k < dim; ++k) s += Ji[k + dim * a] * (sg[k] * Ji[k + dim * b]);
+                }
                 coef[(size_t)c * 8 + t] = det * s;
             }
         coef[(size_t)c * 8 + nterm - 1] = det;
     }
 }
 
-void assemble_coarse_matrix(const MeshTables &M, const double *sigma, double lambda, CoarseMatrix &A)
+void assemble_coarse_matrix(const MeshTables &M, const double *sigma, int sn, double lambda, CoarseMatrix &A)
 {
     const int dim = M.dim, N = dim + 1;
+    const bool full = sn != dim;
     A.node2int.assign(M.nnodes, -1);
     A.interior.clear();
     for (int64_t g = 0; g < M.nnodes; ++g)
@@ -632,7 +643,7 @@ void assemble_coarse_matrix(const MeshTables &M, const double *sigma, double lam
             const int64_t c = M.node_all_ent[q] >> 3;
             const int i = M.node_all_ent[q] & 7;
             const double *Ji = &M.jinv[(size_t)c * dim * dim];
-            const double *sg = &sigma[(size_t)c * dim];
+            const double *sg = &sigma[(size_t)c * sn];
             const int32_t *el = &M.cells[c * N];
             const double vol = M.detj[c] * volf;
             // gradients = Jinv * refgrads (src/cell_values.jl:117)
@@ -649,7 +660,15 @@ void assemble_coarse_matrix(const MeshTables &M, const double *sigma, double lam
                 const int32_t cj = A.node2int[el[j]];
                 if (cj < 0) continue;
                 double k = 0.0;
-                for (int a = 0; a < dim; ++a) k += g[a][i] * sg[a] * g[a][j];
+                if (full) {   // g_i . sigma g_j
+                    for (int a = 0; a < dim; ++a) {
+                        double sj = 0.0;
+                        for (int b = 0; b < dim; ++b) sj += sg[sym_index(dim, a, b)] * g[b][j];
+                        k += g[a][i] * sj;
+                    }
+                } else {
+                    for (int a = 0; a < dim; ++a) k += g[a][i] * sg[a] * g[a][j];
+                }
                 buf.push_back({cj, vol * (k + lambda * massf * (i == j ? 2.0 : 1.0))});
             }
         }

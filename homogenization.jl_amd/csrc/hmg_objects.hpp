@@ -220,9 +220,14 @@ struct hmg_ctx {
     hipEvent_t ev_packed = nullptr, ev_summed = nullptr;
     int64_t comm_calls = 0, comm_doubles = 0;
     int64_t small_launches = 0;              // launches of the pipelined small-level apply
+    int64_t wc_launches = 0;                 // launches of k_apply<.., WC>: class weights from the cache (level 6)
     int64_t wave_launches = 0;               // launches of the one-wave-per-cell apply (hmg_ctx_counter)
     int64_t slab2_launches = 0;              // launches of the role-split slab apply (hmg_apply_slab.hip)
     int64_t rows_launches = 0;               // launches of the row-band apply of 2D cells larger than the LDS (hmg_apply_rows.hip)
+    int64_t wc_max_classes = 0;              // option "weight_cache_classes": most distinct coefficient rows that still get a
+                                             // class-weight cache (0: no limit by count; 1024: what the library did before)
+    int64_t wc_classes = 0, wc_bytes = 0;    // rows cached by this context's grids / bytes of their caches (ensure_weight_cache)
+    int64_t wc_refusals = 0;                 // operators whose cache did not fit the device memory (counter "weight_cache_refusals")
     int64_t spare_bytes = 0;                 // spare direction vectors held by this context's grids (reserve_top_spare)
     int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
     int64_t smoother_diag_bytes = 0;         // inverse diagonals held by this context's grids (hmg_grid_set_smoother)
@@ -263,10 +268,18 @@ struct hmg_grid {
     bool fuse_cg = true;
     DevBuf<double> d_coef;
     std::vector<double> sigma, coef;
+    int sig_n = 0;                               // numbers per cell in sigma / sigma_global: dim (diagonal tensors,
+                                                 // hmg_grid_set_operator) or dim (dim + 1) / 2 (hmg_grid_set_operator_tensor)
     // class-weight cache (k_apply_wave): cells with bitwise equal coefficient rows share a class
     DevBuf<int32_t> d_cell_class;
     DevBuf<double> d_coef_rep;
     int nclasses = 0;
+    std::vector<int32_t> cell_class;             // host copy of the class table (hmg_grid_table_i32 "cell_class"), empty: none
+    int64_t wc_limit = 0;                        // the context's option "weight_cache_classes" as it stood when the operator was set
+                                                 // (a domain shrink re-classes the cells under the same limit)
+    bool wc_trim = false;                        // a new operator sizes the cache blocks to its rows; a domain shrink or a new
+                                                 // lambda after it keeps the blocks it has (fewer rows of the same operator)
+    int64_t wc_counted_classes = 0, wc_counted_bytes = 0;   // this grid's share of the context's "weight_cache_*" counters
     double wc_lambda = 0.0;
     bool wc_ready = false;
     double lambda = 0.0;
@@ -399,6 +412,8 @@ double read_scalar(hmg_ctx *c, int slot);
 // ---- hmg_upload.cpp ----
 // (re)forms the class-weight cache when the operator or lambda has changed; called in front of every apply
 void ensure_weight_cache(hmg_grid *g);
+// hands the cache back (grid destruction, a new class table) and takes its share out of the context's counters
+void release_weight_cache(hmg_grid *g);
 
 // ---- hmg_smooth.cpp ----
 void set_slab(hmg_grid *g, const LevelDev &lv);

@@ -4,6 +4,7 @@
 #include "../../include/hmg.h"
 #include "hmg_objects.hpp"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <unordered_map>
@@ -185,21 +186,23 @@ void upload_levels(hmg_grid *g)
 // the cell's coefficient row (|J| P_kl, |J|), and on the meshes this library is built for most rows repeat: a checkerboard
 // has at most 8 sigma triples x 6 tetrahedron orientations = 48 distinct ones.  Cells are classed by the BITS of their row;
 // per class, sign of alpha and level the 15 x 15 weights are formed once on the device (launch_weight_cache), by the same
-// products in the same order as the kernels form them per cell.  More than WC_MAX_CLASSES distinct rows (perturbed or
-// unstructured meshes): no cache, the level keeps the 256-thread kernel.
-constexpr int WC_MAX_CLASSES = 1024;
-
+// products in the same order as the kernels form them per cell.  A field with a row of its own in every cell (one grain
+// orientation per cube, a perturbed mesh) is classed like any other: 3 840 B per class and level.  No cache, and the older
+// kernels, where the rows outnumber the context's option "weight_cache_classes" (0, the default: no limit by count) or where
+// the cache does not fit the device memory (ensure_weight_cache).
 void build_cell_classes(hmg_grid *g)
 {
     g->nclasses = 0;
     g->wc_ready = false;
     g->md.cell_class = nullptr;
     g->md.nclasses = 0;
+    g->cell_class.clear();
     for (auto &d : g->ld) d.wcache = nullptr;
     bool any = false;
     for (const auto &d : g->ld) any = any || d.level >= 2;
     if (!any || g->dim != 3) return;
     const int64_t n = g->cur().ncells;
+    const int64_t limit = g->wc_limit;
     struct Key {
         uint64_t b[8];
         bool operator==(const Key &o) const { return std::memcmp(b, o.b, sizeof(b)) == 0; }
@@ -220,7 +223,10 @@ void build_cell_classes(hmg_grid *g)
         std::memcpy(k.b, g->coef.data() + (size_t)c * 8, sizeof(k.b));
         auto it = ids.find(k);
         if (it == ids.end()) {
-            if ((int)ids.size() >= WC_MAX_CLASSES) return;           // too many distinct rows: no cache
+            if (limit > 0 && (int64_t)ids.size() >= limit) {          // too many distinct rows: no cache
+                release_weight_cache(g);
+                return;
+            }
             it = ids.emplace(k, (int32_t)ids.size()).first;
             rep.insert(rep.end(), g->coef.begin() + (size_t)c * 8, g->coef.begin() + (size_t)c * 8 + 8);
         }
@@ -230,31 +236,69 @@ void build_cell_classes(hmg_grid *g)
     hipStream_t s = g->ctx ? g->ctx->stream : nullptr;
     g->d_cell_class.upload(cls, s);
     g->d_coef_rep.upload(rep, s);
+    g->cell_class.swap(cls);
     g->md.cell_class = g->d_cell_class.p;
     g->md.nclasses = g->nclasses;
 }
 
 }  // namespace
 
+void release_weight_cache(hmg_grid *g)
+{
+    bool held = false;
+    for (auto &b : g->lb) held = held || (b && b->wcache.p);
+    if (held && g->ctx) (void)hipStreamSynchronize(g->ctx->stream);   // (kernels that read the cache)
+    for (auto &b : g->lb)
+        if (b) b->wcache.release();
+    for (auto &d : g->ld) d.wcache = nullptr;
+    if (g->ctx) {
+        g->ctx->wc_classes -= g->wc_counted_classes;
+        g->ctx->wc_bytes -= g->wc_counted_bytes;
+    }
+    g->wc_counted_classes = g->wc_counted_bytes = 0;
+    g->wc_ready = false;
+}
+
 // (re)forms the cached weights when the operator or lambda has changed since they were formed; called in front of every
-// apply (a host comparison when nothing has changed)
+// apply (a host comparison when nothing has changed).  The memory is taken where the operator is set, never in a V-cycle; if
+// it is not there the grid keeps the kernels that form their weights per cell, and the context's counters
+// "weight_cache_classes" / "weight_cache_bytes" do not count it.
 void ensure_weight_cache(hmg_grid *g)
 {
     if (!g->md.cell_class || (g->wc_ready && g->wc_lambda == g->lambda)) return;
+    const size_t per_level = (size_t)g->nclasses * 2 * WAVE_WSTRIDE;
+    int64_t bytes = 0;
     for (int l = 0; l < g->nlevels; ++l) {
         LevelDev &D = g->ld[l];
         if (D.level < 2 || D.ncls != 15) continue;           // (every 3D level an operator is applied on: k_apply<.., WC>, k_apply_wave)
         LevelBufs &B = *g->lb[l];
-        if (B.wcache.n != (size_t)g->nclasses * 2 * WAVE_WSTRIDE) {
+        if (B.wcache.n < per_level || (g->wc_trim && B.wcache.n != per_level)) {
             HIPCHK(hipStreamSynchronize(g->ctx->stream));   // (kernels that read the old cache)
-            B.wcache.alloc((size_t)g->nclasses * 2 * WAVE_WSTRIDE);
+            B.wcache.release();
+            void *q = nullptr;
+            if (device_malloc(&q, per_level * sizeof(double)) != hipSuccess) {
+                (void)hipGetLastError();
+                release_weight_cache(g);
+                g->md.cell_class = nullptr;                  // every launcher's eligibility test reads this
+                g->cell_class.clear();                       // ... and table "cell_class" reports no classes
+                g->ctx->wc_refusals += 1;
+                return;
+            }
+            B.wcache.p = (double *)q;
+            B.wcache.n = per_level;
         }
         launch_weight_cache(g->ctx->L, D, g->d_coef_rep.p, g->nclasses, g->lambda, B.wcache.p);
         D.wcache = B.wcache.p;
+        bytes += (int64_t)(B.wcache.n * sizeof(double));      // (what is held: after a domain shrink more than the rows in use)
     }
+    g->ctx->wc_classes += (int64_t)g->nclasses - g->wc_counted_classes;
+    g->ctx->wc_bytes += bytes - g->wc_counted_bytes;
+    g->wc_counted_classes = g->nclasses;
+    g->wc_counted_bytes = bytes;
     g->wc_lambda = g->lambda;
     g->md.wc_lambda = g->lambda;
     g->wc_ready = true;
+    g->wc_trim = false;
 }
 
 namespace {
@@ -263,13 +307,13 @@ void upload_operator(hmg_grid *g)
 {
     const MeshTables &M = g->cur();
     if (g->part) {   // local sigma = rows of the global field
-        const int dim = g->dim;
-        g->sigma.resize((size_t)M.ncells * dim);
+        const int sn = g->sig_n;
+        g->sigma.resize((size_t)M.ncells * sn);
         for (int64_t q = 0; q < M.ncells; ++q)
-            for (int a = 0; a < dim; ++a)
-                g->sigma[(size_t)q * dim + a] = g->sigma_global[(size_t)g->part->cells_g[q] * dim + a];
+            for (int a = 0; a < sn; ++a)
+                g->sigma[(size_t)q * sn + a] = g->sigma_global[(size_t)g->part->cells_g[q] * sn + a];
     }
-    build_cell_coefficients(M, g->sigma.data(), g->coef);
+    build_cell_coefficients(M, g->sigma.data(), g->sig_n, g->coef);
     g->coarse_ready = false;
     DryUploads dry_scope(!g->ctx, &g->upload_hash);
     g->d_coef.upload(g->coef, g->ctx ? g->ctx->stream : nullptr);
@@ -390,19 +434,63 @@ int hmg_grid_create_partition_rehearsal(hmg_ctx *ctx, int dim, int nlevels, int6
     return create_grid(ctx, dim, nlevels, nnodes, coords, ncells, cells, true, owner, cut_owner, rank, nranks, out);
 }
 
-int hmg_grid_set_operator(hmg_grid *g, const double *sigma, double lambda)
+// sn numbers per cell (hmg_grid::sig_n) of the whole mesh: the GLOBAL one on a partitioned grid
+static void set_operator(hmg_grid *g, const double *sigma, int sn, double lambda)
 {
-    HMG_TRY
-    need(g && sigma, "null argument");
     if (g->part)
-        g->sigma_global.assign(sigma, sigma + (size_t)g->part->global.ncells * g->dim);
+        g->sigma_global.assign(sigma, sigma + (size_t)g->part->global.ncells * sn);
     else
-        g->sigma.assign(sigma, sigma + (size_t)g->mesh_full.ncells * g->dim);
+        g->sigma.assign(sigma, sigma + (size_t)g->mesh_full.ncells * sn);
+    g->sig_n = sn;
+    g->wc_limit = g->ctx ? g->ctx->wc_max_classes : 0;   // read here, and only here: hmg_grid_shrink keeps it
+    g->wc_trim = true;
     g->lambda = lambda;
     g->has_op = true;
     g->op_epoch += 1;
     g->dinv_ready = false;
     upload_operator(g);
+}
+
+int hmg_grid_set_operator(hmg_grid *g, const double *sigma, double lambda)
+{
+    HMG_TRY
+    need(g && sigma, "null argument");
+    set_operator(g, sigma, g->dim, lambda);
+    HMG_END
+}
+
+int hmg_grid_set_operator_tensor(hmg_grid *g, const double *sigma, double lambda)
+{
+    HMG_TRY
+    need(g && sigma, "null argument");
+    const int dim = g->dim, nc = sym_ncomp(dim);
+    const int64_t n = g->part ? g->part->global.ncells : g->mesh_full.ncells;
+    bool diagonal = true;
+    for (int64_t c = 0; c < n; ++c) {   // (nothing of the grid changes before the whole field has passed)
+        const double *s = sigma + (size_t)c * nc;
+        for (int t = 0; t < nc; ++t)
+            if (!std::isfinite(s[t])) throw std::runtime_error("sigma of cell " + std::to_string(c) + " is not finite");
+        // positive definite: the leading minors
+        bool spd;
+        if (dim == 2) {
+            spd = s[0] > 0.0 && s[0] * s[2] - s[1] * s[1] > 0.0;
+            diagonal = diagonal && s[1] == 0.0;
+        } else {
+            const double m2 = s[0] * s[3] - s[1] * s[1];
+            const double m3 = s[0] * (s[3] * s[5] - s[4] * s[4]) - s[1] * (s[1] * s[5] - s[4] * s[2]) + s[2] * (s[1] * s[4] - s[3] * s[2]);
+            spd = s[0] > 0.0 && m2 > 0.0 && m3 > 0.0;
+            diagonal = diagonal && s[1] == 0.0 && s[2] == 0.0 && s[4] == 0.0;
+        }
+        if (!spd) throw std::runtime_error("sigma of cell " + std::to_string(c) + " is not positive definite");
+    }
+    if (diagonal) {   // the diagonal entry's arithmetic and tables, to the bit
+        std::vector<double> d((size_t)n * dim);
+        for (int64_t c = 0; c < n; ++c)
+            for (int a = 0; a < dim; ++a) d[(size_t)c * dim + a] = sigma[(size_t)c * nc + sym_index(dim, a, a)];
+        set_operator(g, d.data(), dim, lambda);
+    } else {
+        set_operator(g, sigma, nc, lambda);
+    }
     HMG_END
 }
 
@@ -475,6 +563,9 @@ int hmg_grid_table_i32(const hmg_grid *g, int level, const char *which, int32_t 
         const auto &m = w == "dmask" ? g->cur().dmask : g->cur().dupmask;
         tmp.assign(m.begin(), m.end());
         src = &tmp;
+    } else if (w == "cell_class") {    // the cell's class in the class-weight cache; empty: this operator has no class table
+        if (g->md.cell_class || !g->ctx) src = &g->cell_class;
+        else src = &tmp;
     } else if (w == "upload_hash") {   // host-only grids: checksum of every table a device grid would have uploaded so far (two halves)
         tmp = {(int32_t)(uint32_t)(g->upload_hash & 0xffffffffu), (int32_t)(uint32_t)(g->upload_hash >> 32)};
         src = &tmp;

@@ -64,9 +64,9 @@ class PartitionedGrid(api.ImplicitFineGrid):
         self._exchange = None
 
     def set_operator(self, sigmas_global, lam):
-        s = np.ascontiguousarray(sigmas_global, dtype=np.float64)
-        assert s.shape == (self.global_base.elements.shape[0], self.global_base.dim)
-        L.check(self._lib.hmg_grid_set_operator(self.h, s.ctypes.data_as(L.p_f64), float(lam)))
+        s, tensor = api.pack_sigmas(sigmas_global, self.global_base.elements.shape[0], self.global_base.dim)
+        entry = self._lib.hmg_grid_set_operator_tensor if tensor else self._lib.hmg_grid_set_operator
+        L.check(entry(self.h, s.ctypes.data_as(L.p_f64), float(lam)))
 
     def exchange_doubles(self):
         n = int(self._lib.hmg_grid_cut_buffer_doubles(self.h, 0))

@@ -139,9 +139,34 @@ def generate_conductivity(dim: int, n: int, seed: int, values=(1.0, 9.0)):
     return np.where(rng.random((n,) * dim + (dim,)) < 0.5, values[0], values[1])
 
 
+def generate_polycrystal(dim: int, n: int, seed: int, principal=None):
+    """One grain per unit cube: sigma = R diag(principal) R^T with one rotation R per cube -- 2D: the angle uniform in [0, pi);
+    3D: a uniform random rotation (a unit quaternion from four normal deviates).  Shape (n,) * dim + (dim, dim), exactly
+    symmetric: a `sigma_grid` for the drivers.  principal defaults to (1, 9) / (1, 9, 100)."""
+    principal = np.asarray((1.0, 9.0, 100.0)[:dim] if principal is None else principal, dtype=np.float64)
+    if principal.shape != (dim,):
+        raise ValueError(f"principal must hold {dim} conductivities")
+    rng = np.random.default_rng(seed)
+    ncube = n ** dim
+    if dim == 2:
+        t = rng.random(ncube) * math.pi
+        c, s = np.cos(t), np.sin(t)
+        R = np.stack([np.stack([c, -s], axis=-1), np.stack([s, c], axis=-1)], axis=-2)
+    else:
+        q = rng.standard_normal((ncube, 4))
+        w, x, y, z = (q / np.linalg.norm(q, axis=1, keepdims=True)).T
+        R = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)], axis=-1),
+                      np.stack([2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)], axis=-1),
+                      np.stack([2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], axis=-1)], axis=-2)
+    S = np.einsum("cik,k,cjk->cij", R, principal, R)
+    S = 0.5 * (S + np.swapaxes(S, 1, 2))
+    return np.ascontiguousarray(S.reshape((n,) * dim + (dim, dim)))
+
+
 def conductivity_per_element(mesh: Mesh, sigma_grid, offset, native: bool = True):
-    """ref: src/examples/homogenized_coefficients.jl:494-503 (native: the library's threaded host code; False: numpy)"""
-    if native:
+    """ref: src/examples/homogenized_coefficients.jl:494-503 (native: the library's threaded host code; False: numpy).  A grid of
+    full tensors, shape (n,) * dim + (dim, dim) (generate_polycrystal), takes the numpy path and gives (ncells, dim, dim)."""
+    if native and np.ndim(sigma_grid) == mesh.dim + 1:
         from . import _lib as L
         dim = mesh.dim
         nodes = np.ascontiguousarray(mesh.nodes, dtype=np.float64)
@@ -157,7 +182,7 @@ def conductivity_per_element(mesh: Mesh, sigma_grid, offset, native: bool = True
                                                       out.ctypes.data_as(L.p_f64)))
         return out
     idx = np.trunc(_centers(mesh) + np.asarray(offset, dtype=np.float64)).astype(np.int64) - 1
-    return np.ascontiguousarray(sigma_grid[tuple(idx[:, a] for a in range(mesh.dim))])
+    return np.ascontiguousarray(np.asarray(sigma_grid)[tuple(idx[:, a] for a in range(mesh.dim))])
 
 
 def random_unit_vec(dim):

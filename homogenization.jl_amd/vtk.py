@@ -103,8 +103,13 @@ def construct_full_grid(implicit, level: int):
 
 
 def export_domain(base, cond, name="checkerboard"):
-    """ref: src/examples/homogenized_coefficients.jl:69-79 -- cell data "a" = the diagonal of the conductivity."""
-    return write_vtu(name, base.nodes, base.elements - 1, cell_data={"a": np.asarray(cond, dtype=np.float64)})
+    """ref: src/examples/homogenized_coefficients.jl:69-79 -- cell data "a" = the diagonal of the conductivity; full tensors
+    (ncells, dim, dim): their dim (dim + 1) / 2 components by rows of the upper triangle (3D: 11, 12, 13, 22, 23, 33)."""
+    a = np.asarray(cond, dtype=np.float64)
+    if a.ndim == 3:
+        iu = np.triu_indices(a.shape[1])
+        a = np.ascontiguousarray(a[:, iu[0], iu[1]])
+    return write_vtu(name, base.nodes, base.elements - 1, cell_data={"a": a})
 
 
 def export_unknown(implicit, x, k: int, level: int, name=None, field="v"):

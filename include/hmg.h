@@ -58,6 +58,13 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *   "apply_pack" 1: 3D level-2 cells four to a wave (hmg_apply_small.hip); 0: one cell per wave, as on levels 3-4.
  *   "apply_small" 1: levels 2-4 by the pipelined one-wave kernel where the class-weight cache exists; 0: the generic kernel.
  *   "weight_cache" 1: level 6 takes its class weights from the cache hmg_grid_set_operator fills; 0: combines them per cell.
+ *   "weight_cache_classes" 0: every operator of a 3D grid gets a class-weight cache, whatever the number of distinct coefficient
+ *       rows (3 840 B per row and level: a field with a row per cell, such as one grain orientation per cube, costs 755 MB per
+ *       level at 196 608 cells); n: only operators of at most n distinct rows (1024: the limit this library had before the
+ *       option existed), the others keep the kernels that combine their weights per cell.  Read when an operator is set
+ *       (hmg_grid_set_operator, hmg_grid_set_operator_tensor) and kept by the grid: hmg_grid_shrink classes the remaining cells
+ *       under the limit of its operator, whatever the option says by then, and keeps the memory it has.  A cache that does not
+ *       fit the device memory is left out in the same way: hmg_ctx_counter "weight_cache_classes", "weight_cache_refusals".
  *   "apply_wave" 1: level 5 (969 nodes) by one wave per cell where the cache exists and |alpha| = 1 (hmg_apply_wave.hip);
  *       0: the 256-thread kernel.  "wave_grid" 16: its persistent waves per CU; "wave_grid_total": as an absolute number.
  *   "apply_slab2" 1: cells larger than the LDS (level 7) by one persistent 1024-thread workgroup per CU, loader waves
@@ -121,7 +128,12 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    (levels 2-4, hmg_apply_small.hip), "slab2_launches" (level 7, hmg_apply_slab.hip), "comm_calls", "comm_nranks" (ranks of the RCCL communicator made by hmg_comm_init, 0 without
    one), "device_allocs" (device / pinned allocations the library has made in this process: constant across hmg_vcycle once the
    grid, its operator, its level-1 system and the level vectors exist), "spare_bytes" (spare direction vectors held by this
-   context's grids, see hmg_grid_reserve_spare), "lazy_top_form" (the form the last finest-level post-smoother inside hmg_vcycle
+   context's grids, see hmg_grid_reserve_spare), "weight_cache_classes" (coefficient rows cached by this context's grids: 0 for a
+   grid whose rows outnumber option "weight_cache_classes" or whose cache did not fit the device memory), "weight_cache_bytes"
+   (bytes those caches hold: rows x 2 x 240 x 8 per 3D level >= 2 when the operator is set; a domain shrink keeps them),
+   "weight_cache_refusals" (operators whose cache did not fit the device memory: their grids run the kernels that combine the
+   weights per cell, and table "cell_class" is empty) and "weight_cache_launches" (launches of the level-6 apply that took its
+   weights from the cache), "lazy_top_form" (the form the last finest-level post-smoother inside hmg_vcycle
    took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "lazy_pre_form" (the x-updates the
    last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
@@ -139,6 +151,15 @@ int hmg_grid_create(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const do
 int hmg_grid_destroy(hmg_grid *grid);
 /* L2PlusDivAGrad(diff, mass, constraint, lambda, sigmas)  (src/build_local_operators.jl:26-32) */
 int hmg_grid_set_operator(hmg_grid *grid, const double *sigma /* dim*ncells */, double lambda);
+/* The same operator with a full symmetric conductivity tensor per cell (no counterpart in the reference): sigma holds
+ * dim (dim + 1) / 2 numbers per cell, in the order of the coefficient row -- 3D: 11, 12, 13, 22, 23, 33; 2D: 11, 12, 22.  A
+ * partitioned grid takes the GLOBAL field, like hmg_grid_set_operator.  A tensor that is not finite or not positive definite
+ * (leading minors) is refused with its cell in hmg_last_error(), and the previous operator stays in force.  Everything that
+ * depends on the operator takes the tensor: coefficient rows |J| J^-1 sigma J^-T, the level-1 matrix (g_i . sigma g_j),
+ * hmg_rhs_axi_grad (-|J| J^-1 (sigma xi)), hmg_grid_set_lambda, hmg_grid_shrink, cell classes and the weight cache, the
+ * Jacobi smoother's diagonal, hmg_fcg_*, hmg_integrate.  A field whose off-diagonal entries are all exactly zero goes through
+ * the arithmetic of hmg_grid_set_operator: the same bits in every table. */
+int hmg_grid_set_operator_tensor(hmg_grid *grid, const double *sigma /* ncomp*ncells */, double lambda);
 int hmg_grid_set_lambda(hmg_grid *grid, double lambda);
 /* Domain shrink to a prefix of cells / nodes + new Dirichlet boundary
  * (src/examples/homogenized_coefficients.jl:309-336).  Level vectors keep their storage.  On a partitioned grid
@@ -178,7 +199,8 @@ int64_t hmg_grid_nf(const hmg_grid *grid, int level);   /* nnodes(refined_mesh(i
 int64_t hmg_grid_ld(const hmg_grid *grid, int level);   /* device column stride in doubles */
 /* Table export for tests / host mirrors. which: "hier2slot" (int32[nf]), "slot_ijk" (int32[3*nf]),
  * "slot_cls" (int32[nf]), "par_a","par_b" (int32[nf]), "ctab" (f64), "dmask","dupmask" (int32[ncells]),
- * "interior_nodes" (int32, 0-based), "coef" (f64[8*ncells]).  Returns the element count via *count. */
+ * "interior_nodes" (int32, 0-based), "coef" (f64[8*ncells]), "cell_class" (int32[ncells]: the cell's class in the class-weight
+ * cache, on a host-only grid too; count 0 when the operator has no class table).  Returns the element count via *count. */
 int hmg_grid_table_i32(const hmg_grid *grid, int level, const char *which, int32_t *out, int64_t cap, int64_t *count);
 int hmg_grid_table_f64(const hmg_grid *grid, int level, const char *which, double *out, int64_t cap, int64_t *count);
 

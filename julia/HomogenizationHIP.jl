@@ -102,10 +102,22 @@ sigmas(A::L2PlusDivAGrad) = collect(reinterpret(Float64, A.σs))                
 sigmas(A::SimpleDiffusion{dim}, ne) where {dim} = fill(Float64(A.a), dim * ne)
 lambda(A::L2PlusDivAGrad) = Float64(A.λ)
 lambda(::SimpleDiffusion) = 0.0
+# lambda*I - div(sigma grad) with a full symmetric tensor per cell (no counterpart in the reference, whose sigmas are diagonal):
+# sigmas holds dim (dim + 1) / 2 numbers per cell, upper triangle by rows (3D: 11, 12, 13, 22, 23, 33; 2D: 11, 12, 22)
+mutable struct TensorL2PlusDivAGrad
+    lambda::Float64
+    sigmas::Vector{Float64}
+end
+lambda(A::TensorL2PlusDivAGrad) = A.lambda
+const AnyL2PlusDivAGrad = Union{L2PlusDivAGrad,TensorL2PlusDivAGrad}      # every forwarded method takes either
 function bind!(g::HipGrid, A)
     if g.bound !== A
-        s = A isa SimpleDiffusion ? sigmas(A, ncells(g)) : sigmas(A)
-        check(ccall((:hmg_grid_set_operator, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64), g.h, s, lambda(A)))
+        if A isa TensorL2PlusDivAGrad
+            check(ccall((:hmg_grid_set_operator_tensor, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64), g.h, A.sigmas, A.lambda))
+        else
+            s = A isa SimpleDiffusion ? sigmas(A, ncells(g)) : sigmas(A)
+            check(ccall((:hmg_grid_set_operator, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Float64), g.h, s, lambda(A)))
+        end
         g.bound, g.bound_lambda = A, lambda(A)
     elseif g.bound_lambda != lambda(A)
         check(ccall((:hmg_grid_set_lambda, LIB), Cint, (Ptr{Cvoid}, Float64), g.h, lambda(A)))
@@ -181,10 +193,10 @@ handles(levels::Vector{HipState}) = Ptr{Cvoid}[getfield(l, f).h for l in levels 
 
 # ---- hot-path methods ------------------------------------------------------------------------------------------------
 # mul!(α, base, A, x, y): y += α A x (src/apply_local_operators.jl:40-72, :85-133)
-mul!(α::Float64, base::Mesh, A::Union{L2PlusDivAGrad,SimpleDiffusion}, x::HipMatrix, y::HipMatrix) =
+mul!(α::Float64, base::Mesh, A::Union{AnyL2PlusDivAGrad,SimpleDiffusion}, x::HipMatrix, y::HipMatrix) =
     (bind!(x.grid, A); check(ccall((:hmg_apply, LIB), Cint, (Ptr{Cvoid}, Cint, Float64, Ptr{Cvoid}, Ptr{Cvoid}), x.grid.h, x.level, α, x.h, y.h)); y)
 # local_residual!: r = b - A x, constraint (src/apply_local_operators.jl:7-27)
-local_residual!(implicit, A::Union{L2PlusDivAGrad,SimpleDiffusion}, c::HipState, k::Int) =
+local_residual!(implicit, A::Union{AnyL2PlusDivAGrad,SimpleDiffusion}, c::HipState, k::Int) =
     (bind!(c.x.grid, A); check(ccall((:hmg_residual, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.x.grid.h, k, c.x.h, c.b.h, c.r.h)))
 # typed on Matrix / Vector in the reference (src/implicit_fine_grid.jl:94,148,178): additional methods, nothing changes there
 apply_constraint!(x::HipMatrix, level::Int, z, implicit) =
@@ -283,7 +295,7 @@ end
 rhs_aξ∇v!(b::HipMatrix, ∂ϕ∂xᵢs, implicit, σs, ξ::SVector{dim,Float64}) where {dim} =
     (check(ccall((:hmg_rhs_axi_grad, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), b.grid.h, collect(ξ), b.h)); b)
 local_rhs!(b::HipMatrix, implicit) = (check(ccall((:hmg_local_rhs, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), b.grid.h, b.h)); b)
-next_rhs!(b::HipMatrix, x::HipMatrix, implicit, ops::L2PlusDivAGrad) =
+next_rhs!(b::HipMatrix, x::HipMatrix, implicit, ops::AnyL2PlusDivAGrad) =
     (bind!(x.grid, ops); check(ccall((:hmg_next_rhs, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), x.grid.h, x.h, b.h)); nothing)
 function integrate(g::HipGrid, mode::Integer, v::HipMatrix, second, nsubset::Integer)
     o = Ref(0.0)
@@ -293,16 +305,16 @@ function integrate(g::HipGrid, mode::Integer, v::HipMatrix, second, nsubset::Int
 end
 # subsets are prefixes 1:n of the ∞-norm ordered cells (find_elements_in_radius, :32-43).  The first term's dot(∂ϕ, P) is
 # the entry of rhs_aξ∇v! for the same ξ: the caller's right-hand side b of outer step 0 is passed along.
-integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =
     (bind!(v₀.grid, ops); integrate(v₀.grid, 0, v₀, b, length(subset)))
-integrate_terms(vₖ::HipMatrix, vₖ₋₁::HipMatrix, implicit, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+integrate_terms(vₖ::HipMatrix, vₖ₋₁::HipMatrix, implicit, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =
     (bind!(vₖ.grid, ops); integrate(vₖ.grid, 1, vₖ, vₖ₋₁, length(subset)))
 integrate_area(g::HipGrid, v::HipMatrix, subset::AbstractUnitRange) = integrate(g, 2, v, nothing, length(subset))
 # The two pair forms behind the off-diagonal entries of the homogenized tensor (no counterpart in the reference; api.py has
 # the same two): Mq(v; w) = Σ |J| w⋅(M v), w may be v; Lq(v; s) = Σ |J| v⋅s with a load vector s such as rhs_aξ∇v!'s.
-integrate_pair_mass(v::HipMatrix, w::HipMatrix, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+integrate_pair_mass(v::HipMatrix, w::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =
     (bind!(v.grid, ops); integrate(v.grid, 3, v, w, length(subset)))
-integrate_pair_load(v::HipMatrix, s::HipMatrix, subset::AbstractUnitRange, ops::L2PlusDivAGrad) =
+integrate_pair_load(v::HipMatrix, s::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =
     (bind!(v.grid, ops); integrate(v.grid, 4, v, s, length(subset)))
 
 # ---- checkerboard_homogenization(n, ElT; refinements, smoothing_steps, tolerance, ξ, save, backend = :hip) -----------

@@ -9,7 +9,11 @@ reference's smoother only, so it implies --no-cpu as well.
 solves, one setup) against the d (d + 1) / 2 runs of the scalar driver that polarising by hand takes (xi = e_i and
 (e_i + e_j) / sqrt 2), same field, same seed, in one process: W untimed rounds of both first (code objects, the pool of
 level-vector memory), then R timed rounds that alternate the two; wall clock around whole runs, each of which ends in a device
-synchronise.  Prints the times of every round, their medians, the ratio and the largest difference of the two tensors."""
+synchronise.  Prints the times of every round, their medians, the ratio and the largest difference of the two tensors.
+--polycrystal: the field is driver.generate_polycrystal (one rotated tensor per unit cube, principal conductivities 1 and
+--contrast, in 3D 1, --contrast and their geometric mean) instead of the two-valued diagonal field; the CPU oracle knows diagonal
+tensors only, so it implies --no-cpu.
+--field-seed S: the seed of the coefficient field (default 5), e.g. for a figure over several fields."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,11 +31,17 @@ ap.add_argument("--accelerate", action="store_true")
 ap.add_argument("--smoother", choices=("cg", "jacobi"), default="cg")
 ap.add_argument("--contrast", type=float, default=9.0, help="sigma takes the values 1 and this")
 ap.add_argument("--tensor", action="store_true", help="one tensor run against d (d + 1) / 2 scalar runs")
+ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
+ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
 width = 2 * (driver.compute_box_radius(0, a.n) + driver.compute_boundary_layer(1.0, a.n))
-sgrid = driver.generate_conductivity(a.dim, width, 5, values=(1.0, a.contrast))
+if a.polycrystal:
+    principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
+    sgrid = driver.generate_polycrystal(a.dim, width, a.field_seed, principal)
+else:
+    sgrid = driver.generate_conductivity(a.dim, width, a.field_seed, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
 if a.tensor:
@@ -88,9 +98,9 @@ ctx.sync()
 t_gpu = time.perf_counter() - t0
 out = {"config": f"checkerboard_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
        "width": width, "sigma_gpu": sig, "vcycles": len(hist), "wall_s_gpu_incl_setup": t_gpu,
-       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
+       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal, "field_seed": a.field_seed, "setup_s": tm["setup_s"], "solve_s": tm["solve_s"],
        "outer_steps": tm["outer_steps"], "inexact_vcycles": tm["inexact_vcycles"]}
-if not (a.no_cpu or a.accelerate or a.smoother != "cg"):
+if not (a.no_cpu or a.accelerate or a.smoother != "cg" or a.polycrystal):
     from oracle import oracle as O
     nf = hist and None
     impl_nf = {2: [3, 6, 15, 45, 153, 561], 3: [4, 10, 35, 165, 969, 6545]}[a.dim][a.refinements]
