@@ -5,3 +5,4 @@ from .api import *  # noqa: F401,F403
 from . import api  # noqa: F401
 from . import driver  # noqa: F401
 from . import dist  # noqa: F401
+from . import fields  # noqa: F401

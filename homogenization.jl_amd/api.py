@@ -529,6 +529,29 @@ def integrate_pair_load(v: DeviceMatrix, s: DeviceMatrix, implicit: ImplicitFine
     return _integrate(implicit, 4, v, s, nsubset, None)
 
 
+def cell_moments(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None):
+    """Per coarse cell the mean gradient and the Gram tensor of the gradient of the level vector v -- with xi, of u = xi.x + v
+    (hmg_cell_moments): mean (Ne, d) = (1/|c|) int_c grad u, gram (Ne, d, d) = int_c grad u (x) grad u.  The moments are of the
+    vector as stored (no operator, no constraint); levels whose cell exceeds the LDS (3D level 7, 2D levels 9-11) are refused.
+    What to do with them: fields.py.  No counterpart in the reference."""
+    lib = L.load()
+    d = implicit.base.dim
+    nmom = int(lib.hmg_cell_moments_count(implicit.h))
+    out = np.zeros((implicit.ncells(), nmom), dtype=np.float64)
+    xp = None
+    if xi is not None:
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (d,):
+            raise ValueError(f"xi must have {d} entries")
+        xp = xi.ctypes.data_as(L.p_f64)
+    L.check(lib.hmg_cell_moments(implicit.h, v.h, xp, out.ctypes.data_as(L.p_f64)))
+    iu = np.triu_indices(d)
+    gram = np.zeros((out.shape[0], d, d))
+    gram[:, iu[0], iu[1]] = out[:, d:]
+    gram[:, iu[1], iu[0]] = out[:, d:]
+    return np.ascontiguousarray(out[:, :d]), gram
+
+
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))

@@ -85,8 +85,6 @@ double *vec_alloc(hmg_ctx *c, size_t bytes)
     return (double *)p;
 }
 
-namespace {
-
 void vec_release(hmg_ctx *c, void *p, size_t bytes)
 {
     LifetimeLock lock(lifetime_mutex());
@@ -97,6 +95,8 @@ void vec_release(hmg_ctx *c, void *p, size_t bytes)
     (void)hipStreamSynchronize(c->stream);
     (void)hipFree(p);
 }
+
+namespace {
 
 // scratch of the streaming reductions (one partial per 256-thread block = per 512 entries, see hmg_kernels.hip)
 void ensure_reduce_scratch(hmg_ctx *c, int64_t nentries)
@@ -260,6 +260,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "lazy_top_form") return ctx->last_top_form;
     if (n == "lazy_pre_form") return ctx->last_pre_form;
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;
+    if (n == "cell_moments_kernel_ns") return ctx->moments_kernel_ns;       // the last hmg_cell_moments: kernel alone
+    if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
     return -1;
 }

@@ -1,0 +1,109 @@
+// hmg_cell_moments: per coarse cell the mean gradient and the Gram tensor of the gradient of a level vector.
+//
+// Cell c has the affine map x = p0 + J x^; with Jinv = J^-T (MeshTables::jinv, column-major) d_k v = sum_a Jinv[k,a] d^_a v.  The
+// kernel (hmg_fields.hip) leaves the reference sums of the cell's column,
+//   l_a  = sum_i d_a[i] v_i             d_a[i]     = int_ref d^_a phi_i                   (LevelDev::dphi)
+//   q_ab = sum_i v_i (A^(a,b) v_c)_i    A^(a,b)_ij = int_ref d^_a phi_i d^_b phi_j        (the class table's terms; an
+//                                                                                          off-diagonal term is A^(a,b) + A^(b,a))
+// and this module turns them into physical moments, |ref| = 1/2 (2D), 1/6 (3D), |c| = |J| |ref|:
+//   m_v = Jinv l / |ref|                G_v = |J| Jinv q Jinv^T
+//   m_u = xi + m_v                      G_u = |c| (xi xi^T + xi m_v^T + m_v xi^T) + G_v       for u = xi . x + v
+// Not on a V-cycle's path: it allocates (the raw sums, from the context's pool of level-vector memory) and synchronises.
+#include "../../include/hmg.h"
+#include "hmg_fields.hpp"
+#include "hmg_objects.hpp"
+
+#include <chrono>
+
+extern "C" {
+
+int hmg_cell_moments_count(const hmg_grid *grid)
+{
+    if (!grid) {
+        last_error() = "null grid";
+        return -1;
+    }
+    return grid->dim + sym_ncomp(grid->dim);
+}
+
+int hmg_cell_moments(hmg_grid *g, hmg_vec *v, const double *xi, double *out)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(out != nullptr, "hmg_cell_moments: null output array");
+    need(g->ctx != nullptr, "hmg_cell_moments: this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    need(v != nullptr, "hmg_cell_moments: null vector");
+    check_vec(g, v->level, v, "v");
+    const LevelDev &lv = lev(g, v->level);
+    if (!cell_moments_ok(lv))
+        throw std::runtime_error("hmg_cell_moments: one cell of level " + std::to_string(v->level) + " (" + std::to_string(lv.nf) +
+                                 " nodes) does not fit the LDS; the per-cell moments serve " +
+                                 (g->dim == 3 ? "3D levels up to 6" : "2D levels up to 8"));
+    const MeshTables &M = g->cur();
+    const int dim = g->dim, nq = sym_ncomp(dim), nraw = cell_moments_nraw(dim), nmom = dim + nq;
+    const int64_t nc = g->md.ncells;
+    if (nc == 0) return 0;
+    hmg_ctx *c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const size_t bytes = sizeof(double) * (size_t)nraw * (size_t)nc;
+    std::vector<double> raw((size_t)nraw * (size_t)nc);
+    double *d = vec_alloc(c, bytes);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;             // (times of the last call: hmg_ctx_counter "cell_moments_*_ns")
+    try {
+        HIPCHK(hipEventCreate(&ev0));
+        HIPCHK(hipEventCreate(&ev1));
+        HIPCHK(hipEventRecord(ev0, c->stream));
+        launch_cell_moments(c->L, lv, nc, v->d, d);
+        HIPCHK(hipEventRecord(ev1, c->stream));
+        HIPCHK(hipEventSynchronize(ev1));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+        const auto t0 = std::chrono::steady_clock::now();
+        HIPCHK(hipMemcpyAsync(raw.data(), d, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        c->moments_kernel_ns = (int64_t)((double)ms * 1e6);
+        c->moments_download_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    } catch (...) {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        vec_release(c, d, bytes);
+        throw;
+    }
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    vec_release(c, d, bytes);
+    const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
+    for (int64_t e = 0; e < nc; ++e) {
+        const double *r = &raw[(size_t)e * nraw];
+        const double *Ji = &M.jinv[(size_t)e * dim * dim];          // Jinv[k,a] = Ji[k + dim a]
+        const double det = M.detj[e], vol = det * ref;
+        double q[3][3], mv[3];
+        for (int a = 0; a < dim; ++a)
+            for (int b = a; b < dim; ++b) {
+                const double t = r[sym_index(dim, a, b)];
+                q[a][b] = q[b][a] = a == b ? t : 0.5 * t;
+            }
+        for (int k = 0; k < dim; ++k) {
+            double s = 0.0;
+            for (int a = 0; a < dim; ++a) s += Ji[k + dim * a] * r[nq + a];
+            mv[k] = s / ref;
+        }
+        double *o = out + (size_t)e * nmom;
+        for (int k = 0; k < dim; ++k) o[k] = xi ? xi[k] + mv[k] : mv[k];
+        for (int k = 0; k < dim; ++k)
+            for (int l = k; l < dim; ++l) {
+                double s = 0.0;
+                for (int a = 0; a < dim; ++a) {
+                    double qj = 0.0;
+                    for (int b = 0; b < dim; ++b) qj += q[a][b] * Ji[l + dim * b];
+                    s += Ji[k + dim * a] * qj;
+                }
+                double G = det * s;
+                if (xi) G += vol * (xi[k] * xi[l] + xi[k] * mv[l] + mv[k] * xi[l]);
+                o[dim + sym_index(dim, k, l)] = G;
+            }
+    }
+    HMG_END
+}
+
+}  // extern "C"

@@ -1,0 +1,22 @@
+// Per-cell gradient moments of a level vector (include/hmg.h: hmg_cell_moments): what the host module (hmg_fields.cpp) and the
+// kernel (hmg_fields.hip) share.
+#pragma once
+
+#include "hmg_device.hpp"
+
+namespace hmg {
+
+// Reference sums per cell: the quadratic forms of the stiffness terms of the class table, then the linear forms of dphi.
+//   raw[c][t]      = sum_i v_i (T_t v_c)_i,  t = 0 .. nterm - 2   (term order 11, 12, 13, 22, 23, 33; 2D: 11, 12, 22; an
+//                    off-diagonal term of the class table is A^(a,b) + A^(b,a), so its form is 2 q_ab)
+//   raw[c][nq + a] = sum_i dphi[3 i + a] v_i,  a = 0 .. dim - 1
+inline int cell_moments_nraw(int dim) { return dim * (dim + 1) / 2 + dim; }
+
+// LDS of one workgroup: the class table without its mass term, the lattice image with its guard, one row of partial sums per wave
+size_t cell_moments_lds_bytes(const LevelDev &lv);
+// does one cell of this level fit the LDS of a compute unit, with the tables the kernel needs?
+bool cell_moments_ok(const LevelDev &lv);
+// raw[c][0 .. nraw) for the first ncells columns of v (column stride lv.ld); deterministic: the same bits in every run
+void launch_cell_moments(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, double *raw);
+
+}  // namespace hmg

@@ -13,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from . import api, vtk
+from . import api, fields as cell_fields, vtk
 from .api import Mesh, Tet64, Tri64
 
 _CUBE_TETS = ((0, 1, 2, 6), (0, 1, 4, 6), (1, 3, 2, 6), (1, 3, 6, 7), (1, 5, 4, 6), (1, 5, 6, 7))
@@ -578,3 +578,93 @@ def checkerboard_hypercube_multigrid(n: int, eltype=Tet64, refinements: int = 2,
     if own_ctx:
         ctx.sync()
     return rs, top, implicit
+
+
+def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
+                             values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
+                             fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200):
+    """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
+    a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
+    moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
+
+        energy_form   sum_c sigma_c : G_u(c) / |Omega|           (= xi . Sigma xi)
+        flux_form     sum_c |c| sigma_c m_u(c) / |Omega|         (= Sigma xi, a whole row from one corrector)
+
+    They agree (energy_form = xi . flux_form) to the accuracy of the solve.  The right-hand side is `rhs_axi_grad_v`, the initial
+    guess zero; V-cycles (or, `accelerate`, flexible-CG steps around them) run until the first-copy norm of the residual
+    b - A v has fallen by `tolerance` from its initial value -- or at once if that is rounding noise of the loads (a uniform
+    medium: v = 0).  `sigma_grid`: one tensor per unit cube, (n,) * dim + (dim,) diagonals or + (dim, dim) full tensors; default:
+    the seeded checkerboard of `values`; `cond`: the conductivity per CELL instead, (Ne, dim) or (Ne, dim, dim), as a design or
+    inverse loop moves it.  Returns a dict: "energy_form", "flux_form" (dim), "cycles", "residual" (relative),
+    "volume"; with `fields` also "mean" (Ne, dim), "gram" (Ne, dim, dim), "flux", "energy", "volumes", "cond", "base".  `save` (a
+    file name) writes the coarse mesh with those cell fields (vtk.export_cell_fields).  In this setting, and only in it,
+    gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  No counterpart in the reference."""
+    dim = api._dim_of(eltype)
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = api.Context(0)
+    xi = random_unit_vec(dim) if xi is None else np.asarray(xi, dtype=np.float64)
+    if xi.shape != (dim,):
+        raise ValueError(f"xi must have {dim} entries")
+    base = hypercube(eltype, n)
+    if cond is None:
+        if sigma_grid is None:
+            sigma_grid = generate_conductivity(dim, n, seed, values)
+        cond = conductivity_per_element(base, sigma_grid, (0.0,) * dim)
+    else:
+        cond = np.ascontiguousarray(cond, dtype=np.float64)
+    total_grids = refinements + 1
+    implicit = api.ImplicitFineGrid(ctx, base, total_grids)
+    implicit.set_smoother(smoother)
+    op = api.L2PlusDivAGrad(implicit, 0.0, cond)
+    ops = [op] * total_grids
+    base_level = api.BaseLevel(implicit)
+    states = [api.LevelState(implicit, i + 1) for i in range(total_grids)]
+    top = states[-1]
+    xv = api.DeviceMatrix(implicit, total_grids) if accelerate else top.x      # the iterate (zero-filled)
+    fcg = api.FlexibleCG(implicit, base_level, ops, states, total_grids, smoothing_steps) if accelerate else None
+    xv.fill(0.0)
+    api.rhs_axi_grad_v(top.b, implicit, xi)
+
+    def residual_norm():
+        if accelerate:
+            return fcg.residual_norm()
+        api.local_residual(implicit, op, top, total_grids)                    # r = b - A_loc x, Dirichlet rows zero
+        api.broadcast_interfaces(top.r, implicit, total_grids)
+        return api.norm_unique(top.r)
+
+    if accelerate:
+        fcg.start(xv, top.b)
+    r0 = residual_norm()
+    noise = 1e-13 * api.norm(top.b)                  # the loads of a uniform medium cancel in the interface sum up to rounding
+    rnorm, cycles = r0, 0
+    while rnorm > max(tolerance * r0, noise) and cycles < max_cycles:
+        ok = fcg.step_tolerant() if accelerate else api.vcycle_tolerant(implicit, base_level, ops, states, total_grids,
+                                                                        smoothing_steps)
+        if not ok:
+            warnings.warn(f"dirichlet_homogenization: cycle {cycles + 1} used an inexact level-1 solve")
+        cycles += 1
+        rnorm = residual_norm()
+    if rnorm > max(tolerance * r0, noise):
+        warnings.warn(f"dirichlet_homogenization: residual {rnorm / r0:.3e} of its initial value after {cycles} cycles")
+    mean, gram = api.cell_moments(xv, implicit, xi)
+    vol = cell_fields.cell_volumes(base)
+    omega = float(vol.sum())
+    en = cell_fields.energy(cond, gram)
+    out = {"energy_form": float(en.sum() / omega), "flux_form": cell_fields.flux_row(base, cond, mean), "cycles": cycles,
+           "residual": float(rnorm / r0) if r0 > 0.0 else 0.0, "volume": omega}
+    if fields or save is not None:
+        flux = cell_fields.mean_flux(cond, mean)
+        if save is not None:
+            vtk.export_cell_fields(base, {"a": cond, "mean_gradient": mean, "gram": gram, "mean_flux": flux, "energy": en}, save)
+        if fields:
+            out.update(mean=mean, gram=gram, flux=flux, energy=en, volumes=vol, cond=cond, base=base)
+    if accelerate:
+        fcg.close()
+        xv.close()
+    for st in states:
+        st.close()
+    implicit.close()
+    if own_ctx:
+        ctx.close()
+    return out

@@ -112,6 +112,29 @@ def export_domain(base, cond, name="checkerboard"):
     return write_vtu(name, base.nodes, base.elements - 1, cell_data={"a": a})
 
 
+def export_cell_fields(base, fields: dict, name="cell_fields"):
+    """The coarse mesh with one value set per cell: fields maps a name to (Ne,), (Ne, c) or (Ne, d, d) -- symmetric tensors such as
+    api.cell_moments' gram go out as their d (d + 1) / 2 components by rows of the upper triangle.  The mesh is cut to the cells
+    the arrays cover (a shrunk domain is a prefix)."""
+    data = {}
+    ne = None
+    for key, a in fields.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim == 3:
+            iu = np.triu_indices(a.shape[1])
+            a = np.ascontiguousarray(a[:, iu[0], iu[1]])
+        if ne is None:
+            ne = a.shape[0]
+        if a.shape[0] != ne or a.ndim > 2:
+            raise ValueError(f"cell field {key!r}: {a.shape} does not fit {ne} cells")
+        data[key] = a
+    if ne is None:
+        raise ValueError("no cell field given")
+    if ne > base.elements.shape[0]:
+        raise ValueError(f"{ne} values for {base.elements.shape[0]} cells")
+    return write_vtu(name, base.nodes, base.elements[:ne] - 1, cell_data=data)
+
+
 def export_unknown(implicit, x, k: int, level: int, name=None, field="v"):
     """ref: src/examples/homogenized_coefficients.jl:81-87 -- point data "v" = x[1:nnodes(level), :][:] on the full
     grid of `level`.  `x` is a DeviceMatrix of the finest level or a host (Nf, Ne) array in hierarchical order."""

@@ -269,6 +269,25 @@ int hmg_integrate(hmg_grid *grid, int mode, hmg_vec *v, hmg_vec *second, int64_t
 /* next_rhs!(b, x, implicit, ops): b = lambda*|J|*M*x  (src/examples/homogenized_coefficients.jl:695-713) */
 int hmg_next_rhs(hmg_grid *grid, hmg_vec *x, hmg_vec *b);
 
+/* ---- per-cell gradient moments (no counterpart in the reference) ---------------------------------------------------
+ * For every coarse cell c of the grid's current cells (the prefix after hmg_grid_shrink; the local cells of a partitioned grid,
+ * nothing is exchanged) the mean gradient and the Gram tensor of the gradient of the level vector v -- or, with xi, of
+ * u = xi . x + v:
+ *     m(c) = (1/|c|) int_c grad u            G(c) = int_c grad u (x) grad u
+ * out[c * nmom ..]: m (dim numbers), then G in the order 11, 12, 13, 22, 23, 33 (2D: 11, 12, 22); nmom = hmg_cell_moments_count =
+ * dim + dim (dim + 1) / 2, i.e. 5 in 2D and 9 in 3D.  From these: the mean flux sigma_c m(c) and the flux form of a row of the
+ * homogenized tensor, sum_c |c| sigma_c m(c) / |Omega|; the dissipated energy sigma_c : G(c); field moments per phase; and, for
+ * the plain Dirichlet cell problem (lambda = 0), the sensitivity d(energy)/d(sigma_c) = G_u(c).
+ * The moments are of the vector AS STORED: no operator, no lambda, no Dirichlet mask enters (v should be consistent: every copy
+ * of a shared node the same value).  One kernel of its own reads the column once (8 B/DOF) and writes 72 B (2D: 40 B) of
+ * reference sums per cell; the host applies the cell's J^-1 and |J|.  The sums are folded in a fixed order: the same bits in every run.
+ * It allocates (from the context's pool of level-vector memory) and synchronises: not for the inside of a V-cycle.
+ * Served: every level whose cell fits the LDS with its tables -- 3D levels up to 6, 2D levels up to 8.  Larger cells (3D level 7,
+ * 2D levels 9-11) are refused with a message naming the level; so are a grid without a device context, a vector of another
+ * grid and a null out. */
+int hmg_cell_moments(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */, double *out /* host, nmom*ncells */);
+int hmg_cell_moments_count(const hmg_grid *grid);        /* dim + dim (dim + 1) / 2; works on a host-only grid; -1: null grid */
+
 /* ---- fused fast path ------------------------------------------------------------------------ */
 /* smoothing_steps!(steps, implicit, ops, curr, k)            (src/multigrid.jl:46-71) */
 int hmg_smooth(hmg_grid *grid, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap);

@@ -303,6 +303,25 @@ function integrate(g::HipGrid, mode::Integer, v::HipMatrix, second, nsubset::Int
                 g.h, mode, v.h, second === nothing ? C_NULL : second.h, nsubset, C_NULL, o))
     o[]
 end
+# per-cell gradient moments of a level vector (include/hmg.h, hmg_cell_moments; api.cell_moments): mean gradient (dim x Ne) and
+# Gram tensor (dim x dim x Ne) of v, or of u = ξ⋅x + v when ξ is given
+cell_moments_count(g::HipGrid) = Int(ccall((:hmg_cell_moments_count, LIB), Cint, (Ptr{Cvoid},), g.h))
+function cell_moments(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    g = v.grid
+    nmom = cell_moments_count(g)
+    d = nmom == 5 ? 2 : 3
+    out = zeros(Float64, nmom, ncells(g))
+    check(ccall((:hmg_cell_moments, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), out))
+    gram = zeros(Float64, d, d, ncells(g))
+    t = d
+    for a in 1:d, b in a:d
+        t += 1
+        gram[a, b, :] .= out[t, :]
+        gram[b, a, :] .= out[t, :]
+    end
+    (out[1:d, :], gram)
+end
 # subsets are prefixes 1:n of the ∞-norm ordered cells (find_elements_in_radius, :32-43).  The first term's dot(∂ϕ, P) is
 # the entry of rhs_aξ∇v! for the same ξ: the caller's right-hand side b of outer step 0 is passed along.
 integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =
