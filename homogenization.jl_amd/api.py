@@ -552,6 +552,33 @@ def cell_moments(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None):
     return np.ascontiguousarray(out[:, :d]), gram
 
 
+def cell_pair_moments(v: DeviceMatrix, w: DeviceMatrix, implicit: ImplicitFineGrid, xi_v=None, xi_w=None):
+    """Per coarse cell the symmetrised cross moment of the gradients of two level vectors of one level -- with xi_v / xi_w (each
+    may be None, meaning 0), of u = xi_v.x + v and z = xi_w.x + w (hmg_cell_pair_moments):
+    S (Ne, d, d) = 1/2 int_c (grad u (x) grad z + grad z (x) grad u), exactly symmetric.  w may be v: then S is cell_moments' gram
+    (to rounding).  One pass of 16 B/DOF; the same vectors-as-stored rule and the same refused levels as cell_moments.
+    What to do with it: fields.pair_energy, fields.tensor_sensitivity, driver.dirichlet_homogenization_tensor.  No counterpart
+    in the reference."""
+    lib = L.load()
+    d = implicit.base.dim
+    nq = int(lib.hmg_cell_pair_moments_count(implicit.h))
+    out = np.zeros((implicit.ncells(), nq), dtype=np.float64)
+    xp = []
+    for xi in (xi_v, xi_w):
+        if xi is not None:
+            xi = np.ascontiguousarray(xi, dtype=np.float64)
+            if xi.shape != (d,):
+                raise ValueError(f"xi_v and xi_w must have {d} entries")
+        xp.append(xi)
+    L.check(lib.hmg_cell_pair_moments(implicit.h, v.h, w.h, *[None if xi is None else xi.ctypes.data_as(L.p_f64) for xi in xp],
+                                      out.ctypes.data_as(L.p_f64)))
+    iu = np.triu_indices(d)
+    S = np.zeros((out.shape[0], d, d))
+    S[:, iu[0], iu[1]] = out
+    S[:, iu[1], iu[0]] = out
+    return S
+
+
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))

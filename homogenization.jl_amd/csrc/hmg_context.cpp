@@ -262,6 +262,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;
     if (n == "cell_moments_kernel_ns") return ctx->moments_kernel_ns;       // the last hmg_cell_moments: kernel alone
     if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
+    if (n == "cell_pair_moments_kernel_ns") return ctx->pair_moments_kernel_ns;     // the last hmg_cell_pair_moments, likewise
+    if (n == "cell_pair_moments_download_ns") return ctx->pair_moments_download_ns;
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
     return -1;
 }

@@ -8,12 +8,55 @@
 // and this module turns them into physical moments, |ref| = 1/2 (2D), 1/6 (3D), |c| = |J| |ref|:
 //   m_v = Jinv l / |ref|                G_v = |J| Jinv q Jinv^T
 //   m_u = xi + m_v                      G_u = |c| (xi xi^T + xi m_v^T + m_v xi^T) + G_v       for u = xi . x + v
-// Not on a V-cycle's path: it allocates (the raw sums, from the context's pool of level-vector memory) and synchronises.
+//
+// hmg_cell_pair_moments: the symmetrised cross moment of two vectors v, w of one level.  The kernel (hmg_fields_pair.hip) leaves
+//   q_ab = sum_i v_i (A^(a,b) w_c)_i  (an off-diagonal term: q_ab + q_ba), l^v_a, l^w_a
+// and, with sym(A) = (A + A^T) / 2,
+//   S_vw = |J| Jinv sym(q) Jinv^T       S_uz = S_vw + |c| sym(xi_v xi_w^T + xi_v m_w^T + m_v xi_w^T)
+// for u = xi_v . x + v, z = xi_w . x + w.  S_vv = G_v.
+// Not on a V-cycle's path: both allocate (the raw sums, from the context's pool of level-vector memory) and synchronise.
 #include "../../include/hmg.h"
 #include "hmg_fields.hpp"
 #include "hmg_objects.hpp"
 
 #include <chrono>
+
+namespace {
+
+// the raw sums of one kernel pass, downloaded: `launch` enqueues the kernel that fills `bytes` of device memory; the kernel's time
+// (device events) and the download's (host clock) go to the two counters
+template <class F>
+void raw_sums(hmg_ctx *c, std::vector<double> &raw, F launch, int64_t &kernel_ns, int64_t &download_ns)
+{
+    const size_t bytes = sizeof(double) * raw.size();
+    double *d = vec_alloc(c, bytes);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    try {
+        HIPCHK(hipEventCreate(&ev0));
+        HIPCHK(hipEventCreate(&ev1));
+        HIPCHK(hipEventRecord(ev0, c->stream));
+        launch(d);
+        HIPCHK(hipEventRecord(ev1, c->stream));
+        HIPCHK(hipEventSynchronize(ev1));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
+        const auto t0 = std::chrono::steady_clock::now();
+        HIPCHK(hipMemcpyAsync(raw.data(), d, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        kernel_ns = (int64_t)((double)ms * 1e6);
+        download_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+    } catch (...) {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        vec_release(c, d, bytes);
+        throw;
+    }
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    vec_release(c, d, bytes);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -45,33 +88,9 @@ int hmg_cell_moments(hmg_grid *g, hmg_vec *v, const double *xi, double *out)
     if (nc == 0) return 0;
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
-    const size_t bytes = sizeof(double) * (size_t)nraw * (size_t)nc;
     std::vector<double> raw((size_t)nraw * (size_t)nc);
-    double *d = vec_alloc(c, bytes);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;             // (times of the last call: hmg_ctx_counter "cell_moments_*_ns")
-    try {
-        HIPCHK(hipEventCreate(&ev0));
-        HIPCHK(hipEventCreate(&ev1));
-        HIPCHK(hipEventRecord(ev0, c->stream));
-        launch_cell_moments(c->L, lv, nc, v->d, d);
-        HIPCHK(hipEventRecord(ev1, c->stream));
-        HIPCHK(hipEventSynchronize(ev1));
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-        const auto t0 = std::chrono::steady_clock::now();
-        HIPCHK(hipMemcpyAsync(raw.data(), d, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        c->moments_kernel_ns = (int64_t)((double)ms * 1e6);
-        c->moments_download_ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    } catch (...) {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        vec_release(c, d, bytes);
-        throw;
-    }
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
-    vec_release(c, d, bytes);
+    // (times of the last call: hmg_ctx_counter "cell_moments_*_ns")
+    raw_sums(c, raw, [&](double *d) { launch_cell_moments(c->L, lv, nc, v->d, d); }, c->moments_kernel_ns, c->moments_download_ns);
     const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
     for (int64_t e = 0; e < nc; ++e) {
         const double *r = &raw[(size_t)e * nraw];
@@ -101,6 +120,88 @@ int hmg_cell_moments(hmg_grid *g, hmg_vec *v, const double *xi, double *out)
                 double G = det * s;
                 if (xi) G += vol * (xi[k] * xi[l] + xi[k] * mv[l] + mv[k] * xi[l]);
                 o[dim + sym_index(dim, k, l)] = G;
+            }
+    }
+    HMG_END
+}
+
+int hmg_cell_pair_moments_count(const hmg_grid *grid)
+{
+    if (!grid) {
+        last_error() = "null grid";
+        return -1;
+    }
+    return sym_ncomp(grid->dim);
+}
+
+int hmg_cell_pair_moments(hmg_grid *g, hmg_vec *v, hmg_vec *w, const double *xi_v, const double *xi_w, double *out)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(out != nullptr, "hmg_cell_pair_moments: null output array");
+    need(g->ctx != nullptr, "hmg_cell_pair_moments: this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    need(v != nullptr, "hmg_cell_pair_moments: null vector v");
+    need(w != nullptr, "hmg_cell_pair_moments: null vector w");
+    check_vec(g, v->level, v, "v");
+    need(w->g == g, "vector belongs to another grid: w");
+    if (w->level != v->level)
+        throw std::runtime_error("hmg_cell_pair_moments: v (level " + std::to_string(v->level) + ") and w (level " +
+                                 std::to_string(w->level) + ") are of different levels");
+    check_vec(g, v->level, w, "w");
+    const LevelDev &lv = lev(g, v->level);
+    if (!cell_pair_moments_ok(lv))
+        throw std::runtime_error("hmg_cell_pair_moments: one cell of level " + std::to_string(v->level) + " (" + std::to_string(lv.nf) +
+                                 " nodes) does not fit the LDS; the per-cell moments serve " +
+                                 (g->dim == 3 ? "3D levels up to 6" : "2D levels up to 8"));
+    const MeshTables &M = g->cur();
+    const int dim = g->dim, nq = sym_ncomp(dim), nraw = cell_pair_moments_nraw(dim);
+    const int64_t nc = g->md.ncells;
+    if (nc == 0) return 0;
+    hmg_ctx *c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> raw((size_t)nraw * (size_t)nc);
+    // (times of the last call: hmg_ctx_counter "cell_pair_moments_*_ns")
+    raw_sums(c, raw, [&](double *d) { launch_cell_pair_moments(c->L, lv, nc, v->d, w->d, d); }, c->pair_moments_kernel_ns,
+             c->pair_moments_download_ns);
+    const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
+    const bool with_xi = xi_v || xi_w;
+    double xv[3] = {0.0, 0.0, 0.0}, xw[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < dim; ++k) {
+        if (xi_v) xv[k] = xi_v[k];
+        if (xi_w) xw[k] = xi_w[k];
+    }
+    for (int64_t e = 0; e < nc; ++e) {
+        const double *r = &raw[(size_t)e * nraw];
+        const double *Ji = &M.jinv[(size_t)e * dim * dim];          // Jinv[k,a] = Ji[k + dim a]
+        const double det = M.detj[e], vol = det * ref;
+        double q[3][3], mv[3], mw[3];
+        for (int a = 0; a < dim; ++a)
+            for (int b = a; b < dim; ++b) {
+                const double t = r[sym_index(dim, a, b)];
+                q[a][b] = q[b][a] = a == b ? t : 0.5 * t;           // sym(q): an off-diagonal term of the table is q_ab + q_ba
+            }
+        for (int k = 0; k < dim; ++k) {
+            double sv = 0.0, sw = 0.0;
+            for (int a = 0; a < dim; ++a) {
+                sv += Ji[k + dim * a] * r[nq + a];
+                sw += Ji[k + dim * a] * r[nq + dim + a];
+            }
+            mv[k] = sv / ref;
+            mw[k] = sw / ref;
+        }
+        double *o = out + (size_t)e * nq;
+        for (int k = 0; k < dim; ++k)
+            for (int l = k; l < dim; ++l) {
+                double s = 0.0;
+                for (int a = 0; a < dim; ++a) {
+                    double qj = 0.0;
+                    for (int b = 0; b < dim; ++b) qj += q[a][b] * Ji[l + dim * b];
+                    s += Ji[k + dim * a] * qj;
+                }
+                double S = det * s;
+                if (with_xi)
+                    S += vol * 0.5 * ((xv[k] * xw[l] + xv[l] * xw[k]) + (xv[k] * mw[l] + xv[l] * mw[k]) + (mv[k] * xw[l] + mv[l] * xw[k]));
+                o[sym_index(dim, k, l)] = S;
             }
     }
     HMG_END

@@ -15,41 +15,13 @@
 // Reduction: lanes by data-parallel moves, waves in ascending order by one thread per sum -- a fixed order, the same bits in
 // every run and for every grid size.
 #include "hmg_fields.hpp"
-#include "hmg_stencil.hpp"
+#include "hmg_fields_device.hpp"
 
 namespace hmg {
 
 namespace {
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
-
-template <int DIM>
-__device__ __forceinline__ void read_taps(const double *xs, int L, int len, int A, int B, int hi, bool clamp, double *tap)
-{
-    // tap numbering of stencil_eval_v; clamp: surface nodes, whose zero-weight taps may leave the image on either side
-    auto at = [&](int off) {
-        int q = L + off;
-        if (clamp) q = min(max(q, 0), hi);
-        return lds_ld(xs + q);
-    };
-    tap[0] = lds_ld(xs + L);
-    tap[1] = at(1);
-    tap[2] = at(-1);
-    tap[3] = at(len - 1);
-    tap[4] = at(-len);
-    tap[5] = at(len);
-    tap[6] = at(-len - 1);
-    if (DIM == 3) {
-        tap[7] = at(A - len);
-        tap[8] = at(len + 1 - B);
-        tap[9] = at(A - 1);
-        tap[10] = at(1 - B);
-        tap[11] = at(A);
-        tap[12] = at(-B);
-        tap[13] = at(A + 1 - len);
-        tap[14] = at(len - B);
-    }
-}
 
 template <int DIM, int NT>
 __global__ void __launch_bounds__(NT)

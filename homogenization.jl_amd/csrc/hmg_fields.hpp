@@ -1,5 +1,5 @@
-// Per-cell gradient moments of a level vector (include/hmg.h: hmg_cell_moments): what the host module (hmg_fields.cpp) and the
-// kernel (hmg_fields.hip) share.
+// Per-cell gradient moments of a level vector (include/hmg.h: hmg_cell_moments) and of a pair of them (hmg_cell_pair_moments):
+// what the host module (hmg_fields.cpp) and the kernels (hmg_fields.hip, hmg_fields_pair.hip) share.
 #pragma once
 
 #include "hmg_device.hpp"
@@ -18,5 +18,17 @@ size_t cell_moments_lds_bytes(const LevelDev &lv);
 bool cell_moments_ok(const LevelDev &lv);
 // raw[c][0 .. nraw) for the first ncells columns of v (column stride lv.ld); deterministic: the same bits in every run
 void launch_cell_moments(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, double *raw);
+
+// The bilinear counterpart for two vectors v, w of one level (w may be v):
+//   raw[c][t]            = sum_i v_i (T_t w_c)_i,  t = 0 .. nterm - 2   (the same term order; an off-diagonal term is 2 sym q_ab)
+//   raw[c][nq + a]       = sum_i dphi[3 i + a] v_i
+//   raw[c][nq + dim + a] = sum_i dphi[3 i + a] w_i,  a = 0 .. dim - 1
+inline int cell_pair_moments_nraw(int dim) { return dim * (dim + 1) / 2 + 2 * dim; }
+
+// LDS of one workgroup: as above (one image: w's), with the wider rows of partial sums -- a verdict of its own
+size_t cell_pair_moments_lds_bytes(const LevelDev &lv);
+bool cell_pair_moments_ok(const LevelDev &lv);
+// raw[c][0 .. nraw) for the first ncells columns of v and w (column stride lv.ld); deterministic: the same bits in every run
+void launch_cell_pair_moments(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const double *w, double *raw);
 
 }  // namespace hmg

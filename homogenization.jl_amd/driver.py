@@ -580,6 +580,42 @@ def checkerboard_hypercube_multigrid(n: int, eltype=Tet64, refinements: int = 2,
     return rs, top, implicit
 
 
+def _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_steps, tolerance, max_cycles, who):
+    """One corrector of the plain Dirichlet cell problem, the solve loop `dirichlet_homogenization` and
+    `dirichlet_homogenization_tensor` share: the iterate `xv` starts at zero, the right-hand side of the finest state becomes
+    rhs_a.xi.grad(v), and V-cycles (`fcg` None) or flexible-CG steps run until the first-copy norm of the residual has fallen by
+    `tolerance` from its initial value or is rounding noise of the loads.  Returns (cycles, norm(r), initial norm(r))."""
+    total_grids = len(states)
+    ops = [op] * total_grids
+    top = states[-1]
+    accelerate = fcg is not None
+    xv.fill(0.0)
+    api.rhs_axi_grad_v(top.b, implicit, xi)
+
+    def residual_norm():
+        if accelerate:
+            return fcg.residual_norm()
+        api.local_residual(implicit, op, top, total_grids)                    # r = b - A_loc x, Dirichlet rows zero
+        api.broadcast_interfaces(top.r, implicit, total_grids)
+        return api.norm_unique(top.r)
+
+    if accelerate:
+        fcg.start(xv, top.b)
+    r0 = residual_norm()
+    noise = 1e-13 * api.norm(top.b)                  # the loads of a uniform medium cancel in the interface sum up to rounding
+    rnorm, cycles = r0, 0
+    while rnorm > max(tolerance * r0, noise) and cycles < max_cycles:
+        ok = fcg.step_tolerant() if accelerate else api.vcycle_tolerant(implicit, base_level, ops, states, total_grids,
+                                                                        smoothing_steps)
+        if not ok:
+            warnings.warn(f"{who}: cycle {cycles + 1} used an inexact level-1 solve")
+        cycles += 1
+        rnorm = residual_norm()
+    if rnorm > max(tolerance * r0, noise):
+        warnings.warn(f"{who}: residual {rnorm / r0:.3e} of its initial value after {cycles} cycles")
+    return cycles, rnorm, r0
+
+
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                              fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200):
@@ -623,30 +659,8 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     top = states[-1]
     xv = api.DeviceMatrix(implicit, total_grids) if accelerate else top.x      # the iterate (zero-filled)
     fcg = api.FlexibleCG(implicit, base_level, ops, states, total_grids, smoothing_steps) if accelerate else None
-    xv.fill(0.0)
-    api.rhs_axi_grad_v(top.b, implicit, xi)
-
-    def residual_norm():
-        if accelerate:
-            return fcg.residual_norm()
-        api.local_residual(implicit, op, top, total_grids)                    # r = b - A_loc x, Dirichlet rows zero
-        api.broadcast_interfaces(top.r, implicit, total_grids)
-        return api.norm_unique(top.r)
-
-    if accelerate:
-        fcg.start(xv, top.b)
-    r0 = residual_norm()
-    noise = 1e-13 * api.norm(top.b)                  # the loads of a uniform medium cancel in the interface sum up to rounding
-    rnorm, cycles = r0, 0
-    while rnorm > max(tolerance * r0, noise) and cycles < max_cycles:
-        ok = fcg.step_tolerant() if accelerate else api.vcycle_tolerant(implicit, base_level, ops, states, total_grids,
-                                                                        smoothing_steps)
-        if not ok:
-            warnings.warn(f"dirichlet_homogenization: cycle {cycles + 1} used an inexact level-1 solve")
-        cycles += 1
-        rnorm = residual_norm()
-    if rnorm > max(tolerance * r0, noise):
-        warnings.warn(f"dirichlet_homogenization: residual {rnorm / r0:.3e} of its initial value after {cycles} cycles")
+    cycles, rnorm, r0 = _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_steps, tolerance, max_cycles,
+                                         "dirichlet_homogenization")
     mean, gram = api.cell_moments(xv, implicit, xi)
     vol = cell_fields.cell_volumes(base)
     omega = float(vol.sum())
@@ -662,6 +676,91 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     if accelerate:
         fcg.close()
         xv.close()
+    for st in states:
+        st.close()
+    implicit.close()
+    if own_ctx:
+        ctx.close()
+    return out
+
+
+def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None, seed: int = 0,
+                                    values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
+                                    fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200):
+    """The full homogenized tensor of the plain Dirichlet cell problem of `dirichlet_homogenization` from ONE grid: d corrector
+    solves with xi = e_k on one implicit grid, one operator and one set of level states (the solve loop is
+    `dirichlet_homogenization`'s), the correctors v_k kept in d finest-level vectors; then, with u_k = e_k.x + v_k,
+
+        tensor        Sigma_kl = sum_c sigma_c : S_{u_k u_l}(c) / |Omega|      symmetric by construction
+        tensor_flux   row k = sum_c |c| sigma_c m_{u_k}(c) / |Omega|           the flux form of corrector k
+
+    S_{u_k u_k} = G_{u_k} comes from api.cell_moments (with the mean gradient the flux form needs), S_{u_k u_l}, k < l, from
+    api.cell_pair_moments: d (d + 1) / 2 kernel passes in all, nothing polarised.  xi . tensor . xi is what
+    `dirichlet_homogenization(xi=xi)` returns as "energy_form", to the accuracy of the solves.  The keywords are those of
+    `dirichlet_homogenization` without `xi`.  Returns a dict: "tensor" (d, d), "tensor_flux" (d, d), "cycles" and "residual"
+    (relative), one per solve, "volume"; with `fields` also "pairs" (d, d, Ne, d, d) -- pairs[k, l, c] = S_{u_k u_l}(c), the exact
+    sensitivity d(Sigma_kl |Omega|) / d(sigma_c) (fields.tensor_sensitivity) --, "means" (d, Ne, d), "volumes", "cond", "base".
+    `save` (a file name) writes the coarse mesh with the cell fields of every pair k <= l, "pair_kl" and "energy_kl" = sigma_c :
+    S_{u_k u_l}(c) (vtk.export_cell_fields).  Memory beyond `dirichlet_homogenization`: d finest-level vectors.  No counterpart
+    in the reference."""
+    dim = api._dim_of(eltype)
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = api.Context(0)
+    base = hypercube(eltype, n)
+    if cond is None:
+        if sigma_grid is None:
+            sigma_grid = generate_conductivity(dim, n, seed, values)
+        cond = conductivity_per_element(base, sigma_grid, (0.0,) * dim)
+    else:
+        cond = np.ascontiguousarray(cond, dtype=np.float64)
+    total_grids = refinements + 1
+    implicit = api.ImplicitFineGrid(ctx, base, total_grids)
+    implicit.set_smoother(smoother)
+    op = api.L2PlusDivAGrad(implicit, 0.0, cond)
+    base_level = api.BaseLevel(implicit)
+    states = [api.LevelState(implicit, i + 1) for i in range(total_grids)]
+    top = states[-1]
+    xv = api.DeviceMatrix(implicit, total_grids) if accelerate else top.x      # the iterate
+    fcg = api.FlexibleCG(implicit, base_level, [op] * total_grids, states, total_grids, smoothing_steps) if accelerate else None
+    V = [api.DeviceMatrix(implicit, total_grids) for _ in range(dim)]          # the correctors v_k
+    ne = base.elements.shape[0]
+    pairs = np.zeros((dim, dim, ne, dim, dim))
+    means = np.zeros((dim, ne, dim))
+    cycles, residual = [], []
+    eye = np.eye(dim)
+    for k in range(dim):
+        cyc, rnorm, r0 = _dirichlet_solve(implicit, op, base_level, states, xv, fcg, eye[k], smoothing_steps, tolerance,
+                                          max_cycles, f"dirichlet_homogenization_tensor, direction {k}")
+        cycles.append(cyc)
+        residual.append(float(rnorm / r0) if r0 > 0.0 else 0.0)
+        V[k].copyto(xv)
+        means[k], pairs[k, k] = api.cell_moments(V[k], implicit, eye[k])
+    for k in range(dim):
+        for l in range(k + 1, dim):
+            pairs[k, l] = pairs[l, k] = api.cell_pair_moments(V[k], V[l], implicit, eye[k], eye[l])
+    vol = cell_fields.cell_volumes(base)
+    omega = float(vol.sum())
+    tensor = np.zeros((dim, dim))
+    for k in range(dim):
+        for l in range(k, dim):
+            tensor[k, l] = tensor[l, k] = float(cell_fields.pair_energy(cond, pairs[k, l]).sum() / omega)
+    out = {"tensor": tensor, "tensor_flux": np.stack([cell_fields.flux_row(base, cond, means[k]) for k in range(dim)]),
+           "cycles": cycles, "residual": residual, "volume": omega}
+    if save is not None:
+        cells = {"a": cond}
+        for k in range(dim):
+            for l in range(k, dim):
+                cells[f"pair_{k + 1}{l + 1}"] = pairs[k, l]
+                cells[f"energy_{k + 1}{l + 1}"] = cell_fields.pair_energy(cond, pairs[k, l])
+        vtk.export_cell_fields(base, cells, save)
+    if fields:
+        out.update(pairs=pairs, means=means, volumes=vol, cond=cond, base=base)
+    if accelerate:
+        fcg.close()
+        xv.close()
+    for v in V:
+        v.close()
     for st in states:
         st.close()
     implicit.close()

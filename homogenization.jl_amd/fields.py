@@ -1,7 +1,8 @@
 """
 What one does with a corrector once it is solved, from two per-cell quantities (api.cell_moments, include/hmg.h:
 hmg_cell_moments): the mean gradient `mean` (Ne, d) and the Gram tensor of the gradient `gram` (Ne, d, d) of u = xi.x + v over
-every coarse cell.  Plain numpy on those arrays; nothing here touches a level vector or the device.
+every coarse cell -- and, for two correctors, from their symmetrised cross moment `pair` (Ne, d, d) (api.cell_pair_moments:
+pair_energy, tensor_sensitivity).  Plain numpy on those arrays; nothing here touches a level vector or the device.
 
 `cond` is the conductivity per cell as `L2PlusDivAGrad` takes it: (Ne, d), the diagonals of diagonal tensors, or (Ne, d, d), full
 symmetric tensors.  No counterpart in the reference.
@@ -80,3 +81,29 @@ def sensitivity(gram, diagonal=False):
     Not the gradient of the screened multi-step drivers' value, which is no energy minimum."""
     gram = np.asarray(gram, dtype=np.float64)
     return np.ascontiguousarray(np.einsum("ekk->ek", gram)) if diagonal else gram
+
+
+def pair_energy(cond, pair):
+    """sigma_c : S(c) = int_c grad u . sigma grad z for the symmetrised cross moment S of two fields (api.cell_pair_moments): the
+    per-cell energy density of an entry of the homogenized tensor, Sigma_kl |Omega| = sum_c sigma_c : S_{u_k u_l}(c), (Ne,).  Not
+    a dissipation: for two different fields it has either sign."""
+    pair = np.asarray(pair, dtype=np.float64)
+    if pair.ndim != 3 or pair.shape[1] != pair.shape[2]:
+        raise ValueError(f"pair must have shape (Ne, d, d), not {pair.shape}")
+    s = _cond(cond, pair.shape[0], pair.shape[1])
+    return np.einsum("ek,ekk->e", s, pair) if s.ndim == 2 else np.einsum("ekl,ekl->e", s, pair)
+
+
+def tensor_sensitivity(pairs, diagonal=False):
+    """d(Sigma_kl |Omega|) / d(sigma_c,mn) of the plain Dirichlet cell problem (lambda = 0, driver.dirichlet_homogenization_tensor)
+    as entry [k, l, c, m, n] of a (d, d, Ne, d, d) array: `pairs` itself, pairs[k, l, c] = S_{u_k u_l}(c), the cross moment of
+    the correctors u_k = e_k.x + v_k.  The entries of sigma_c are taken as independent variables: moving a symmetric off-diagonal
+    pair sigma_mn = sigma_nm together gives 2 S_mn.  diagonal=True: the diagonals, [k, l, c, m] of (d, d, Ne, d), for a `cond` of
+    diagonals.  Exact because Sigma_kl |Omega| = a(u_k, u_l) and BOTH correctors are stationary: the first-order change of
+    either corrector is a test function, against which the other's residual vanishes.  It does not hold where a corrector is not
+    the solution of that problem: an unconverged solve, or the screened multi-step drivers, whose value is no such bilinear
+    form at a solution."""
+    pairs = np.asarray(pairs, dtype=np.float64)
+    if pairs.ndim != 5 or not (pairs.shape[0] == pairs.shape[1] == pairs.shape[3] == pairs.shape[4]):
+        raise ValueError(f"pairs must have shape (d, d, Ne, d, d), not {pairs.shape}")
+    return np.ascontiguousarray(np.einsum("klcmm->klcm", pairs)) if diagonal else pairs

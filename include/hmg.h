@@ -287,6 +287,23 @@ int hmg_next_rhs(hmg_grid *grid, hmg_vec *x, hmg_vec *b);
  * grid and a null out. */
 int hmg_cell_moments(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */, double *out /* host, nmom*ncells */);
 int hmg_cell_moments_count(const hmg_grid *grid);        /* dim + dim (dim + 1) / 2; works on a host-only grid; -1: null grid */
+/* The bilinear counterpart for TWO vectors v, w of one level and grid: per coarse cell the symmetrised cross moment of their
+ * gradients -- or, with xi_v / xi_w (each may be NULL, meaning 0), of u = xi_v . x + v and z = xi_w . x + w:
+ *     S(c) = 1/2 int_c (grad u (x) grad z + grad z (x) grad u)
+ *          = S_vw(c) + |c| sym(xi_v (x) xi_w + xi_v (x) m_w + m_v (x) xi_w),     sym(A) = (A + A^T) / 2, m the mean gradients
+ * out[c * nq ..]: S in the order 11, 12, 13, 22, 23, 33 (2D: 11, 12, 22); nq = hmg_cell_pair_moments_count = dim (dim + 1) / 2.
+ * Only the symmetric part is defined (the class table stores its off-diagonal stiffness terms symmetrised, and sigma : S with
+ * a symmetric sigma needs no more).  S of (v, v) is G of hmg_cell_moments (to rounding; not bit for bit).  With d correctors
+ * u_k = e_k . x + v_k of the plain Dirichlet cell problem: Sigma_kl |Omega| = sum_c sigma_c : S_{u_k u_l}(c), its per-cell
+ * energy density, and d(Sigma_kl |Omega|)/d(sigma_c) = S_{u_k u_l}(c).
+ * One kernel of its own: only w goes into the LDS image, v is read per node straight from its column -- 16 B/DOF read, 96 B
+ * (2D: 56 B) of reference sums written per cell.  w may be v.  Otherwise the rules of hmg_cell_moments: the vectors as stored,
+ * the current cells, local cells of a partitioned grid, a fixed summation order (the same bits in every run), allocation from
+ * the pool and a synchronisation; the same levels served (3D up to 6, 2D up to 8) and refused (naming the level); refused too:
+ * a grid without a device context, a null vector or out, a vector of another grid, v and w of different levels. */
+int hmg_cell_pair_moments(hmg_grid *grid, hmg_vec *v, hmg_vec *w, const double *xi_v /* dim, or NULL */,
+                          const double *xi_w /* dim, or NULL */, double *out /* host, nq*ncells */);
+int hmg_cell_pair_moments_count(const hmg_grid *grid);   /* dim (dim + 1) / 2; works on a host-only grid; -1: null grid */
 
 /* ---- fused fast path ------------------------------------------------------------------------ */
 /* smoothing_steps!(steps, implicit, ops, curr, k)            (src/multigrid.jl:46-71) */

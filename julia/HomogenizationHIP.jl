@@ -322,6 +322,26 @@ function cell_moments(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} =
     end
     (out[1:d, :], gram)
 end
+# the bilinear counterpart for two vectors of one level (hmg_cell_pair_moments; api.cell_pair_moments): the symmetrised cross moment
+# (dim x dim x Ne) of the gradients of v and w, or of ξv⋅x + v and ξw⋅x + w
+cell_pair_moments_count(g::HipGrid) = Int(ccall((:hmg_cell_pair_moments_count, LIB), Cint, (Ptr{Cvoid},), g.h))
+function cell_pair_moments(v::HipMatrix, w::HipMatrix, ξv::Union{Nothing,AbstractVector{Float64}} = nothing,
+                           ξw::Union{Nothing,AbstractVector{Float64}} = nothing)
+    g = v.grid
+    nq = cell_pair_moments_count(g)
+    d = nq == 3 ? 2 : 3
+    out = zeros(Float64, nq, ncells(g))
+    check(ccall((:hmg_cell_pair_moments, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                g.h, v.h, w.h, ξv === nothing ? C_NULL : collect(Float64, ξv), ξw === nothing ? C_NULL : collect(Float64, ξw), out))
+    S = zeros(Float64, d, d, ncells(g))
+    t = 0
+    for a in 1:d, b in a:d
+        t += 1
+        S[a, b, :] .= out[t, :]
+        S[b, a, :] .= out[t, :]
+    end
+    S
+end
 # subsets are prefixes 1:n of the ∞-norm ordered cells (find_elements_in_radius, :32-43).  The first term's dot(∂ϕ, P) is
 # the entry of rhs_aξ∇v! for the same ξ: the caller's right-hand side b of outer step 0 is passed along.
 integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =

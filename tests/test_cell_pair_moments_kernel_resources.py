@@ -1,0 +1,63 @@
+"""The per-cell pair-moments kernel (csrc/hmg_fields_pair.hip), cross-compiled for gfx950 (no GPU needed): every instantiation
+(2D / 3D x 64, 256, 512 threads) without scratch and without a spilled register.  Its LDS is dynamic (class table + lattice image
+of one operand + wave partials, sized by the host), so none is asserted.  What the compiler reports is recorded in
+profiles/cell_pair_moments_kernel_resources.txt (`python tests/test_cell_pair_moments_kernel_resources.py` rewrites it)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+KERNEL = "k_cell_pair_moments"
+INSTANCES = {(d, nt) for d in (2, 3) for nt in (64, 256, 512)}
+FIELDS = ["SGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "SGPRs Spill", "VGPRs Spill",
+          "LDS Size [bytes/block]"]
+REPORT = os.path.join(ROOT, "profiles", "cell_pair_moments_kernel_resources.txt")
+
+
+def resources(workdir):
+    src = os.path.join(ROOT, "homogenization.jl_amd", "csrc", "hmg_fields_pair.hip")
+    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c", src,
+                          "-o", os.path.join(str(workdir), "f.o")], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    found = {}
+    for blk in re.split(r"remark: [^\n]*Function Name: ", out.stderr)[1:]:
+        name = blk.split()[0]
+        m = re.search(KERNEL + r"ILi(\d+)ELi(\d+)E", name)
+        if m is None:
+            continue
+        vals = {}
+        for f in FIELDS:
+            q = re.search(re.escape(f) + r": (\d+)", blk)
+            if q:
+                vals[f] = int(q.group(1))
+        found[(int(m.group(1)), int(m.group(2)))] = vals
+    return found
+
+
+def write_report(found):
+    with open(REPORT, "w") as f:
+        f.write("csrc/hmg_fields_pair.hip for gfx950, hipcc -O3 -Rpass-analysis=kernel-resource-usage (LDS is dynamic: sized by the host)\n")
+        f.write(f"{'kernel':<34}" + "".join(f"{c:>10}" for c in ("SGPRs", "VGPRs", "AGPRs", "scratch", "occupancy", "spills")) + "\n")
+        for (d, nt), v in sorted(found.items()):
+            f.write(f"{KERNEL + '<' + str(d) + ', ' + str(nt) + '>':<34}" +
+                    "".join(f"{v[c]:>10}" for c in ("SGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")) +
+                    f"{v['SGPRs Spill'] + v['VGPRs Spill']:>10}\n")
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_cell_pair_moments_kernel_has_no_scratch_and_no_spills(tmp_path):
+    found = resources(tmp_path)
+    assert set(found) == INSTANCES, sorted(found)
+    for inst, v in found.items():
+        assert v["ScratchSize [bytes/lane]"] == 0, (inst, v)
+        assert v["SGPRs Spill"] == 0 and v["VGPRs Spill"] == 0, (inst, v)
+
+
+if __name__ == "__main__":
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        write_report(resources(d))
+    print(open(REPORT).read())

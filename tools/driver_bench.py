@@ -13,7 +13,10 @@ synchronise.  Prints the times of every round, their medians, the ratio and the 
 --polycrystal: the field is driver.generate_polycrystal (one rotated tensor per unit cube, principal conductivities 1 and
 --contrast, in 3D 1, --contrast and their geometric mean) instead of the two-valued diagonal field; the CPU oracle knows diagonal
 tensors only, so it implies --no-cpu.
---field-seed S: the seed of the coefficient field (default 5), e.g. for a figure over several fields."""
+--field-seed S: the seed of the coefficient field (default 5), e.g. for a figure over several fields.
+--dirichlet-tensor: driver.dirichlet_homogenization_tensor on hypercube(n) (d solves of the plain Dirichlet cell problem on one grid,
+then d (d + 1) / 2 per-cell moment passes): one line with the wall time of a run after --warmup untimed ones, the cycles and the
+kernel counters of its last single-vector and its last pair pass ("cell_moments_kernel_ns", "cell_pair_moments_kernel_ns")."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,6 +36,7 @@ ap.add_argument("--contrast", type=float, default=9.0, help="sigma takes the val
 ap.add_argument("--tensor", action="store_true", help="one tensor run against d (d + 1) / 2 scalar runs")
 ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
 ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
+ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
@@ -44,6 +48,30 @@ else:
     sgrid = driver.generate_conductivity(a.dim, width, a.field_seed, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
+if a.dirichlet_tensor:
+    if a.polycrystal:
+        principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
+        sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
+    else:
+        sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
+    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate, smoother=a.smoother)
+    for _ in range(a.warmup):
+        driver.dirichlet_homogenization_tensor(a.n, tag, **kw)
+    ctx.sync()
+    t0 = time.perf_counter()
+    r = driver.dirichlet_homogenization_tensor(a.n, tag, **kw)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    print(json.dumps({"config": f"dirichlet_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
+                      "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
+                      "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
+                      "cell_moments_kernel_ns": ctx.counter("cell_moments_kernel_ns"),
+                      "cell_moments_download_ns": ctx.counter("cell_moments_download_ns"),
+                      "cell_pair_moments_kernel_ns": ctx.counter("cell_pair_moments_kernel_ns"),
+                      "cell_pair_moments_download_ns": ctx.counter("cell_pair_moments_download_ns"),
+                      "tensor": r["tensor"].tolist(),
+                      "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
+    sys.exit(0)
 if a.tensor:
     kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, seed=7, accelerate=a.accelerate,
               smoother=a.smoother)
