@@ -532,7 +532,9 @@ def integrate_pair_load(v: DeviceMatrix, s: DeviceMatrix, implicit: ImplicitFine
 def cell_moments(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None):
     """Per coarse cell the mean gradient and the Gram tensor of the gradient of the level vector v -- with xi, of u = xi.x + v
     (hmg_cell_moments): mean (Ne, d) = (1/|c|) int_c grad u, gram (Ne, d, d) = int_c grad u (x) grad u.  The moments are of the
-    vector as stored (no operator, no constraint); levels whose cell exceeds the LDS (3D level 7, 2D levels 9-11) are refused.
+    vector as stored (no operator, no constraint); levels whose cell exceeds the LDS (3D level 7, 2D levels 9-11) are refused
+    unless the context option "cell_moments_windows" is 1 (then they walk through a rolling LDS window: the pair kernel with v given
+    twice, 8 B/DOF; 2: every level the window kernels can address does, an A/B knob).
     What to do with them: fields.py.  No counterpart in the reference."""
     lib = L.load()
     d = implicit.base.dim
@@ -556,7 +558,8 @@ def cell_pair_moments(v: DeviceMatrix, w: DeviceMatrix, implicit: ImplicitFineGr
     """Per coarse cell the symmetrised cross moment of the gradients of two level vectors of one level -- with xi_v / xi_w (each
     may be None, meaning 0), of u = xi_v.x + v and z = xi_w.x + w (hmg_cell_pair_moments):
     S (Ne, d, d) = 1/2 int_c (grad u (x) grad z + grad z (x) grad u), exactly symmetric.  w may be v: then S is cell_moments' gram
-    (to rounding).  One pass of 16 B/DOF; the same vectors-as-stored rule and the same refused levels as cell_moments.
+    (to rounding; to the last bit where both go through the window kernels).  One pass of 16 B/DOF; the same vectors-as-stored
+    rule, the same refused levels and the same context option "cell_moments_windows" as cell_moments.
     What to do with it: fields.pair_energy, fields.tensor_sensitivity, driver.dirichlet_homogenization_tensor.  No counterpart
     in the reference."""
     lib = L.load()

@@ -11,6 +11,7 @@
 // upload_levels).  Same arithmetic per node as k_apply / k_apply_slab (stencil_eval_c for surface nodes, stencil_eval_v with the
 // interior weight row for the rest).
 #include "hmg_device.hpp"
+#include "hmg_rows_window.hpp"
 #include "hmg_stencil.hpp"
 
 #include <stdexcept>
@@ -18,37 +19,6 @@
 namespace hmg {
 
 namespace {
-
-constexpr int RW_NT = 1024;          // threads per workgroup: two resident per CU (<= 64 VGPRs, 2 x 78 KB of LDS)
-constexpr int RW_WIN = 9600;         // window doubles: rows [j0-1, j1] + guard
-constexpr int RW_GUARD = 8;          // zero entries behind the window (the last evaluated row reads one past it)
-constexpr int RW_MV = 3;             // values per thread of the window move (two rows of <= 1025 nodes)
-
-__host__ __device__ __forceinline__ int rows_ro(int m, int j)   // RO(j) = lattice nodes in rows < j (j clamped to [0, m+1])
-{
-    j = j < 0 ? 0 : j > m + 1 ? m + 1 : j;
-    return j * (m + 1) - ((j * (j - 1)) >> 1);
-}
-
-// last row (exclusive) of the band that starts at row j0: the window [j0-1, j1] plus the guard fits RW_WIN
-__host__ __device__ __forceinline__ int rows_band_end(int m, int j0)
-{
-    const int lo = rows_ro(m, j0 - 1);
-    int j1 = j0 + 1;
-    while (j1 <= m && rows_ro(m, j1 + 2) - lo + RW_GUARD <= RW_WIN) ++j1;
-    return j1;
-}
-
-// row of lattice position L (0 <= L < nf): RO(j) <= L < RO(j+1)
-__device__ __forceinline__ int rows_row_of(int m, int L)
-{
-    const float b = (float)(2 * m + 3);
-    int j = (int)((b - __builtin_sqrtf(b * b - 8.0f * (float)L)) * 0.5f);
-    j = j < 0 ? 0 : j > m ? m : j;
-    while (j > 0 && rows_ro(m, j) > L) --j;
-    while (j < m && rows_ro(m, j + 1) <= L) ++j;
-    return j;
-}
 
 // the row-band form of every launch (class weights combined per cell; flags bit 2 -- restriction weights -- is refused by the launcher)
 template <bool FUSED, bool WD>

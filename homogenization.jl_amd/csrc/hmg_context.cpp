@@ -264,6 +264,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
     if (n == "cell_pair_moments_kernel_ns") return ctx->pair_moments_kernel_ns;     // the last hmg_cell_pair_moments, likewise
     if (n == "cell_pair_moments_download_ns") return ctx->pair_moments_download_ns;
+    if (n == "cell_moments_window_launches") return ctx->moments_window_launches;   // launches of the window kernels (option "cell_moments_windows")
+    if (n == "cell_moments_windows") return ctx->moments_windows;                   // ... and that option's value (a caller that sets it for one pass restores it)
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
     return -1;
 }
@@ -321,6 +323,11 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         ctx->L.wave_grid = std::max<int64_t>(1, value);
     else if (n == "cell_order")            // 1 = default: XCD-aware cell order of the register-blocked full-grid apply launches
         ctx->L.cell_order = value != 0;
+    else if (n == "cell_moments_windows") {   // 0 = default: per-cell moments refuse cells larger than the LDS; 1: those take the window
+        if (value < 0 || value > 2)           // kernels; 2: every level the window kernels can address does (test and A/B knob)
+            throw std::runtime_error("option cell_moments_windows: 0, 1 or 2");
+        ctx->moments_windows = (int)value;
+    }
     else if (n == "coarse_poly")           // Chebyshev iterates per preconditioner application of the level-1 PCG (1 = Jacobi)
         ctx->coarse_poly = std::max<int>(1, std::min<int>(16, (int)value));
     else if (n == "coarse_maxit")

@@ -14,6 +14,10 @@
 // and, with sym(A) = (A + A^T) / 2,
 //   S_vw = |J| Jinv sym(q) Jinv^T       S_uz = S_vw + |c| sym(xi_v xi_w^T + xi_v m_w^T + m_v xi_w^T)
 // for u = xi_v . x + v, z = xi_w . x + w.  S_vv = G_v.
+// Cells larger than the LDS (3D level 7, 2D levels 9..11) are refused unless the context option "cell_moments_windows" routes them
+// to the window kernels (hmg_fields_window.hip: 1 -- levels that do not fit only; 2 -- every level those kernels can address).  There
+// both entry points run the pair kernel, hmg_cell_moments with its vector given twice: the leading nq + dim sums of a pair row are
+// its own raw sums, and the transforms below are the same on either path.
 // Not on a V-cycle's path: both allocate (the raw sums, from the context's pool of level-vector memory) and synchronise.
 #include "../../include/hmg.h"
 #include "hmg_fields.hpp"
@@ -56,6 +60,38 @@ void raw_sums(hmg_ctx *c, std::vector<double> &raw, F launch, int64_t &kernel_ns
     vec_release(c, d, bytes);
 }
 
+// the level's rolling-window lists (those set_slab hands to the operator apply), without touching the grid's launch state
+SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv)
+{
+    const LevelBufs &B = *g->lb[lv.level - 1];
+    SlabTables st{};
+    st.head = B.slab_head.p;
+    st.ld_word = B.slab_ld_word.p;
+    st.cp_word = B.slab_cp_word.p;
+    st.cp_slot = B.slab_cp_slot.p;
+    st.nslab = B.nslab;
+    st.lds_nodes = B.slab_lds_nodes;
+    st.max_surf = B.slab_max_surf;
+    st.max_int = B.slab_max_int;
+    return st;
+}
+
+// does this call take the window kernels?  fits: the verdict of the LDS-resident kernel.  Throws the refusal where no kernel serves.
+bool takes_window(const hmg_grid *g, const LevelDev &lv, const SlabTables &st, bool fits, const char *fn)
+{
+    const int mode = g->ctx->moments_windows;
+    const bool can = mode != 0 && cell_moments_window_ok(lv, st);
+    if (can && (mode == 2 || !fits)) return true;
+    if (!fits)
+        throw std::runtime_error(std::string(fn) + ": one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
+                                 " nodes) does not fit the LDS; the per-cell moments serve " +
+                                 (g->dim == 3 ? "3D levels up to 6" : "2D levels up to 8") +
+                                 (mode == 0 && cell_moments_window_ok(lv, st)
+                                      ? "; the context option \"cell_moments_windows\" = 1 takes larger cells through the window kernels"
+                                      : ""));
+    return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -78,19 +114,24 @@ int hmg_cell_moments(hmg_grid *g, hmg_vec *v, const double *xi, double *out)
     need(v != nullptr, "hmg_cell_moments: null vector");
     check_vec(g, v->level, v, "v");
     const LevelDev &lv = lev(g, v->level);
-    if (!cell_moments_ok(lv))
-        throw std::runtime_error("hmg_cell_moments: one cell of level " + std::to_string(v->level) + " (" + std::to_string(lv.nf) +
-                                 " nodes) does not fit the LDS; the per-cell moments serve " +
-                                 (g->dim == 3 ? "3D levels up to 6" : "2D levels up to 8"));
+    const SlabTables st = slab_tables(g, lv);
+    const bool window = takes_window(g, lv, st, cell_moments_ok(lv), "hmg_cell_moments");
     const MeshTables &M = g->cur();
-    const int dim = g->dim, nq = sym_ncomp(dim), nraw = cell_moments_nraw(dim), nmom = dim + nq;
+    // (window: the pair kernel with v given twice leaves rows of the pair layout, whose leading nq + dim sums are this call's)
+    const int dim = g->dim, nq = sym_ncomp(dim), nraw = window ? cell_pair_moments_nraw(dim) : cell_moments_nraw(dim), nmom = dim + nq;
     const int64_t nc = g->md.ncells;
     if (nc == 0) return 0;
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> raw((size_t)nraw * (size_t)nc);
     // (times of the last call: hmg_ctx_counter "cell_moments_*_ns")
-    raw_sums(c, raw, [&](double *d) { launch_cell_moments(c->L, lv, nc, v->d, d); }, c->moments_kernel_ns, c->moments_download_ns);
+    raw_sums(c, raw, [&](double *d) {
+        if (window) {
+            launch_cell_pair_moments_window(c->L, lv, st, nc, v->d, v->d, d);
+            c->moments_window_launches += 1;
+        } else
+            launch_cell_moments(c->L, lv, nc, v->d, d);
+    }, c->moments_kernel_ns, c->moments_download_ns);
     const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
     for (int64_t e = 0; e < nc; ++e) {
         const double *r = &raw[(size_t)e * nraw];
@@ -149,10 +190,8 @@ int hmg_cell_pair_moments(hmg_grid *g, hmg_vec *v, hmg_vec *w, const double *xi_
                                  std::to_string(w->level) + ") are of different levels");
     check_vec(g, v->level, w, "w");
     const LevelDev &lv = lev(g, v->level);
-    if (!cell_pair_moments_ok(lv))
-        throw std::runtime_error("hmg_cell_pair_moments: one cell of level " + std::to_string(v->level) + " (" + std::to_string(lv.nf) +
-                                 " nodes) does not fit the LDS; the per-cell moments serve " +
-                                 (g->dim == 3 ? "3D levels up to 6" : "2D levels up to 8"));
+    const SlabTables st = slab_tables(g, lv);
+    const bool window = takes_window(g, lv, st, cell_pair_moments_ok(lv), "hmg_cell_pair_moments");
     const MeshTables &M = g->cur();
     const int dim = g->dim, nq = sym_ncomp(dim), nraw = cell_pair_moments_nraw(dim);
     const int64_t nc = g->md.ncells;
@@ -161,8 +200,13 @@ int hmg_cell_pair_moments(hmg_grid *g, hmg_vec *v, hmg_vec *w, const double *xi_
     HIPCHK(hipSetDevice(c->device));
     std::vector<double> raw((size_t)nraw * (size_t)nc);
     // (times of the last call: hmg_ctx_counter "cell_pair_moments_*_ns")
-    raw_sums(c, raw, [&](double *d) { launch_cell_pair_moments(c->L, lv, nc, v->d, w->d, d); }, c->pair_moments_kernel_ns,
-             c->pair_moments_download_ns);
+    raw_sums(c, raw, [&](double *d) {
+        if (window) {
+            launch_cell_pair_moments_window(c->L, lv, st, nc, v->d, w->d, d);
+            c->moments_window_launches += 1;
+        } else
+            launch_cell_pair_moments(c->L, lv, nc, v->d, w->d, d);
+    }, c->pair_moments_kernel_ns, c->pair_moments_download_ns);
     const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
     const bool with_xi = xi_v || xi_w;
     double xv[3] = {0.0, 0.0, 0.0}, xw[3] = {0.0, 0.0, 0.0};

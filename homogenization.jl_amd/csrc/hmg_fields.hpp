@@ -1,5 +1,5 @@
 // Per-cell gradient moments of a level vector (include/hmg.h: hmg_cell_moments) and of a pair of them (hmg_cell_pair_moments):
-// what the host module (hmg_fields.cpp) and the kernels (hmg_fields.hip, hmg_fields_pair.hip) share.
+// what the host module (hmg_fields.cpp) and the kernels (hmg_fields.hip, hmg_fields_pair.hip, hmg_fields_window.hip) share.
 #pragma once
 
 #include "hmg_device.hpp"
@@ -30,5 +30,15 @@ size_t cell_pair_moments_lds_bytes(const LevelDev &lv);
 bool cell_pair_moments_ok(const LevelDev &lv);
 // raw[c][0 .. nraw) for the first ncells columns of v and w (column stride lv.ld); deterministic: the same bits in every run
 void launch_cell_pair_moments(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const double *w, double *raw);
+
+// Cells larger than the LDS (hmg_fields_window.hip): the same raw sums, in the pair layout, from a rolling window of the LDS -- slabs
+// of k-planes in 3D (st: the level's SlabTables, the lists of k_apply_slab), bands of lattice rows in 2D (closed forms, st unused).
+// v == w (the same pointer) reads the column once; the single-vector sums are the first nq + dim of every row.
+// can the window kernels address this level?  3D: levels with slab tables; 2D: m >= 2
+bool cell_moments_window_ok(const LevelDev &lv, const SlabTables &st);
+// raw[c][0 .. nraw) of the pair layout for the first ncells columns; throws on a level it cannot address and on null bases before
+// any launch; deterministic: the same bits in every run and for every number of cells
+void launch_cell_pair_moments_window(const Launch &L, const LevelDev &lv, const SlabTables &st, int64_t ncells, const double *v,
+                                     const double *w, double *raw);
 
 }  // namespace hmg

@@ -7,7 +7,7 @@
 //   hmg_coarse.cpp   level-1 system, its PCG and the probes budgeted solves leave behind
 //   hmg_comm.cpp     cut exchange, the RCCL communicator and the exchange settings of a grid
 //   hmg_fcg.cpp      flexible CG around the V-cycle
-//   hmg_fields.cpp   per-cell gradient moments of a level vector and of a pair of them
+//   hmg_fields.cpp   per-cell gradient moments of a level vector and of a pair of them, through the LDS-resident or the window kernels
 //   hmg_capi.cpp     vector operations, primitives, right-hand sides, integrals: argument checks and one call each
 //
 // Every extern "C" entry point lives in the module it fronts; hmg_capi.cpp keeps those that front none.
@@ -235,6 +235,9 @@ struct hmg_ctx {
     int64_t smoother_diag_builds = 0;        // times a grid of this context formed them (ensure_smoother_diag)
     int64_t moments_kernel_ns = 0, moments_download_ns = 0;   // the last hmg_cell_moments: its kernel (device events) and the download of its sums (host clock)
     int64_t pair_moments_kernel_ns = 0, pair_moments_download_ns = 0;   // the last hmg_cell_pair_moments, likewise
+    int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window
+                                             // kernels (hmg_fields_window.hip); 2 so does every level those kernels can address (A/B knob)
+    int64_t moments_window_launches = 0;     // launches of the window kernels (hmg_ctx_counter "cell_moments_window_launches")
     int64_t coarse_x_folds = 0;              // residuals that finished the coarser level's x on the way (option fold_coarse_x)
     int last_pre_form = 0;                   // x-updates the last pre-smoother of a V-cycle's down leg left to its local residual: 0 .. 3
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update

@@ -7,6 +7,7 @@ vector on the host.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import warnings
@@ -616,9 +617,27 @@ def _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_st
     return cycles, rnorm, r0
 
 
+@contextlib.contextmanager
+def _large_cells(ctx, on: bool):
+    """Around the moment passes of the Dirichlet drivers: with `on`, the context option "cell_moments_windows" is at least 1 inside
+    (cells larger than the LDS -- 3D level 7, 2D levels 9-11 -- go through the window kernels) and back at its previous value
+    behind, also when a pass raises.  The context may be the caller's."""
+    if not on:
+        yield
+        return
+    prev = ctx.counter("cell_moments_windows")
+    if prev == 0:
+        ctx.set_option("cell_moments_windows", 1)
+    try:
+        yield
+    finally:
+        ctx.set_option("cell_moments_windows", prev)
+
+
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
-                             fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200):
+                             fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
+                             large_cells: bool = False):
     """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
     a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
     moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
@@ -634,7 +653,9 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     inverse loop moves it.  Returns a dict: "energy_form", "flux_form" (dim), "cycles", "residual" (relative),
     "volume"; with `fields` also "mean" (Ne, dim), "gram" (Ne, dim, dim), "flux", "energy", "volumes", "cond", "base".  `save` (a
     file name) writes the coarse mesh with those cell fields (vtk.export_cell_fields).  In this setting, and only in it,
-    gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  No counterpart in the reference."""
+    gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  `large_cells`: the moment pass may
+    run on a top level whose cell exceeds the LDS (3D level 7, 2D levels 9-11; context option "cell_moments_windows" = 1 around
+    the pass, restored behind it); without it such a level is refused after the solve.  No counterpart in the reference."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -661,7 +682,8 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     fcg = api.FlexibleCG(implicit, base_level, ops, states, total_grids, smoothing_steps) if accelerate else None
     cycles, rnorm, r0 = _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_steps, tolerance, max_cycles,
                                          "dirichlet_homogenization")
-    mean, gram = api.cell_moments(xv, implicit, xi)
+    with _large_cells(ctx, large_cells):
+        mean, gram = api.cell_moments(xv, implicit, xi)
     vol = cell_fields.cell_volumes(base)
     omega = float(vol.sum())
     en = cell_fields.energy(cond, gram)
@@ -686,7 +708,8 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
 
 def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None, seed: int = 0,
                                     values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
-                                    fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200):
+                                    fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
+                                    large_cells: bool = False):
     """The full homogenized tensor of the plain Dirichlet cell problem of `dirichlet_homogenization` from ONE grid: d corrector
     solves with xi = e_k on one implicit grid, one operator and one set of level states (the solve loop is
     `dirichlet_homogenization`'s), the correctors v_k kept in d finest-level vectors; then, with u_k = e_k.x + v_k,
@@ -697,7 +720,7 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
     S_{u_k u_k} = G_{u_k} comes from api.cell_moments (with the mean gradient the flux form needs), S_{u_k u_l}, k < l, from
     api.cell_pair_moments: d (d + 1) / 2 kernel passes in all, nothing polarised.  xi . tensor . xi is what
     `dirichlet_homogenization(xi=xi)` returns as "energy_form", to the accuracy of the solves.  The keywords are those of
-    `dirichlet_homogenization` without `xi`.  Returns a dict: "tensor" (d, d), "tensor_flux" (d, d), "cycles" and "residual"
+    `dirichlet_homogenization` without `xi` (`large_cells` included: it holds around every moment pass).  Returns a dict: "tensor" (d, d), "tensor_flux" (d, d), "cycles" and "residual"
     (relative), one per solve, "volume"; with `fields` also "pairs" (d, d, Ne, d, d) -- pairs[k, l, c] = S_{u_k u_l}(c), the exact
     sensitivity d(Sigma_kl |Omega|) / d(sigma_c) (fields.tensor_sensitivity) --, "means" (d, Ne, d), "volumes", "cond", "base".
     `save` (a file name) writes the coarse mesh with the cell fields of every pair k <= l, "pair_kl" and "energy_kl" = sigma_c :
@@ -735,10 +758,12 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
         cycles.append(cyc)
         residual.append(float(rnorm / r0) if r0 > 0.0 else 0.0)
         V[k].copyto(xv)
-        means[k], pairs[k, k] = api.cell_moments(V[k], implicit, eye[k])
-    for k in range(dim):
-        for l in range(k + 1, dim):
-            pairs[k, l] = pairs[l, k] = api.cell_pair_moments(V[k], V[l], implicit, eye[k], eye[l])
+        with _large_cells(ctx, large_cells):
+            means[k], pairs[k, k] = api.cell_moments(V[k], implicit, eye[k])
+    with _large_cells(ctx, large_cells):
+        for k in range(dim):
+            for l in range(k + 1, dim):
+                pairs[k, l] = pairs[l, k] = api.cell_pair_moments(V[k], V[l], implicit, eye[k], eye[l])
     vol = cell_fields.cell_volumes(base)
     omega = float(vol.sum())
     tensor = np.zeros((dim, dim))

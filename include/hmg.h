@@ -283,8 +283,12 @@ int hmg_next_rhs(hmg_grid *grid, hmg_vec *x, hmg_vec *b);
  * reference sums per cell; the host applies the cell's J^-1 and |J|.  The sums are folded in a fixed order: the same bits in every run.
  * It allocates (from the context's pool of level-vector memory) and synchronises: not for the inside of a V-cycle.
  * Served: every level whose cell fits the LDS with its tables -- 3D levels up to 6, 2D levels up to 8.  Larger cells (3D level 7,
- * 2D levels 9-11) are refused with a message naming the level; so are a grid without a device context, a vector of another
- * grid and a null out. */
+ * 2D levels 9-11) are refused with a message naming the level, unless hmg_ctx_set_option "cell_moments_windows" is 1: then such
+ * a cell walks through a rolling window of the LDS, as in the operator apply of those levels (slabs of k-planes in 3D, bands of
+ * lattice rows in 2D; the pair kernel with v given twice: 8 B/DOF, the same rules, the same bits in every run).  Value 2 sends
+ * every level the window kernels can address through them (3D levels 6 and 7, 2D levels from 2: a test and A/B knob); 0 is the
+ * default.  hmg_ctx_counter "cell_moments_window_launches" counts their launches, "cell_moments_windows" reads the option back.
+ * Refused too: a grid without a device context, a vector of another grid and a null out. */
 int hmg_cell_moments(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */, double *out /* host, nmom*ncells */);
 int hmg_cell_moments_count(const hmg_grid *grid);        /* dim + dim (dim + 1) / 2; works on a host-only grid; -1: null grid */
 /* The bilinear counterpart for TWO vectors v, w of one level and grid: per coarse cell the symmetrised cross moment of their
@@ -293,13 +297,16 @@ int hmg_cell_moments_count(const hmg_grid *grid);        /* dim + dim (dim + 1) 
  *          = S_vw(c) + |c| sym(xi_v (x) xi_w + xi_v (x) m_w + m_v (x) xi_w),     sym(A) = (A + A^T) / 2, m the mean gradients
  * out[c * nq ..]: S in the order 11, 12, 13, 22, 23, 33 (2D: 11, 12, 22); nq = hmg_cell_pair_moments_count = dim (dim + 1) / 2.
  * Only the symmetric part is defined (the class table stores its off-diagonal stiffness terms symmetrised, and sigma : S with
- * a symmetric sigma needs no more).  S of (v, v) is G of hmg_cell_moments (to rounding; not bit for bit).  With d correctors
+ * a symmetric sigma needs no more).  S of (v, v) is G of hmg_cell_moments (to rounding; bit for bit only where both calls take the
+ * window kernels, which are one kernel and one host transform).  With d correctors
  * u_k = e_k . x + v_k of the plain Dirichlet cell problem: Sigma_kl |Omega| = sum_c sigma_c : S_{u_k u_l}(c), its per-cell
  * energy density, and d(Sigma_kl |Omega|)/d(sigma_c) = S_{u_k u_l}(c).
  * One kernel of its own: only w goes into the LDS image, v is read per node straight from its column -- 16 B/DOF read, 96 B
  * (2D: 56 B) of reference sums written per cell.  w may be v.  Otherwise the rules of hmg_cell_moments: the vectors as stored,
  * the current cells, local cells of a partitioned grid, a fixed summation order (the same bits in every run), allocation from
- * the pool and a synchronisation; the same levels served (3D up to 6, 2D up to 8) and refused (naming the level); refused too:
+ * the pool and a synchronisation; the same levels served (3D up to 6, 2D up to 8) and refused (naming the level), and the same
+ * option "cell_moments_windows" for larger cells (only w goes into the window; v is read per node, or from the window's centre
+ * tap where v and w are one vector); refused too:
  * a grid without a device context, a null vector or out, a vector of another grid, v and w of different levels. */
 int hmg_cell_pair_moments(hmg_grid *grid, hmg_vec *v, hmg_vec *w, const double *xi_v /* dim, or NULL */,
                           const double *xi_w /* dim, or NULL */, double *out /* host, nq*ncells */);

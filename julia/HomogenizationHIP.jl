@@ -305,6 +305,8 @@ function integrate(g::HipGrid, mode::Integer, v::HipMatrix, second, nsubset::Int
 end
 # per-cell gradient moments of a level vector (include/hmg.h, hmg_cell_moments; api.cell_moments): mean gradient (dim x Ne) and
 # Gram tensor (dim x dim x Ne) of v, or of u = ξ⋅x + v when ξ is given
+# (cells larger than the LDS -- 3D level 7, 2D levels 9-11 -- are refused unless the context option "cell_moments_windows" is 1:
+#  set_option!(ctx, "cell_moments_windows", 1); the same holds for cell_pair_moments below)
 cell_moments_count(g::HipGrid) = Int(ccall((:hmg_cell_moments_count, LIB), Cint, (Ptr{Cvoid},), g.h))
 function cell_moments(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing)
     g = v.grid

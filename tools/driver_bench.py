@@ -16,7 +16,9 @@ tensors only, so it implies --no-cpu.
 --field-seed S: the seed of the coefficient field (default 5), e.g. for a figure over several fields.
 --dirichlet-tensor: driver.dirichlet_homogenization_tensor on hypercube(n) (d solves of the plain Dirichlet cell problem on one grid,
 then d (d + 1) / 2 per-cell moment passes): one line with the wall time of a run after --warmup untimed ones, the cycles and the
-kernel counters of its last single-vector and its last pair pass ("cell_moments_kernel_ns", "cell_pair_moments_kernel_ns")."""
+kernel counters of its last single-vector and its last pair pass ("cell_moments_kernel_ns", "cell_pair_moments_kernel_ns").
+--large-cells (with --dirichlet-tensor): the driver's keyword large_cells=True -- a top level whose cell exceeds the LDS (3D level 7,
+2D levels 9-11: --refinements 6 / 8-10) takes the window kernels; the line then carries "cell_moments_window_launches" too."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,6 +39,7 @@ ap.add_argument("--tensor", action="store_true", help="one tensor run against d 
 ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
 ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
+ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor: moment passes of cells larger than the LDS")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
@@ -54,7 +57,8 @@ if a.dirichlet_tensor:
         sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
     else:
         sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
-    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate, smoother=a.smoother)
+    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate, smoother=a.smoother,
+              large_cells=a.large_cells)
     for _ in range(a.warmup):
         driver.dirichlet_homogenization_tensor(a.n, tag, **kw)
     ctx.sync()
@@ -69,6 +73,7 @@ if a.dirichlet_tensor:
                       "cell_moments_download_ns": ctx.counter("cell_moments_download_ns"),
                       "cell_pair_moments_kernel_ns": ctx.counter("cell_pair_moments_kernel_ns"),
                       "cell_pair_moments_download_ns": ctx.counter("cell_pair_moments_download_ns"),
+                      "large_cells": a.large_cells, "cell_moments_window_launches": ctx.counter("cell_moments_window_launches"),
                       "tensor": r["tensor"].tolist(),
                       "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
     sys.exit(0)
