@@ -9,15 +9,15 @@
 //   m_v = Jinv l / |ref|                G_v = |J| Jinv q Jinv^T
 //   m_u = xi + m_v                      G_u = |c| (xi xi^T + xi m_v^T + m_v xi^T) + G_v       for u = xi . x + v
 //
-// hmg_cell_pair_moments: the symmetrised cross moment of two vectors v, w of one level.  The kernel (hmg_fields_pair.hip) leaves
+// hmg_cell_pair_moments: the symmetrised cross moment of two vectors v, w of one level.  The same kernel leaves
 //   q_ab = sum_i v_i (A^(a,b) w_c)_i  (an off-diagonal term: q_ab + q_ba), l^v_a, l^w_a
 // and, with sym(A) = (A + A^T) / 2,
 //   S_vw = |J| Jinv sym(q) Jinv^T       S_uz = S_vw + |c| sym(xi_v xi_w^T + xi_v m_w^T + m_v xi_w^T)
 // for u = xi_v . x + v, z = xi_w . x + w.  S_vv = G_v.
+// hmg_cell_moments is the pair of a vector with itself: one handle given twice is read once, and its rows hold one set of l.
 // Cells larger than the LDS (3D level 7, 2D levels 9..11) are refused unless the context option "cell_moments_windows" routes them
-// to the window kernels (hmg_fields_window.hip: 1 -- levels that do not fit only; 2 -- every level those kernels can address).  There
-// both entry points run the pair kernel, hmg_cell_moments with its vector given twice: the leading nq + dim sums of a pair row are
-// its own raw sums, and the transforms below are the same on either path.
+// to the window kernels (hmg_fields_window.hip: 1 -- levels that do not fit only; 2 -- every level those kernels can address); the
+// rows and the transforms below are the same on either path.
 // Not on a V-cycle's path: both allocate (the raw sums, from the context's pool of level-vector memory) and synchronise.
 #include "../../include/hmg.h"
 #include "hmg_fields.hpp"
@@ -92,6 +92,79 @@ bool takes_window(const hmg_grid *g, const LevelDev &lv, const SlabTables &st, b
     return false;
 }
 
+// the raw rows of one call (hmg_fields.hpp), downloaded: nraw sums per cell, one set of l where w is v
+struct RawRows {
+    int nraw = 0;
+    bool same = false;
+    std::vector<double> sums;
+};
+
+// What both entry points (fn) do before their transforms: the checks of v and w as level vectors of g, the choice of the kernel,
+// its launch and the download.  pair: the times go to the counters "cell_pair_moments_*_ns", otherwise to "cell_moments_*_ns"
+// (the last call's, hmg_ctx_counter).
+RawRows cell_raw_rows(hmg_grid *g, hmg_vec *v, hmg_vec *w, bool pair, const char *fn)
+{
+    check_vec(g, v->level, v, "v");
+    if (w != v) {
+        need(w->g == g, "vector belongs to another grid: w");
+        if (w->level != v->level)
+            throw std::runtime_error(std::string(fn) + ": v (level " + std::to_string(v->level) + ") and w (level " +
+                                     std::to_string(w->level) + ") are of different levels");
+        check_vec(g, v->level, w, "w");
+    }
+    const LevelDev &lv = lev(g, v->level);
+    const SlabTables st = slab_tables(g, lv);
+    RawRows R;
+    R.same = v->d == w->d;
+    R.nraw = cell_moments_nraw(g->dim, R.same);
+    const bool window = takes_window(g, lv, st, cell_moments_ok(lv, R.same), fn);
+    const int64_t nc = g->md.ncells;
+    if (nc == 0) return R;
+    hmg_ctx *c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    R.sums.resize((size_t)R.nraw * (size_t)nc);
+    raw_sums(c, R.sums, [&](double *d) {
+        if (window) {
+            launch_cell_pair_moments_window(c->L, lv, st, nc, v->d, w->d, d);
+            c->moments_window_launches += 1;
+        } else
+            launch_cell_pair_moments(c->L, lv, nc, v->d, w->d, d);
+    }, pair ? c->pair_moments_kernel_ns : c->moments_kernel_ns, pair ? c->pair_moments_download_ns : c->moments_download_ns);
+    return R;
+}
+
+// sym(q) of a raw row: an off-diagonal term of the class table is q_ab + q_ba
+void unpack_sym(int dim, const double *r, double q[3][3])
+{
+    for (int a = 0; a < dim; ++a)
+        for (int b = a; b < dim; ++b) {
+            const double t = r[sym_index(dim, a, b)];
+            q[a][b] = q[b][a] = a == b ? t : 0.5 * t;
+        }
+}
+
+// m = Jinv l / |ref|;  Jinv[k,a] = Ji[k + dim a]
+void mean_gradient(int dim, const double *Ji, const double *l, double ref, double m[3])
+{
+    for (int k = 0; k < dim; ++k) {
+        double s = 0.0;
+        for (int a = 0; a < dim; ++a) s += Ji[k + dim * a] * l[a];
+        m[k] = s / ref;
+    }
+}
+
+// (|J| Jinv q Jinv^T)_kl
+double physical_form(int dim, const double *Ji, double det, const double q[3][3], int k, int l)
+{
+    double s = 0.0;
+    for (int a = 0; a < dim; ++a) {
+        double qj = 0.0;
+        for (int b = 0; b < dim; ++b) qj += q[a][b] * Ji[l + dim * b];
+        s += Ji[k + dim * a] * qj;
+    }
+    return det * s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,53 +185,23 @@ int hmg_cell_moments(hmg_grid *g, hmg_vec *v, const double *xi, double *out)
     need(out != nullptr, "hmg_cell_moments: null output array");
     need(g->ctx != nullptr, "hmg_cell_moments: this grid was created without a device context (host tables only): no compute path exists on the CPU");
     need(v != nullptr, "hmg_cell_moments: null vector");
-    check_vec(g, v->level, v, "v");
-    const LevelDev &lv = lev(g, v->level);
-    const SlabTables st = slab_tables(g, lv);
-    const bool window = takes_window(g, lv, st, cell_moments_ok(lv), "hmg_cell_moments");
+    const RawRows R = cell_raw_rows(g, v, v, false, "hmg_cell_moments");
     const MeshTables &M = g->cur();
-    // (window: the pair kernel with v given twice leaves rows of the pair layout, whose leading nq + dim sums are this call's)
-    const int dim = g->dim, nq = sym_ncomp(dim), nraw = window ? cell_pair_moments_nraw(dim) : cell_moments_nraw(dim), nmom = dim + nq;
+    const int dim = g->dim, nq = sym_ncomp(dim), nmom = dim + nq;
     const int64_t nc = g->md.ncells;
-    if (nc == 0) return 0;
-    hmg_ctx *c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<double> raw((size_t)nraw * (size_t)nc);
-    // (times of the last call: hmg_ctx_counter "cell_moments_*_ns")
-    raw_sums(c, raw, [&](double *d) {
-        if (window) {
-            launch_cell_pair_moments_window(c->L, lv, st, nc, v->d, v->d, d);
-            c->moments_window_launches += 1;
-        } else
-            launch_cell_moments(c->L, lv, nc, v->d, d);
-    }, c->moments_kernel_ns, c->moments_download_ns);
     const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
     for (int64_t e = 0; e < nc; ++e) {
-        const double *r = &raw[(size_t)e * nraw];
-        const double *Ji = &M.jinv[(size_t)e * dim * dim];          // Jinv[k,a] = Ji[k + dim a]
+        const double *r = &R.sums[(size_t)e * R.nraw];
+        const double *Ji = &M.jinv[(size_t)e * dim * dim];
         const double det = M.detj[e], vol = det * ref;
         double q[3][3], mv[3];
-        for (int a = 0; a < dim; ++a)
-            for (int b = a; b < dim; ++b) {
-                const double t = r[sym_index(dim, a, b)];
-                q[a][b] = q[b][a] = a == b ? t : 0.5 * t;
-            }
-        for (int k = 0; k < dim; ++k) {
-            double s = 0.0;
-            for (int a = 0; a < dim; ++a) s += Ji[k + dim * a] * r[nq + a];
-            mv[k] = s / ref;
-        }
+        unpack_sym(dim, r, q);
+        mean_gradient(dim, Ji, r + nq, ref, mv);
         double *o = out + (size_t)e * nmom;
         for (int k = 0; k < dim; ++k) o[k] = xi ? xi[k] + mv[k] : mv[k];
         for (int k = 0; k < dim; ++k)
             for (int l = k; l < dim; ++l) {
-                double s = 0.0;
-                for (int a = 0; a < dim; ++a) {
-                    double qj = 0.0;
-                    for (int b = 0; b < dim; ++b) qj += q[a][b] * Ji[l + dim * b];
-                    s += Ji[k + dim * a] * qj;
-                }
-                double G = det * s;
+                double G = physical_form(dim, Ji, det, q, k, l);
                 if (xi) G += vol * (xi[k] * xi[l] + xi[k] * mv[l] + mv[k] * xi[l]);
                 o[dim + sym_index(dim, k, l)] = G;
             }
@@ -183,30 +226,10 @@ int hmg_cell_pair_moments(hmg_grid *g, hmg_vec *v, hmg_vec *w, const double *xi_
     need(g->ctx != nullptr, "hmg_cell_pair_moments: this grid was created without a device context (host tables only): no compute path exists on the CPU");
     need(v != nullptr, "hmg_cell_pair_moments: null vector v");
     need(w != nullptr, "hmg_cell_pair_moments: null vector w");
-    check_vec(g, v->level, v, "v");
-    need(w->g == g, "vector belongs to another grid: w");
-    if (w->level != v->level)
-        throw std::runtime_error("hmg_cell_pair_moments: v (level " + std::to_string(v->level) + ") and w (level " +
-                                 std::to_string(w->level) + ") are of different levels");
-    check_vec(g, v->level, w, "w");
-    const LevelDev &lv = lev(g, v->level);
-    const SlabTables st = slab_tables(g, lv);
-    const bool window = takes_window(g, lv, st, cell_pair_moments_ok(lv), "hmg_cell_pair_moments");
+    const RawRows R = cell_raw_rows(g, v, w, true, "hmg_cell_pair_moments");
     const MeshTables &M = g->cur();
-    const int dim = g->dim, nq = sym_ncomp(dim), nraw = cell_pair_moments_nraw(dim);
+    const int dim = g->dim, nq = sym_ncomp(dim);
     const int64_t nc = g->md.ncells;
-    if (nc == 0) return 0;
-    hmg_ctx *c = g->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    std::vector<double> raw((size_t)nraw * (size_t)nc);
-    // (times of the last call: hmg_ctx_counter "cell_pair_moments_*_ns")
-    raw_sums(c, raw, [&](double *d) {
-        if (window) {
-            launch_cell_pair_moments_window(c->L, lv, st, nc, v->d, w->d, d);
-            c->moments_window_launches += 1;
-        } else
-            launch_cell_pair_moments(c->L, lv, nc, v->d, w->d, d);
-    }, c->pair_moments_kernel_ns, c->pair_moments_download_ns);
     const double ref = dim == 3 ? 1.0 / 6.0 : 0.5;
     const bool with_xi = xi_v || xi_w;
     double xv[3] = {0.0, 0.0, 0.0}, xw[3] = {0.0, 0.0, 0.0};
@@ -215,34 +238,17 @@ int hmg_cell_pair_moments(hmg_grid *g, hmg_vec *v, hmg_vec *w, const double *xi_
         if (xi_w) xw[k] = xi_w[k];
     }
     for (int64_t e = 0; e < nc; ++e) {
-        const double *r = &raw[(size_t)e * nraw];
-        const double *Ji = &M.jinv[(size_t)e * dim * dim];          // Jinv[k,a] = Ji[k + dim a]
+        const double *r = &R.sums[(size_t)e * R.nraw];
+        const double *Ji = &M.jinv[(size_t)e * dim * dim];
         const double det = M.detj[e], vol = det * ref;
         double q[3][3], mv[3], mw[3];
-        for (int a = 0; a < dim; ++a)
-            for (int b = a; b < dim; ++b) {
-                const double t = r[sym_index(dim, a, b)];
-                q[a][b] = q[b][a] = a == b ? t : 0.5 * t;           // sym(q): an off-diagonal term of the table is q_ab + q_ba
-            }
-        for (int k = 0; k < dim; ++k) {
-            double sv = 0.0, sw = 0.0;
-            for (int a = 0; a < dim; ++a) {
-                sv += Ji[k + dim * a] * r[nq + a];
-                sw += Ji[k + dim * a] * r[nq + dim + a];
-            }
-            mv[k] = sv / ref;
-            mw[k] = sw / ref;
-        }
+        unpack_sym(dim, r, q);
+        mean_gradient(dim, Ji, r + nq, ref, mv);
+        mean_gradient(dim, Ji, r + nq + (R.same ? 0 : dim), ref, mw);   // (w is v: one set of l, m_w = m_v)
         double *o = out + (size_t)e * nq;
         for (int k = 0; k < dim; ++k)
             for (int l = k; l < dim; ++l) {
-                double s = 0.0;
-                for (int a = 0; a < dim; ++a) {
-                    double qj = 0.0;
-                    for (int b = 0; b < dim; ++b) qj += q[a][b] * Ji[l + dim * b];
-                    s += Ji[k + dim * a] * qj;
-                }
-                double S = det * s;
+                double S = physical_form(dim, Ji, det, q, k, l);
                 if (with_xi)
                     S += vol * 0.5 * ((xv[k] * xw[l] + xv[l] * xw[k]) + (xv[k] * mw[l] + xv[l] * mw[k]) + (mv[k] * xw[l] + mv[l] * xw[k]));
                 o[sym_index(dim, k, l)] = S;

@@ -1,9 +1,10 @@
 // HIP kernels for AMD CDNA4 (gfx950, wave64).
 //
 // Per-cell pair moments of cells LARGER than the LDS (3D level 7, 2D levels 9..11): the raw sums of k_cell_pair_moments
-// (hmg_fields_pair.hip, hmg_fields.hpp),
-//   raw[c][t]            = sum_i v_i (T_t w_c)_i,   raw[c][nq + a] = sum_i dphi[3 i + a] v_i,   raw[c][nq + dim + a] = sum_i dphi[3 i + a] w_i,
-// formed while the cell walks through a ROLLING window of the LDS, as the operator applies of those levels do:
+// (hmg_fields.hip, hmg_fields.hpp) in the same row layout,
+//   raw[c][t]            = sum_i v_i (T_t w_c)_i,   raw[c][nq + a] = sum_i dphi[3 i + a] v_i,   raw[c][nq + dim + a] = sum_i dphi[3 i + a] w_i
+// (the last set only where w is another vector), formed while the cell walks through a ROLLING window of the LDS, as the operator
+// applies of those levels do:
 //   k_cell_pair_moments_slab (3D) follows k_apply_slab (hmg_kernels.hip): slabs of k-planes from SlabTables -- the window holds
 //     planes [k0-1, k1], planes k0-1 and k0 move to its front LDS -> LDS, the new planes come from HBM through ld_word, the nodes
 //     of planes [k0, k1) are taken from cp_word / cp_slot, surface entries first (decode32w), then the cell interior (decode_lattice);
@@ -21,7 +22,7 @@
 // LDS: 3D window (<= 70 KB) + table (10.8 KB) + partial sums (1.5 KB): one 1024-thread workgroup per CU, which the register need
 // asks for anyway (12 sums + 15 taps + 6 products = 66 VGPRs of doubles: not a 64-VGPR kernel; one workgroup leaves 128).  2D:
 // window 76.8 KB + table and sums 2 KB, 60 VGPRs: two workgroups per CU, as k_apply_rows (no occupancy bound in __launch_bounds__:
-// it caps the scalar registers at 80 and the kernel spilled them; tests/test_cell_moments_window_kernel_resources.py holds the 64).
+// it caps the scalar registers at 80 and the kernel spilled them; tests/test_cell_moments_kernel_resources.py holds the 64).
 #include "hmg_fields.hpp"
 #include "hmg_fields_device.hpp"
 #include "hmg_rows_window.hpp"
@@ -65,29 +66,11 @@ __device__ __forceinline__ void window_taps(const double *xs, int L, int len, in
     }
 }
 
-// lanes by data-parallel moves, waves in ascending order by one thread per sum: red is [NT / 64][NR]
-template <int NR, int NT>
-__device__ __forceinline__ void fold_cell(const double (&acc)[NR], double *red, double *__restrict__ out)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const double ws = wave_sum63(acc[r]);
-        if (lane == 63) red[wave * NR + r] = ws;
-    }
-    __syncthreads();
-    if (tid < NR) {
-        double sum = 0.0;
-        for (int k = 0; k < NT / 64; ++k) sum += red[k * NR + tid];
-        out[tid] = sum;
-    }
-}
-
 template <bool SAME>
 __global__ void __launch_bounds__(SW_NT)
 k_cell_pair_moments_slab(LevelDev lv, const double *v, const double *w, SlabTables st, double *__restrict__ raw)
 {
-    constexpr int DIM = 3, NDIR = 15, NTERM = 7, NQ = NTERM - 1, NR = NQ + 2 * DIM, NT = SW_NT, HB = SW_HB, MV = SW_MV;
+    constexpr int DIM = 3, NDIR = 15, NTERM = 7, NQ = NTERM - 1, NR = NQ + (SAME ? 1 : 2) * DIM, NT = SW_NT, HB = SW_HB, MV = SW_MV;
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
     const int m = lv.m;
@@ -193,7 +176,7 @@ k_cell_pair_moments_slab(LevelDev lv, const double *v, const double *w, SlabTabl
 #pragma unroll
                 for (int a = 0; a < DIM; ++a) {
                     acc[NQ + a] += dp[a] * vs;
-                    acc[NQ + DIM + a] += dp[a] * tap[0];
+                    if constexpr (!SAME) acc[NQ + DIM + a] += dp[a] * tap[0];
                 }
             }
         }
@@ -230,14 +213,14 @@ k_cell_pair_moments_slab(LevelDev lv, const double *v, const double *w, SlabTabl
         }
         lo_prev = lo;
     }
-    fold_cell<NR, NT>(acc, red, raw + cell * NR);
+    fold_cell<NR, NT>(acc, tid >> 6, red, raw + cell * NR);
 }
 
 template <bool SAME>
 __global__ void __launch_bounds__(RW_NT)
 k_cell_pair_moments_rows(LevelDev lv, const double *v, const double *w, double *__restrict__ raw)
 {
-    constexpr int DIM = 2, NDIR = 7, NTERM = 4, NQ = NTERM - 1, NR = NQ + 2 * DIM, NT = RW_NT, HB = 4;
+    constexpr int DIM = 2, NDIR = 7, NTERM = 4, NQ = NTERM - 1, NR = NQ + (SAME ? 1 : 2) * DIM, NT = RW_NT, HB = 4;
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
     const int m = lv.m, nei = lv.nei, off_int = lv.off_int;
@@ -337,14 +320,14 @@ k_cell_pair_moments_rows(LevelDev lv, const double *v, const double *w, double *
 #pragma unroll
                     for (int a = 0; a < DIM; ++a) {
                         acc[NQ + a] += dp[a] * vs;
-                        acc[NQ + DIM + a] += dp[a] * tap[0];
+                        if constexpr (!SAME) acc[NQ + DIM + a] += dp[a] * tap[0];
                     }
                 }
             }
         }
         lo_prev = lo;
     }
-    fold_cell<NR, NT>(acc, red, raw + cell * NR);
+    fold_cell<NR, NT>(acc, tid >> 6, red, raw + cell * NR);
 }
 
 size_t slab_lds_bytes(const LevelDev &lv, const SlabTables &st)

@@ -200,6 +200,22 @@ def test_window_kernels_against_the_lds_kernels(ctx, shapes, name, level):
     dw.close()
 
 
+@pytest.mark.parametrize("name,level", [("cube7", 3), ("cube7", 5), ("cube7", 6), ("square9", 2), ("square9", 8), ("cube7", 7),
+                                        ("square9", 9)])
+def test_equal_values_in_two_handles_give_the_bits_of_one_handle(oracle, shapes, name, level):
+    """two handles take the two-column instantiation of a kernel, one handle given twice the one-column instantiation: on equal
+    values the same bits.  One level per thread count of the LDS kernel (3D levels 3, 5, 6: 64, 256, 512 threads; 2D level 2,
+    m = 2 without interior, and level 8) and one per window kernel (3D level 7, 2D level 9; the module's option value 1)."""
+    base, implicit, g = shapes(name, GRIDS[name][2])[:3]
+    v = F.consistent_random(oracle, implicit, level, np.random.default_rng(100 + level))
+    dv, dc = hmg.DeviceMatrix(g, level).from_host(v), hmg.DeviceMatrix(g, level).from_host(v)
+    xv, xw = np.array([0.6, -0.3, 0.5])[:base.dim], np.array([-0.2, 0.9, 0.4])[:base.dim]
+    for a, b in ((None, None), (xv, xw)):
+        np.testing.assert_array_equal(hmg.cell_pair_moments(dv, dc, g, a, b), hmg.cell_pair_moments(dv, dv, g, a, b))
+    dv.close()
+    dc.close()
+
+
 def test_shrink_gives_the_prefix_bit_for_bit(oracle, ctx):
     O = oracle
     m = O.order_nodes_and_elements_by_magnitude(O.hypercube(2, 4, origin=(-2.0, -2.0)))

@@ -1,4 +1,4 @@
-"""GPU tests of the per-cell pair moments (hmg_cell_pair_moments, csrc/hmg_fields_pair.hip) against the CPU statement of
+"""GPU tests of the per-cell pair moments (hmg_cell_pair_moments, csrc/hmg_fields.hip) against the CPU statement of
 tests/_cell_pair_moments_form.py (pinned by tests/test_cell_pair_moments_statement.py), and of what is built on them
 (driver.dirichlet_homogenization_tensor, fields.tensor_sensitivity).  The shapes are those of tests/test_gpu_cell_moments.py, the
 smallest that reach every path: 3D 48 cells on levels 2-4 (one wave per workgroup), 5 (256 threads) and six cells on level 6 (512

@@ -51,7 +51,7 @@ k, d, w, p = min(kern), min(down), min(wall), min(apply_ms)
 lines = [
     f"per-cell gradient moments, {a.width}^3 cubes x 6 tetrahedra = {g.ncells()} cells, level {L} ({g.nf(L)} nodes per cell, {ndof} DOFs)",
     f"best of {a.reps} synchronised calls, one process, the same vectors",
-    f"k_cell_moments (device events)        {k:9.3f} ms   {8 * ndof / (k * 1e-3) / 1e12:6.3f} TB/s on 8 B/DOF",
+    f"k_cell_pair_moments, one column       {k:9.3f} ms   {8 * ndof / (k * 1e-3) / 1e12:6.3f} TB/s on 8 B/DOF",
     f"download of {g.ncells()} x 9 sums      {d:9.3f} ms",
     f"hmg_cell_moments, whole call (host)   {w:9.3f} ms   (kernel + download + the host's transform per cell)",
     f"plain apply y += A x (host clock)     {p:9.3f} ms   {24 * ndof / (p * 1e-3) / 1e12:6.3f} TB/s on 24 B/DOF",

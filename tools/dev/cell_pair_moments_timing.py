@@ -45,9 +45,9 @@ for width in a.width:
     lines += [
         f"{width}^3 cubes x 6 tetrahedra = {g.ncells()} cells, level {L} ({g.nf(L)} nodes per cell, {ndof} DOFs, "
         f"{8 * ndof / 1e9:.3f} GB per vector); best of {a.reps} calls after a warm-up, device events",
-        f"  k_cell_moments                  {s:9.3f} ms   {8 * ndof / 1e9:7.3f} GB read   {8 * ndof / (s * 1e-3) / 1e12:6.3f} TB/s on  8 B/DOF",
+        f"  hmg_cell_moments (v)            {s:9.3f} ms   {8 * ndof / 1e9:7.3f} GB read   {8 * ndof / (s * 1e-3) / 1e12:6.3f} TB/s on  8 B/DOF",
         f"  k_cell_pair_moments (v, w)      {p:9.3f} ms   {16 * ndof / 1e9:7.3f} GB read   {16 * ndof / (p * 1e-3) / 1e12:6.3f} TB/s on 16 B/DOF",
-        f"  k_cell_pair_moments (v, v)      {q:9.3f} ms   (one handle twice: the second read of the column comes from cache)",
+        f"  k_cell_pair_moments (v, v)      {q:9.3f} ms   (one handle twice: the column is read once, as by hmg_cell_moments)",
         f"  pair / single                   {p / s:9.3f}      (expectation from the bytes: about 2)",
     ]
     x.close()
