@@ -582,6 +582,54 @@ def cell_pair_moments(v: DeviceMatrix, w: DeviceMatrix, implicit: ImplicitFineGr
     return S
 
 
+def fine_elements(implicit: ImplicitFineGrid, level: int) -> int:
+    """Fine elements per coarse cell on `level`: 2^(d (level - 1)) (hmg_grid_fine_elements; a host-only grid answers too)."""
+    n = int(L.load().hmg_grid_fine_elements(implicit.h, int(level)))
+    if n < 0:
+        raise ValueError(f"level {level} is not a level of this grid")
+    return n
+
+
+def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None, thresholds=None):
+    """Per coarse cell, over its fine elements T, the extrema of q_T = grad u . Q_c grad u with u = xi.x + v (xi None: 0) and how
+    many elements exceed each threshold (hmg_cell_extrema): qmax (Ne,), qmin (Ne,), counts (Ne, nthr) int64.  `form` is the
+    symmetric Q_c per cell, (Ne, d, d), or (Ne, d) for diagonals; None is the identity, q = |grad u|^2 (fields.energy_form,
+    fields.flux_form make the usual ones).  Up to 8 finite thresholds, the same for all cells.  The vector as stored; 3D levels
+    up to 6, 2D levels up to 8, larger cells are refused whatever "cell_moments_windows" says.  One pass of 8 B/DOF; the same bits
+    in every run.  What to do with the results: fields.exceedance_volume, fields.concentration.  No counterpart in the reference."""
+    lib = L.load()
+    d = implicit.base.dim
+    ne = implicit.ncells()
+    xp = fp = tp = None
+    if xi is not None:
+        xi = np.ascontiguousarray(xi, dtype=np.float64)
+        if xi.shape != (d,):
+            raise ValueError(f"xi must have {d} entries")
+        xp = xi.ctypes.data_as(L.p_f64)
+    if form is not None:
+        q = np.asarray(form, dtype=np.float64)
+        iu = np.triu_indices(d)
+        if q.shape == (ne, d):
+            full = np.zeros((ne, d, d))
+            full[:, np.arange(d), np.arange(d)] = q
+            q = full
+        if q.shape != (ne, d, d):
+            raise ValueError(f"form must have shape ({ne}, {d}, {d}) or ({ne}, {d}), not {q.shape}")
+        if not np.array_equal(q, np.swapaxes(q, 1, 2)):
+            raise ValueError("form must be symmetric in every cell")
+        packed = np.ascontiguousarray(q[:, iu[0], iu[1]])
+        fp = packed.ctypes.data_as(L.p_f64)
+    thr = np.zeros(0) if thresholds is None else np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
+    if thr.ndim != 1:
+        raise ValueError("thresholds must be a list of numbers")
+    nthr = int(thr.shape[0])
+    if nthr:
+        tp = thr.ctypes.data_as(L.p_f64)
+    out = np.zeros((ne, 2 + nthr), dtype=np.float64)
+    L.check(lib.hmg_cell_extrema(implicit.h, v.h, xp, fp, nthr, tp, out.ctypes.data_as(L.p_f64)))
+    return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]), np.rint(out[:, 2:]).astype(np.int64)
+
+
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))

@@ -266,7 +266,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_pair_moments_download_ns") return ctx->pair_moments_download_ns;
     if (n == "cell_moments_window_launches") return ctx->moments_window_launches;   // launches of the window kernels (option "cell_moments_windows")
     if (n == "cell_moments_windows") return ctx->moments_windows;                   // ... and that option's value (a caller that sets it for one pass restores it)
-    if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;     // as the RCCL communicator was created; 0: none
+    if (n == "cell_extrema_kernel_ns") return ctx->extrema_kernel_ns;               // the last hmg_cell_extrema: kernel alone
+    if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;    // as the RCCL communicator was created; 0: none
     return -1;
 }
 

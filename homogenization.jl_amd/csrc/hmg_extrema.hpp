@@ -1,0 +1,34 @@
+// Per-cell extrema and exceedance counts of a quadratic form of the fine-element gradients of a level vector (include/hmg.h:
+// hmg_cell_extrema): what the host module (hmg_extrema.cpp) and the kernel (hmg_extrema.hip) share.
+#pragma once
+
+#include "hmg_device.hpp"
+
+namespace hmg {
+
+// The fine elements of a cell are the Kuhn simplices {p, p + pi1, p + pi1 + pi2, p + s} of the lattice basis a, b, c (2D: a, b),
+// s = a + b + c, p the lexicographically lowest vertex.  The kernel reaches the 7 (2D: 3) nodes above p through these taps of
+// stencil_eval_v's numbering; build_element_tables (hmg_extrema.cpp) derives the taps from the stencil's direction list and
+// refuses a grid where they differ.
+constexpr int EX_TAP_A = 11, EX_TAP_B = 8, EX_TAP_C = 4, EX_TAP_AB = 5, EX_TAP_AC = 13, EX_TAP_BC = 10, EX_TAP_S = 1;   // 3D
+constexpr int EX2_TAP_A = 5, EX2_TAP_B = 4, EX2_TAP_S = 1;                                                             // 2D
+constexpr int EX_MAX_THRESHOLDS = 8;
+
+struct ExtremaThresholds {
+    double t[EX_MAX_THRESHOLDS];
+};
+
+// numbers per cell in the folded row: Q~ = M^T Q M (order 11, 12, 13, 22, 23, 33; 2D: 11, 12, 22), then xi~ = M^-1 xi
+inline int cell_extrema_nrow(int dim) { return dim * (dim + 1) / 2 + dim; }
+
+// LDS of one workgroup: the lattice image with its guard, per wave a maximum, a minimum and the counters
+size_t cell_extrema_lds_bytes(const LevelDev &lv);
+// the levels served: those whose cell fits the LDS with the image (3D up to 6, 2D up to 8)
+bool cell_extrema_ok(const LevelDev &lv);
+// out[c][0] = max, out[c][1] = min of q over the fine elements of cell c, out[c][2 + j] = number of elements with q > thr.t[j],
+// j < nthr, for the first ncells columns of v (column stride lv.ld).  elem_mask: one byte per slot (ElementTables::mask);
+// rows: cell_extrema_nrow(dim) numbers per cell.  The same bits in every run and for every grid size.
+void launch_cell_extrema(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const uint8_t *elem_mask,
+                         const double *rows, const ExtremaThresholds &thr, int nthr, double *out);
+
+}  // namespace hmg

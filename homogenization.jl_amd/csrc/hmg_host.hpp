@@ -128,6 +128,21 @@ std::vector<LevelTables> build_level_tables(int dim, int nlevels);
 // Stencil direction list: offsets (di,dj,dk); entry 0 is the node itself.
 int stencil_dirs(int dim, const int (**dirs)[3]);
 
+// Fine elements of the refined reference simplex as Kuhn simplices of its lattice (hmg_extrema.cpp).  Among the stencil's
+// directions the lexicographically positive ones that are no sum of two others form a basis a < b (< c) whose sum s is a
+// direction too; every element is {p, p + pi1, p + pi1 + pi2, p + s}, pi a permutation of the basis, p its lowest vertex.
+struct ElementTables {
+    int dim = 0;
+    std::vector<int32_t> dirs;   // dim x dim: a, b(, c) in slot_ijk coordinates, one after the other
+    std::vector<uint8_t> mask;   // per slot: bit k -- the simplex of permutation k (lexicographic order) with p at the slot exists
+    int taps[7] = {0, 0, 0, 0, 0, 0, 0};   // stencil_eval_v's tap of a, b, c, a+b, a+c, b+c, s (2D: a, b, s)
+    int64_t nelem = 0;           // elements = bits set = 2^(dim (level - 1))
+};
+// Built from T.ref_cells, not from a formula; throws where an element is no such simplex, where the elements rebuilt from
+// (slot, bit) are not exactly that list, where their number is not 2^(dim (level - 1)), or where the taps are not those the
+// kernel was written for (hmg_extrema.hpp).
+ElementTables build_element_tables(const LevelTables &T);
+
 // ---------------------------------------------------------------------------------------------
 // Base-mesh tables.
 // ---------------------------------------------------------------------------------------------

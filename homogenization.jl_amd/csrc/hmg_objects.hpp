@@ -8,6 +8,7 @@
 //   hmg_comm.cpp     cut exchange, the RCCL communicator and the exchange settings of a grid
 //   hmg_fcg.cpp      flexible CG around the V-cycle
 //   hmg_fields.cpp   per-cell gradient moments of a level vector and of a pair of them, through the LDS-resident or the window kernels
+//   hmg_extrema.cpp  fine-element table of a level; per-cell extrema and exceedance counts of a quadratic form of the gradient
 //   hmg_capi.cpp     vector operations, primitives, right-hand sides, integrals: argument checks and one call each
 //
 // Every extern "C" entry point lives in the module it fronts; hmg_capi.cpp keeps those that front none.
@@ -171,6 +172,14 @@ struct ApplyTimer {
     size_t used = 0;
 };
 
+// Field state of a grid (hmg_extrema.cpp): per level the fine-element table, built and checked at grid creation on the host, and
+// its device copy, uploaded by the first hmg_cell_extrema on that level -- outside LevelDev, a kernel argument of its own, and
+// outside the checksum of a host-only grid (the tables of the operator's kernels are what that pins).
+struct FieldState {
+    std::vector<ElementTables> elem;                         // [nlevels]
+    std::vector<std::unique_ptr<DevBuf<uint8_t>>> d_mask;    // [nlevels], null until used
+};
+
 // state of the last coarse solve, copied to pinned host memory behind the solve and read when somebody asks
 struct CoarseProbe {
     double *h = nullptr;            // pinned: S_DONE, S_ITER, S_CRR, b.b
@@ -235,6 +244,7 @@ struct hmg_ctx {
     int64_t smoother_diag_builds = 0;        // times a grid of this context formed them (ensure_smoother_diag)
     int64_t moments_kernel_ns = 0, moments_download_ns = 0;   // the last hmg_cell_moments: its kernel (device events) and the download of its sums (host clock)
     int64_t pair_moments_kernel_ns = 0, pair_moments_download_ns = 0;   // the last hmg_cell_pair_moments, likewise
+    int64_t extrema_kernel_ns = 0;           // the last hmg_cell_extrema: its kernel (device events)
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window
                                              // kernels (hmg_fields_window.hip); 2 so does every level those kernels can address (A/B knob)
     int64_t moments_window_launches = 0;     // launches of the window kernels (hmg_ctx_counter "cell_moments_window_launches")
@@ -346,6 +356,8 @@ struct hmg_grid {
     double *ex_buf = nullptr;
     int64_t ex_cap = 0;
     DevBuf<double> own_exbuf;                    // hmg_grid_use_comm: library-owned exchange buffer
+
+    FieldState fields;                           // fine-element tables of hmg_cell_extrema (hmg_extrema.cpp)
 
     uint64_t upload_hash = 1469598103934665603ull;   // host-only grids: checksum of every table a device grid would upload (DryUploads)
 

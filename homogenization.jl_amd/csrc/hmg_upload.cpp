@@ -387,6 +387,7 @@ static int create_grid(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const
     g->dim = dim;
     g->nlevels = nlevels;
     g->lt = build_level_tables(dim, nlevels);
+    for (const LevelTables &T : g->lt) g->fields.elem.push_back(build_element_tables(T));   // (host tables: hmg_cell_extrema)
     if (part) {
         g->part.reset(new Partition);
         // The analysis looks at this rank's cells and their one-cell halo (the global pass keeps only what the replicated level-1
@@ -648,6 +649,12 @@ int hmg_grid_table_i32(const hmg_grid *g, int level, const char *which, int32_t 
             src = &T.slot_ijk;
         else if (w == "ref_cells")
             src = &T.ref_cells;
+        else if (w == "elem_mask") {   // per slot: which Kuhn simplices with their lowest vertex there are fine elements (hmg_extrema.cpp)
+            const auto &mk = g->fields.elem.at(level - 1).mask;
+            tmp.assign(mk.begin(), mk.end());
+            src = &tmp;
+        } else if (w == "elem_dirs")   // ... and their lattice basis in slot_ijk coordinates, dim x dim
+            src = &g->fields.elem.at(level - 1).dirs;
         else if (w == "par_a")
             src = &T.par_a;
         else if (w == "par_b")

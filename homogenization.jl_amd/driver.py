@@ -637,7 +637,7 @@ def _large_cells(ctx, on: bool):
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                              fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
-                             large_cells: bool = False):
+                             large_cells: bool = False, extrema: bool = False, thresholds=None):
     """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
     a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
     moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
@@ -655,7 +655,12 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     file name) writes the coarse mesh with those cell fields (vtk.export_cell_fields).  In this setting, and only in it,
     gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  `large_cells`: the moment pass may
     run on a top level whose cell exceeds the LDS (3D level 7, 2D levels 9-11; context option "cell_moments_windows" = 1 around
-    the pass, restored behind it); without it such a level is refused after the solve.  No counterpart in the reference."""
+    the pass, restored behind it); without it such a level is refused after the solve.  `extrema`: a second pass, over the fine
+    elements (api.cell_extrema with Q = sigma_c; top levels up to 6 in 3D and 8 in 2D), adds "peak_energy_density" and
+    "min_energy_density" (Ne each: the extrema of grad u . sigma_c grad u in every cell), "concentration" = peak / energy_form and,
+    with `thresholds` (up to 8 multiples of energy_form), "exceedance" (Ne, nthr): the volume of every cell on which the energy
+    density exceeds each; they are in the returned dict with or without `fields`, and with `save` in the file.  No counterpart
+    in the reference."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -689,10 +694,20 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     en = cell_fields.energy(cond, gram)
     out = {"energy_form": float(en.sum() / omega), "flux_form": cell_fields.flux_row(base, cond, mean), "cycles": cycles,
            "residual": float(rnorm / r0) if r0 > 0.0 else 0.0, "volume": omega}
+    peaks = {}
+    if extrema:
+        thr = np.zeros(0) if thresholds is None else np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        qmax, qmin, counts = api.cell_extrema(xv, implicit, xi, cell_fields.energy_form(cond), thr * out["energy_form"])
+        peaks = {"peak_energy_density": qmax, "min_energy_density": qmin,
+                 "concentration": cell_fields.concentration(qmax, out["energy_form"])}
+        if thr.size:
+            peaks["exceedance"] = cell_fields.exceedance_volume(counts, vol, api.fine_elements(implicit, total_grids))
+        out.update(peaks)
     if fields or save is not None:
         flux = cell_fields.mean_flux(cond, mean)
         if save is not None:
-            vtk.export_cell_fields(base, {"a": cond, "mean_gradient": mean, "gram": gram, "mean_flux": flux, "energy": en}, save)
+            vtk.export_cell_fields(base, {"a": cond, "mean_gradient": mean, "gram": gram, "mean_flux": flux, "energy": en, **peaks},
+                                   save)
         if fields:
             out.update(mean=mean, gram=gram, flux=flux, energy=en, volumes=vol, cond=cond, base=base)
     if accelerate:

@@ -2,7 +2,8 @@
 What one does with a corrector once it is solved, from two per-cell quantities (api.cell_moments, include/hmg.h:
 hmg_cell_moments): the mean gradient `mean` (Ne, d) and the Gram tensor of the gradient `gram` (Ne, d, d) of u = xi.x + v over
 every coarse cell -- and, for two correctors, from their symmetrised cross moment `pair` (Ne, d, d) (api.cell_pair_moments:
-pair_energy, tensor_sensitivity).  Plain numpy on those arrays; nothing here touches a level vector or the device.
+pair_energy, tensor_sensitivity) -- and, for the pass over the fine elements (api.cell_extrema), the forms to give it and what
+its extrema and counts mean (energy_form, flux_form, exceedance_volume, concentration).  Plain numpy on those arrays; nothing here touches a level vector or the device.
 
 `cond` is the conductivity per cell as `L2PlusDivAGrad` takes it: (Ne, d), the diagonals of diagonal tensors, or (Ne, d, d), full
 symmetric tensors.  No counterpart in the reference.
@@ -107,3 +108,45 @@ def tensor_sensitivity(pairs, diagonal=False):
     if pairs.ndim != 5 or not (pairs.shape[0] == pairs.shape[1] == pairs.shape[3] == pairs.shape[4]):
         raise ValueError(f"pairs must have shape (d, d, Ne, d, d), not {pairs.shape}")
     return np.ascontiguousarray(np.einsum("klcmm->klcm", pairs)) if diagonal else pairs
+
+
+def _full(cond, what="cond"):
+    s = np.asarray(cond, dtype=np.float64)
+    if s.ndim == 2:
+        out = np.zeros(s.shape + (s.shape[1],))
+        i = np.arange(s.shape[1])
+        out[:, i, i] = s
+        return out
+    if s.ndim != 3 or s.shape[1] != s.shape[2]:
+        raise ValueError(f"{what} must have shape (Ne, d) or (Ne, d, d), not {s.shape}")
+    return s
+
+
+def energy_form(cond):
+    """The form of api.cell_extrema whose q is the energy density grad u . sigma_c grad u: Q = sigma_c (symmetrised), (Ne, d, d)."""
+    s = _full(cond)
+    return 0.5 * (s + np.swapaxes(s, 1, 2))
+
+
+def flux_form(cond):
+    """The form whose q is the squared flux |sigma_c grad u|^2: Q = sigma_c^T sigma_c, (Ne, d, d), exactly symmetric."""
+    s = _full(cond)
+    q = np.einsum("emk,eml->ekl", s, s)
+    return 0.5 * (q + np.swapaxes(q, 1, 2))
+
+
+def exceedance_volume(counts, volumes, nel):
+    """Volume of every cell on which q exceeds each threshold: counts |c| / nel, (Ne, nthr) -- the fine elements of a cell all
+    have the volume |c| / nel, nel = api.fine_elements(implicit, level)."""
+    counts = np.asarray(counts, dtype=np.float64)
+    vol = np.asarray(volumes, dtype=np.float64)
+    if counts.ndim != 2 or vol.shape != (counts.shape[0],):
+        raise ValueError("counts must be (Ne, nthr) and volumes (Ne,)")
+    if nel <= 0:
+        raise ValueError("nel must be positive")
+    return counts * (vol[:, None] / float(nel))
+
+
+def concentration(qmax, mean_density):
+    """Peak over mean: qmax (Ne,) over a mean density -- a number (the homogenized energy density, say) or one per cell."""
+    return np.asarray(qmax, dtype=np.float64) / np.asarray(mean_density, dtype=np.float64)

@@ -312,6 +312,29 @@ int hmg_cell_pair_moments(hmg_grid *grid, hmg_vec *v, hmg_vec *w, const double *
                           const double *xi_w /* dim, or NULL */, double *out /* host, nq*ncells */);
 int hmg_cell_pair_moments_count(const hmg_grid *grid);   /* dim (dim + 1) / 2; works on a host-only grid; -1: null grid */
 
+/* ---- per-cell extrema over the fine elements (no counterpart in the reference) ----------------------------------------
+ * The per-cell moments above are integrals; this is the pass over the FINE ELEMENTS of every coarse cell.  For every current coarse
+ * cell c and every fine element T of it (2^(dim (level-1)) of them, hmg_grid_fine_elements; the P1 gradient is constant on each)
+ *     q_T = grad u|_T . Q_c grad u|_T,     u = xi . x + v   (xi = NULL means 0)
+ * with a symmetric Q_c per cell in physical coordinates: form[c * nq ..] in the order of hmg_grid_set_operator_tensor (3D 11, 12,
+ * 13, 22, 23, 33; 2D 11, 12, 22), any finite symmetric matrix, definite or not; form = NULL means the identity, q = |grad u|^2.
+ * Q = sigma_c gives the energy density, Q = sigma_c^T sigma_c the squared flux.
+ * out[c * (2 + nthr) ..]: max_T q_T, min_T q_T, then for each j < nthr the number of elements with q_T > thresholds[j], written
+ * as a double (an exact integer).  0 <= nthr <= 8; the thresholds are finite and the same for all cells.
+ * One kernel of its own reads the column once (8 B/DOF) and one byte of element mask per node; the host folds the cell's J, Q_c
+ * and xi into one row of 9 (2D: 5) numbers per cell.  Maxima, minima and integer counts do not depend on any order: the same
+ * bits in every run and for every launch shape.
+ * Otherwise the rules of hmg_cell_moments: the vector as stored (no operator, no lambda, no mask), the current cells after a
+ * shrink, the local cells of a partitioned grid with nothing exchanged; it allocates from the pool (the level's element mask once,
+ * at the first call on that level) and synchronises.  hmg_ctx_counter "cell_extrema_kernel_ns": the last call's kernel time.
+ * Served: 3D levels up to 6, 2D levels up to 8.  Refused, with a message naming the call: 3D level 7 and 2D levels 9-11 (naming
+ * the level; whatever "cell_moments_windows" says -- there is no window form), a grid without a device context, a null v or out,
+ * a vector of another grid, nthr outside 0..8, nthr > 0 with null thresholds, thresholds or form entries that are not finite. */
+int hmg_cell_extrema(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
+                     const double *form /* nq*ncells, or NULL */, int nthr, const double *thresholds /* nthr, or NULL */,
+                     double *out /* host, (2 + nthr)*ncells */);
+int64_t hmg_grid_fine_elements(const hmg_grid *grid, int level);   /* 2^(dim (level-1)); host-only grid too; -1: null grid or bad level */
+
 /* ---- fused fast path ------------------------------------------------------------------------ */
 /* smoothing_steps!(steps, implicit, ops, curr, k)            (src/multigrid.jl:46-71) */
 int hmg_smooth(hmg_grid *grid, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap);

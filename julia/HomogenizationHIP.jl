@@ -344,6 +344,21 @@ function cell_pair_moments(v::HipMatrix, w::HipMatrix, ξv::Union{Nothing,Abstra
     end
     S
 end
+# per-cell extrema over the fine elements (hmg_cell_extrema; api.cell_extrema): for q = ∇u ⋅ Q_c ∇u, u = ξ⋅x + v, on every fine
+# element of every coarse cell the maximum and the minimum (Ne each) and the number of elements above each threshold (nthr x Ne).
+# form: nq x Ne, the symmetric Q_c in the order 11, 12, 13, 22, 23, 33 (2D: 11, 12, 22); nothing: the identity.  3D levels up to 6,
+# 2D levels up to 8.
+fine_elements(g::HipGrid, level::Integer) = Int(ccall((:hmg_grid_fine_elements, LIB), Int64, (Ptr{Cvoid}, Cint), g.h, level))
+function cell_extrema(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                      form::Union{Nothing,AbstractMatrix{Float64}} = nothing, thresholds::AbstractVector{Float64} = Float64[])
+    g = v.grid
+    nthr = length(thresholds)
+    out = zeros(Float64, 2 + nthr, ncells(g))
+    check(ccall((:hmg_cell_extrema, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}),
+                g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), form === nothing ? C_NULL : Matrix{Float64}(form), nthr,
+                nthr == 0 ? C_NULL : collect(Float64, thresholds), out))
+    (out[1, :], out[2, :], round.(Int64, out[3:end, :]))
+end
 # subsets are prefixes 1:n of the ∞-norm ordered cells (find_elements_in_radius, :32-43).  The first term's dot(∂ϕ, P) is
 # the entry of rhs_aξ∇v! for the same ξ: the caller's right-hand side b of outer step 0 is passed along.
 integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =

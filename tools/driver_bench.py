@@ -18,7 +18,11 @@ tensors only, so it implies --no-cpu.
 then d (d + 1) / 2 per-cell moment passes): one line with the wall time of a run after --warmup untimed ones, the cycles and the
 kernel counters of its last single-vector and its last pair pass ("cell_moments_kernel_ns", "cell_pair_moments_kernel_ns").
 --large-cells (with --dirichlet-tensor): the driver's keyword large_cells=True -- a top level whose cell exceeds the LDS (3D level 7,
-2D levels 9-11: --refinements 6 / 8-10) takes the window kernels; the line then carries "cell_moments_window_launches" too."""
+2D levels 9-11: --refinements 6 / 8-10) takes the window kernels; the line then carries "cell_moments_window_launches" too.
+--extrema: driver.dirichlet_homogenization on hypercube(n) with extrema=True and thresholds at 1, 2 and 4 times the homogenized
+energy density (one solve, the moment pass, then the pass over the fine elements): one line with the wall time of a run after
+--warmup untimed ones, the largest concentration, the exceedance volume fractions and the kernel counters of the two passes
+("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -40,6 +44,7 @@ ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor p
 ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
 ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor: moment passes of cells larger than the LDS")
+ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
@@ -51,6 +56,32 @@ else:
     sgrid = driver.generate_conductivity(a.dim, width, a.field_seed, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
+if a.extrema:
+    if a.polycrystal:
+        principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
+        sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
+    else:
+        sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
+    xi = np.ones(a.dim) / np.sqrt(a.dim)
+    kw = dict(refinements=a.refinements, xi=xi, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate,
+              smoother=a.smoother, extrema=True, thresholds=[1.0, 2.0, 4.0], fields=True)
+    for _ in range(a.warmup):
+        driver.dirichlet_homogenization(a.n, tag, **kw)
+    ctx.sync()
+    t0 = time.perf_counter()
+    r = driver.dirichlet_homogenization(a.n, tag, **kw)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    print(json.dumps({"config": f"dirichlet_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}, "
+                                "extrema=True)",
+                      "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
+                      "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
+                      "energy_form": r["energy_form"], "max_concentration": float(r["concentration"].max()),
+                      "min_energy_density_over_mean": float(r["min_energy_density"].min() / r["energy_form"]),
+                      "exceedance_fraction_at_1_2_4": (r["exceedance"].sum(axis=0) / r["volume"]).tolist(),
+                      "cell_moments_kernel_ns": ctx.counter("cell_moments_kernel_ns"),
+                      "cell_extrema_kernel_ns": ctx.counter("cell_extrema_kernel_ns")}))
+    sys.exit(0)
 if a.dirichlet_tensor:
     if a.polycrystal:
         principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
