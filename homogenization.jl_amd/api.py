@@ -532,7 +532,8 @@ def integrate_pair_load(v: DeviceMatrix, s: DeviceMatrix, implicit: ImplicitFine
 def cell_moments(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None):
     """Per coarse cell the mean gradient and the Gram tensor of the gradient of the level vector v -- with xi, of u = xi.x + v
     (hmg_cell_moments): mean (Ne, d) = (1/|c|) int_c grad u, gram (Ne, d, d) = int_c grad u (x) grad u.  The moments are of the
-    vector as stored (no operator, no constraint); levels whose cell exceeds the LDS (3D level 7, 2D levels 9-11) are refused
+    vector as stored (no operator, no constraint); on a dist.PartitionedGrid Ne is the number of local cells.  Every level from 1
+    is served whose cell fits the LDS (3D 1 to 6, 2D 1 to 8); levels whose cell exceeds it (3D level 7, 2D levels 9-11) are refused
     unless the context option "cell_moments_windows" is 1 (then they walk through a rolling LDS window: the pair kernel with v given
     twice, 8 B/DOF; 2: every level the window kernels can address does, an A/B knob).
     What to do with them: fields.py.  No counterpart in the reference."""
@@ -595,8 +596,12 @@ def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None
     many elements exceed each threshold (hmg_cell_extrema): qmax (Ne,), qmin (Ne,), counts (Ne, nthr) int64.  `form` is the
     symmetric Q_c per cell, (Ne, d, d), or (Ne, d) for diagonals; None is the identity, q = |grad u|^2 (fields.energy_form,
     fields.flux_form make the usual ones).  Up to 8 finite thresholds, the same for all cells.  The vector as stored; 3D levels
-    up to 6, 2D levels up to 8, larger cells are refused whatever "cell_moments_windows" says.  One pass of 8 B/DOF; the same bits
-    in every run.  What to do with the results: fields.exceedance_volume, fields.concentration.  No counterpart in the reference."""
+    1 to 6, 2D levels 1 to 8, larger cells are refused whatever "cell_moments_windows" says.  One pass of 8 B/DOF; the same bits
+    in every run.  On a dist.PartitionedGrid Ne is the number of LOCAL cells: `form` and all three results are per local cell
+    (form = global_form[implicit.local_cells]; a form of global length is refused), while the operator's sigma is the global field.
+    qmax and qmin of a cell are NaN exactly when q_T is NaN on one of its elements (a NaN in the cell's column, inf - inf); an
+    infinite q_T is a value; a NaN element is counted for no threshold; other cells are untouched.
+    What to do with the results: fields.exceedance_volume, fields.concentration.  No counterpart in the reference."""
     lib = L.load()
     d = implicit.base.dim
     ne = implicit.ncells()

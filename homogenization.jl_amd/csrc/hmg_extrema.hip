@@ -16,6 +16,11 @@
 // 7 (2D: 3) nodes above it -- every address clamped into the image and its guard, so that an element that does not exist reads
 // some node of the image instead of leaving it -- and evaluates the 6 (2D: 2) forms; those whose bit is clear take no part.
 // Maxima, minima and integer counts do not depend on any order: the same bits in every run and for every grid size.
+// NaN: a comparison never picks one, so every thread notes whether some EXISTING element of its slots had a NaN q_T (integer
+// maxima of the values' high words: 6 full-rate operations per slot, half the cost of 6 double-precision compares) and turns its
+// maximum and minimum into NaN behind the slot loop; the picks of the folds across lanes and waves take a NaN and keep one.
+// A cell's maximum and minimum are NaN exactly when one of its elements' values is; an infinite value is a value like any other;
+// the counts compare, and a NaN compares false.
 #include "hmg_extrema.hpp"
 #include "hmg_stencil.hpp"
 
@@ -36,10 +41,16 @@ __device__ __forceinline__ double dpp_other(double v)
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+// the larger (MAX) or smaller of a and b; a NaN on either side is the result
+template <bool MAX>
+__device__ __forceinline__ double ext_pick(double a, double b)
+{
+    return ((MAX ? b > a : b < a) || b != b) ? b : a;
+}
 template <bool MAX>
 __device__ __forceinline__ double wave_ext63(double v)
 {
-    auto pick = [](double a, double b) { return MAX ? (b > a ? b : a) : (b < a ? b : a); };
+    auto pick = [](double a, double b) { return ext_pick<MAX>(a, b); };
     v = pick(v, dpp_other<0x111, 0xf>(v));     // row_shr:1
     v = pick(v, dpp_other<0x112, 0xf>(v));     // row_shr:2
     v = pick(v, dpp_other<0x114, 0xf>(v));     // row_shr:4
@@ -98,6 +109,10 @@ k_cell_extrema(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8
             Q[1] *= 2.0;
         __syncthreads();                          // image (first cell: guard too) complete; red[] of the last cell read
         double mx = -inf, mn = inf;
+        // the largest high word, signed and unsigned, of the values of this thread's existing elements: above +inf's a positive NaN,
+        // above -inf's a negative one (a value is the result of arithmetic: its NaN is quiet, with a bit in the high word)
+        int hs = 0;
+        unsigned hu = 0;
         int cnt[NTHR];
 #pragma unroll
         for (int j = 0; j < NTHR; ++j) cnt[j] = 0;
@@ -142,6 +157,8 @@ k_cell_extrema(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8
                 const bool on = (mk >> k) & 1u;
                 qh[k] = on ? q[k] : -inf;
                 const double ql = on ? q[k] : inf;
+                hs = max(hs, __double2hiint(qh[k]));
+                hu = max(hu, (unsigned)__double2hiint(qh[k]));
                 mx = qh[k] > mx ? qh[k] : mx;
                 mn = ql < mn ? ql : mn;
             }
@@ -153,6 +170,7 @@ k_cell_extrema(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8
                 }
         }
         // lanes by data-parallel moves, waves through LDS, one thread per output
+        if (hs > 0x7ff00000 || hu > 0xfff00000u) mx = mn = __builtin_nan("");
         mx = wave_ext63<true>(mx);
         mn = wave_ext63<false>(mn);
 #pragma unroll
@@ -169,10 +187,10 @@ k_cell_extrema(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8
             double r;
             if (tid == 0) {
                 r = red[0];
-                for (int k = 1; k < NW; ++k) r = red[2 * k] > r ? red[2 * k] : r;
+                for (int k = 1; k < NW; ++k) r = ext_pick<true>(r, red[2 * k]);
             } else if (tid == 1) {
                 r = red[1];
-                for (int k = 1; k < NW; ++k) r = red[2 * k + 1] < r ? red[2 * k + 1] : r;
+                for (int k = 1; k < NW; ++k) r = ext_pick<false>(r, red[2 * k + 1]);
             } else {
                 int s = 0;
                 for (int k = 0; k < NW; ++k) s += redc[k * NTHR + tid - 2];

@@ -282,8 +282,12 @@ int hmg_next_rhs(hmg_grid *grid, hmg_vec *x, hmg_vec *b);
  * of a shared node the same value).  One kernel of its own reads the column once (8 B/DOF) and writes 72 B (2D: 40 B) of
  * reference sums per cell; the host applies the cell's J^-1 and |J|.  The sums are folded in a fixed order: the same bits in every run.
  * It allocates (from the context's pool of level-vector memory) and synchronises: not for the inside of a V-cycle.
- * Served: every level whose cell fits the LDS with its tables -- 3D levels up to 6, 2D levels up to 8.  Larger cells (3D level 7,
- * 2D levels 9-11) are refused with a message naming the level, unless hmg_ctx_set_option "cell_moments_windows" is 1: then such
+ * On a partitioned grid c runs over the LOCAL cells (ascending global ids, the grid's "part_cells"; after a shrink those below the
+ * global prefix): out has one row per local cell, and so has every per-cell array the calls of this family take (the form of
+ * hmg_cell_extrema) -- whereas hmg_grid_set_operator / hmg_grid_set_operator_tensor take the GLOBAL field.  The rows equal the
+ * unpartitioned grid's rows of those cells bit for bit.
+ * Served: every level whose cell fits the LDS with its tables -- 3D levels 1 to 6, 2D levels 1 to 8 (level 1: the cell itself, one
+ * element).  Larger cells (3D level 7, 2D levels 9-11) are refused with a message naming the level, unless hmg_ctx_set_option "cell_moments_windows" is 1: then such
  * a cell walks through a rolling window of the LDS, as in the operator apply of those levels (slabs of k-planes in 3D, bands of
  * lattice rows in 2D; the pair kernel with v given twice: 8 B/DOF, the same rules, the same bits in every run).  Value 2 sends
  * every level the window kernels can address through them (3D levels 6 and 7, 2D levels from 2: a test and A/B knob); 0 is the
@@ -304,7 +308,7 @@ int hmg_cell_moments_count(const hmg_grid *grid);        /* dim + dim (dim + 1) 
  * One kernel of its own: only w goes into the LDS image, v is read per node straight from its column -- 16 B/DOF read, 96 B
  * (2D: 56 B) of reference sums written per cell.  w may be v.  Otherwise the rules of hmg_cell_moments: the vectors as stored,
  * the current cells, local cells of a partitioned grid, a fixed summation order (the same bits in every run), allocation from
- * the pool and a synchronisation; the same levels served (3D up to 6, 2D up to 8) and refused (naming the level), and the same
+ * the pool and a synchronisation; the same levels served (3D 1 to 6, 2D 1 to 8) and refused (naming the level), and the same
  * option "cell_moments_windows" for larger cells (only w goes into the window; v is read per node, or from the window's centre
  * tap where v and w are one vector); refused too:
  * a grid without a device context, a null vector or out, a vector of another grid, v and w of different levels. */
@@ -327,7 +331,13 @@ int hmg_cell_pair_moments_count(const hmg_grid *grid);   /* dim (dim + 1) / 2; w
  * Otherwise the rules of hmg_cell_moments: the vector as stored (no operator, no lambda, no mask), the current cells after a
  * shrink, the local cells of a partitioned grid with nothing exchanged; it allocates from the pool (the level's element mask once,
  * at the first call on that level) and synchronises.  hmg_ctx_counter "cell_extrema_kernel_ns": the last call's kernel time.
- * Served: 3D levels up to 6, 2D levels up to 8.  Refused, with a message naming the call: 3D level 7 and 2D levels 9-11 (naming
+ * On a partitioned grid form and out are indexed by LOCAL cell (form[c * nq ..] belongs to the c-th local cell: hand in the rows
+ * of the global field at the grid's "part_cells"), unlike the sigma of hmg_grid_set_operator*, which is the global field.
+ * NaN: max_T q_T and min_T q_T of a cell are NaN exactly when q_T is NaN on some fine element of THAT cell (a NaN entry of the
+ * cell's column makes it so on every element that touches the node; so does inf - inf); other cells are not touched.  An
+ * infinite q_T is a value like any other: it may be the maximum or the minimum.  The counts keep their meaning: q_T > threshold
+ * is false for a NaN, so a NaN element is counted nowhere.  (The moment calls propagate a NaN through their sums.)
+ * Served: 3D levels 1 to 6, 2D levels 1 to 8 (level 1: one element per cell, max = min).  Refused, with a message naming the call: 3D level 7 and 2D levels 9-11 (naming
  * the level; whatever "cell_moments_windows" says -- there is no window form), a grid without a device context, a null v or out,
  * a vector of another grid, nthr outside 0..8, nthr > 0 with null thresholds, thresholds or form entries that are not finite. */
 int hmg_cell_extrema(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
