@@ -38,6 +38,7 @@ int hmg_vec_upload(hmg_vec *v, const double *host)
 {
     HMG_TRY
     need(v && host, "null argument");
+    settle(v);
     staged_copy(v, const_cast<double *>(host), true);
     HMG_END
 }
@@ -46,6 +47,7 @@ int hmg_vec_download(hmg_vec *v, double *host)
 {
     HMG_TRY
     need(v && host, "null argument");
+    settle(v);
     staged_copy(v, host, false);
     HMG_END
 }
@@ -54,6 +56,7 @@ int hmg_vec_fill(hmg_vec *v, double value)
 {
     HMG_TRY
     need(v != nullptr, "null vector");
+    settle_overwritten(v);
     launch_fill(v->g->ctx->L, v->d, vec_len(v), value);
     HMG_END
 }
@@ -62,6 +65,7 @@ int hmg_vec_fill_random(hmg_vec *v, uint64_t seed, int64_t cell_offset)
 {
     HMG_TRY
     need(v != nullptr, "null vector");
+    settle(v);
     launch_fill_random(v->g->ctx->L, lev(v->g, v->level), v->g->md.ncells, v->d, seed, cell_offset);
     HMG_END
 }
@@ -71,6 +75,7 @@ int hmg_vec_copy(hmg_vec *dst, hmg_vec *src)
     HMG_TRY
     need(dst && src, "null vector");
     check_vec(dst->g, dst->level, src, "src");
+    if (dst != src) settle_overwritten(dst);
     launch_copy(dst->g->ctx->L, dst->d, src->d, vec_len(dst));
     HMG_END
 }
@@ -80,6 +85,7 @@ int hmg_vec_axpy(double alpha, hmg_vec *x, hmg_vec *y)
     HMG_TRY
     need(x && y, "null vector");
     check_vec(y->g, y->level, x, "x");
+    settle(y);
     launch_axpy(y->g->ctx->L, alpha, x->d, y->d, vec_len(y));
     HMG_END
 }
@@ -89,6 +95,7 @@ int hmg_vec_xpby(hmg_vec *r, double beta, hmg_vec *p)
     HMG_TRY
     need(r && p, "null vector");
     check_vec(p->g, p->level, r, "r");
+    settle(p);
     launch_xpby(p->g->ctx->L, r->d, beta, p->d, vec_len(p));
     HMG_END
 }
@@ -98,6 +105,7 @@ int hmg_vec_dot(hmg_vec *x, hmg_vec *y, double *out)
     HMG_TRY
     need(x && y && out, "null argument");
     check_vec(x->g, x->level, y, "y");
+    settle(x);
     launch_dot(x->g->ctx->L, x->d, y->d, vec_len(x), S_TMP);
     scalar_sum(x->g, S_TMP, 1);
     *out = read_scalar(x->g->ctx, S_TMP);
@@ -108,6 +116,7 @@ int hmg_vec_norm_unique(hmg_vec *r, double *out)
 {
     HMG_TRY
     need(r && out, "null argument");
+    settle(r);
     launch_norm2_unique(r->g->ctx->L, lev(r->g, r->level), r->g->md, r->d, S_TMP);
     scalar_sum(r->g, S_TMP, 1);
     *out = std::sqrt(read_scalar(r->g->ctx, S_TMP));

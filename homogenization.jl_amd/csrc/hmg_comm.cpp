@@ -325,6 +325,7 @@ int hmg_grid_set_exchange(hmg_grid *g, hmg_exchange_fn exchange, hmg_exchange_fn
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    if (g->ctx) materialize_r(g);                // (a pending r-update was recorded for a grid without sums over ranks)
     g->exchange = exchange;
     g->scalar_sum = scalar_sum_fn;
     g->cut_agreed_ready = false;
@@ -339,6 +340,7 @@ int hmg_grid_set_exchange_async(hmg_grid *g, hmg_exchange_fn begin, int (*end)(v
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    if (g->ctx) materialize_r(g);                // (a pending r-update was recorded for a grid without sums over ranks)
     g->ex_begin = begin;
     g->ex_end = end;
     g->dinv_ready = false;

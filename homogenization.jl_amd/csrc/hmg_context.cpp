@@ -148,6 +148,14 @@ void grid_unref(hmg_grid *grid)
     ctx_unref(c);
 }
 
+void release_vec(hmg_vec *v)
+{
+    if (v->own && v->d) vec_release(v->g->ctx, v->d, v->bytes);
+    hmg_grid *g = v->g;
+    delete v;
+    grid_unref(g);
+}
+
 double read_scalar(hmg_ctx *c, int slot)
 {
     double h = 0.0;
@@ -259,6 +267,10 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "smoother_diag_builds") return ctx->smoother_diag_builds;
     if (n == "lazy_top_form") return ctx->last_top_form;
     if (n == "lazy_pre_form") return ctx->last_pre_form;
+    if (n == "lazy_r_form") return ctx->last_r_form;          // the last hmg_vcycle / hmg_fcg_step: 1 its top level's r-update is (or was) pending
+    if (n == "r_materialized") return ctx->r_materialized;    // pending r-updates launched by a later call
+    if (n == "r_materialized_by_read") return ctx->r_materialized_read;   // ... of them: by a call that was handed r or Ap
+    if (n == "r_dropped") return ctx->r_dropped;              // ... and those that never had to be
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;
     if (n == "cell_moments_kernel_ns") return ctx->moments_kernel_ns;       // the last hmg_cell_moments: kernel alone
     if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
@@ -289,7 +301,7 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         {"coarse_probe", &hmg_ctx::coarse_probe}, {"fuse_cg", &hmg_ctx::fuse_cg_default}, {"fold_x", &hmg_ctx::fold_x},
         {"swap_rp", &hmg_ctx::swap_rp}, {"fold_prolong", &hmg_ctx::fold_prolong}, {"zero_entry", &hmg_ctx::zero_entry},
         {"fold_restrict", &hmg_ctx::fold_restrict}, {"lazy_dead", &hmg_ctx::lazy_dead}, {"lazy_pre", &hmg_ctx::lazy_pre}, {"fold_coarse_x", &hmg_ctx::fold_coarse_x}, {"fold_faces", &hmg_ctx::fold_faces},
-        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
+        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"lazy_r", &hmg_ctx::lazy_r}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
         {"comm_rehearsal", &hmg_ctx::comm_rehearsal}};
     for (const auto &f : flags)
         if (n == f.first) {
@@ -475,14 +487,25 @@ int hmg_vec_destroy(hmg_vec *v)
 {
     HMG_TRY
     if (v) {
-        if (v->own && v->d) vec_release(v->g->ctx, v->d, v->bytes);
-        hmg_grid *g = v->g;
-        delete v;
-        grid_unref(g);
+        LifetimeLock lock(lifetime_mutex());
+        if (!pending_keeps(v)) release_vec(v);
     }
     HMG_END
 }
 
-void *hmg_vec_device_ptr(hmg_vec *v) { return v ? (void *)v->d : nullptr; }
+// From here on the memory can be read behind the library's back: a pending r-update on the vector is formed now, and V-cycles on it
+// take the eager tail.
+void *hmg_vec_device_ptr(hmg_vec *v)
+{
+    if (!v) return nullptr;
+    try {
+        settle(v);
+    } catch (const std::exception &e) {
+        (void)fail(e);
+        return nullptr;
+    }
+    v->exposed = true;
+    return (void *)v->d;
+}
 
 }  // extern "C"

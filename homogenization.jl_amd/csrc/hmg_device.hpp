@@ -277,11 +277,15 @@ void launch_cg_update(const Launch &L, double *x, double *r, const double *p, co
 void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const double *q, int64_t n, int s_num, int s_den,
                        int s_out);
 // the same with the face part of q's interface sum taken on the fly (q unsummed on the shared faces)
+// (scal: where s_num / s_den are read, default the bank; the r.r goes to the bank's s_out either way)
 void launch_cg_rupdate_faces(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                             const double *q, int64_t n, int s_num, int s_den, int s_out);
+                             const double *q, int64_t n, int s_num, int s_den, int s_out, const double *scal = nullptr);
 void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
                                const double *q, int64_t n, int s_num, int s_den, int s_out, double *x, const double *p, int a_num,
                                int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den);
+// ... its x-updates alone (the r half stays pending); alpha_out[0] = scal[s_num]/scal[s_den], alpha_out[1] = 1.0
+void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
+                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out);
 // x += (scal[a_num]/scal[a_den]) p; with_p: p = r + (scal[s_num]/scal[s_den]) p
 void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, int a_num, int a_den,
                          int s_num, int s_den, int with_p);

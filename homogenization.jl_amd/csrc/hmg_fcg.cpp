@@ -67,7 +67,8 @@ void check_states(hmg_fcg *f, hmg_vec **states)
 {
     need(states != nullptr, "null states");
     for (int l = 1; l <= f->level; ++l)
-        for (int k = 0; k < 5; ++k) check_vec(f->g, l, states[5 * (l - 1) + k], "states[]");
+        for (int k = 0; k < 5; ++k)   // (a pending r-update of the last V-cycle: settled or dropped by whoever touches r or Ap next)
+            check_vec(f->g, l, states[5 * (l - 1) + k], "states[]", /*settle_pending=*/false);
 }
 
 void need_current(hmg_fcg *f, const char *what)

@@ -1894,6 +1894,14 @@ k_cg_rupdate(const double *r, double *rout, const double *__restrict__ q, int64_
 struct XUSlots {
     int a_num, a_den, b_num, b_den, z_num, z_den;
 };
+// the two pending x-updates of a lazy last step, p_i formed on the fly: (x + ax p) + alpha (r + beta p).  One function for the
+// r-update that carries them and for the x-only tail (k_cg_x_tail): the roundings cannot drift apart.
+__device__ __forceinline__ double xupd2(double ax, double beta, double alpha, double xv, double pv, double rv)
+{
+    const double t1 = axpy1(ax, pv, xv);
+    const double p2 = axpy1(beta, pv, rv);
+    return axpy1(alpha, p2, t1);
+}
 template <int XU>
 __global__ void __launch_bounds__(SB)
 k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, int64_t n, const double *__restrict__ scal,
@@ -1906,11 +1914,7 @@ k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, 
     const double ax = XU ? scal[xs.a_num] / scal[xs.a_den] : 0.0;
     const double beta = XU ? scal[xs.b_num] / scal[xs.b_den] : 0.0;
     const double az = XU == 2 ? scal[xs.z_num] / scal[xs.z_den] : 0.0;
-    auto xupd = [&](double xv, double pv, double rv) {
-        const double t1 = axpy1(ax, pv, xv);
-        const double p2 = axpy1(beta, pv, rv);
-        return axpy1(alpha, p2, t1);
-    };
+    auto xupd = [&](double xv, double pv, double rv) { return xupd2(ax, beta, alpha, xv, pv, rv); };
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     double acc = 0.0;
     auto summed = [&](int64_t e, double own) {          // q[e] with its face partner, if it has one
@@ -1961,6 +1965,41 @@ k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, 
     }
     const double s = block_sum(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The x half of k_cg_rupdate_faces<XU> alone (XU = 1, 2), for a caller that leaves the r half pending (hmg_vcycle, option lazy_r):
+// reads x, p (, p0) and r, writes x -- no q, no partner gather, no r store, no reduction.  The step length it formed goes to
+// alpha_out[0] with a 1.0 behind it: k_cg_rupdate_faces<0> run later with alpha_out as its scalars (slots 0 / 1) forms the same
+// alpha, whatever the scalar bank holds by then.
+template <int XU>
+__global__ void __launch_bounds__(SB)
+k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ p0, const double *__restrict__ r, int64_t n,
+            const double *__restrict__ scal, int s_num, int s_den, XUSlots xs, double *alpha_out)
+{
+    static_assert(XU == 1 || XU == 2, "one or two stored directions");
+    const double alpha = scal[s_num] / scal[s_den];
+    const double ax = scal[xs.a_num] / scal[xs.a_den];
+    const double beta = scal[xs.b_num] / scal[xs.b_den];
+    const double az = XU == 2 ? scal[xs.z_num] / scal[xs.z_den] : 0.0;
+    const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
+    if (i < (n >> 1)) {
+        double2 xv = reinterpret_cast<double2 *>(x)[i];
+        const double2 pv = reinterpret_cast<const double2 *>(p)[i];
+        const double2 rv = reinterpret_cast<const double2 *>(r)[i];
+        if (XU == 2) {
+            const double2 zv = reinterpret_cast<const double2 *>(p0)[i];
+            xv.x = axpy1(az, zv.x, xv.x);
+            xv.y = axpy1(az, zv.y, xv.y);
+        }
+        xv.x = xupd2(ax, beta, alpha, xv.x, pv.x, rv.x);
+        xv.y = xupd2(ax, beta, alpha, xv.y, pv.y, rv.y);
+        reinterpret_cast<double2 *>(x)[i] = xv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (n & 1) x[n - 1] = xupd2(ax, beta, alpha, XU == 2 ? axpy1(az, p0[n - 1], x[n - 1]) : x[n - 1], p[n - 1], r[n - 1]);
+        alpha_out[0] = alpha;
+        alpha_out[1] = 1.0;
+    }
 }
 
 // x += alpha p (alpha = scal[a_num]/scal[a_den]) and, if with_p, p = r + beta p (beta = scal[s_num]/scal[s_den])
@@ -2127,11 +2166,11 @@ void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const dou
 }
 
 void launch_cg_rupdate_faces(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                             const double *q, int64_t n, int s_num, int s_den, int s_out)
+                             const double *q, int64_t n, int s_num, int s_den, int s_out, const double *scal)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_rupdate_faces<0>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, L.scal, s_num, s_den,
+    hipLaunchKernelGGL(k_cg_rupdate_faces<0>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, scal ? scal : L.scal, s_num, s_den,
                        reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi,
                        (double *)nullptr, (const double *)nullptr, (const double *)nullptr, XUSlots{0, 0, 0, 0, 0, 0});
     check_launch();
@@ -2156,6 +2195,21 @@ void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDe
                            p0, xs);
     check_launch();
     reduce_finish(L, nb, s_out);
+}
+
+// the x-updates of launch_cg_rupdate_faces_x alone; alpha_out[0..2) = s_num/s_den, 1.0
+void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
+                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out)
+{
+    if (!alpha_out || n <= 0) throw std::runtime_error("x-only tail without a place for its step length");
+    const int64_t nb = stream_blocks(n);
+    check_grid(nb);
+    const XUSlots xs{a_num, a_den, b_num, b_den, z_num, z_den};
+    if (p0)
+        hipLaunchKernelGGL(k_cg_x_tail<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, L.scal, s_num, s_den, xs, alpha_out);
+    else
+        hipLaunchKernelGGL(k_cg_x_tail<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, L.scal, s_num, s_den, xs, alpha_out);
+    check_launch();
 }
 
 void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, int a_num, int a_den,

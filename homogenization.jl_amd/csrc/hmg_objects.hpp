@@ -207,6 +207,7 @@ struct hmg_ctx {
     bool lean_post = true;      // V-cycle: the post-smoother's dead tail is dropped too (see smooth_form())
     bool lazy_post = true;      // ... and below the finest level its dead last step writes nothing: both x-updates in one pass
     bool fold_coarse_x = true;  // ... and the level below the finest leaves them to the finest level's first residual, which reads that x anyway (see coarse_x_folds())
+    bool lazy_r = true;         // hmg_vcycle / hmg_fcg_step: the finest level's last r-update only finishes x; r_3 is formed when somebody reads it (PendingR)
     int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
     bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
     bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
@@ -250,6 +251,10 @@ struct hmg_ctx {
     int64_t moments_window_launches = 0;     // launches of the window kernels (hmg_ctx_counter "cell_moments_window_launches")
     int64_t coarse_x_folds = 0;              // residuals that finished the coarser level's x on the way (option fold_coarse_x)
     int last_pre_form = 0;                   // x-updates the last pre-smoother of a V-cycle's down leg left to its local residual: 0 .. 3
+    int last_r_form = 0;                     // what the last hmg_vcycle / hmg_fcg_step left of its top level's r: 0 formed, 1 pending (x-only tail)
+    int64_t r_materialized = 0;              // pending residuals formed by a later call (the eager r-update, launched late) ...
+    int64_t r_materialized_read = 0;         // ... those of them because a call was handed r or Ap (the others: setters, the tuner)
+    int64_t r_dropped = 0;                   // ... and those nobody read: overwritten by the next V-cycle, a copy or a fill, or destroyed
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
     // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB
@@ -267,6 +272,22 @@ struct hmg_ctx {
     std::vector<struct hmg_grid *> probe_grids;
 };
 
+// The last r-update of a V-cycle, not launched yet (option lazy_r): r still holds r_2, Ap the unsummed A p_2, alpha[0] / alpha[1]
+// the step length.  Forming it is launch_cg_rupdate_faces on (r, r, Ap) with alpha[] as its scalars and its r.r into `slot` --
+// the launch the eager tail makes (materialize_r()).  Open on unpartitioned grids and library-owned, never exposed vectors only.
+// A caller that reads r after every cycle (a driver that watches the residual norm) would pay for the split: 40 + 26 B/DOF instead of
+// 58.  So the grid remembers whether the last V-cycle's r was read (hmg_grid::r_reader): if it was, the next tail runs the eager
+// launch and leaves a record that is already `formed` -- nothing left to launch, it only notes whether r is read again; a record
+// that is dropped unread clears the flag and the next V-cycle defers again.  The bits do not depend on the path.
+struct PendingR {
+    hmg_vec *r = nullptr, *Ap = nullptr;
+    int level = 0;
+    int slot = -1;
+    bool formed = false;
+    bool orphan_Ap = false;     // Ap's handle was destroyed while r still needs its memory: the record owns it until it closes
+};
+// (hmg_*_destroy may come from any thread, a finalizer's for one: it never launches.  Whoever touches the record holds the lifetime lock.)
+
 struct hmg_grid {
     int refs = 1;
     hmg_ctx *ctx = nullptr;
@@ -280,7 +301,10 @@ struct hmg_grid {
     DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
     DevBuf<uint16_t> d_dmask, d_dupmask;
     DevBuf<uint8_t> d_mult;
-    DevBuf<double> d_blockpart;
+    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last two doubles: the step length of a pending r-update
+    PendingR pend;
+    bool r_reader = false;                       // a caller's read settled a record and none was dropped unread since (see PendingR)
+    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 2 : nullptr; }
     bool fuse_cg = true;
     DevBuf<double> d_coef;
     std::vector<double> sigma, coef;
@@ -371,6 +395,7 @@ struct hmg_vec {
     bool own = false;
     int64_t alloc_cells = 0;
     size_t bytes = 0;        // own: size of the allocation behind d
+    bool exposed = false;    // hmg_vec_device_ptr has handed d out: somebody may read the memory behind the library's back
 };
 
 namespace hmg {
@@ -408,12 +433,30 @@ inline const LevelDev &lev(const hmg_grid *g, int level)
     return g->ld[level - 1];
 }
 
-inline void check_vec(const hmg_grid *g, int level, const hmg_vec *v, const char *name)
+// ---- the pending r-update of a grid (hmg_smooth.cpp) ----
+// forms it now, if there is one: afterwards vectors and scalar bank are what the eager tail leaves.  read: the caller is about to
+// read r or Ap (settle()) -- only that is remembered as a read (hmg_grid::r_reader); a setter that settles the record is not one
+void materialize_r(hmg_grid *g, bool read = false);
+// every entry point that is handed a vector goes through one of these three before it touches it:
+// the vector is read or partly written -- a pending r or Ap is settled first
+inline void settle(const hmg_vec *v)
+{
+    if (v && v->g && v->g->pend.r && (v == v->g->pend.r || v == v->g->pend.Ap)) materialize_r(v->g, /*read=*/true);
+}
+// every entry of the vector is about to be overwritten unread: a pending r is dropped, a pending Ap settled
+void settle_overwritten(const hmg_vec *v);
+// hmg_vec_destroy, under the lifetime lock, no launch: a pending r is dropped; true: v is the Ap a pending r still needs -- the
+// record keeps the object and its memory, and hands them back (release_vec) when it closes
+bool pending_keeps(hmg_vec *v);
+
+// settle_pending = false: the caller settles or drops the record itself (the entries of hmg_vcycle and hmg_fcg_step)
+inline void check_vec(const hmg_grid *g, int level, const hmg_vec *v, const char *name, bool settle_pending = true)
 {
     if (!v) throw std::runtime_error(std::string("null vector: ") + name);
     if (v->g != g) throw std::runtime_error(std::string("vector belongs to another grid: ") + name);
     if (v->level != level) throw std::runtime_error(std::string("vector has the wrong level: ") + name);
     if (v->alloc_cells < g->md.ncells) throw std::runtime_error(std::string("vector too small: ") + name);
+    if (settle_pending) settle(v);
 }
 
 inline int64_t vec_len(const hmg_vec *v) { return (int64_t)v->g->ld[v->level - 1].ld * v->g->md.ncells; }
@@ -425,6 +468,8 @@ inline bool has_exchange(const hmg_grid *g) { return g->exchange || g->ex_begin 
 double *vec_alloc(hmg_ctx *c, size_t bytes);
 // ... and back into the pool (stream-ordered: what was enqueued on the context's stream before runs before the next owner's work)
 void vec_release(hmg_ctx *c, void *p, size_t bytes);
+// what hmg_vec_destroy does with a vector nobody needs any more: memory to the pool, the object, its reference to the grid
+void release_vec(hmg_vec *v);
 void grid_unref(hmg_grid *grid);
 // scal[slot] on the host: synchronises the stream, so the pending probes are judged as well
 double read_scalar(hmg_ctx *c, int slot);

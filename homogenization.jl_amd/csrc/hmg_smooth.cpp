@@ -260,6 +260,8 @@ struct SmoothForm {
     bool hand_up = false;   // (set by the caller, tail DeadX2) both x-updates are left to the finer level's first residual (coarse_x_folds())
     bool x_zero = false;    // (set by the caller) x is a coarse level's zero initial guess that is not in memory
                             // (zero_entry_ok): the first residual is the constrained copy of b, b - A 0 to the last bit
+    bool lazy_r = false;    // (set by the caller, tails Top2 / Top3) the last launch finishes x only and leaves the r-update
+                            // pending on the grid (lazy_r_ok())
 };
 
 // What a pre-smoother leaves to its caller (tails DeadDefer, DeadDefer2 and DeadDefer3), or a post-smoother below the finest level
@@ -510,6 +512,30 @@ void smooth_pcg(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_v
     }
 }
 
+// May the finest level's post-smoother inside hmg_vcycle leave its last r-update pending (option lazy_r)?  Not where the memory
+// can be read behind the library's back (caller-owned vectors, pointers handed out -- p too: it changes places with r), and not on
+// a partitioned grid, where the deferred sum over the ranks would be a collective at a place no rank can foresee.
+bool lazy_r_ok(const hmg_grid *g, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap)
+{
+    if (!g->ctx->lazy_r || g->smoother != 0 || g->part || has_exchange(g) || g->scalar_sum) return false;
+    for (const hmg_vec *v : {r, p, Ap})
+        if (!v->own || v->exposed) return false;
+    return r != Ap && g->pend_alpha() != nullptr && vec_len(r) > 0;
+}
+
+// formed: the eager launch has run (the caller reads r after every cycle, hmg_grid::r_reader); the record only watches
+void open_pending(hmg_grid *g, int level, hmg_vec *r, hmg_vec *Ap, int slot, bool formed)
+{
+    LifetimeLock lock(lifetime_mutex());
+    need(!g->pend.r, "a pending r-update was not settled before the next one");
+    g->pend.r = r;
+    g->pend.Ap = Ap;
+    g->pend.level = level;
+    g->pend.slot = slot;
+    g->pend.formed = formed;
+    g->ctx->last_r_form = formed ? 0 : 1;
+}
+
 DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
                  const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
 {
@@ -655,9 +681,15 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         // (p.Ap of this step to its own slot: S_PAP keeps the previous step's for the first of the two x-updates)
         a.xout = a.xacc = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
+        if (f.lazy_r && !g->r_reader) {
+            launch_cg_x_tail(L, r->d, n, cur, S_PAP2, x->d, p->d, other, S_PAP, cur, other, nullptr, 0, 0, g->pend_alpha());
+            open_pending(g, level, r, Ap, other, false);
+            return {};
+        }
         launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, other, x->d, p->d, other, S_PAP, cur, other,
                                   nullptr, 0, 0);
         scalar_sum(g, other, 1);
+        if (f.lazy_r) open_pending(g, level, r, Ap, other, true);
         return {};
     case Tail::Top3:
         // rs_{i-2} in `other`, rs_{i-1} in `cur`, rs_i in S_RS3;  p.Ap_{i-2} in S_PAP, p.Ap_{i-1} in S_PAP2;  p_{i-2} in p, p_{i-1} in the spare
@@ -666,9 +698,15 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.s_num = S_RS3;
         a.s_den = cur;
         apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
+        if (f.lazy_r && !g->r_reader) {
+            launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
+            open_pending(g, level, r, Ap, other, false);
+            return {};
+        }
         launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, S_RS3, S_PAP3, other, x->d, g->top_spare.p, cur, S_PAP2,
                                   S_RS3, cur, p->d, other, S_PAP);
         scalar_sum(g, other, 1);
+        if (f.lazy_r) open_pending(g, level, r, Ap, other, true);
         return {};
     }
     return {};
@@ -762,7 +800,9 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
 // Up leg (src/multigrid.jl:112-115): coarse-grid correction x_k += P x_{k-1}, post-smoother (role PostTop on the finest
 // level, PostBelow below it).
 // cx: what level k - 1's post-smoother left of its x (hand_up); hand_up: may this level's post-smoother leave its own in turn?
-DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const DeferredX *cx = nullptr, bool hand_up = false)
+// lazy_r: the caller is hmg_vcycle / hmg_fcg_step on its top level and has settled the grid's pending record
+DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const DeferredX *cx = nullptr, bool hand_up = false,
+                    bool lazy_r = false)
 {
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
@@ -775,6 +815,7 @@ DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, cons
     if (!fold_p) launch_prolong_add(L, lev(g, k), lev(g, k - 1), g->md.ncells, nxt[0]->d, cur[0]->d);
     SmoothForm form = smooth_form(g, k, steps, role);
     form.hand_up = hand_up && form.tail == Tail::DeadX2;
+    form.lazy_r = lazy_r && (form.tail == Tail::Top2 || form.tail == Tail::Top3) && lazy_r_ok(g, cur[2], cur[3], cur[4]);
     return smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form, fold_p ? nxt[0] : nullptr, cx);
 }
 
@@ -809,14 +850,100 @@ DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec 
     const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
     if (top) g->ctx->last_pre_form = deferred;
     const DeferredX cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
-    if (top) g->ctx->last_top_form = 0;
-    return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up);
+    if (top) g->ctx->last_top_form = g->ctx->last_r_form = 0;
+    return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up, /*lazy_r=*/top);
+}
+
+}  // namespace
+
+// The eager launch, now: launch_cg_rupdate_faces<0> on (r, r, Ap) with the stored step length (alpha / 1.0 is alpha) and its r.r
+// into the slot the eager tail would have written.  (No sum over ranks: the record opens on unpartitioned grids only.)
+namespace {
+
+// the record is settled or dropped: an Ap it had to keep alive goes now
+void close_pending(hmg_grid *g)
+{
+    hmg_vec *orphan = g->pend.orphan_Ap ? g->pend.Ap : nullptr;
+    g->pend = PendingR{};
+    if (orphan) release_vec(orphan);
+}
+
+void drop_pending(hmg_grid *g)
+{
+    if (!g->pend.formed) g->ctx->r_dropped += 1;
+    g->r_reader = false;                         // nobody read it: the next V-cycle defers
+    close_pending(g);
+}
+
+}  // namespace
+
+void materialize_r(hmg_grid *g, bool read)
+{
+    LifetimeLock lock(lifetime_mutex());
+    const PendingR q = g->pend;
+    if (!q.r) return;
+    if (!q.formed) {
+        HIPCHK(hipSetDevice(g->ctx->device));
+        launch_cg_rupdate_faces(g->ctx->L, lev(g, q.level), g->md, q.r->d, q.r->d, q.Ap->d, vec_len(q.r), 0, 1, q.slot, g->pend_alpha());
+        g->ctx->r_materialized += 1;
+        if (read) g->ctx->r_materialized_read += 1;
+    }
+    close_pending(g);
+    if (read) g->r_reader = true;                // (the next V-cycle forms its r at once and watches again)
+}
+
+void settle_overwritten(const hmg_vec *v)
+{
+    if (!v || !v->g || !v->g->pend.r) return;
+    LifetimeLock lock(lifetime_mutex());
+    hmg_grid *g = v->g;
+    if (v == g->pend.Ap)
+        materialize_r(g);
+    else if (v == g->pend.r)
+        drop_pending(g);
+}
+
+bool pending_keeps(hmg_vec *v)
+{
+    hmg_grid *g = v->g;
+    if (!g || !g->pend.r) return false;
+    if (v == g->pend.r)
+        drop_pending(g);
+    else if (v == g->pend.Ap) {
+        if (!g->pend.formed) {
+            g->pend.orphan_Ap = true;
+            return true;
+        }
+        close_pending(g);                        // (a record that only watches needs no Ap)
+    }
+    return false;
+}
+
+namespace {
+
+// Entry of a V-cycle on the top level k: a record on the very r and Ap this cycle is about to overwrite (its first residual writes
+// every entry of r, src/multigrid.jl:50; Ap is scratch) is dropped; any other is settled, the x-only tail needs the grid's
+// step-length buffer for itself.
+void enter_top(hmg_grid *g, int k, hmg_vec **st)
+{
+    const PendingR &q = g->pend;
+    if (!q.r) return;
+    bool same = k >= 2 && k == q.level;
+    for (int i = 0; i < 5 * k && same; ++i) {
+        const bool is_r = i == 5 * (k - 1) + 2, is_Ap = i == 5 * (k - 1) + 4;
+        same = (st[i] == q.r) == is_r && (st[i] == q.Ap) == is_Ap;
+    }
+    if (same)
+        settle_overwritten(q.r);
+    else
+        materialize_r(g);
 }
 
 }  // namespace
 
 void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess)
 {
+    if (top) enter_top(g, k, st);
     (void)vcycle_level(g, k, steps, steps_coarse, st, top, zero_guess, /*hand_up=*/false);
 }
 
@@ -832,6 +959,7 @@ int hmg_grid_reserve_spare(hmg_grid *g, int enable)
     if (enable) {
         (void)reserve_top_spare(g, true);
     } else {
+        materialize_r(g);                        // (x is finished; the record does not rest on the spare vector, but the form changes here)
         release_top_spare(g);
         g->top_spare_refused = true;             // ... and the first vector of the finest level does not bring it back
     }
@@ -847,6 +975,7 @@ int hmg_grid_set_smoother(hmg_grid *g, int kind)
     need(g->ctx != nullptr, "this grid was created without a device context (host tables only)");
     need(kind == 0 || kind == 1, "smoother kind must be 0 (CG) or 1 (Jacobi-preconditioned CG)");
     HIPCHK(hipSetDevice(g->ctx->device));
+    materialize_r(g);                            // (the Jacobi smoother forms its diagonal in the Ap of the next call)
     if (kind == 1 && g->dinv.size() != (size_t)g->nlevels) {
         release_smoother_diag(g);
         std::vector<std::unique_ptr<DevBuf<double>>> bufs((size_t)g->nlevels);
@@ -931,6 +1060,7 @@ int hmg_level_tune_placement(hmg_grid *g, int level, int steps, hmg_vec **states
     }
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
+    materialize_r(g);                            // (memory blocks change hands below)
     ensure_smoother_diag(g, level, state[4]->d);
     const size_t bytes = state[0]->bytes;
     const int64_t n = vec_len(state[0]);
@@ -1043,7 +1173,7 @@ int hmg_vcycle(hmg_grid *g, int top_level, int steps, int steps_coarse, hmg_vec 
     need(g && g->has_op && states, "null argument or operator not set");
     need(top_level >= 1 && top_level <= g->nlevels, "top_level out of range");
     for (int l = 1; l <= top_level; ++l)
-        for (int q = 0; q < 5; ++q) check_vec(g, l, states[5 * (l - 1) + q], "states[]");
+        for (int q = 0; q < 5; ++q) check_vec(g, l, states[5 * (l - 1) + q], "states[]", /*settle_pending=*/false);   // (vcycle() does)
     ensure_smoother_diag(g, top_level, states);
     vcycle(g, top_level, steps, steps_coarse, states);
     HMG_END

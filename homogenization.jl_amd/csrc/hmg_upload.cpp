@@ -35,7 +35,8 @@ void upload_mesh(hmg_grid *g)
 #else
     constexpr size_t BP = 2;
 #endif
-    if (g->d_blockpart.n < (size_t)M.ncells * BP) g->d_blockpart.alloc((size_t)M.ncells * BP);
+    // (+ 2: the step length of a pending r-update lives behind the partials, hmg_grid::pend_alpha())
+    if (g->d_blockpart.n < (size_t)M.ncells * BP + 2) g->d_blockpart.alloc((size_t)M.ncells * BP + 2);
     g->d_cells_cut.upload(K.cells_cut, s);
     g->d_cells_inner.upload(K.cells_inner, s);
     g->d_cell_perm.upload(K.cell_perm, s);
@@ -511,6 +512,7 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    if (g->ctx) materialize_r(g);                // (a pending r-update belongs to the cells and face partners of the grid as it is)
     g->op_epoch += 1;
     g->dinv_ready = false;
     if (g->part) {
@@ -726,6 +728,7 @@ int hmg_grid_set_cut(hmg_grid *g, int64_t ngf, int64_t nge, int64_t ngn, int64_t
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    if (g->ctx) materialize_r(g);                // (a pending r-update was recorded for a grid without sums over ranks)
     // (a host-made cut list knows global ids only: all-reduce over the global cut buffer)
     g->sharers = false;
     set_cut_kind(g, 0, ngf, nlf, face_gid, face_cell_lid, nullptr, nullptr);

@@ -99,6 +99,27 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *   "lazy_top" 2: on the top level the last r-update carries the pending x-updates of the last two steps (three steps or
  *       more; the direction of the step before goes to a spare vector of the top level's size, reserved when the first
  *       vector of the finest level is created or wrapped, or by hmg_grid_reserve_spare); 1: of the last step; 0: neither.
+ *   "lazy_r" 1: inside hmg_vcycle and hmg_fcg_step the top level's last launch finishes x only (40 instead of 58 B/DOF with the
+ *       three-update form, 32 instead of 50 with the two-update form) and the r-update it would have carried stays PENDING on the
+ *       grid: r holds r_2, Ap the unsummed A p_2 and a two-double buffer of the grid the step length.  The first call that is
+ *       handed r or Ap forms r -- the very launch the eager tail makes (26 B/DOF), so r, its r.r in the scalar bank and every
+ *       value derived from them are the same to the last bit -- and a call that cannot have needed it drops the record instead:
+ *       the next hmg_vcycle / hmg_fcg_step on the same vectors (its first residual overwrites r), hmg_vec_copy or hmg_vec_fill over
+ *       all of r, hmg_vec_destroy of r.  hmg_grid_shrink, hmg_grid_set_smoother, hmg_grid_reserve_spare(grid, 0),
+ *       hmg_grid_set_exchange, hmg_grid_set_exchange_async, hmg_grid_set_cut and hmg_level_tune_placement form it first.
+ *       A caller that does read r after a cycle would pay 40 + 26 B/DOF for the 58 of the eager tail, so a grid whose last record
+ *       was settled by a read takes the eager tail in its next cycle and only notes whether r is read again ("lazy_r_form" 0); the
+ *       first cycle whose r goes unread brings the x-only tail back.  Only a call that is handed r or Ap counts as a read, not a
+ *       setter that settles the record.
+ *       The hmg_*_destroy calls never launch (they may come from a finalizer's thread): if Ap is destroyed while r is pending,
+ *       its memory stays with the grid until r has been formed or dropped (the grid itself outlives r anyway).  Until then that
+ *       block is NOT in the pool of option "vec_pool": an hmg_vec_create that replaces the destroyed Ap at once allocates a new
+ *       block ("device_allocs" + 1) and the device holds one more vector of that level for a while -- 10 GB at 1.3e9 entries.
+ *       A host that recycles state vectors between V-cycles reads or destroys r first, or keeps Ap.
+ *       Needs the "lazy_top" forms; the eager tail runs where the memory can be read behind the library's back (r, p or Ap
+ *       wrapped by hmg_vec_wrap, or handed out once by hmg_vec_device_ptr), on a partitioned grid (the deferred sum over the ranks
+ *       would be a collective at a place no rank can foresee) and with smoother kind 1.  0: the eager tail always.
+ *       hmg_ctx_counter "lazy_r_form", "r_materialized", "r_materialized_by_read", "r_dropped".
  *   "fold_prolong" 1: the prolongation rides in the post-smoother's first residual.
  *   "prolong_in_image" 1: on level 6 that residual stages the coarse column at the even nodes of the LDS lattice image
  *       (three workgroups per CU stay resident); 0: in LDS of its own behind it.
@@ -135,7 +156,10 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    weights per cell, and table "cell_class" is empty) and "weight_cache_launches" (launches of the level-6 apply that took its
    weights from the cache), "lazy_top_form" (the form the last finest-level post-smoother inside hmg_vcycle
    took: 2 = three-update form with the spare vector, 1 = two-update form, 0 = plain), "lazy_pre_form" (the x-updates the
-   last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "coarse_x_folds" (residuals
+   last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "lazy_r_form" (1: the
+   last hmg_vcycle / hmg_fcg_step left its top level's r-update pending, option "lazy_r"; 0: it ran the eager tail), "r_materialized" (pending
+   r-updates formed by a later call; "r_materialized_by_read": those of them formed because a call was handed r or Ap, the others
+   by hmg_grid_shrink and the other setters, the placement tuner or a V-cycle on other vectors) and "r_dropped" (those that never had to be formed), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
    hmg_fcg objects), "smoother_diag_bytes" (inverse diagonals held by this context's grids, see hmg_grid_set_smoother) and
    "smoother_diag_builds" (times a grid of this context formed them); -1 for an unknown name.  No counterpart in
@@ -208,6 +232,8 @@ int hmg_grid_table_f64(const hmg_grid *grid, int level, const char *which, doubl
 int hmg_vec_create(hmg_grid *grid, int level, hmg_vec **out);                 /* zeros(Nf, Ne) */
 int hmg_vec_wrap(hmg_grid *grid, int level, void *device_ptr, hmg_vec **out); /* caller-owned ld*Ne doubles */
 int hmg_vec_destroy(hmg_vec *v);
+/* The device pointer of the vector.  From this call on the library assumes that the memory is read behind its back: a pending
+ * r-update on the vector (option "lazy_r") is formed now, and V-cycles that use the vector as r, p or Ap take the eager tail. */
 void *hmg_vec_device_ptr(hmg_vec *v);
 int hmg_vec_upload(hmg_vec *v, const double *host);      /* Nf x Ne, hierarchical order */
 int hmg_vec_download(hmg_vec *v, double *host);
@@ -378,7 +404,10 @@ int hmg_coarse_last_iterations(const hmg_grid *grid);
 int64_t hmg_coarse_misses(const hmg_grid *grid);   /* budgeted solves that ran out of iterations so far */
 /* vcycle!(implicit, base, ops, levels, k, steps); coarser levels use steps_coarse (the reference
  * does not forward `steps`, src/multigrid.jl:109, so pass 2 for parity).
- * states: 5*nlevels handles ordered level-major as x,b,r,p,Ap of level 1, then level 2, ... */
+ * states: 5*nlevels handles ordered level-major as x,b,r,p,Ap of level 1, then level 2, ...
+ * On return x of the top level is finished.  Its r is what the reference leaves to every call of this ABI, but with option
+ * "lazy_r" (the default) it is formed by the first call that is handed r or Ap: that first read costs one pass of 26 B/DOF,
+ * which a run of V-cycles never pays.  p and Ap of the top level are scratch ("lean_post"). */
 int hmg_vcycle(hmg_grid *grid, int top_level, int steps, int steps_coarse, hmg_vec **states);
 /* The two halves of one level of vcycle! (same `states` layout; only levels `level` and `level - 1` are touched):
  *   down  smoothing_steps!, local_residual!, restrict_to!(next.b, P, curr.r), fill!(next.x, 0)   (src/multigrid.jl:100-106)
