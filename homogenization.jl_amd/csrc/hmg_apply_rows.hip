@@ -1,7 +1,7 @@
 // 2D cells larger than the LDS (levels 9..11: 33 153 .. 525 825 nodes per cell, 265 KB .. 4.2 MB per column): operator apply,
 // prolongation and the unique-copy norm on levels that have no packed addressing words (build_level_tables).
 //
-// Row-band apply (k_apply_rows): the 2D counterpart of k_apply_slab (hmg_kernels.hip) with lattice rows in place of k-planes.  In
+// Row-band apply (k_apply_rows): the 2D counterpart of k_apply_slab (hmg_apply.hip) with lattice rows in place of k-planes.  In
 // 2D the lattice image is L(i,j) = RO(j) + i, RO(j) = j (m+1) - j (j-1) / 2, row j holds m+1-j nodes, and the 7-point stencil
 // reaches the rows j-1 and j+1 only.  One workgroup per cell walks the cell in bands of rows [j0, j1) through a ROLLING window: the
 // LDS holds rows [j0-1, j1] (+ a zero guard), the nodes of rows [j0, j1) are evaluated, rows j1-1 and j1 move to the front of the
@@ -10,6 +10,7 @@
 // No per-level tables: a node's storage slot and entity class follow from (i,j) (rows_slot, checked against the host tables by
 // upload_levels).  Same arithmetic per node as k_apply / k_apply_slab (stencil_eval_c for surface nodes, stencil_eval_v with the
 // interior weight row for the rest).
+#include "hmg_apply_launch.hpp"
 #include "hmg_device.hpp"
 #include "hmg_rows_window.hpp"
 #include "hmg_stencil.hpp"
@@ -301,24 +302,17 @@ void launch_apply_rows(const Launch &L, const LevelDev &lv, const MeshDev &mesh,
     // the window of the widest band (rows 0..2 at least) plus the guard must fit, and the move of two rows must fit RW_MV per thread
     if (rows_ro(lv.m, 3) + RW_GUARD > RW_WIN || 2 * (lv.m + 1) > RW_MV * RW_NT || lv.ncls * lv.ndir > WSZ)
         throw std::runtime_error("operator apply (row bands): a band of rows does not fit the window");
-    if (!a.x) throw std::runtime_error("operator apply: null input vector");
-    if (!fused && !a.out) throw std::runtime_error("operator apply: a plain launch needs an output vector");
-    if (fused && (!a.blockpart || !a.scal)) throw std::runtime_error("operator apply: fused launch without its reduction scratch");
-    if (!mesh.coef) throw std::runtime_error("operator apply: no operator coefficients on the device (hmg_grid_set_operator)");
-    if ((a.flags & 1) && !mesh.dmask) throw std::runtime_error("operator apply: constraint requested without a Dirichlet mask");
+    check_apply_bases(a, mesh, fused, true);
     if (a.xcoarse || a.rcoarse) throw std::runtime_error("operator apply (row bands): no level transfer is folded into this kernel");
     if (a.flags & (4 | 64)) throw std::runtime_error("operator apply (row bands): restriction weights / in-image prolongation are not supported");
     if ((a.flags & 8) && !(fused && wd)) throw std::runtime_error("operator apply (row bands): the driver-integral form needs its instantiation");
-    if (fused && (a.xacc || a.x3) && !a.x2) throw std::runtime_error("operator apply: a pending x-update without its direction vector");
-    if (fused && a.xacc && a.x3) throw std::runtime_error("operator apply: xacc and x3 exclude each other");
-    if ((a.flags & 128) && !(fused && a.x3 && a.x2 && a.xout))
-        throw std::runtime_error("operator apply: the zero-input form exists for the residual with two pending x-updates only");
-    const int64_t nblocks = a.cell_list ? a.ncell_list : a.ncells_prefix ? a.ncells_prefix : mesh.ncells;
+    check_apply_pending(a, fused);
+    check_apply_zero_input(a, fused);
+    const int64_t nblocks = apply_work_items(a, mesh);
     if (nblocks == 0) return;
     if (nblocks > 0x7fffffffLL) throw std::runtime_error("operator apply (row bands): too many cells for one launch");
     if (L.n_rows_launches) *L.n_rows_launches += 1;
-    ApplyArgs b = a;
-    b.nwork = nblocks;
+    const ApplyArgs b = apply_work_args(L, mesh, a, nblocks, false);   // (cells in storage order)
     if (!fused)
         launch_rows<false, false>(L, lv, mesh, b, nblocks);
     else if (wd)

@@ -1,7 +1,7 @@
 // Operator apply for cells larger than the LDS (3D level 7: 47 905 nodes, 374 KiB), round 5: ONE persistent 1024-thread workgroup
 // per CU whose waves have ROLES.  ref: src/apply_local_operators.jl:85-133 (+ :7-27 residual, constraint, the fused CG pass).
 //
-// k_apply_slab (hmg_kernels.hip) walks a cell in slabs of k-planes through a rolling LDS window and does, per slab, one thing after
+// k_apply_slab (hmg_apply.hip) walks a cell in slabs of k-planes through a rolling LDS window and does, per slab, one thing after
 // the other: rearrange the window, HBM -> LDS, evaluate -- two workgroups per CU overlap only by being out of step, at 64 VGPRs per
 // thread, with every LDS read of the evaluation a round trip of its own (profiles/r05_level7_phase_timing.txt: rearranging 14-23 %,
 // the HBM phase 28-60 %, the evaluation 25-51 % of a workgroup's life, one after the other).  Here:
@@ -21,6 +21,7 @@
 // thrown away).
 // Same arithmetic per node in the same order as k_apply_slab: out, xout, xacc are equal to its results to the last bit
 // (tests/test_gpu_slab2.py); the per-cell partial sums of p.Ap and r.r are summed in another, fixed, order.
+#include "hmg_apply_launch.hpp"
 #include "hmg_stencil.hpp"
 
 namespace hmg {
@@ -664,14 +665,10 @@ static void launch_slab2(const Launch &L, const LevelDev &lv, const MeshDev &mes
     auto kern = k_apply_slab2<FUSED, NS, SRC, OUT, SLOT ? 8 : 4, SLOT>;
     const size_t bytes = slab2_lds_bytes(mesh);
     HMG_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    const int64_t nblocks = a.cell_list ? a.ncell_list : a.ncells_prefix ? a.ncells_prefix : mesh.ncells;
+    const int64_t nblocks = apply_work_items(a, mesh);
     if (nblocks == 0) return;
-    ApplyArgs b = a;
-    b.nwork = nblocks;
-    if (L.cell_order && !a.cell_list && !a.ncells_prefix && mesh.cell_perm) {   // (XCD-aware cell order: workgroup b -> XCD b % 8, and
-        b.cell_list = mesh.cell_perm;                                           //  the grid is a multiple of 8, so b + i G stays there)
-        b.ncell_list = nblocks;
-    }
+    // (XCD-aware cell order: workgroup b -> XCD b % 8, and the grid is a multiple of 8, so b + i G stays there)
+    const ApplyArgs b = apply_work_args(L, mesh, a, nblocks, true);
     // one resident workgroup per CU walks its cells (option slab2_grid: another number -- a multiple of 8 keeps a workgroup's cells on its XCD)
     const int64_t grid = std::min<int64_t>(nblocks, L.slab2_grid > 0 ? L.slab2_grid : (int64_t)L.num_cu);
     if ((nblocks + grid - 1) / grid > S2_MAXCELLS) throw std::runtime_error("operator apply: more cells per workgroup than the slab kernel stages");
@@ -681,16 +678,10 @@ static void launch_slab2(const Launch &L, const LevelDev &lv, const MeshDev &mes
 
 void launch_apply_slab2(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused)
 {
-    if (!a.x) throw std::runtime_error("operator apply: null input vector");
-    if (!fused && !a.out) throw std::runtime_error("operator apply: a plain launch needs an output vector");
-    if (fused && (!a.blockpart || !a.scal)) throw std::runtime_error("operator apply: fused launch without its reduction scratch");
-    if (!mesh.coef && !(a.flags & 4)) throw std::runtime_error("operator apply: no operator coefficients on the device (hmg_grid_set_operator)");
-    if ((a.flags & 1) && !mesh.dmask) throw std::runtime_error("operator apply: constraint requested without a Dirichlet mask");
+    check_apply_bases(a, mesh, fused, !(a.flags & 4));   // (the restriction through the window reads no coefficients)
     if (a.xcoarse || a.rcoarse) throw std::runtime_error("operator apply: the slab kernel folds no level transfer");
-    if (fused && (a.xacc || a.x3) && !a.x2) throw std::runtime_error("operator apply: a pending x-update without its direction vector");
-    if (fused && a.xacc && a.x3) throw std::runtime_error("operator apply: xacc and x3 exclude each other");
-    if ((a.flags & 128) && !(fused && a.x3 && a.x2 && a.xout))
-        throw std::runtime_error("operator apply: the zero-input form exists for the residual with two pending x-updates only");
+    check_apply_pending(a, fused);
+    check_apply_zero_input(a, fused);
     if (L.n_slab2_launches) *L.n_slab2_launches += 1;
     const bool src = a.src != nullptr, out = a.out != nullptr;
     if (a.flags & 4) {   // the restriction through the window (launch_restrict_slab)

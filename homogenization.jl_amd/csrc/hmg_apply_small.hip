@@ -18,6 +18,7 @@
 //
 // ref: src/apply_local_operators.jl:85-133 (+ :18-27, constraint src/implicit_fine_grid.jl:94-139, CG extras src/multigrid.jl:54-68,
 // interpolate_and_sum_to! src/interpolation.jl:64-74 in the folded form)
+#include "hmg_apply_launch.hpp"
 #include "hmg_device.hpp"
 #include "hmg_stencil.hpp"
 
@@ -390,16 +391,11 @@ bool apply_small_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, co
 
 void launch_apply_small(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a0, bool fused)
 {
-    ApplyArgs a = a0;
-    const int64_t nblocks = a.cell_list ? a.ncell_list : a.ncells_prefix ? a.ncells_prefix : mesh.ncells;
+    const int64_t nblocks = apply_work_items(a0, mesh);
     if (nblocks == 0) return;
-    if (!a.x) throw std::runtime_error("operator apply: null input vector");
-    if (!fused && !a.out) throw std::runtime_error("operator apply: a plain launch needs an output vector");
-    if (fused && (!a.blockpart || !a.scal)) throw std::runtime_error("operator apply: fused launch without its reduction scratch");
-    if ((a.flags & 1) && !mesh.dmask) throw std::runtime_error("operator apply: constraint requested without a Dirichlet mask");
-    if ((a.flags & 128) && !(fused && a.x3 && a.x2 && a.xout && !a.xcoarse))
-        throw std::runtime_error("operator apply: the zero-input form exists for the residual with two pending x-updates only");
-    a.nwork = nblocks;
+    check_apply_bases(a0, mesh, fused, false);
+    check_apply_zero_input(a0, fused);
+    const ApplyArgs a = apply_work_args(L, mesh, a0, nblocks, false);   // (cells in storage order)
     if (lv.nf <= 16 && L.apply_pack && nblocks >= 4 && nblocks < (int64_t(1) << 31)) {
         const int64_t nquad = (nblocks + 3) / 4;
         const dim3 gq((unsigned)std::min<int64_t>(nquad, (int64_t)16 * L.num_cu)), bq(64);

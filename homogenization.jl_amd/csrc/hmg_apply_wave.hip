@@ -26,6 +26,7 @@
 // Reference behaviour reproduced: src/apply_local_operators.jl:85-133 (+ :18-27 residual, constraint mask
 // src/implicit_fine_grid.jl:94-139, the CG extras of src/multigrid.jl:54-68, restrict_to! / interpolate_and_sum_to!
 // src/interpolation.jl:52-74 in the folded forms).
+#include "hmg_apply_launch.hpp"
 #include "hmg_device.hpp"
 #include "hmg_stencil.hpp"
 
@@ -502,22 +503,12 @@ bool apply_wave_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, con
 
 void launch_apply_wave(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a0, bool fused)
 {
-    ApplyArgs a = a0;
-    const int64_t nblocks = a.cell_list ? a.ncell_list : a.ncells_prefix ? a.ncells_prefix : mesh.ncells;
+    const int64_t nblocks = apply_work_items(a0, mesh);
     if (nblocks == 0) return;
-    if (!a.x) throw std::runtime_error("operator apply: null input vector");
-    if (!fused && !a.out) throw std::runtime_error("operator apply: a plain launch needs an output vector");
-    if (fused && (!a.blockpart || !a.scal)) throw std::runtime_error("operator apply: fused launch without its reduction scratch");
-    if ((a.flags & 1) && !mesh.dmask) throw std::runtime_error("operator apply: constraint requested without a Dirichlet mask");
-    if (a.xcoarse && !a.xout) throw std::runtime_error("operator apply: folded prolongation without xout");
-    if (a.rcoarse && a.ldrc <= 0) throw std::runtime_error("operator apply: epilogue restriction without the coarse column stride");
-    if ((a.flags & 128) && !(fused && a.x3 && a.x2 && a.xout && !a.xcoarse))
-        throw std::runtime_error("operator apply: the zero-input form exists for the residual with two pending x-updates only");
-    a.nwork = nblocks;
-    if (L.cell_order && !a.cell_list && !a.ncells_prefix && mesh.cell_perm) {   // XCD x walks the x-th eighth of the cells
-        a.cell_list = mesh.cell_perm;
-        a.ncell_list = nblocks;
-    }
+    check_apply_bases(a0, mesh, fused, false);
+    check_apply_transfers(a0);
+    check_apply_zero_input(a0, fused);
+    const ApplyArgs a = apply_work_args(L, mesh, a0, nblocks, true);
     int64_t grid = std::min<int64_t>(nblocks, L.wave_grid > 0 ? L.wave_grid : 16 * (int64_t)L.num_cu);
     if (grid >= 8) grid -= grid % 8;               // (wave b stays on XCD b % 8 for every cell it walks)
     const size_t lds = sizeof(double) * (size_t)(WVZ + WNF + lv.lds_g1);

@@ -1,4 +1,5 @@
-// Device-side view of the tables and the kernel launch API (implemented in hmg_kernels.hip).
+// Device-side view of the tables and the kernel launch API (implemented in hmg_apply.hip, the hmg_apply_*.hip families and
+// hmg_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -227,6 +228,8 @@ bool apply_defers3(const Launch &L, const LevelDev &lv);
 // scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.scal / a.mult / a.blockpart are filled in here.
 void launch_apply_fused_kernel(const Launch &L, const LevelDev &lv, const MeshDev &mesh, ApplyArgs a);
 void launch_apply_fused_reduce(const Launch &L, const MeshDev &mesh, int slot_pap, int slot_rr);
+// scal[slot] = partials[0] + ... + partials[n - 1], one block in a fixed order (k_finalize, hmg_kernels.hip); the caller checks the launch
+void launch_finalize(const Launch &L, const double *partials, int n, int slot);
 void launch_apply_args(const Launch &L, const LevelDev &lv, const MeshDev &mesh, ApplyArgs a);
 // one-wave-per-cell path (hmg_apply_wave.hip): can this launch take it / launch it (a.scal, a.mult, a.blockpart filled in)
 bool apply_wave_ok(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, bool fused);

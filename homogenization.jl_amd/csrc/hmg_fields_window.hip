@@ -5,7 +5,7 @@
 //   raw[c][t]            = sum_i v_i (T_t w_c)_i,   raw[c][nq + a] = sum_i dphi[3 i + a] v_i,   raw[c][nq + dim + a] = sum_i dphi[3 i + a] w_i
 // (the last set only where w is another vector), formed while the cell walks through a ROLLING window of the LDS, as the operator
 // applies of those levels do:
-//   k_cell_pair_moments_slab (3D) follows k_apply_slab (hmg_kernels.hip): slabs of k-planes from SlabTables -- the window holds
+//   k_cell_pair_moments_slab (3D) follows k_apply_slab (hmg_apply.hip): slabs of k-planes from SlabTables -- the window holds
 //     planes [k0-1, k1], planes k0-1 and k0 move to its front LDS -> LDS, the new planes come from HBM through ld_word, the nodes
 //     of planes [k0, k1) are taken from cp_word / cp_slot, surface entries first (decode32w), then the cell interior (decode_lattice);
 //   k_cell_pair_moments_rows (2D) follows k_apply_rows (hmg_apply_rows.hip): bands of lattice rows in closed form (rows_band_end,

@@ -127,7 +127,7 @@ BlockedInterior build_blocked_interior(const LevelTables &T)
             }
     if ((int)covered != T.nint) throw std::runtime_error("blocked interior: tables do not cover the interior");
     // the same instantiation evaluates the faces one class per wave and skips the taps that leave the cell (face_tap_mask in
-    // hmg_kernels.hip: f0 k = 0, f1 j = 0, f2 i = 0, f3 i+j+k = m; an edge node keeps the taps both of its faces keep,
+    // hmg_stencil.hpp: f0 k = 0, f1 j = 0, f2 i = 0, f3 i+j+k = m; an edge node keeps the taps both of its faces keep,
     // edge_tap_mask): check them against the class table, and the run counts the kernel is compiled for (4 waves x 2 runs of
     // 64 per face, 3 runs of 64 for corners + edges)
     const uint32_t f0 = 1u << 8 | 1u << 10 | 1u << 12 | 1u << 14, f1 = 1u << 4 | 1u << 6 | 1u << 7 | 1u << 13,
@@ -383,7 +383,7 @@ MeshKernelTables build_mesh_kernel_tables(const MeshTables &M, bool xcd_lists)
         K.face_partner[(size_t)cb * 4 + lb] = (ca << 2) | la;
     }
     // the class-weight-cache kernels read the masks of two neighbouring cells as ONE 32-bit word (HMG_KP(uint32_t, dmask)[cell >> 1]
-    // in hmg_kernels.hip / hmg_apply_wave.hip / hmg_apply_small.hip): an even number of entries, whatever the cell count
+    // in hmg_apply.hip / hmg_apply_wave.hip / hmg_apply_small.hip): an even number of entries, whatever the cell count
     K.dmask = M.dmask;
     if (K.dmask.size() & 1) K.dmask.push_back((uint16_t)0);
     // XCD-aware cell order of the full-grid apply launches (option cell_order): workgroups are dispatched round-robin over

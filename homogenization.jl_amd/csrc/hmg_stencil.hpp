@@ -1,4 +1,4 @@
-// Device-side building blocks of the kernels of hmg_kernels.hip: error checking,
+// Device-side building blocks of the kernels of hmg_apply.hip and hmg_kernels.hip: error checking,
 // reductions, LDS reads, addressing-word decoders, stencil evaluators (per node, per face run, register-blocked).
 #pragma once
 #include "hmg_device.hpp"

@@ -44,7 +44,7 @@ WAVE_BUDGET = {
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_hot_instantiations_fit_their_register_budget(tmp_path):
-    src = os.path.join(ROOT, "homogenization.jl_amd", "csrc", "hmg_kernels.hip")
+    src = os.path.join(ROOT, "homogenization.jl_amd", "csrc", "hmg_apply.hip")
     out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Rpass-analysis=kernel-resource-usage", "-c", src,
                           "-o", str(tmp_path / "k.o")], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
