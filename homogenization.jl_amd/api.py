@@ -596,8 +596,10 @@ def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None
     many elements exceed each threshold (hmg_cell_extrema): qmax (Ne,), qmin (Ne,), counts (Ne, nthr) int64.  `form` is the
     symmetric Q_c per cell, (Ne, d, d), or (Ne, d) for diagonals; None is the identity, q = |grad u|^2 (fields.energy_form,
     fields.flux_form make the usual ones).  Up to 8 finite thresholds, the same for all cells.  The vector as stored; 3D levels
-    1 to 6, 2D levels 1 to 8, larger cells are refused whatever "cell_moments_windows" says.  One pass of 8 B/DOF; the same bits
-    in every run.  On a dist.PartitionedGrid Ne is the number of LOCAL cells: `form` and all three results are per local cell
+    1 to 6 and 2D levels 1 to 8; larger cells (3D level 7, 2D levels 9 to 11) are refused unless the context option
+    "cell_extrema_windows" is 1 (then they walk through a rolling LDS window; 2 sends every level the window kernels address
+    through them, with the same bits; "cell_moments_windows" has no say here, and the counter "cell_extrema_window_launches" counts
+    the window launches).  One pass of 8 B/DOF; the same bits in every run.  On a dist.PartitionedGrid Ne is the number of LOCAL cells: `form` and all three results are per local cell
     (form = global_form[implicit.local_cells]; a form of global length is refused), while the operator's sigma is the global field.
     qmax and qmin of a cell are NaN exactly when q_T is NaN on one of its elements (a NaN in the cell's column, inf - inf); an
     infinite q_T is a value; a NaN element is counted for no threshold; other cells are untouched.

@@ -279,6 +279,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_moments_window_launches") return ctx->moments_window_launches;   // launches of the window kernels (option "cell_moments_windows")
     if (n == "cell_moments_windows") return ctx->moments_windows;                   // ... and that option's value (a caller that sets it for one pass restores it)
     if (n == "cell_extrema_kernel_ns") return ctx->extrema_kernel_ns;               // the last hmg_cell_extrema: kernel alone
+    if (n == "cell_extrema_window_launches") return ctx->extrema_window_launches;   // launches of its window kernels (option "cell_extrema_windows")
+    if (n == "cell_extrema_windows") return ctx->extrema_windows;                   // ... and that option's value
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;    // as the RCCL communicator was created; 0: none
     return -1;
 }
@@ -340,6 +342,11 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         if (value < 0 || value > 2)           // kernels; 2: every level the window kernels can address does (test and A/B knob)
             throw std::runtime_error("option cell_moments_windows: 0, 1 or 2");
         ctx->moments_windows = (int)value;
+    }
+    else if (n == "cell_extrema_windows") {   // the same for hmg_cell_extrema (hmg_extrema_window.hip): 0 = default, 1, 2
+        if (value < 0 || value > 2)
+            throw std::runtime_error("option cell_extrema_windows: 0, 1 or 2");
+        ctx->extrema_windows = (int)value;
     }
     else if (n == "coarse_poly")           // Chebyshev iterates per preconditioner application of the level-1 PCG (1 = Jacobi)
         ctx->coarse_poly = std::max<int>(1, std::min<int>(16, (int)value));

@@ -13,6 +13,9 @@
 // so for u = xi . x + v and a symmetric Q_c
 //   q_T = grad u . Q_c grad u = (xi~ + g~_T) . Q~_c (xi~ + g~_T)        Q~_c = M_c^T Q_c M_c,  xi~ = M_c^-1 xi
 // and the kernel (hmg_extrema.hip) sees one row (Q~, xi~) per cell and never J.
+// Cells larger than the LDS (3D level 7, 2D levels 9..11) are refused unless the context option "cell_extrema_windows" routes them
+// to the window kernels (hmg_extrema_window.hip: 1 -- levels that do not fit only; 2 -- every level those kernels can address);
+// mask, rows and results are the same on either path, and so are the bits on a level both serve.
 // Not on a V-cycle's path: the call allocates (rows and results, from the context's pool of level-vector memory; the element
 // mask of a level once, at its first call) and synchronises.
 #include "../../include/hmg.h"
@@ -237,10 +240,18 @@ int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *fo
     check_vec(g, v->level, v, "v");
     const LevelDev &lv = lev(g, v->level);
     const int dim = g->dim, nq = sym_ncomp(dim), nrow = cell_extrema_nrow(dim);
-    if (!cell_extrema_ok(lv) || !cell_moments_ok(lv, true))
+    // the kernel: k_cell_extrema where the cell fits the LDS, the window kernels by the option "cell_extrema_windows" (1: levels
+    // that do not fit; 2: every level they address)
+    const SlabTables st = slab_tables(g, lv);
+    const bool fits = cell_extrema_ok(lv) && cell_moments_ok(lv, true), can = cell_extrema_window_ok(lv, st);
+    const int mode = g->ctx->extrema_windows;
+    const bool window = mode != 0 && can && (mode == 2 || !fits);
+    if (!window && !fits)
         throw std::runtime_error("hmg_cell_extrema: one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
                                  " nodes) does not fit the LDS; the per-cell extrema serve " +
-                                 (dim == 3 ? "3D levels up to 6" : "2D levels up to 8") + " and have no window form");
+                                 (dim == 3 ? "3D levels up to 6" : "2D levels up to 8") +
+                                 (can ? "; the context option \"cell_extrema_windows\" = 1 takes larger cells through the window kernels"
+                                      : "; no window kernel addresses this level"));
     const MeshTables &M = g->cur();
     const int64_t nc = g->md.ncells;
     if (form)
@@ -313,7 +324,11 @@ int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *fo
         HIPCHK(hipEventCreate(&ev1));
         HIPCHK(hipMemcpyAsync(d_rows, rows.data(), row_bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipEventRecord(ev0, c->stream));
-        launch_cell_extrema(c->L, lv, nc, v->d, d_mask, d_rows, thr, nthr, d_out);
+        if (window) {
+            launch_cell_extrema_window(c->L, lv, st, nc, v->d, d_mask, d_rows, thr, nthr, d_out);
+            c->extrema_window_launches += 1;
+        } else
+            launch_cell_extrema(c->L, lv, nc, v->d, d_mask, d_rows, thr, nthr, d_out);
         HIPCHK(hipEventRecord(ev1, c->stream));
         HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));

@@ -21,7 +21,10 @@
 // maximum and minimum into NaN behind the slot loop; the picks of the folds across lanes and waves take a NaN and keep one.
 // A cell's maximum and minimum are NaN exactly when one of its elements' values is; an infinite value is a value like any other;
 // the counts compare, and a NaN compares false.
+// The evaluation of a node and the fold of a cell are extrema_node / extrema_fold of hmg_extrema_device.hpp, which the window
+// kernels of cells larger than the LDS (hmg_extrema_window.hip) call too: the same bits on a level both serve.
 #include "hmg_extrema.hpp"
+#include "hmg_extrema_device.hpp"
 #include "hmg_stencil.hpp"
 
 #include <algorithm>
@@ -32,172 +35,37 @@ namespace {
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
 
-// maximum / minimum / integer sum over the wave by data-parallel moves (the pattern of wave_sum63): the result arrives in lane 63.
-// Lanes a move does not reach keep `old`: the lane's own value for the extrema, 0 for the sum.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_other(double v)
-{
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-// the larger (MAX) or smaller of a and b; a NaN on either side is the result
-template <bool MAX>
-__device__ __forceinline__ double ext_pick(double a, double b)
-{
-    return ((MAX ? b > a : b < a) || b != b) ? b : a;
-}
-template <bool MAX>
-__device__ __forceinline__ double wave_ext63(double v)
-{
-    auto pick = [](double a, double b) { return ext_pick<MAX>(a, b); };
-    v = pick(v, dpp_other<0x111, 0xf>(v));     // row_shr:1
-    v = pick(v, dpp_other<0x112, 0xf>(v));     // row_shr:2
-    v = pick(v, dpp_other<0x114, 0xf>(v));     // row_shr:4
-    v = pick(v, dpp_other<0x118, 0xf>(v));     // row_shr:8
-    v = pick(v, dpp_other<0x142, 0xa>(v));     // row_bcast:15
-    v = pick(v, dpp_other<0x143, 0xc>(v));     // row_bcast:31
-    return v;
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_addi(int v)
-{
-    return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ int wave_isum63(int v)
-{
-    v = dpp_addi<0x111, 0xf>(v);
-    v = dpp_addi<0x112, 0xf>(v);
-    v = dpp_addi<0x114, 0xf>(v);
-    v = dpp_addi<0x118, 0xf>(v);
-    v = dpp_addi<0x142, 0xa>(v);
-    v = dpp_addi<0x143, 0xc>(v);
-    return v;
-}
-
 template <int DIM, int NT>
 __global__ void __launch_bounds__(NT)
 k_cell_extrema(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8_t *__restrict__ elem_mask,
                const double *__restrict__ rows, ExtremaThresholds thr, int nthr, double *__restrict__ out)
 {
-    constexpr int NQ = DIM == 3 ? 6 : 3, NROW = NQ + DIM, NEL = DIM == 3 ? 6 : 2, NW = NT / 64;
-    constexpr int NTHR = EX_MAX_THRESHOLDS;
+    constexpr int NQ = DIM == 3 ? 6 : 3, NROW = NQ + DIM, NW = NT / 64;
     extern __shared__ double smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nf = lv.nf, m = lv.m;
     double *xs = smem;                            // lattice image of v, g1 zeros behind it
     double *red = xs + ((nf + g1 + 1) & ~1);      // [NW][2]: maximum, minimum
-    int *redc = (int *)(red + 2 * NW);            // [NW][NTHR]
+    int *redc = (int *)(red + 2 * NW);            // [NW][EX_MAX_THRESHOLDS]
     for (int q = tid; q < g1; q += NT) xs[nf + q] = 0.0;
     const int hi = nf + g1 - 1;
-    const double inf = __builtin_huge_val();
     for (int64_t cell = blockIdx.x; cell < ncells; cell += gridDim.x) {
         const double *vc = v + cell * lv.ld;
         for (int t = tid; t < nf; t += NT) xs[lv.lpos[t]] = vc[t];
-        // the cell's row: Q~ (off-diagonal entries doubled here, once per cell) and xi~, the same in every lane
-        const double *row = rows + cell * NROW;
         double Q[NQ], X[DIM];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) Q[q] = row[q];
-#pragma unroll
-        for (int a = 0; a < DIM; ++a) X[a] = row[NQ + a];
-        if (DIM == 3) {
-            Q[1] *= 2.0;
-            Q[2] *= 2.0;
-            Q[4] *= 2.0;
-        } else
-            Q[1] *= 2.0;
+        extrema_row<DIM>(rows + cell * NROW, Q, X);
         __syncthreads();                          // image (first cell: guard too) complete; red[] of the last cell read
-        double mx = -inf, mn = inf;
-        // the largest high word, signed and unsigned, of the values of this thread's existing elements: above +inf's a positive NaN,
-        // above -inf's a negative one (a value is the result of arithmetic: its NaN is quiet, with a bit in the high word)
-        int hs = 0;
-        unsigned hu = 0;
-        int cnt[NTHR];
-#pragma unroll
-        for (int j = 0; j < NTHR; ++j) cnt[j] = 0;
+        ExtremaAcc acc;
+        acc.reset();
         for (int t = tid; t < nf; t += NT) {
             const unsigned mk = elem_mask[t];
             if (mk == 0) continue;                // no element has its lowest vertex here (the faces i = m - j - k, ...)
             int L, len, A, B, cls;
             decode32<DIM>(lv.pos32[t], m, L, len, A, B, cls);
-            auto at = [&](int off) { return lds_ld(xs + min(max(L + off, 0), hi)); };
-            double q[NEL];
-            const double u0 = lds_ld(xs + L);
-            if constexpr (DIM == 3) {
-                // taps 11, 8, 4, 5, 13, 10, 1 of stencil_eval_v (hmg_extrema.hpp)
-                const double ua = at(A), ub = at(len + 1 - B), uc = at(-len), uab = at(len), uac = at(A + 1 - len), ubc = at(1 - B),
-                             us = at(1);
-                auto form = [&](double ga, double gb, double gc) {
-                    ga += X[0];
-                    gb += X[1];
-                    gc += X[2];
-                    return ga * (Q[0] * ga + Q[1] * gb + Q[2] * gc) + gb * (Q[3] * gb + Q[4] * gc) + gc * (Q[5] * gc);
-                };
-                q[0] = form(ua - u0, uab - ua, us - uab);      // a, b, c
-                q[1] = form(ua - u0, us - uac, uac - ua);      // a, c, b
-                q[2] = form(uab - ub, ub - u0, us - uab);      // b, a, c
-                q[3] = form(us - ubc, ub - u0, ubc - ub);      // b, c, a
-                q[4] = form(uac - uc, us - uac, uc - u0);      // c, a, b
-                q[5] = form(us - ubc, ubc - uc, uc - u0);      // c, b, a
-            } else {
-                // taps 5, 4, 1
-                const double ua = at(len), ub = at(-len), us = at(1);
-                auto form = [&](double ga, double gb) {
-                    ga += X[0];
-                    gb += X[1];
-                    return ga * (Q[0] * ga + Q[1] * gb) + gb * (Q[2] * gb);
-                };
-                q[0] = form(ua - u0, us - ua);                 // a, b
-                q[1] = form(us - ub, ub - u0);                 // b, a
-            }
-            double qh[NEL];                       // for the maximum and the counts: -inf where the element does not exist
-#pragma unroll
-            for (int k = 0; k < NEL; ++k) {
-                const bool on = (mk >> k) & 1u;
-                qh[k] = on ? q[k] : -inf;
-                const double ql = on ? q[k] : inf;
-                hs = max(hs, __double2hiint(qh[k]));
-                hu = max(hu, (unsigned)__double2hiint(qh[k]));
-                mx = qh[k] > mx ? qh[k] : mx;
-                mn = ql < mn ? ql : mn;
-            }
-#pragma unroll
-            for (int j = 0; j < NTHR; ++j)
-                if (j < nthr) {                   // (the same in every lane: a scalar branch)
-#pragma unroll
-                    for (int k = 0; k < NEL; ++k) cnt[j] += qh[k] > thr.t[j] ? 1 : 0;
-                }
+            extrema_node<DIM>(xs, L, len, A, B, 0, hi, mk, Q, X, thr, nthr, acc);
         }
-        // lanes by data-parallel moves, waves through LDS, one thread per output
-        if (hs > 0x7ff00000 || hu > 0xfff00000u) mx = mn = __builtin_nan("");
-        mx = wave_ext63<true>(mx);
-        mn = wave_ext63<false>(mn);
-#pragma unroll
-        for (int j = 0; j < NTHR; ++j)
-            if (j < nthr) cnt[j] = wave_isum63(cnt[j]);
-        if (lane == 63) {
-            red[2 * wave] = mx;
-            red[2 * wave + 1] = mn;
-#pragma unroll
-            for (int j = 0; j < NTHR; ++j) redc[wave * NTHR + j] = cnt[j];
-        }
-        __syncthreads();                          // every wave is done with the image: the next cell's may be written
-        if (tid < 2 + nthr) {
-            double r;
-            if (tid == 0) {
-                r = red[0];
-                for (int k = 1; k < NW; ++k) r = ext_pick<true>(r, red[2 * k]);
-            } else if (tid == 1) {
-                r = red[1];
-                for (int k = 1; k < NW; ++k) r = ext_pick<false>(r, red[2 * k + 1]);
-            } else {
-                int s = 0;
-                for (int k = 0; k < NW; ++k) s += redc[k * NTHR + tid - 2];
-                r = (double)s;
-            }
-            out[cell * (2 + nthr) + tid] = r;
-        }
+        // (its barrier: every wave is done with the image, the next cell's may be written)
+        extrema_fold<NW>(acc, nthr, wave, red, redc, out, cell);
     }
 }
 

@@ -1,5 +1,5 @@
 // Per-cell extrema and exceedance counts of a quadratic form of the fine-element gradients of a level vector (include/hmg.h:
-// hmg_cell_extrema): what the host module (hmg_extrema.cpp) and the kernel (hmg_extrema.hip) share.
+// hmg_cell_extrema): what the host module (hmg_extrema.cpp) and the kernels (hmg_extrema.hip, hmg_extrema_window.hip) share.
 #pragma once
 
 #include "hmg_device.hpp"
@@ -30,5 +30,15 @@ bool cell_extrema_ok(const LevelDev &lv);
 // rows: cell_extrema_nrow(dim) numbers per cell.  The same bits in every run and for every grid size.
 void launch_cell_extrema(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const uint8_t *elem_mask,
                          const double *rows, const ExtremaThresholds &thr, int nthr, double *out);
+
+// Cells larger than the LDS (hmg_extrema_window.hip): the same results in the same rows from a rolling window of the LDS -- slabs of
+// k-planes in 3D (st: the level's SlabTables, the lists of k_apply_slab), bands of lattice rows in 2D (closed forms, st unused).
+// Both kernel families evaluate a node with one function (hmg_extrema_device.hpp): the same bits on a level both serve.
+// can the window kernels address this level?  3D: levels with slab tables; 2D: m >= 2
+bool cell_extrema_window_ok(const LevelDev &lv, const SlabTables &st);
+// out[c][0 .. 2 + nthr) for the first ncells columns; throws on a level it cannot address, on nthr outside 0 .. 8, on null bases and
+// on more than 2^31 - 1 cells before any launch; the same bits in every run and for every number of cells
+void launch_cell_extrema_window(const Launch &L, const LevelDev &lv, const SlabTables &st, int64_t ncells, const double *v,
+                                const uint8_t *elem_mask, const double *rows, const ExtremaThresholds &thr, int nthr, double *out);
 
 }  // namespace hmg

@@ -25,6 +25,26 @@
 
 #include <chrono>
 
+namespace hmg {
+
+// (declared in hmg_objects.hpp: hmg_extrema.cpp walks the same lists)
+SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv)
+{
+    const LevelBufs &B = *g->lb[lv.level - 1];
+    SlabTables st{};
+    st.head = B.slab_head.p;
+    st.ld_word = B.slab_ld_word.p;
+    st.cp_word = B.slab_cp_word.p;
+    st.cp_slot = B.slab_cp_slot.p;
+    st.nslab = B.nslab;
+    st.lds_nodes = B.slab_lds_nodes;
+    st.max_surf = B.slab_max_surf;
+    st.max_int = B.slab_max_int;
+    return st;
+}
+
+}  // namespace hmg
+
 namespace {
 
 // the raw sums of one kernel pass, downloaded: `launch` enqueues the kernel that fills `bytes` of device memory; the kernel's time
@@ -58,22 +78,6 @@ void raw_sums(hmg_ctx *c, std::vector<double> &raw, F launch, int64_t &kernel_ns
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
     vec_release(c, d, bytes);
-}
-
-// the level's rolling-window lists (those set_slab hands to the operator apply), without touching the grid's launch state
-SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv)
-{
-    const LevelBufs &B = *g->lb[lv.level - 1];
-    SlabTables st{};
-    st.head = B.slab_head.p;
-    st.ld_word = B.slab_ld_word.p;
-    st.cp_word = B.slab_cp_word.p;
-    st.cp_slot = B.slab_cp_slot.p;
-    st.nslab = B.nslab;
-    st.lds_nodes = B.slab_lds_nodes;
-    st.max_surf = B.slab_max_surf;
-    st.max_int = B.slab_max_int;
-    return st;
 }
 
 // does this call take the window kernels?  fits: the verdict of the LDS-resident kernel.  Throws the refusal where no kernel serves.

@@ -249,6 +249,9 @@ struct hmg_ctx {
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window
                                              // kernels (hmg_fields_window.hip); 2 so does every level those kernels can address (A/B knob)
     int64_t moments_window_launches = 0;     // launches of the window kernels (hmg_ctx_counter "cell_moments_window_launches")
+    int extrema_windows = 0;                 // option "cell_extrema_windows": the same three values for hmg_cell_extrema and its window
+                                             // kernels (hmg_extrema_window.hip); an option of its own, so that neither call changes with the other's
+    int64_t extrema_window_launches = 0;     // launches of those (hmg_ctx_counter "cell_extrema_window_launches")
     int64_t coarse_x_folds = 0;              // residuals that finished the coarser level's x on the way (option fold_coarse_x)
     int last_pre_form = 0;                   // x-updates the last pre-smoother of a V-cycle's down leg left to its local residual: 0 .. 3
     int last_r_form = 0;                     // what the last hmg_vcycle / hmg_fcg_step left of its top level's r: 0 formed, 1 pending (x-only tail)
@@ -479,6 +482,11 @@ double read_scalar(hmg_ctx *c, int slot);
 void ensure_weight_cache(hmg_grid *g);
 // hands the cache back (grid destruction, a new class table) and takes its share out of the context's counters
 void release_weight_cache(hmg_grid *g);
+
+// ---- hmg_fields.cpp ----
+// the level's rolling-window lists (those set_slab hands to the operator apply), without touching the grid's launch state: what
+// the window kernels of the per-cell moments and extrema walk
+SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv);
 
 // ---- hmg_smooth.cpp ----
 void set_slab(hmg_grid *g, const LevelDev &lv);

@@ -619,19 +619,23 @@ def _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_st
 
 @contextlib.contextmanager
 def _large_cells(ctx, on: bool):
-    """Around the moment passes of the Dirichlet drivers: with `on`, the context option "cell_moments_windows" is at least 1 inside
-    (cells larger than the LDS -- 3D level 7, 2D levels 9-11 -- go through the window kernels) and back at its previous value
-    behind, also when a pass raises.  The context may be the caller's."""
+    """Around the per-cell passes of the Dirichlet drivers: with `on`, the context options "cell_moments_windows" and
+    "cell_extrema_windows" are at least 1 inside (cells larger than the LDS -- 3D level 7, 2D levels 9-11 -- go through the window
+    kernels of the moments and of the extrema) and back at their previous values behind, also when a pass raises.  The context may
+    be the caller's."""
     if not on:
         yield
         return
-    prev = ctx.counter("cell_moments_windows")
-    if prev == 0:
-        ctx.set_option("cell_moments_windows", 1)
+    names = ("cell_moments_windows", "cell_extrema_windows")
+    prev = {name: ctx.counter(name) for name in names}
     try:
+        for name in names:
+            if prev[name] == 0:
+                ctx.set_option(name, 1)
         yield
     finally:
-        ctx.set_option("cell_moments_windows", prev)
+        for name in names:
+            ctx.set_option(name, prev[name])
 
 
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
@@ -653,10 +657,11 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     inverse loop moves it.  Returns a dict: "energy_form", "flux_form" (dim), "cycles", "residual" (relative),
     "volume"; with `fields` also "mean" (Ne, dim), "gram" (Ne, dim, dim), "flux", "energy", "volumes", "cond", "base".  `save` (a
     file name) writes the coarse mesh with those cell fields (vtk.export_cell_fields).  In this setting, and only in it,
-    gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  `large_cells`: the moment pass may
-    run on a top level whose cell exceeds the LDS (3D level 7, 2D levels 9-11; context option "cell_moments_windows" = 1 around
-    the pass, restored behind it); without it such a level is refused after the solve.  `extrema`: a second pass, over the fine
-    elements (api.cell_extrema with Q = sigma_c; top levels up to 6 in 3D and 8 in 2D), adds "peak_energy_density" and
+    gram[c] is the exact sensitivity d(energy_form |Omega|) / d(sigma_c) (fields.sensitivity).  `large_cells`: the per-cell passes
+    may run on a top level whose cell exceeds the LDS (3D level 7, 2D levels 9-11; context options "cell_moments_windows" and
+    "cell_extrema_windows" = 1 around the passes, restored behind them); without it such a level is refused after the solve.
+    `extrema`: a second pass, over the fine elements (api.cell_extrema with Q = sigma_c; top levels up to 6 in 3D and 8 in 2D,
+    with `large_cells` 3D level 7 and 2D levels 9-11 too), adds "peak_energy_density" and
     "min_energy_density" (Ne each: the extrema of grad u . sigma_c grad u in every cell), "concentration" = peak / energy_form and,
     with `thresholds` (up to 8 multiples of energy_form), "exceedance" (Ne, nthr): the volume of every cell on which the energy
     density exceeds each; they are in the returned dict with or without `fields`, and with `save` in the file.  No counterpart
@@ -697,7 +702,8 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     peaks = {}
     if extrema:
         thr = np.zeros(0) if thresholds is None else np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
-        qmax, qmin, counts = api.cell_extrema(xv, implicit, xi, cell_fields.energy_form(cond), thr * out["energy_form"])
+        with _large_cells(ctx, large_cells):
+            qmax, qmin, counts = api.cell_extrema(xv, implicit, xi, cell_fields.energy_form(cond), thr * out["energy_form"])
         peaks = {"peak_energy_density": qmax, "min_energy_density": qmin,
                  "concentration": cell_fields.concentration(qmax, out["energy_form"])}
         if thr.size:

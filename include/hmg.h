@@ -363,9 +363,15 @@ int hmg_cell_pair_moments_count(const hmg_grid *grid);   /* dim (dim + 1) / 2; w
  * cell's column makes it so on every element that touches the node; so does inf - inf); other cells are not touched.  An
  * infinite q_T is a value like any other: it may be the maximum or the minimum.  The counts keep their meaning: q_T > threshold
  * is false for a NaN, so a NaN element is counted nowhere.  (The moment calls propagate a NaN through their sums.)
- * Served: 3D levels 1 to 6, 2D levels 1 to 8 (level 1: one element per cell, max = min).  Refused, with a message naming the call: 3D level 7 and 2D levels 9-11 (naming
- * the level; whatever "cell_moments_windows" says -- there is no window form), a grid without a device context, a null v or out,
- * a vector of another grid, nthr outside 0..8, nthr > 0 with null thresholds, thresholds or form entries that are not finite. */
+ * Served: 3D levels 1 to 6, 2D levels 1 to 8 (level 1: one element per cell, max = min).  Larger cells (3D level 7, 2D levels
+ * 9-11) are refused with a message naming the level, unless hmg_ctx_set_option "cell_extrema_windows" is 1: then such a level
+ * walks through a rolling window of the LDS (slabs of planes in 3D, bands of lattice rows in 2D; the same 8 B/DOF, the same
+ * mask, rows and results).  2 sends every level the window kernels address through them (3D levels 6 and 7, 2D levels 2 to 11):
+ * a test and A/B knob -- both kernels evaluate a node with one function, so the bits are those of the default path.  0 is the
+ * default; "cell_moments_windows" has no say here.  hmg_ctx_counter "cell_extrema_window_launches" counts the window launches,
+ * "cell_extrema_windows" reads the option back.
+ * Refused as well, with a message naming the call: a grid without a device context, a null v or out, a vector of another grid,
+ * nthr outside 0..8, nthr > 0 with null thresholds, thresholds or form entries that are not finite. */
 int hmg_cell_extrema(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
                      const double *form /* nq*ncells, or NULL */, int nthr, const double *thresholds /* nthr, or NULL */,
                      double *out /* host, (2 + nthr)*ncells */);

@@ -347,7 +347,7 @@ end
 # per-cell extrema over the fine elements (hmg_cell_extrema; api.cell_extrema): for q = ∇u ⋅ Q_c ∇u, u = ξ⋅x + v, on every fine
 # element of every coarse cell the maximum and the minimum (Ne each) and the number of elements above each threshold (nthr x Ne).
 # form: nq x Ne, the symmetric Q_c in the order 11, 12, 13, 22, 23, 33 (2D: 11, 12, 22); nothing: the identity.  3D levels up to 6,
-# 2D levels up to 8.
+# 2D levels up to 8; larger cells (3D level 7, 2D levels 9-11) once set_option!(ctx, "cell_extrema_windows", 1) was called.
 fine_elements(g::HipGrid, level::Integer) = Int(ccall((:hmg_grid_fine_elements, LIB), Int64, (Ptr{Cvoid}, Cint), g.h, level))
 function cell_extrema(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing,
                       form::Union{Nothing,AbstractMatrix{Float64}} = nothing, thresholds::AbstractVector{Float64} = Float64[])

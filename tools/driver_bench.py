@@ -22,7 +22,9 @@ kernel counters of its last single-vector and its last pair pass ("cell_moments_
 --extrema: driver.dirichlet_homogenization on hypercube(n) with extrema=True and thresholds at 1, 2 and 4 times the homogenized
 energy density (one solve, the moment pass, then the pass over the fine elements): one line with the wall time of a run after
 --warmup untimed ones, the largest concentration, the exceedance volume fractions and the kernel counters of the two passes
-("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D."""
+("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D; with --large-cells
+(the driver's keyword large_cells=True) 3D level 7 and 2D levels 9-11 too, through the window kernels of both passes: the line then
+carries "cell_moments_window_launches" and "cell_extrema_window_launches"."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,7 +45,7 @@ ap.add_argument("--tensor", action="store_true", help="one tensor run against d 
 ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
 ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
-ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor: moment passes of cells larger than the LDS")
+ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor or --extrema: per-cell passes of cells larger than the LDS")
 ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
@@ -64,7 +66,7 @@ if a.extrema:
         sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
     xi = np.ones(a.dim) / np.sqrt(a.dim)
     kw = dict(refinements=a.refinements, xi=xi, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate,
-              smoother=a.smoother, extrema=True, thresholds=[1.0, 2.0, 4.0], fields=True)
+              smoother=a.smoother, extrema=True, thresholds=[1.0, 2.0, 4.0], fields=True, large_cells=a.large_cells)
     for _ in range(a.warmup):
         driver.dirichlet_homogenization(a.n, tag, **kw)
     ctx.sync()
@@ -73,14 +75,16 @@ if a.extrema:
     ctx.sync()
     wall = time.perf_counter() - t0
     print(json.dumps({"config": f"dirichlet_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}, "
-                                "extrema=True)",
+                                f"extrema=True{', large_cells=True' if a.large_cells else ''})",
                       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
                       "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
                       "energy_form": r["energy_form"], "max_concentration": float(r["concentration"].max()),
                       "min_energy_density_over_mean": float(r["min_energy_density"].min() / r["energy_form"]),
                       "exceedance_fraction_at_1_2_4": (r["exceedance"].sum(axis=0) / r["volume"]).tolist(),
                       "cell_moments_kernel_ns": ctx.counter("cell_moments_kernel_ns"),
-                      "cell_extrema_kernel_ns": ctx.counter("cell_extrema_kernel_ns")}))
+                      "cell_extrema_kernel_ns": ctx.counter("cell_extrema_kernel_ns"), "large_cells": a.large_cells,
+                      "cell_moments_window_launches": ctx.counter("cell_moments_window_launches"),
+                      "cell_extrema_window_launches": ctx.counter("cell_extrema_window_launches")}))
     sys.exit(0)
 if a.dirichlet_tensor:
     if a.polycrystal:
