@@ -51,6 +51,8 @@ SIGNATURES = {
     "hmg_grid_set_operator_tensor": (c_int, [vp, p_f64, c_f64]),
     "hmg_grid_set_lambda": (c_int, [vp, c_f64]),
     "hmg_grid_shrink": (c_int, [vp, c_i64, c_i64]),
+    "hmg_grid_set_dirichlet_faces": (c_int, [vp, c_i64, p_i64]),
+    "hmg_grid_dirichlet_faces": (c_i64, [vp, p_i64, c_i64]),
     "hmg_grid_reserve_spare": (c_int, [vp, c_int]),
     "hmg_grid_set_smoother": (c_int, [vp, c_int]),
     "hmg_grid_smoother": (c_int, [vp]),

@@ -67,6 +67,21 @@ def pack_sigmas(sigmas, ncells, dim):
     return np.ascontiguousarray(s[:, iu[0], iu[1]]), True
 
 
+def cell_faces(base: Mesh):
+    """Every face of every cell of a base mesh (3D: triangles, 2D: edges) as an (Ne * (dim + 1), dim) array of 1-based node ids,
+    ascending within a face, cell by cell."""
+    el = np.sort(np.asarray(base.elements, dtype=np.int64), axis=1)
+    n = el.shape[1]
+    return np.concatenate([np.delete(el, l, axis=1)[:, None, :] for l in range(n)], axis=1).reshape(-1, n - 1)
+
+
+def boundary_faces(base: Mesh):
+    """The default constrained set of an ImplicitFineGrid: the faces that belong to one cell, (nfaces, dim), 1-based node ids,
+    ascending within a face, faces in lexicographic order (what `ImplicitFineGrid.dirichlet_faces()` answers on a fresh grid)."""
+    faces, count = np.unique(cell_faces(base), axis=0, return_counts=True)
+    return np.ascontiguousarray(faces[count == 1])
+
+
 class Context:
     """One GPU + one HIP stream. stream: a raw hipStream_t (int) such as
     torch.cuda.current_stream().cuda_stream, or None for a library-owned stream."""
@@ -155,8 +170,8 @@ class Context:
 
 
 class ImplicitFineGrid:
-    """ImplicitFineGrid(base, levels) + the ZeroDirichletConstraint of the base mesh boundary.
-    ctx=None builds host tables only (no compute)."""
+    """ImplicitFineGrid(base, levels) + the ZeroDirichletConstraint of the base mesh boundary (or of the faces given to
+    `set_dirichlet_faces`).  ctx=None builds host tables only (no compute)."""
 
     def __init__(self, ctx: Context | None, base: Mesh, levels: int):
         self._lib = L.load()
@@ -220,6 +235,31 @@ class ImplicitFineGrid:
 
     def shrink(self, ncells_prefix, nnodes_prefix):
         L.check(self._lib.hmg_grid_shrink(self.h, ncells_prefix, nnodes_prefix))
+
+    def set_dirichlet_faces(self, faces=None):
+        """The faces on which v = 0 holds (include/hmg.h: hmg_grid_set_dirichlet_faces): an (nfaces, dim) array of 1-based node
+        ids of the base mesh (3D: triangles, 2D: edges; any order within a face), None for the default -- the faces that belong to
+        one cell, `boundary_faces(base)` -- or an empty array for no constraint.  The constrained set is the closure of the faces.
+        The level-1 system is due again afterwards (`coarse_setup`; a solve forms it if it is missing) and a FlexibleCG needs a
+        new `start`.  Refused on a shrunk grid; `shrink` is refused while a set of the caller's is held."""
+        if faces is None:
+            L.check(self._lib.hmg_grid_set_dirichlet_faces(self.h, -1, None))
+            return
+        f = np.ascontiguousarray(faces, dtype=np.int64)
+        if f.size == 0:
+            f = f.reshape(0, self.base.dim)
+        if f.ndim != 2 or f.shape[1] != self.base.dim:
+            raise ValueError(f"faces must have shape (nfaces, {self.base.dim}), not {f.shape}")
+        L.check(self._lib.hmg_grid_set_dirichlet_faces(self.h, f.shape[0], f.ctypes.data_as(L.p_i64)))
+
+    def dirichlet_faces(self):
+        """The current set as an (nfaces, dim) array: 1-based ids, ascending within a face, faces in lexicographic order."""
+        n = int(self._lib.hmg_grid_dirichlet_faces(self.h, None, 0))
+        if n < 0:
+            raise L.HmgError(self._lib.hmg_last_error().decode())
+        out = np.zeros((n, self.base.dim), dtype=np.int64)
+        self._lib.hmg_grid_dirichlet_faces(self.h, out.ctypes.data_as(L.p_i64), out.size)
+        return out
 
     def reserve_spare(self, enable=True):
         """The sixth finest-level vector of the default V-cycle form (include/hmg.h: hmg_grid_reserve_spare): True reserves it now

@@ -66,6 +66,9 @@ void coarse_setup(hmg_grid *g)
 {
     need(g->has_op, "hmg_grid_set_operator must be called first");
     const MeshTables &M = g->part ? g->part->global : g->cur();
+    if (g->lambda == 0.0 && std::find(M.node_on_boundary.begin(), M.node_on_boundary.end(), (uint8_t)1) == M.node_on_boundary.end())
+        throw std::runtime_error("hmg_coarse_setup: no node is constrained (hmg_grid_set_dirichlet_faces with an empty set) and "
+                                 "lambda = 0: the level-1 matrix is singular");
     assemble_coarse_matrix(M, g->part ? g->sigma_global.data() : g->sigma.data(), g->sig_n, g->lambda, g->cm);
     DryUploads dry_scope(!g->ctx, &g->upload_hash);
     hipStream_t s = g->ctx ? g->ctx->stream : nullptr;

@@ -192,6 +192,17 @@ void build_mesh_tables(int dim, int64_t nnodes, const double *coords, int64_t nc
 void restrict_mesh_tables(const MeshTables &full, int64_t ncells_prefix, int64_t nnodes_prefix,
                           MeshTables &out);
 
+// The constrained set as a list of faces (3D: triangles, 2D: edges; hmg_grid_set_dirichlet_faces).  A list holds dim 0-based
+// node ids per face, ascending within a face, the faces once each in lexicographic order.
+// boundary_faces: the faces that belong to one cell, the set build_mesh_tables constrains.
+std::vector<int32_t> boundary_faces(const MeshTables &mesh);
+// A caller's list (1-based ids, any order) in that form.  Throws, naming the first offender, on an id out of range, a node named
+// twice in a face, or a face that no cell of the mesh has; duplicates are accepted once.  Nothing of the mesh changes.
+std::vector<int32_t> normalize_dirichlet_faces(const MeshTables &mesh, int64_t nfaces, const int64_t *faces_1based);
+// dmask and node_on_boundary from the closure of the set: a chosen face sets its face bit in every cell that contains it, each
+// of its edges / nodes the edge / node bit in every cell around it.  With boundary_faces(mesh) the tables of build_mesh_tables.
+void set_dirichlet_closure(MeshTables &mesh, const std::vector<int32_t> &faces);
+
 // Per-cell operator coefficients: coef[cell*8 + t] = |J| * P_t for the unique entries of
 // P = J^-1 sigma J^-T (3D: 11,12,13,22,23,33; 2D: 11,12,22), then |J| at t = nterm-1.
 // sigma holds `sn` numbers per cell: dim (the diagonal of a diagonal tensor; the reference's arithmetic, to the bit) or

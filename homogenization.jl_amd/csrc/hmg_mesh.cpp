@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <stdexcept>
+#include <string>
 #include <unordered_set>
 
 namespace hmg {
@@ -312,6 +313,127 @@ void restrict_mesh_tables(const MeshTables &full, int64_t ncells_prefix, int64_t
     for (int32_t v : M.cells)
         if (v >= nnodes_prefix) throw std::runtime_error("shrink: a kept cell references a dropped node");
     build_from_cells0(M);
+}
+
+// ---- the constrained set as a list of faces (hmg_grid_set_dirichlet_faces) ----
+namespace {
+
+using FaceKey = std::array<int32_t, 3>;   // ascending node ids; 2D: an edge, the third entry -1
+
+// every face (3D) / edge (2D) of the cells once, in lexicographic order, with the number of cells that contain it
+void list_cell_faces(const MeshTables &M, std::vector<FaceKey> &keys, std::vector<uint8_t> &copies)
+{
+    const int dim = M.dim, N = dim + 1, per = dim == 3 ? 4 : 3;
+    std::vector<FaceKey> all((size_t)M.ncells * per);
+    for (int64_t c = 0; c < M.ncells; ++c) {
+        const int32_t *el = &M.cells[c * N];
+        for (int l = 0; l < per; ++l)
+            all[(size_t)c * per + l] = dim == 3 ? FaceKey{el[TET_FACES[l][0]], el[TET_FACES[l][1]], el[TET_FACES[l][2]]}
+                                                : FaceKey{el[TRI_EDGES[l][0]], el[TRI_EDGES[l][1]], -1};
+    }
+    std::sort(all.begin(), all.end());
+    keys.clear();
+    copies.clear();
+    for (size_t i = 0; i < all.size();) {
+        size_t j = i + 1;
+        while (j < all.size() && all[j] == all[i]) ++j;
+        keys.push_back(all[i]);
+        copies.push_back((uint8_t)std::min<size_t>(j - i, 255));
+        i = j;
+    }
+}
+
+std::vector<int32_t> flatten_faces(int dim, const std::vector<FaceKey> &keys)
+{
+    std::vector<int32_t> out;
+    out.reserve(keys.size() * dim);
+    for (const FaceKey &k : keys) out.insert(out.end(), k.begin(), k.begin() + dim);
+    return out;
+}
+
+}  // namespace
+
+std::vector<int32_t> boundary_faces(const MeshTables &M)
+{
+    std::vector<FaceKey> keys, bnd;
+    std::vector<uint8_t> copies;
+    list_cell_faces(M, keys, copies);
+    for (size_t q = 0; q < keys.size(); ++q)
+        if (copies[q] == 1) bnd.push_back(keys[q]);
+    return flatten_faces(M.dim, bnd);
+}
+
+std::vector<int32_t> normalize_dirichlet_faces(const MeshTables &M, int64_t nfaces, const int64_t *faces_1based)
+{
+    const int dim = M.dim;
+    const char *what = dim == 3 ? "face " : "edge ";
+    std::vector<FaceKey> keys, set((size_t)nfaces);
+    std::vector<uint8_t> copies;
+    list_cell_faces(M, keys, copies);
+    for (int64_t f = 0; f < nfaces; ++f) {
+        FaceKey k{-1, -1, -1};
+        for (int q = 0; q < dim; ++q) {
+            const int64_t v = faces_1based[f * dim + q] - 1;
+            if (v < 0 || v >= M.nnodes)
+                throw std::runtime_error(std::string("Dirichlet faces: ") + what + std::to_string(f) + " has a node id out of range (ids are 1-based)");
+            k[q] = (int32_t)v;
+        }
+        std::sort(k.begin(), k.begin() + dim);
+        for (int q = 0; q + 1 < dim; ++q)
+            if (k[q] == k[q + 1])
+                throw std::runtime_error(std::string("Dirichlet faces: ") + what + std::to_string(f) + " names a node twice");
+        if (!std::binary_search(keys.begin(), keys.end(), k))
+            throw std::runtime_error(std::string("Dirichlet faces: ") + what + std::to_string(f) + " is not a " + (dim == 3 ? "face" : "edge") +
+                                     " of any cell of the grid");
+        set[(size_t)f] = k;
+    }
+    std::sort(set.begin(), set.end());
+    set.erase(std::unique(set.begin(), set.end()), set.end());   // (duplicates are accepted once)
+    return flatten_faces(dim, set);
+}
+
+void set_dirichlet_closure(MeshTables &M, const std::vector<int32_t> &faces)
+{
+    const int dim = M.dim, N = dim + 1;
+    const int nface = dim == 3 ? 4 : 0, nedge = dim == 3 ? 6 : 3;
+    const size_t nf = faces.size() / dim;
+    // the closure: the chosen faces (sorted already), their edges, their nodes
+    std::vector<FaceKey> fset;
+    std::vector<std::array<int32_t, 2>> eset;
+    std::vector<uint8_t> node(M.nnodes, 0);
+    for (size_t f = 0; f < nf; ++f) {
+        const int32_t *k = &faces[f * dim];
+        for (int q = 0; q < dim; ++q) node[k[q]] = 1;
+        if (dim == 3) {
+            fset.push_back({k[0], k[1], k[2]});
+            eset.push_back({k[0], k[1]});
+            eset.push_back({k[0], k[2]});
+            eset.push_back({k[1], k[2]});
+        } else
+            eset.push_back({k[0], k[1]});
+    }
+    std::sort(eset.begin(), eset.end());
+    eset.erase(std::unique(eset.begin(), eset.end()), eset.end());
+    // every cell finds its own entities in it: a face bit in the one or two cells that contain the face, an edge / node bit in
+    // every cell around the edge / node
+    M.dmask.assign(M.ncells, 0);
+    parallel_for(M.ncells, [&](int64_t c0, int64_t c1) {
+        for (int64_t c = c0; c < c1; ++c) {
+            const int32_t *el = &M.cells[c * N];
+            uint16_t m = 0;
+            for (int l = 0; l < nface; ++l)
+                if (std::binary_search(fset.begin(), fset.end(), FaceKey{el[TET_FACES[l][0]], el[TET_FACES[l][1]], el[TET_FACES[l][2]]}))
+                    m |= (uint16_t)(1u << l);
+            for (int l = 0; l < nedge; ++l) {
+                const int *t = dim == 3 ? TET_EDGES[l] : TRI_EDGES[l];
+                if (std::binary_search(eset.begin(), eset.end(), std::array<int32_t, 2>{el[t[0]], el[t[1]]})) m |= (uint16_t)(1u << (nface + l));
+            }
+            for (int l = 0; l < N; ++l)
+                if (node[el[l]]) m |= (uint16_t)(1u << (nface + nedge + l));
+            M.dmask[c] = m;
+        }
+    });
+    M.node_on_boundary.assign(node.begin(), node.end());
 }
 
 namespace {

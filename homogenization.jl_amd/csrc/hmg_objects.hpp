@@ -300,6 +300,8 @@ struct hmg_grid {
     std::vector<LevelDev> ld;
     MeshTables mesh_full, mesh;
     bool shrunk = false;
+    bool dir_custom = false;                     // mesh_full's masks are the closure of a caller's faces (hmg_grid_set_dirichlet_faces) ...
+    std::vector<int32_t> dir_faces;              // ... these (the form of boundary_faces()); empty with the default set
     MeshDev md{};
     DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
     DevBuf<uint16_t> d_dmask, d_dupmask;

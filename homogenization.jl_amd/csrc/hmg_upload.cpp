@@ -512,6 +512,8 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    need(!g->dir_custom, "hmg_grid_shrink: the grid holds a caller's Dirichlet faces (hmg_grid_set_dirichlet_faces); restore the "
+                         "default set first (nfaces = -1)");
     if (g->ctx) materialize_r(g);                // (a pending r-update belongs to the cells and face partners of the grid as it is)
     g->op_epoch += 1;
     g->dinv_ready = false;
@@ -541,6 +543,66 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
     upload_mesh(g);
     if (g->has_op) upload_operator(g);
     HMG_END
+}
+
+// The constrained set: the closure of the faces the caller names instead of the faces that belong to one cell.  No kernel knows
+// that a constrained face lies on the outside -- the constraint is the per-cell entity bitmask every apply family fuses into its
+// epilogue --, so the call forms the masks on the host and writes them into the device buffer the kernels already read (MeshDev
+// travels by value: the pointer stays).  Towards everything cached it is a new operator: a pending r-update is formed first
+// (with the masks it was recorded under), hmg_fcg objects need a new start, the Jacobi smoother's diagonal and the level-1
+// system are formed again; the class-weight cache does not depend on the masks and is kept.
+int hmg_grid_set_dirichlet_faces(hmg_grid *g, int64_t nfaces, const int64_t *faces)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(!g->part, "hmg_grid_set_dirichlet_faces: a partitioned grid keeps the default set (the faces that belong to one cell of the "
+                   "whole mesh)");
+    need(!g->shrunk, "hmg_grid_set_dirichlet_faces: the grid has been shrunk; a shrunk grid keeps the default set of its prefix");
+    need(nfaces >= -1, "hmg_grid_set_dirichlet_faces: nfaces must be -1 (the default set), 0 (no constraint) or the number of faces");
+    need(nfaces <= 0 || faces != nullptr, "hmg_grid_set_dirichlet_faces: null face list");
+    MeshTables &M = g->mesh_full;
+    // (everything is checked before anything changes)
+    const std::vector<int32_t> dflt = boundary_faces(M);
+    std::vector<int32_t> set = nfaces < 0 ? dflt : normalize_dirichlet_faces(M, nfaces, faces);
+    if (g->ctx) {
+        HIPCHK(hipSetDevice(g->ctx->device));
+        materialize_r(g);
+    }
+    set_dirichlet_closure(M, set);
+    g->dir_custom = set != dflt;                 // (the default set named face by face is the default set)
+    if (g->dir_custom)
+        g->dir_faces.swap(set);
+    else
+        g->dir_faces.clear();
+    std::vector<uint16_t> dm = M.dmask;          // (padded as build_mesh_kernel_tables pads it)
+    if (dm.size() & 1) dm.push_back((uint16_t)0);
+    if (g->ctx) {
+        need(g->d_dmask.p != nullptr && g->d_dmask.n == dm.size(), "hmg_grid_set_dirichlet_faces: the grid has no mask buffer of this size");
+        HIPCHK(hipMemcpyAsync(g->d_dmask.p, dm.data(), dm.size() * sizeof(uint16_t), hipMemcpyHostToDevice, g->ctx->stream));
+        HIPCHK(hipStreamSynchronize(g->ctx->stream));
+    } else {
+        DryUploads dry_scope(true, &g->upload_hash);
+        DryUploads::note(dm.data(), dm.size() * sizeof(uint16_t));
+    }
+    g->op_epoch += 1;
+    g->dinv_ready = false;
+    g->coarse_ready = false;
+    HMG_END
+}
+
+int64_t hmg_grid_dirichlet_faces(const hmg_grid *g, int64_t *out, int64_t cap)
+{
+    if (!g) return -1;
+    try {
+        const std::vector<int32_t> dflt = g->dir_custom ? std::vector<int32_t>() : boundary_faces(g->part ? g->part->global : g->cur());
+        const std::vector<int32_t> &set = g->dir_custom ? g->dir_faces : dflt;
+        if (out)
+            for (size_t q = 0; q < set.size() && (int64_t)q < cap; ++q) out[q] = (int64_t)set[q] + 1;
+        return (int64_t)(set.size() / (size_t)g->dim);
+    } catch (const std::exception &e) {
+        last_error() = e.what();
+        return -1;
+    }
 }
 
 int64_t hmg_grid_ncells(const hmg_grid *g) { return g ? g->md.ncells : -1; }

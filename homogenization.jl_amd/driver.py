@@ -747,6 +747,16 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
     `save` (a file name) writes the coarse mesh with the cell fields of every pair k <= l, "pair_kl" and "energy_kl" = sigma_c :
     S_{u_k u_l}(c) (vtk.export_cell_fields).  Memory beyond `dirichlet_homogenization`: d finest-level vectors.  No counterpart
     in the reference."""
+    return _tensor_run("dirichlet_homogenization_tensor", None, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance,
+                       smoother, accelerate, fields, save, cond, smoothing_steps, max_cycles, large_cells)
+
+
+def _tensor_run(who, faces, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance, smoother, accelerate, fields, save,
+                cond, smoothing_steps, max_cycles, large_cells):
+    """The d corrector solves and moment passes behind `dirichlet_homogenization_tensor` and the drivers that differ from it in
+    the constrained set only.  faces: None -- the grid's default set, no call --, a function base -> one face array, set once
+    before the solves, or base -> a list of d of them, set in front of solve k.  A set of the caller's is taken back behind the
+    solves, also when one raises."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -758,10 +768,15 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
         cond = conductivity_per_element(base, sigma_grid, (0.0,) * dim)
     else:
         cond = np.ascontiguousarray(cond, dtype=np.float64)
+    face_sets = None if faces is None else faces(base)
     total_grids = refinements + 1
     implicit = api.ImplicitFineGrid(ctx, base, total_grids)
     implicit.set_smoother(smoother)
     op = api.L2PlusDivAGrad(implicit, 0.0, cond)
+    if isinstance(face_sets, np.ndarray):
+        implicit.set_dirichlet_faces(face_sets)
+    elif face_sets is not None:
+        implicit.set_dirichlet_faces(face_sets[0])       # (the level-1 system below is direction 0's)
     base_level = api.BaseLevel(implicit)
     states = [api.LevelState(implicit, i + 1) for i in range(total_grids)]
     top = states[-1]
@@ -773,14 +788,21 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
     means = np.zeros((dim, ne, dim))
     cycles, residual = [], []
     eye = np.eye(dim)
-    for k in range(dim):
-        cyc, rnorm, r0 = _dirichlet_solve(implicit, op, base_level, states, xv, fcg, eye[k], smoothing_steps, tolerance,
-                                          max_cycles, f"dirichlet_homogenization_tensor, direction {k}")
-        cycles.append(cyc)
-        residual.append(float(rnorm / r0) if r0 > 0.0 else 0.0)
-        V[k].copyto(xv)
-        with _large_cells(ctx, large_cells):
-            means[k], pairs[k, k] = api.cell_moments(V[k], implicit, eye[k])
+    try:
+        for k in range(dim):
+            if k > 0 and face_sets is not None and not isinstance(face_sets, np.ndarray):
+                implicit.set_dirichlet_faces(face_sets[k])
+                implicit.coarse_setup()
+            cyc, rnorm, r0 = _dirichlet_solve(implicit, op, base_level, states, xv, fcg, eye[k], smoothing_steps, tolerance,
+                                              max_cycles, f"{who}, direction {k}")
+            cycles.append(cyc)
+            residual.append(float(rnorm / r0) if r0 > 0.0 else 0.0)
+            V[k].copyto(xv)
+            with _large_cells(ctx, large_cells):
+                means[k], pairs[k, k] = api.cell_moments(V[k], implicit, eye[k])
+    finally:
+        if face_sets is not None:
+            implicit.set_dirichlet_faces(None)
     with _large_cells(ctx, large_cells):
         for k in range(dim):
             for l in range(k + 1, dim):
@@ -812,4 +834,87 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
     implicit.close()
     if own_ctx:
         ctx.close()
+    return out
+
+
+def faces_on_plane(base: Mesh, axis: int, value: float):
+    """The faces of a base mesh (3D: triangles, 2D: edges) all of whose nodes have coordinate `axis` equal to `value` (to 1e-9 of
+    the mesh's extent): an (nfaces, dim) array of 1-based node ids for `ImplicitFineGrid.set_dirichlet_faces`."""
+    x = np.asarray(base.nodes, dtype=np.float64)[:, axis]
+    on = np.abs(x - value) <= 1e-9 * max(1.0, float(np.ptp(x)))
+    faces = np.unique(api.cell_faces(base), axis=0)
+    return np.ascontiguousarray(faces[on[faces - 1].all(axis=1)])
+
+
+def block_faces(base: Mesh, block: int):
+    """The faces on the planes x_a = origin_a + j * block, j integer, a = 1 .. dim, of a base mesh of unit cubes whose lowest
+    corner is `origin`: the boundaries of its block^dim blocks, the outer boundary included.  (nfaces, dim), 1-based ids."""
+    nodes = np.asarray(base.nodes, dtype=np.float64)
+    rel = nodes - nodes.min(axis=0)
+    on = np.abs(rel / block - np.rint(rel / block)) <= 1e-9              # (Nn, dim): the node lies on a plane of axis a
+    faces = np.unique(api.cell_faces(base), axis=0)
+    rf = rel[faces - 1]                                                   # (nfaces, dim nodes, dim axes)
+    flat = np.abs(rf - rf[:, :1, :]).max(axis=1) <= 1e-9                  # the face is normal to axis a ...
+    return np.ascontiguousarray(faces[(flat & on[faces - 1].all(axis=1)).any(axis=1)])    # ... and that plane is a block boundary
+
+
+def uniaxial_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None, seed: int = 0,
+                                   values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
+                                   fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
+                                   large_cells: bool = False):
+    """The homogenized tensor of the mixed ("uniaxial") cell problems on `hypercube(eltype, n)`: for k = 1 .. d the potential
+    u_k = e_k.x + v_k is fixed on the two faces of the cube normal to e_k (v_k = 0 there) and the other faces are insulated --
+    the natural condition, which `rhs_axi_grad_v` yields wherever the constraint is absent.  One grid and one operator; in front
+    of solve k the two faces become the grid's Dirichlet set (`ImplicitFineGrid.set_dirichlet_faces`, `faces_on_plane`), the
+    default set is restored behind the solves.  Row k of "tensor_flux" is the mean flux of u_k, "tensor" the energy form
+    sum_c sigma_c : S_{u_k u_l}(c) / |Omega| (its diagonal is the effective conductivity a two-electrode measurement along e_k
+    sees; exact for a laminate: the harmonic mean across the layers, the arithmetic mean along them).  The space of v_k contains
+    the one of `dirichlet_homogenization_tensor`, so the diagonal is at most that driver's.  Keywords and the returned dict are
+    `dirichlet_homogenization_tensor`'s.  No counterpart in the reference."""
+    def sides(base):
+        x = np.asarray(base.nodes, dtype=np.float64)
+        return [np.concatenate([faces_on_plane(base, k, x[:, k].min()), faces_on_plane(base, k, x[:, k].max())])
+                for k in range(base.dim)]
+    return _tensor_run("uniaxial_homogenization_tensor", sides, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance,
+                       smoother, accelerate, fields, save, cond, smoothing_steps, max_cycles, large_cells)
+
+
+def block_homogenization_tensor(n: int, block: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None,
+                                seed: int = 0, values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg",
+                                accelerate: bool = False, fields: bool = False, save=None, cond=None, smoothing_steps: int = 3,
+                                max_cycles: int = 200, large_cells: bool = False):
+    """Block upscaling in one run: the plain Dirichlet cell problem of `dirichlet_homogenization_tensor` on every block^dim block
+    of `hypercube(eltype, n)` at once.  With v = 0 on the block boundaries (`block_faces`, set once) the blocks are independent
+    cell problems inside one grid: one table build, d solves, and the per-cell moments summed per block give
+    "tensor", shape (n / block,) * dim + (dim, dim) -- block [i, j(, k)] is the cube's i-th block along the first axis, as
+    `sigma_grid` is indexed --, exactly symmetric and directly usable as the `sigma_grid` of a run at the next scale, and
+    "tensor_flux" of the same shape (row k: the flux form of corrector k).  Block b's tensor is what
+    `dirichlet_homogenization_tensor` gives on that block's cells as a mesh of their own, to the accuracy of the solves (the
+    residual that stops them is the whole grid's).  "cycles", "residual" and "volume" (of one block) as there; `fields` adds that
+    driver's fields of the whole grid and "block_of_cell" (Ne, dim).  No counterpart in the reference."""
+    dim = api._dim_of(eltype)
+    if block < 1 or n % block:
+        raise ValueError(f"block must divide n = {n}")
+    run = _tensor_run("block_homogenization_tensor", lambda base: block_faces(base, block), n, eltype, refinements, ctx,
+                      sigma_grid, seed, values, tolerance, smoother, accelerate, True, save, cond, smoothing_steps, max_cycles,
+                      large_cells)
+    base, cond, vol, pairs, means = run["base"], run["cond"], run["volumes"], run["pairs"], run["means"]
+    nb = n // block
+    centers = _centers(base)
+    bidx = np.floor((centers - np.asarray(base.nodes).min(axis=0)) / block).astype(np.int64)
+    flat = np.ravel_multi_index(tuple(bidx[:, a] for a in range(dim)), (nb,) * dim)
+    omega = float(block) ** dim
+    tensor = np.zeros((nb ** dim, dim, dim))
+    tflux = np.zeros((nb ** dim, dim, dim))
+    for k in range(dim):
+        flux = cell_fields.mean_flux(cond, means[k]) * vol[:, None]
+        for a in range(dim):
+            tflux[:, k, a] = np.bincount(flat, weights=flux[:, a], minlength=nb ** dim) / omega
+        for l in range(k, dim):
+            e = np.bincount(flat, weights=cell_fields.pair_energy(cond, pairs[k, l]), minlength=nb ** dim) / omega
+            tensor[:, k, l] = tensor[:, l, k] = e
+    out = {"tensor": tensor.reshape((nb,) * dim + (dim, dim)), "tensor_flux": tflux.reshape((nb,) * dim + (dim, dim)),
+           "cycles": run["cycles"], "residual": run["residual"], "volume": omega}
+    if fields:
+        out.update(pairs=pairs, means=means, volumes=vol, cond=cond, base=base, block_of_cell=bidx)
     return out

@@ -190,6 +190,24 @@ int hmg_grid_set_lambda(hmg_grid *grid, double lambda);
  * the prefix lengths are GLOBAL; every rank keeps its cells below the prefix (a prefix of its own columns) and the
  * cut entities, masks and ownership are re-derived. */
 int hmg_grid_shrink(hmg_grid *grid, int64_t ncells_prefix, int64_t nnodes_prefix);
+/* The faces on which the constraint holds (no counterpart in the reference, whose constraint is the boundary of the base mesh).
+ * faces: dim node ids per face (3D: triangles, 2D: edges), 1-based ids of the base mesh, any order within a face.
+ * nfaces = -1 (faces NULL): back to the default, the faces that belong to one cell.  nfaces = 0: no constraint at all.
+ * The constrained set is the closure of the chosen faces: a chosen face sets its face bit in the mask of every cell that
+ * contains it (one or two), each of its edges the edge bit in every cell around that edge, each of its nodes the node bit in every
+ * cell around that node.  The closure alone decides: a face whose nodes are all constrained but which was not chosen stays free.
+ * Tables "dmask" and "interior_nodes" and the level-1 system follow the set.  Everything is checked before anything changes: an
+ * id out of range, a node twice in a face, a face that no cell has are refused, naming the first offender; duplicates are
+ * accepted once.  No kernel changes and no memory is allocated: the new masks go into the buffer the kernels already read.
+ * Towards what is cached the call is a new operator (hmg_grid_set_operator): a pending r-update is formed first, hmg_fcg_step
+ * asks for hmg_fcg_start, the Jacobi smoother's diagonal goes stale, hmg_coarse_setup is due again; the class-weight cache is
+ * kept.  A grid without a device context takes the call.  Refused: a partitioned grid, a grid that has been shrunk; and, while a
+ * caller's set is held, hmg_grid_shrink (restore the default first) and, with an empty set and lambda = 0, hmg_coarse_setup (the
+ * level-1 matrix is singular).  The default set named face by face is the default set, bit for bit. */
+int hmg_grid_set_dirichlet_faces(hmg_grid *grid, int64_t nfaces, const int64_t *faces);
+/* the current set (sorted ids within a face, faces in lexicographic order), at most cap ids into out (which may be NULL);
+ * returns the number of faces, -1 for a null grid */
+int64_t hmg_grid_dirichlet_faces(const hmg_grid *grid, int64_t *out, int64_t cap);
 /* The reference's LevelState holds five vectors per level (src/multigrid.jl:18-25).  With option "lazy_top" = 2 (the default) the
  * finest level's post-smoother inside hmg_vcycle uses a SIXTH vector of that level's size (+20 % on the finest level's footprint)
  * to save 8 B/DOF of traffic per V-cycle.  It belongs to the grid and is setup, not hot-path, memory: reserved automatically when

@@ -133,6 +133,27 @@ bind!(g::HipGrid, ops::AbstractVector, k::Int) = bind!(g, ops[k])
 shrink!(g::HipGrid, ncells_prefix::Integer, nnodes_prefix::Integer) =
     check(ccall((:hmg_grid_shrink, LIB), Cint, (Ptr{Cvoid}, Int64, Int64), g.h, ncells_prefix, nnodes_prefix))
 
+# The faces on which the constraint holds (include/hmg.h: hmg_grid_set_dirichlet_faces; no counterpart in the reference, whose
+# ZeroDirichletConstraint is the boundary of the base mesh).  faces: dim x nfaces, 1-based node ids of the base mesh (3D: triangles,
+# 2D: edges); nothing: back to the faces that belong to one cell; a matrix without columns: no constraint.  The constrained set is
+# the closure of the faces.  The level-1 system is due again afterwards (HipBaseLevel).
+function set_dirichlet_faces!(g::HipGrid, faces::Union{Nothing,AbstractMatrix{<:Integer}})
+    if faces === nothing
+        check(ccall((:hmg_grid_set_dirichlet_faces, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}), g.h, -1, C_NULL))
+    else
+        f = Matrix{Int64}(faces)
+        check(ccall((:hmg_grid_set_dirichlet_faces, LIB), Cint, (Ptr{Cvoid}, Int64, Ptr{Int64}), g.h, size(f, 2), f))
+    end
+    g
+end
+# the current set, dim x nfaces (sorted ids within a face, faces in lexicographic order)
+function dirichlet_faces(g::HipGrid, dim::Integer)
+    n = ccall((:hmg_grid_dirichlet_faces, LIB), Int64, (Ptr{Cvoid}, Ptr{Int64}, Int64), g.h, C_NULL, 0)
+    f = Matrix{Int64}(undef, dim, max(n, 0))
+    ccall((:hmg_grid_dirichlet_faces, LIB), Int64, (Ptr{Cvoid}, Ptr{Int64}, Int64), g.h, f, length(f))
+    f
+end
+
 # The sixth finest-level vector of the library's default V-cycle form (include/hmg.h: hmg_grid_reserve_spare).  true: reserve it now
 # (an error if the device memory is not there); false: release it and keep the reference's five-vector footprint.  Without a call
 # it is reserved when the first HipMatrix of the finest level is created.

@@ -24,7 +24,12 @@ energy density (one solve, the moment pass, then the pass over the fine elements
 --warmup untimed ones, the largest concentration, the exceedance volume fractions and the kernel counters of the two passes
 ("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D; with --large-cells
 (the driver's keyword large_cells=True) 3D level 7 and 2D levels 9-11 too, through the window kernels of both passes: the line then
-carries "cell_moments_window_launches" and "cell_extrema_window_launches"."""
+carries "cell_moments_window_launches" and "cell_extrema_window_launches".
+--uniaxial: driver.uniaxial_homogenization_tensor on hypercube(n) (d solves on one grid, the two faces normal to e_k as the grid's
+Dirichlet set in front of solve k): one line with the wall time of a run after --warmup untimed ones, the cycles and the tensor.
+--blocks B: driver.block_homogenization_tensor(n, B) (the Dirichlet cell problems of all (n / B)^d blocks in d solves on one grid)
+against the same number of dirichlet_homogenization_tensor(B) runs on the blocks' own meshes, in one process: the two wall times
+after --warmup untimed rounds of both, their ratio and the largest relative difference of a block's tensor."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -47,6 +52,9 @@ ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficie
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
 ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor or --extrema: per-cell passes of cells larger than the LDS")
 ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
+ap.add_argument("--uniaxial", action="store_true", help="the uniaxial tensor driver on hypercube(n): wall time, cycles, tensor")
+ap.add_argument("--blocks", type=int, default=0, metavar="B", help="block upscaling of hypercube(n) in blocks of B cubes per axis "
+                "against one Dirichlet tensor run per block")
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
 a = ap.parse_args()
@@ -85,6 +93,40 @@ if a.extrema:
                       "cell_extrema_kernel_ns": ctx.counter("cell_extrema_kernel_ns"), "large_cells": a.large_cells,
                       "cell_moments_window_launches": ctx.counter("cell_moments_window_launches"),
                       "cell_extrema_window_launches": ctx.counter("cell_extrema_window_launches")}))
+    sys.exit(0)
+if a.uniaxial or a.blocks:
+    if a.polycrystal:
+        principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
+        sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
+    else:
+        sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
+    kw = dict(refinements=a.refinements, tolerance=a.tolerance, ctx=ctx, accelerate=a.accelerate, smoother=a.smoother)
+    common = {"accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal, "warmup": a.warmup}
+
+    def timed(run):
+        for _ in range(a.warmup):
+            run()
+        ctx.sync()
+        t0 = time.perf_counter()
+        r = run()
+        ctx.sync()
+        return r, time.perf_counter() - t0
+
+    if a.uniaxial:
+        r, wall = timed(lambda: driver.uniaxial_homogenization_tensor(a.n, tag, sigma_grid=sgrid, **kw))
+        print(json.dumps({"config": f"uniaxial_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
+                          **common, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"], "tensor": r["tensor"].tolist(),
+                          "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
+        sys.exit(0)
+    nb = a.n // a.blocks
+    subs = {idx: np.ascontiguousarray(sgrid[tuple(slice(a.blocks * i, a.blocks * (i + 1)) for i in idx)]) for idx in np.ndindex(*(nb,) * a.dim)}
+    r, wall = timed(lambda: driver.block_homogenization_tensor(a.n, a.blocks, tag, sigma_grid=sgrid, **kw))
+    alone, wall_alone = timed(lambda: {idx: driver.dirichlet_homogenization_tensor(a.blocks, tag, sigma_grid=s, **kw)["tensor"]
+                                       for idx, s in subs.items()})
+    diff = max(float(np.abs(r["tensor"][idx] - t).max() / np.abs(t).max()) for idx, t in alone.items())
+    print(json.dumps({"config": f"block_homogenization_tensor({a.n}, {a.blocks}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
+                      **common, "blocks": nb ** a.dim, "wall_s": wall, "wall_s_one_run_per_block": wall_alone, "ratio": wall_alone / wall,
+                      "cycles": r["cycles"], "residual": r["residual"], "max_rel_diff_of_a_block_tensor": diff}))
     sys.exit(0)
 if a.dirichlet_tensor:
     if a.polycrystal:
