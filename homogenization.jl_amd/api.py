@@ -151,7 +151,9 @@ class Context:
         return n.value, ms.value, by.value
 
     def counter(self, name: str) -> int:
-        """Diagnostic counters of the library ("wave_launches": launches of the one-wave-per-cell level-5 apply)."""
+        """Diagnostic counters of the library by name, as include/hmg.h lists them at hmg_ctx_counter ("wave_launches": launches of
+        the one-wave-per-cell level-5 apply; "lazy_r_form" / "lazy_ap_form": what the last V-cycle left pending; "ap_rebuilt": pending
+        r-updates that had to form their Ap again first; ...).  -1 for an unknown name."""
         return int(self._lib.hmg_ctx_counter(self.h, name.encode()))
 
     def apply_timing(self):

@@ -1298,7 +1298,7 @@ void launch_apply_args(const Launch &L, const LevelDev &lv, const MeshDev &mesh,
 
 void launch_apply_fused_kernel(const Launch &L, const LevelDev &lv, const MeshDev &mesh, ApplyArgs a)
 {
-    a.scal = L.scal;
+    if (!a.scal) a.scal = L.scal;                // (a caller's own scalars: the rebuilt Ap of a pending r-update, materialize_r())
     if (!(a.flags & 32)) a.mult = mesh.mult;     // (bit 5: caller wants unit multiplicities -- a.mult stays null)
     a.blockpart = mesh.blockpart;
     if (a.flags & 8) {                            // the driver integrals: src multiplies (own instantiations)

@@ -139,6 +139,9 @@ void grid_unref(hmg_grid *grid)
         (void)hipStreamSynchronize(c->stream);
     }
     probe_unlist(grid);
+    if (c) {   // (a record goes with its r, which holds the grid: none is open here; nothing is launched either way)
+        c->pend_grids.erase(std::remove(c->pend_grids.begin(), c->pend_grids.end(), grid), c->pend_grids.end());
+    }
     release_top_spare(grid);
     release_weight_cache(grid);
     release_smoother_diag(grid);
@@ -271,6 +274,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "r_materialized") return ctx->r_materialized;    // pending r-updates launched by a later call
     if (n == "r_materialized_by_read") return ctx->r_materialized_read;   // ... of them: by a call that was handed r or Ap
     if (n == "r_dropped") return ctx->r_dropped;              // ... and those that never had to be
+    if (n == "lazy_ap_form") return ctx->last_ap_form;        // the last hmg_vcycle / hmg_fcg_step: 1 its record was left without a stored Ap (option lazy_ap)
+    if (n == "ap_rebuilt") return ctx->ap_rebuilt;            // pending r-updates that had to run the last CG step's apply again first
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;
     if (n == "cell_moments_kernel_ns") return ctx->moments_kernel_ns;       // the last hmg_cell_moments: kernel alone
     if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
@@ -298,12 +303,19 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
     HMG_TRY
     need(ctx && name, "null argument");
     std::string n(name);
+    // a pending r-update that has its Ap still to rebuild rests on the kernel choice: formed under the options it was recorded with
+    // (a copy: the list shrinks as the records close; a setter is not a reader; records that hold their Ap stay as they are)
+    {
+        LifetimeLock lock(lifetime_mutex());
+        const std::vector<hmg_grid *> open = ctx->pend_grids;
+        for (hmg_grid *g : open) settle_rebuild(g);
+    }
     // the on / off options of the V-cycle's forms (what each one does: the members of hmg_ctx)
     static const std::pair<const char *, bool hmg_ctx::*> flags[] = {
         {"coarse_probe", &hmg_ctx::coarse_probe}, {"fuse_cg", &hmg_ctx::fuse_cg_default}, {"fold_x", &hmg_ctx::fold_x},
         {"swap_rp", &hmg_ctx::swap_rp}, {"fold_prolong", &hmg_ctx::fold_prolong}, {"zero_entry", &hmg_ctx::zero_entry},
         {"fold_restrict", &hmg_ctx::fold_restrict}, {"lazy_dead", &hmg_ctx::lazy_dead}, {"lazy_pre", &hmg_ctx::lazy_pre}, {"fold_coarse_x", &hmg_ctx::fold_coarse_x}, {"fold_faces", &hmg_ctx::fold_faces},
-        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"lazy_r", &hmg_ctx::lazy_r}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
+        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"lazy_r", &hmg_ctx::lazy_r}, {"lazy_ap", &hmg_ctx::lazy_ap}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
         {"comm_rehearsal", &hmg_ctx::comm_rehearsal}};
     for (const auto &f : flags)
         if (n == f.first) {

@@ -225,7 +225,8 @@ bool apply_folds_coarse_x(const Launch &L, const LevelDev &lv);
 bool apply_defers3(const Launch &L, const LevelDev &lv);
 // Fused CG pass, see k_apply<.., FUSED>: the kernel (possibly over a cell list, several launches) leaves
 // per-cell partial sums in mesh.blockpart; the reduce step turns them into scal[slot_pap] = sum mult*xin*out and
-// scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.scal / a.mult / a.blockpart are filled in here.
+// scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.mult / a.blockpart are filled in here, and a.scal where the caller left
+// it null (the bank; a caller's own a.scal is where the kernel reads its s_num / s_den ... from, the sums go to the bank either way).
 void launch_apply_fused_kernel(const Launch &L, const LevelDev &lv, const MeshDev &mesh, ApplyArgs a);
 void launch_apply_fused_reduce(const Launch &L, const MeshDev &mesh, int slot_pap, int slot_rr);
 // scal[slot] = partials[0] + ... + partials[n - 1], one block in a fixed order (k_finalize, hmg_kernels.hip); the caller checks the launch
@@ -286,7 +287,8 @@ void launch_cg_rupdate_faces(const Launch &L, const LevelDev &lv, const MeshDev 
 void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
                                const double *q, int64_t n, int s_num, int s_den, int s_out, double *x, const double *p, int a_num,
                                int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den);
-// ... its x-updates alone (the r half stays pending); alpha_out[0] = scal[s_num]/scal[s_den], alpha_out[1] = 1.0
+// ... its x-updates alone (the r half stays pending); alpha_out[0] = scal[s_num]/scal[s_den], alpha_out[1] = 1.0,
+// alpha_out[2] = scal[b_num], alpha_out[3] = scal[b_den] (four doubles)
 void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
                       int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out);
 // x += (scal[a_num]/scal[a_den]) p; with_p: p = r + (scal[s_num]/scal[s_den]) p

@@ -644,7 +644,8 @@ k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, 
 // The x half of k_cg_rupdate_faces<XU> alone (XU = 1, 2), for a caller that leaves the r half pending (hmg_vcycle, option lazy_r):
 // reads x, p (, p0) and r, writes x -- no q, no partner gather, no r store, no reduction.  The step length it formed goes to
 // alpha_out[0] with a 1.0 behind it: k_cg_rupdate_faces<0> run later with alpha_out as its scalars (slots 0 / 1) forms the same
-// alpha, whatever the scalar bank holds by then.
+// alpha, whatever the scalar bank holds by then.  alpha_out[2] / alpha_out[3]: numerator and denominator of this step's beta, for a
+// caller that did not store Ap either (option lazy_ap) and runs the step's apply again with alpha_out as its scalars.
 template <int XU>
 __global__ void __launch_bounds__(SB)
 k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ p0, const double *__restrict__ r, int64_t n,
@@ -673,6 +674,8 @@ k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ 
         if (n & 1) x[n - 1] = xupd2(ax, beta, alpha, XU == 2 ? axpy1(az, p0[n - 1], x[n - 1]) : x[n - 1], p[n - 1], r[n - 1]);
         alpha_out[0] = alpha;
         alpha_out[1] = 1.0;
+        alpha_out[2] = scal[xs.b_num];           // beta as the apply of this step read it: the same division forms it again
+        alpha_out[3] = scal[xs.b_den];
     }
 }
 
@@ -871,7 +874,7 @@ void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDe
     reduce_finish(L, nb, s_out);
 }
 
-// the x-updates of launch_cg_rupdate_faces_x alone; alpha_out[0..2) = s_num/s_den, 1.0
+// the x-updates of launch_cg_rupdate_faces_x alone; alpha_out[0..4) = s_num/s_den, 1.0, scal[b_num], scal[b_den]
 void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
                       int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out)
 {

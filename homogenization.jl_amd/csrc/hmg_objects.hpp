@@ -208,6 +208,7 @@ struct hmg_ctx {
     bool lazy_post = true;      // ... and below the finest level its dead last step writes nothing: both x-updates in one pass
     bool fold_coarse_x = true;  // ... and the level below the finest leaves them to the finest level's first residual, which reads that x anyway (see coarse_x_folds())
     bool lazy_r = true;         // hmg_vcycle / hmg_fcg_step: the finest level's last r-update only finishes x; r_3 is formed when somebody reads it (PendingR)
+    bool lazy_ap = true;        // ... and the CG step in front of it does not store A p_2 (three-update form): the record rebuilds it when r is read (PendingR::ap_stored)
     int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
     bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
     bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
@@ -258,6 +259,8 @@ struct hmg_ctx {
     int64_t r_materialized = 0;              // pending residuals formed by a later call (the eager r-update, launched late) ...
     int64_t r_materialized_read = 0;         // ... those of them because a call was handed r or Ap (the others: setters, the tuner)
     int64_t r_dropped = 0;                   // ... and those nobody read: overwritten by the next V-cycle, a copy or a fill, or destroyed
+    int last_ap_form = 0;                    // 1: the last hmg_vcycle / hmg_fcg_step left that pending r without a stored Ap (option lazy_ap)
+    int64_t ap_rebuilt = 0;                  // pending residuals whose Ap had to be formed first: the last CG step's apply, launched late
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
     // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB
@@ -273,6 +276,8 @@ struct hmg_ctx {
     // grids of this context whose last budgeted level-1 solve still has its probe in flight: judged at the next call that
     // synchronises the stream anyway (norms, dot products, integrals, hmg_ctx_sync, downloads)
     std::vector<struct hmg_grid *> probe_grids;
+    // grids of this context with an open PendingR record: an option that shapes the apply settles them before it takes effect
+    std::vector<struct hmg_grid *> pend_grids;
 };
 
 // The last r-update of a V-cycle, not launched yet (option lazy_r): r still holds r_2, Ap the unsummed A p_2, alpha[0] / alpha[1]
@@ -282,11 +287,19 @@ struct hmg_ctx {
 // 58.  So the grid remembers whether the last V-cycle's r was read (hmg_grid::r_reader): if it was, the next tail runs the eager
 // launch and leaves a record that is already `formed` -- nothing left to launch, it only notes whether r is read again; a record
 // that is dropped unread clears the flag and the next V-cycle defers again.  The bits do not depend on the path.
+// Option lazy_ap (three-update form): the last CG step ran in the dead form -- p_2.Ap_2 for the step length, nothing stored -- and Ap
+// holds no A p_2 (ap_stored = false).  Forming r then starts with the launch the eager tail would have made: the fused apply on x = r
+// (still r_2), x2 = the spare vector (still p_1), beta_2 = alpha[2] / alpha[3] as k_cg_x_tail saved it, out = Ap, the edge / node
+// interface sum, p.Ap into S_PAP3.  Such a record rests on the spare vector, the operator (sigma, lambda, masks, class-weight cache)
+// and the kernel choice as well: whatever changes one of them settles the record first (hmg_grid_set_operator*, _set_lambda,
+// hmg_ctx_set_option through hmg_ctx::pend_grids, a smoother that is about to write the spare vector).  Ap's memory is the column to
+// rebuild into, so the rules for r and Ap are the same for both kinds of record.
 struct PendingR {
     hmg_vec *r = nullptr, *Ap = nullptr;
     int level = 0;
     int slot = -1;
     bool formed = false;
+    bool ap_stored = true;      // false: Ap is still to be rebuilt (option lazy_ap)
     bool orphan_Ap = false;     // Ap's handle was destroyed while r still needs its memory: the record owns it until it closes
 };
 // (hmg_*_destroy may come from any thread, a finalizer's for one: it never launches.  Whoever touches the record holds the lifetime lock.)
@@ -306,10 +319,10 @@ struct hmg_grid {
     DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
     DevBuf<uint16_t> d_dmask, d_dupmask;
     DevBuf<uint8_t> d_mult;
-    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last two doubles: the step length of a pending r-update
+    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last four doubles: step length and beta of a pending r-update
     PendingR pend;
     bool r_reader = false;                       // a caller's read settled a record and none was dropped unread since (see PendingR)
-    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 2 : nullptr; }
+    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 4 : nullptr; }
     bool fuse_cg = true;
     DevBuf<double> d_coef;
     std::vector<double> sigma, coef;
@@ -442,6 +455,12 @@ inline const LevelDev &lev(const hmg_grid *g, int level)
 // forms it now, if there is one: afterwards vectors and scalar bank are what the eager tail leaves.  read: the caller is about to
 // read r or Ap (settle()) -- only that is remembered as a read (hmg_grid::r_reader); a setter that settles the record is not one
 void materialize_r(hmg_grid *g, bool read = false);
+// a record that has its Ap still to rebuild (option lazy_ap) is settled before what the rebuild rests on changes: the operator, lambda,
+// the spare vector, the context's options.  Not a read.  A record that holds its Ap stays open.
+inline void settle_rebuild(hmg_grid *g)
+{
+    if (g && g->ctx && g->pend.r && !g->pend.ap_stored) materialize_r(g);
+}
 // every entry point that is handed a vector goes through one of these three before it touches it:
 // the vector is read or partly written -- a pending r or Ap is settled first
 inline void settle(const hmg_vec *v)

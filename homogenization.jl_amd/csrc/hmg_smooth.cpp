@@ -524,16 +524,29 @@ bool lazy_r_ok(const hmg_grid *g, const hmg_vec *r, const hmg_vec *p, const hmg_
 }
 
 // formed: the eager launch has run (the caller reads r after every cycle, hmg_grid::r_reader); the record only watches
-void open_pending(hmg_grid *g, int level, hmg_vec *r, hmg_vec *Ap, int slot, bool formed)
+// ap_stored = false: the last CG step ran in the dead form, Ap is rebuilt when the record is settled (option lazy_ap)
+void open_pending(hmg_grid *g, int level, hmg_vec *r, hmg_vec *Ap, int slot, bool formed, bool ap_stored = true)
 {
     LifetimeLock lock(lifetime_mutex());
     need(!g->pend.r, "a pending r-update was not settled before the next one");
+    need(ap_stored || !formed, "a formed r-update without its Ap");
     g->pend.r = r;
     g->pend.Ap = Ap;
     g->pend.level = level;
     g->pend.slot = slot;
     g->pend.formed = formed;
+    g->pend.ap_stored = ap_stored;
     g->ctx->last_r_form = formed ? 0 : 1;
+    g->ctx->last_ap_form = ap_stored ? 0 : 1;
+    auto &open = g->ctx->pend_grids;
+    if (std::find(open.begin(), open.end(), g) == open.end()) open.push_back(g);
+}
+
+// Can the last step of the three-update form run without storing A p_2 (option lazy_ap)?  Where the record is opened unformed, and
+// the dead launch is the one every fused apply family has (Tail::DeadDefer2 takes it on every level: x, x2, no out, no xout, no xacc).
+bool lazy_ap_ok(const hmg_grid *g, const SmoothForm &f)
+{
+    return g->ctx->lazy_ap && f.tail == Tail::Top3 && f.lazy_r && !g->r_reader;
 }
 
 DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
@@ -543,6 +556,9 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
     const LevelDev &lv = lev(g, level);
     const Launch &L = g->ctx->L;
     const int64_t n = vec_len(x);
+    // (a record without a stored Ap rests on the spare vector, which these two tails write: on other vectors than the record's --
+    //  hmg_vcycle_down / _up next to a V-cycle's states -- nothing else has settled it)
+    if (f.tail == Tail::Top3 || f.tail == Tail::DeadDefer3) settle_rebuild(g);
     first_residual(g, level, x, b, r, f, xcoarse, cx);
     if (g->smoother == 1) {
         smooth_pcg(g, level, steps, x, r, p, Ap, f);
@@ -697,6 +713,15 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.xout = a.xacc = nullptr;
         a.s_num = S_RS3;
         a.s_den = cur;
+        if (lazy_ap_ok(g, f)) {
+            // A p_2 has one reader, the pending r-update: the step delivers p_2.Ap_2 alone -- the pre-smoother's dead launch (16 instead
+            // of 24 B/DOF, no interface sum) -- and the record forms Ap again if somebody reads r (materialize_r())
+            a.out = nullptr;
+            apply_then_sum(g, lv, a, true, S_PAP3, -1);
+            launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
+            open_pending(g, level, r, Ap, other, false, /*ap_stored=*/false);
+            return {};
+        }
         apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
         if (f.lazy_r && !g->r_reader) {
             launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
@@ -850,7 +875,7 @@ DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec 
     const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
     if (top) g->ctx->last_pre_form = deferred;
     const DeferredX cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
-    if (top) g->ctx->last_top_form = g->ctx->last_r_form = 0;
+    if (top) g->ctx->last_top_form = g->ctx->last_r_form = g->ctx->last_ap_form = 0;
     return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up, /*lazy_r=*/top);
 }
 
@@ -865,6 +890,10 @@ void close_pending(hmg_grid *g)
 {
     hmg_vec *orphan = g->pend.orphan_Ap ? g->pend.Ap : nullptr;
     g->pend = PendingR{};
+    if (g->ctx) {
+        auto &open = g->ctx->pend_grids;
+        open.erase(std::remove(open.begin(), open.end(), g), open.end());
+    }
     if (orphan) release_vec(orphan);
 }
 
@@ -884,6 +913,24 @@ void materialize_r(hmg_grid *g, bool read)
     if (!q.r) return;
     if (!q.formed) {
         HIPCHK(hipSetDevice(g->ctx->device));
+        if (!q.ap_stored) {
+            // the apply of the last CG step as the eager tail launches it: p_2 = r_2 + beta_2 p_1 formed in LDS, Ap = A p_2 with the
+            // edge / node interface sum, p.Ap into S_PAP3 again -- beta_2 from the numbers the x-only tail saved behind the step length
+            need(g->top_spare.p != nullptr && g->pend_alpha() != nullptr, "a pending r-update has lost the spare vector it rests on");
+            const LevelDev &lv = lev(g, q.level);
+            ApplyArgs a{};
+            a.alpha = 1.0;
+            a.lambda = g->lambda;
+            a.x = q.r->d;
+            a.x2 = g->top_spare.p;
+            a.out = q.Ap->d;
+            a.scal = g->pend_alpha();
+            a.s_num = 2;
+            a.s_den = 3;
+            a.flags = 1;
+            apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
+            g->ctx->ap_rebuilt += 1;
+        }
         launch_cg_rupdate_faces(g->ctx->L, lev(g, q.level), g->md, q.r->d, q.r->d, q.Ap->d, vec_len(q.r), 0, 1, q.slot, g->pend_alpha());
         g->ctx->r_materialized += 1;
         if (read) g->ctx->r_materialized_read += 1;
@@ -959,7 +1006,7 @@ int hmg_grid_reserve_spare(hmg_grid *g, int enable)
     if (enable) {
         (void)reserve_top_spare(g, true);
     } else {
-        materialize_r(g);                        // (x is finished; the record does not rest on the spare vector, but the form changes here)
+        materialize_r(g);                        // (x is finished; a record without a stored Ap rebuilds it from the spare vector)
         release_top_spare(g);
         g->top_spare_refused = true;             // ... and the first vector of the finest level does not bring it back
     }

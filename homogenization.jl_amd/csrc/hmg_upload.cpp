@@ -35,8 +35,8 @@ void upload_mesh(hmg_grid *g)
 #else
     constexpr size_t BP = 2;
 #endif
-    // (+ 2: the step length of a pending r-update lives behind the partials, hmg_grid::pend_alpha())
-    if (g->d_blockpart.n < (size_t)M.ncells * BP + 2) g->d_blockpart.alloc((size_t)M.ncells * BP + 2);
+    // (+ 4: the step length of a pending r-update and its step's beta live behind the partials, hmg_grid::pend_alpha())
+    if (g->d_blockpart.n < (size_t)M.ncells * BP + 4) g->d_blockpart.alloc((size_t)M.ncells * BP + 4);
     g->d_cells_cut.upload(K.cells_cut, s);
     g->d_cells_inner.upload(K.cells_inner, s);
     g->d_cell_perm.upload(K.cell_perm, s);
@@ -439,6 +439,7 @@ int hmg_grid_create_partition_rehearsal(hmg_ctx *ctx, int dim, int nlevels, int6
 // sn numbers per cell (hmg_grid::sig_n) of the whole mesh: the GLOBAL one on a partitioned grid
 static void set_operator(hmg_grid *g, const double *sigma, int sn, double lambda)
 {
+    settle_rebuild(g);                           // (a pending r-update may have its Ap still to form, with the operator it was recorded under)
     if (g->part)
         g->sigma_global.assign(sigma, sigma + (size_t)g->part->global.ncells * sn);
     else
@@ -500,6 +501,7 @@ int hmg_grid_set_lambda(hmg_grid *g, double lambda)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    settle_rebuild(g);                           // (... and with its lambda and class-weight cache)
     g->lambda = lambda;
     g->op_epoch += 1;
     g->dinv_ready = false;

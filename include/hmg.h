@@ -120,6 +120,18 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *       wrapped by hmg_vec_wrap, or handed out once by hmg_vec_device_ptr), on a partitioned grid (the deferred sum over the ranks
  *       would be a collective at a place no rank can foresee) and with smoother kind 1.  0: the eager tail always.
  *       hmg_ctx_counter "lazy_r_form", "r_materialized", "r_materialized_by_read", "r_dropped".
+ *   "lazy_ap" 1: where "lazy_r" leaves the r-update of the three-update form pending (three steps or more, the spare vector
+ *       reserved), the CG step in front of it does not store Ap = A p_2 either: it delivers p_2.Ap_2 for the step length (the
+ *       pre-smoother's dead launch, 16 instead of 24 B/DOF, and no edge / node interface sum behind it).  That Ap had one reader,
+ *       the pending r-update; a record that is dropped unread never needed it.  A record that is settled forms Ap first, by the
+ *       launch the eager tail would have made (r_2, the spare vector's p_1, beta_2 from two more doubles of the grid's buffer; 24
+ *       B/DOF and the interface sum), then r as above: Ap, r, the scalar bank and every value derived from them are the same to the
+ *       last bit.  Three prices: r dropped unread 8 B/DOF and one interface sum less than "lazy_ap" 0; the first read of a solve
+ *       16 B/DOF more (one finest-level apply); a caller that reads r after every cycle runs the eager tail from its second cycle
+ *       on and pays nothing further.  Such a record also rests on the spare vector, the operator and the kernel choice, so
+ *       hmg_grid_set_operator, hmg_grid_set_operator_tensor, hmg_grid_set_lambda and every hmg_ctx_set_option on the grid's
+ *       context form it first as well (not a read).  The two-update form, partitioned grids and the other eager cases of
+ *       "lazy_r" store Ap as before.  0: Ap is always stored.  hmg_ctx_counter "lazy_ap_form", "ap_rebuilt".
  *   "fold_prolong" 1: the prolongation rides in the post-smoother's first residual.
  *   "prolong_in_image" 1: on level 6 that residual stages the coarse column at the even nodes of the LDS lattice image
  *       (three workgroups per CU stay resident); 0: in LDS of its own behind it.
@@ -159,7 +171,9 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    last pre-smoother of the topmost down leg left to its local residual: 3 with option "lazy_pre" and the spare vector, else 2, 1 or 0), "lazy_r_form" (1: the
    last hmg_vcycle / hmg_fcg_step left its top level's r-update pending, option "lazy_r"; 0: it ran the eager tail), "r_materialized" (pending
    r-updates formed by a later call; "r_materialized_by_read": those of them formed because a call was handed r or Ap, the others
-   by hmg_grid_shrink and the other setters, the placement tuner or a V-cycle on other vectors) and "r_dropped" (those that never had to be formed), "coarse_x_folds" (residuals
+   by hmg_grid_shrink and the other setters, the placement tuner or a V-cycle on other vectors) and "r_dropped" (those that never had to be formed), "lazy_ap_form" (1: that
+   pending r-update was left without a stored Ap, option "lazy_ap") and "ap_rebuilt" (pending r-updates that had to run the last CG step's apply again
+   before they could be formed), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
    hmg_fcg objects), "smoother_diag_bytes" (inverse diagonals held by this context's grids, see hmg_grid_set_smoother) and
    "smoother_diag_builds" (times a grid of this context formed them); -1 for an unknown name.  No counterpart in
