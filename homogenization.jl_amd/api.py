@@ -679,6 +679,105 @@ def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None
     return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]), np.rint(out[:, 2:]).astype(np.int64)
 
 
+def _points_of(implicit, points):
+    d = implicit.base.dim
+    p = np.ascontiguousarray(points, dtype=np.float64)
+    if p.ndim == 1 and p.shape[0] == d:
+        p = p.reshape(1, d)
+    if p.ndim != 2 or p.shape[1] != d:
+        raise ValueError(f"points must have shape (npoints, {d}), not {p.shape}")
+    return p
+
+
+def _vec_of(implicit, name, x):
+    if x is None:
+        return None, None
+    d = implicit.base.dim
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (d,):
+        raise ValueError(f"{name} must have {d} entries")
+    return x, x.ctypes.data_as(L.p_f64)
+
+
+def locator_counter(name: str) -> int:
+    """The process-wide counters of the sampling locator ("sample_locator_builds", "sample_locator_bytes",
+    "sample_locator_max_candidates"): hmg_ctx_counter answers them without a context, so a host-only grid can be asked too."""
+    return int(L.load().hmg_ctx_counter(None, name.encode()))
+
+
+def locate(implicit: ImplicitFineGrid, level: int, points):
+    """Where points of physical space lie in `level` of the grid (hmg_grid_locate; host only, a grid without a context too):
+    (cell, nodes, weights, gweights) with cell (n,) int32 -- the lowest current coarse cell that contains the point up to a slack of
+    2^-40 in barycentric coordinates, -1 for none or a coordinate that is not finite --, nodes (n, d + 1) int32 -- the vertices of
+    the fine element the point is evaluated in, as 0-based HIERARCHICAL ids: rows of `DeviceMatrix.to_host()` --, weights (n, d + 1)
+    -- its P1 weights there, >= 0 --, and gweights (n, d + 1, d) with gradient = sum_k x_host[nodes[k], cell] gweights[k].  A vertex
+    whose weight is exactly 0 is reported as the element's first vertex (the gradient identity then needs the element's own
+    vertices: it holds wherever all weights are positive).  The element of a point on a fine face, edge or node is fixed by the
+    rule in include/hmg.h.  Points without a cell: nodes -1, weights and gweights NaN."""
+    lib = L.load()
+    d = implicit.base.dim
+    p = _points_of(implicit, points)
+    n = p.shape[0]
+    cell = np.zeros(n, dtype=np.int32)
+    nodes = np.zeros((n, d + 1), dtype=np.int32)
+    w = np.zeros((n, d + 1))
+    gw = np.zeros((n, d + 1, d))
+    L.check(lib.hmg_grid_locate(implicit.h, int(level), n, p.ctypes.data_as(L.p_f64), cell.ctypes.data_as(L.p_i32),
+                                nodes.ctypes.data_as(L.p_i32), w.ctypes.data_as(L.p_f64), gw.ctypes.data_as(L.p_f64)))
+    return cell, nodes, w, gw
+
+
+def sample(v: DeviceMatrix, implicit: ImplicitFineGrid, points, xi=None, gradient=True, value=True, cell=True):
+    """u = xi.x + v and its gradient at points of physical space, evaluated on the device from the vector as stored (hmg_sample):
+    a dict with "value" (n,), "gradient" (n, d) and "cell" (n,) int32 -- the entries switched off by gradient / value / cell =
+    False are missing.  Per point: the coarse cell of `locate`, the P1 interpolant of v on one fine element of v's level, its
+    constant gradient there; NaN / -1 where no cell contains the point.  Only the points go up and the results come down.
+    The call reads the vector through `v.device_ptr()`, which settles a pending r-update of v and marks it exposed: sampling a
+    LevelState's r, p or Ap keeps the eager tail of `vcycle` for that vector from then on; sampling x changes nothing.
+    Not on partitioned grids.  Counters: "sample_launches", "sample_kernel_ns", "sample_download_ns"."""
+    lib = L.load()
+    d = implicit.base.dim
+    p = _points_of(implicit, points)
+    n = p.shape[0]
+    xi, xp = _vec_of(implicit, "xi", xi)
+    out = {}
+    if value:
+        out["value"] = np.zeros(n)
+    if gradient:
+        out["gradient"] = np.zeros((n, d))
+    if cell:
+        out["cell"] = np.zeros(n, dtype=np.int32)
+    L.check(lib.hmg_sample(implicit.h, int(v.level), ctypes.c_void_p(v.device_ptr()), xp, n, p.ctypes.data_as(L.p_f64),
+                           out["value"].ctypes.data_as(L.p_f64) if value else None,
+                           out["gradient"].ctypes.data_as(L.p_f64) if gradient else None,
+                           out["cell"].ctypes.data_as(L.p_i32) if cell else None))
+    return out
+
+
+def sample_raster(v: DeviceMatrix, implicit: ImplicitFineGrid, origin, du, dv, nu: int, nv: int, xi=None, gradient=True):
+    """`sample` on the pixels x(a, b) = origin + a du + b dv, 0 <= a < nu, 0 <= b < nv, of a slice of any orientation
+    (hmg_sample_raster): the points are formed on the device, fma(b, dv, fma(a, du, origin)) per component, nothing is uploaded.
+    Returns a dict of arrays shaped (nv, nu): "value", "cell" (int32), and "gradient" (nv, nu, d) unless gradient = False.  Pixels
+    outside the domain: NaN / -1."""
+    lib = L.load()
+    d = implicit.base.dim
+    nu, nv = int(nu), int(nv)
+    xi, xp = _vec_of(implicit, "xi", xi)
+    o, op = _vec_of(implicit, "origin", np.asarray(origin, dtype=np.float64))
+    u, up = _vec_of(implicit, "du", np.asarray(du, dtype=np.float64))
+    w, wp = _vec_of(implicit, "dv", np.asarray(dv, dtype=np.float64))
+    if nu < 0 or nv < 0:
+        raise ValueError("nu and nv must not be negative")
+    out = {"value": np.zeros((nv, nu)), "cell": np.zeros((nv, nu), dtype=np.int32)}
+    if gradient:
+        out["gradient"] = np.zeros((nv, nu, d))
+    L.check(lib.hmg_sample_raster(implicit.h, int(v.level), ctypes.c_void_p(v.device_ptr()), xp, op, up, wp, nu, nv,
+                                  out["value"].ctypes.data_as(L.p_f64),
+                                  out["gradient"].ctypes.data_as(L.p_f64) if gradient else None,
+                                  out["cell"].ctypes.data_as(L.p_i32)))
+    return out
+
+
 def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     ops._bind()
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))

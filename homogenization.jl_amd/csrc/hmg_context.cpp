@@ -252,8 +252,16 @@ int hmg_ctx_sync(hmg_ctx *ctx)
 
 int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
 {
-    if (!ctx || !name) return -1;
+    if (!name) return -1;
     const std::string n(name);
+    // (process-wide: a host-only grid has a locator and no context)
+    if (n == "sample_locator_builds") return sample_locator_counter(0);
+    if (n == "sample_locator_bytes") return sample_locator_counter(1);
+    if (n == "sample_locator_max_candidates") return sample_locator_counter(2);
+    if (!ctx) return -1;
+    if (n == "sample_launches") return ctx->sample_launches;                        // launches of k_sample (hmg_sample, hmg_sample_raster)
+    if (n == "sample_kernel_ns") return ctx->sample_kernel_ns;                      // the last of those calls: kernel alone
+    if (n == "sample_download_ns") return ctx->sample_download_ns;                  // ... and the download of its results
     if (n == "wave_launches") return ctx->wave_launches;
     if (n == "slab2_launches") return ctx->slab2_launches;
     if (n == "rows_launches") return ctx->rows_launches;

@@ -178,6 +178,8 @@ struct MeshTables {
     std::vector<int32_t> cells_cut, cells_inner;
 
     // cell geometry: detJ and Jinv = inv(J') (column-major dim x dim)
+    // (point sampling does not read jinv: inverse_jacobian in hmg_sample.cpp inverts J again in long double -- the two inverses
+    //  differ in the last bits, by up to eps times the cell's condition number)
     std::vector<double> detj, jinv;
 };
 

@@ -9,6 +9,7 @@
 //   hmg_fcg.cpp      flexible CG around the V-cycle
 //   hmg_fields.cpp   per-cell gradient moments of a level vector and of a pair of them, through the LDS-resident or the window kernels
 //   hmg_extrema.cpp  fine-element table of a level; per-cell extrema and exceedance counts of a quadratic form of the gradient
+//   hmg_sample.cpp   locator of the current cells; a level vector's value, gradient and cell at points and on raster slices
 //   hmg_capi.cpp     vector operations, primitives, right-hand sides, integrals: argument checks and one call each
 //
 // Every extern "C" entry point lives in the module it fronts; hmg_capi.cpp keeps those that front none.
@@ -180,6 +181,22 @@ struct FieldState {
     std::vector<std::unique_ptr<DevBuf<uint8_t>>> d_mask;    // [nlevels], null until used
 };
 
+// Sampling state of a grid (hmg_sample.cpp): the locator of the current cells -- built by the first hmg_grid_locate / hmg_sample /
+// hmg_sample_raster, and again after hmg_grid_shrink (which clears `ready`) --, per level used the lattice -> slot table, and their
+// device copies, made by the first device call.  Like FieldState outside LevelDev / MeshDev and outside the checksum of a
+// host-only grid: grid creation and its allocations are what they were.
+struct SampleState {
+    bool ready = false, on_device = false;
+    int nb[3] = {1, 1, 1};
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, inv_h[3] = {0, 0, 0};
+    std::vector<int32_t> bin_ptr, bin_cell;                  // CSR: per bin its candidate cells, ascending
+    std::vector<double> geo;                                 // per cell X0 and J^-1 (row-major)
+    DevBuf<double> d_tables;                                 // geo, then bin_ptr and bin_cell: one allocation
+    std::vector<char> level_ready;                           // [nlevels] basis and slot formula checked, table built
+    std::vector<std::vector<int32_t>> slot_of;               // [nlevels] 3D: lattice node -> storage slot
+    std::vector<std::unique_ptr<DevBuf<int32_t>>> d_slot_of; // [nlevels], null until used on the device
+};
+
 // state of the last coarse solve, copied to pinned host memory behind the solve and read when somebody asks
 struct CoarseProbe {
     double *h = nullptr;            // pinned: S_DONE, S_ITER, S_CRR, b.b
@@ -247,6 +264,8 @@ struct hmg_ctx {
     int64_t moments_kernel_ns = 0, moments_download_ns = 0;   // the last hmg_cell_moments: its kernel (device events) and the download of its sums (host clock)
     int64_t pair_moments_kernel_ns = 0, pair_moments_download_ns = 0;   // the last hmg_cell_pair_moments, likewise
     int64_t extrema_kernel_ns = 0;           // the last hmg_cell_extrema: its kernel (device events)
+    int64_t sample_launches = 0;             // launches of k_sample (hmg_sample, hmg_sample_raster)
+    int64_t sample_kernel_ns = 0, sample_download_ns = 0;   // the last of those calls: its kernel (device events), its downloads (host clock)
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window
                                              // kernels (hmg_fields_window.hip); 2 so does every level those kernels can address (A/B knob)
     int64_t moments_window_launches = 0;     // launches of the window kernels (hmg_ctx_counter "cell_moments_window_launches")
@@ -400,6 +419,7 @@ struct hmg_grid {
     DevBuf<double> own_exbuf;                    // hmg_grid_use_comm: library-owned exchange buffer
 
     FieldState fields;                           // fine-element tables of hmg_cell_extrema (hmg_extrema.cpp)
+    SampleState sample;                          // locator and lattice tables of hmg_grid_locate / hmg_sample* (hmg_sample.cpp)
 
     uint64_t upload_hash = 1469598103934665603ull;   // host-only grids: checksum of every table a device grid would upload (DryUploads)
 
@@ -508,6 +528,12 @@ void release_weight_cache(hmg_grid *g);
 // the level's rolling-window lists (those set_slab hands to the operator apply), without touching the grid's launch state: what
 // the window kernels of the per-cell moments and extrema walk
 SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv);
+
+// ---- hmg_sample.cpp ----
+// hmg_ctx_counter "sample_locator_builds" (0), "sample_locator_bytes" (1), "sample_locator_max_candidates" (2): locators built in
+// this process, and the table bytes and the longest candidate list of the last one.  Process-wide like device_allocs; the only
+// counters hmg_ctx_counter answers for a NULL context ("device_allocs" is not: it stays behind the null check)
+int64_t sample_locator_counter(int which);
 
 // ---- hmg_smooth.cpp ----
 void set_slab(hmg_grid *g, const LevelDev &lv);

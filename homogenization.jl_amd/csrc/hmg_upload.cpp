@@ -519,6 +519,7 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
     if (g->ctx) materialize_r(g);                // (a pending r-update belongs to the cells and face partners of the grid as it is)
     g->op_epoch += 1;
     g->dinv_ready = false;
+    g->sample.ready = false;                     // (the locator of hmg_sample.cpp covers the cells as they were)
     if (g->part) {
         // prefix of the GLOBAL mesh: this rank keeps its cells with a global id below the prefix length (local
         // cells are in ascending global order, so that is a prefix of every local level vector as well); cut

@@ -641,7 +641,7 @@ def _large_cells(ctx, on: bool):
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                              fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
-                             large_cells: bool = False, extrema: bool = False, thresholds=None):
+                             large_cells: bool = False, extrema: bool = False, thresholds=None, slices=None):
     """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
     a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
     moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
@@ -664,8 +664,11 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     with `large_cells` 3D level 7 and 2D levels 9-11 too), adds "peak_energy_density" and
     "min_energy_density" (Ne each: the extrema of grad u . sigma_c grad u in every cell), "concentration" = peak / energy_form and,
     with `thresholds` (up to 8 multiples of energy_form), "exceedance" (Ne, nthr): the volume of every cell on which the energy
-    density exceeds each; they are in the returned dict with or without `fields`, and with `save` in the file.  No counterpart
-    in the reference."""
+    density exceeds each; they are in the returned dict with or without `fields`, and with `save` in the file.
+    `slices`: a list of rasters (origin, du, dv, nu, nv) -- pixel (a, b) at origin + a du + b dv --; u = xi.x + v is sampled on each
+    from the converged corrector on the device (api.sample_raster; any top level) and "slices" in the returned dict is a list of
+    dicts with "value", "cell" (nv, nu), "gradient", "flux" (nv, nu, dim) and "energy_density" (nv, nu), NaN / -1 outside the
+    domain; with `save` slice i is written to `save`_slice<i>.vts (vtk.export_slice).  No counterpart in the reference."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -709,6 +712,15 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
         if thr.size:
             peaks["exceedance"] = cell_fields.exceedance_volume(counts, vol, api.fine_elements(implicit, total_grids))
         out.update(peaks)
+    if slices is not None:
+        out["slices"] = []
+        for i, (origin, du, dv, nu, nv) in enumerate(slices):
+            s = api.sample_raster(xv, implicit, origin, du, dv, nu, nv, xi=xi)
+            s["flux"] = cell_fields.sample_flux(cond, s["cell"], s["gradient"])
+            s["energy_density"] = cell_fields.sample_energy_density(cond, s["cell"], s["gradient"])
+            out["slices"].append(s)
+            if save is not None:
+                vtk.export_slice(f"{save}_slice{i}", origin, du, dv, s)
     if fields or save is not None:
         flux = cell_fields.mean_flux(cond, mean)
         if save is not None:

@@ -3,7 +3,8 @@ What one does with a corrector once it is solved, from two per-cell quantities (
 hmg_cell_moments): the mean gradient `mean` (Ne, d) and the Gram tensor of the gradient `gram` (Ne, d, d) of u = xi.x + v over
 every coarse cell -- and, for two correctors, from their symmetrised cross moment `pair` (Ne, d, d) (api.cell_pair_moments:
 pair_energy, tensor_sensitivity) -- and, for the pass over the fine elements (api.cell_extrema), the forms to give it and what
-its extrema and counts mean (energy_form, flux_form, exceedance_volume, concentration).  Plain numpy on those arrays; nothing here touches a level vector or the device.
+its extrema and counts mean (energy_form, flux_form, exceedance_volume, concentration) -- and, for point samples (api.sample,
+api.sample_raster), the flux and the energy density at every point (sample_flux, sample_energy_density, line_points).  Plain numpy on those arrays; nothing here touches a level vector or the device.
 
 `cond` is the conductivity per cell as `L2PlusDivAGrad` takes it: (Ne, d), the diagonals of diagonal tensors, or (Ne, d, d), full
 symmetric tensors.  No counterpart in the reference.
@@ -150,3 +151,37 @@ def exceedance_volume(counts, volumes, nel):
 def concentration(qmax, mean_density):
     """Peak over mean: qmax (Ne,) over a mean density -- a number (the homogenized energy density, say) or one per cell."""
     return np.asarray(qmax, dtype=np.float64) / np.asarray(mean_density, dtype=np.float64)
+
+
+# ---- point samples (api.sample, api.sample_raster): the flux and the energy density of u at every point --------------------
+def sample_flux(cond, cell, gradient):
+    """sigma_cell grad u at every sampled point: cond (Ne, d) or (Ne, d, d), cell (...) as api.sample / sample_raster return it,
+    gradient (..., d); the result has gradient's shape and is NaN where cell < 0."""
+    cell = np.asarray(cell)
+    g = np.asarray(gradient, dtype=np.float64)
+    if g.shape[:-1] != cell.shape:
+        raise ValueError(f"gradient {g.shape} does not fit cell {cell.shape}")
+    s = _full(cond)
+    if s.shape[1] != g.shape[-1]:
+        raise ValueError(f"cond is for dimension {s.shape[1]}, the gradients have {g.shape[-1]} components")
+    ok = cell >= 0
+    out = np.einsum("...kl,...l->...k", s[np.where(ok, cell, 0)], g)
+    out[~ok] = np.nan
+    return out
+
+
+def sample_energy_density(cond, cell, gradient):
+    """grad u . sigma_cell grad u at every sampled point, cell's shape; NaN where cell < 0."""
+    g = np.asarray(gradient, dtype=np.float64)
+    return np.einsum("...k,...k->...", g, sample_flux(cond, cell, g))
+
+
+def line_points(p0, p1, n):
+    """n points from p0 to p1, both ends included, (n, d): a line profile for api.sample."""
+    p0, p1 = np.asarray(p0, dtype=np.float64), np.asarray(p1, dtype=np.float64)
+    if p0.shape != p1.shape or p0.ndim != 1:
+        raise ValueError("p0 and p1 must be points of one dimension")
+    if n < 2:
+        raise ValueError("a line takes at least its two ends")
+    t = np.linspace(0.0, 1.0, int(n))[:, None]
+    return (1.0 - t) * p0 + t * p1

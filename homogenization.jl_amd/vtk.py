@@ -4,7 +4,8 @@ VTK (.vtu) export of the checkerboard and of a level of the implicit grid -- the
 Output side of the path only: level vectors are read back once per exported level.
 
 Files are VTK XML UnstructuredGrid, inline base64 ("binary") arrays with a UInt64 length header, no compression;
-ParaView / VTK / meshio read them.
+ParaView / VTK / meshio read them.  Raster slices sampled on the device (api.sample_raster) go out as VTK XML StructuredGrid
+(.vts: write_vts, export_slice) with the same arrays.
 """
 from __future__ import annotations
 
@@ -143,3 +144,48 @@ def export_unknown(implicit, x, k: int, level: int, name=None, field="v"):
     nfl = implicit.nf(level)
     v = np.ascontiguousarray(xh[:nfl, :].T).ravel()
     return write_vtu(name or f"ahom_{k}", nodes, cells, point_data={field: v})
+
+
+def write_vts(path, points, point_data=None):
+    """A VTK XML StructuredGrid of nv x nu points (one layer): points (nv, nu, dim) -- a raster slice of any orientation, index
+    [b, a] --, point_data: name -> (nv, nu) or (nv, nu, c) arrays (float64; int32 stays int32).  Same inline base64 arrays as
+    write_vtu.  2D points get z = 0 and 2-component vectors a zero third component, so that ParaView takes them as vectors."""
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 3 or points.shape[2] not in (2, 3):
+        raise ValueError(f"points must have shape (nv, nu, dim), not {points.shape}")
+    nv, nu, dim = points.shape
+    p3 = np.zeros((nv * nu, 3))
+    p3[:, :dim] = points.reshape(-1, dim)
+    if not path.endswith(".vts"):
+        path += ".vts"
+    ext = f"0 {nu - 1} 0 {nv - 1} 0 0"
+    with open(path, "w") as f:
+        f.write('<?xml version="1.0"?>\n<VTKFile type="StructuredGrid" version="1.0" byte_order="LittleEndian" '
+                'header_type="UInt64">\n')
+        f.write(f'<StructuredGrid WholeExtent="{ext}">\n<Piece Extent="{ext}">\n<Points>\n')
+        _array(f, "Points", p3, 3)
+        f.write("</Points>\n")
+        if point_data:
+            f.write("<PointData>\n")
+            for name, a in point_data.items():
+                a = np.asarray(a)
+                a = a.astype(np.int32) if a.dtype == np.int32 else a.astype(np.float64)
+                if a.shape[:2] != (nv, nu) or a.ndim > 3:
+                    raise ValueError(f"point data {name!r}: {a.shape} does not fit {nv} x {nu} points")
+                if a.ndim == 3 and a.shape[2] == 2:
+                    a = np.concatenate([a, np.zeros((nv, nu, 1), dtype=a.dtype)], axis=2)
+                _array(f, name, a.reshape(nv * nu, -1) if a.ndim == 3 else a.ravel(), a.shape[2] if a.ndim == 3 else None)
+            f.write("</PointData>\n")
+        f.write("</Piece>\n</StructuredGrid>\n</VTKFile>\n")
+    return path
+
+
+def export_slice(name, origin, du, dv, sampled):
+    """A raster slice as api.sample_raster returns it (a dict of (nv, nu[, c]) arrays), written with the pixel positions
+    origin + a du + b dv: opens in ParaView whatever the slice's orientation."""
+    origin, du, dv = (np.asarray(x, dtype=np.float64) for x in (origin, du, dv))
+    first = next(iter(sampled.values()))
+    nv, nu = np.asarray(first).shape[:2]
+    a = np.arange(nu, dtype=np.float64)[None, :, None]
+    b = np.arange(nv, dtype=np.float64)[:, None, None]
+    return write_vts(name, origin + a * du + b * dv, sampled)

@@ -176,7 +176,8 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    before they could be formed), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
    hmg_fcg objects), "smoother_diag_bytes" (inverse diagonals held by this context's grids, see hmg_grid_set_smoother) and
-   "smoother_diag_builds" (times a grid of this context formed them); -1 for an unknown name.  No counterpart in
+   "smoother_diag_builds" (times a grid of this context formed them), the "sample_*" counters listed at hmg_sample (those of
+   the locator are process-wide and answered for a NULL context); -1 for an unknown name.  No counterpart in
    the reference. */
 int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name);
 
@@ -408,6 +409,60 @@ int hmg_cell_extrema(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NUL
                      const double *form /* nq*ncells, or NULL */, int nthr, const double *thresholds /* nthr, or NULL */,
                      double *out /* host, (2 + nthr)*ncells */);
 int64_t hmg_grid_fine_elements(const hmg_grid *grid, int level);   /* 2^(dim (level-1)); host-only grid too; -1: null grid or bad level */
+
+/* ---- sampling a level vector at points and on raster slices (no counterpart in the reference) --------------------------
+ * For a point x of physical space, a level and a level vector v of that level, as stored (no interface sum, no mask):
+ *   cell      the current coarse cell (the prefix after hmg_grid_shrink) that contains x: all barycentric coordinates of x in it
+ *             are >= -tau, tau = 2^-40 in reference coordinates; among several (faces, edges, nodes of the base mesh) the LOWEST
+ *             cell id.  No such cell, or a coordinate that is not finite: cell = -1 and every other output of the point is NaN.
+ *   value     xi . x + sum_k w_k v[slot_k, cell] over the dim + 1 vertices of ONE fine element of the level that contains x, w_k
+ *             its P1 (barycentric) weights there: >= 0 (the slack is clamped away) and summing to 1 within rounding.
+ *   gradient  xi + the gradient of the P1 interpolant on that element (constant per element), dim numbers.
+ * xi = NULL means 0.  The element: with t = 2^(level-1) x^ (x^ the reference coordinates of x in the cell, negative ones set to 0)
+ * and Y = (t_i + t_j + t_k, t_i + t_j, t_i) (2D: (t_i + t_j, t_i)), clamped from the left to m >= Y_0 >= Y_1 >= Y_2, take
+ * P_a = min(floor(Y_a), m - 1) and f_a = Y_a - P_a in [0, 1]; the vertices are P, P + e_p1, P + e_p1 + e_p2, P + (1, 1, 1) in
+ * that basis, p the order of f descending, EQUAL f IN ASCENDING a.  This rule names an element of the cell for every point of the
+ * closed cell (a point on a fine face, edge or node takes the element the rule gives, always the same one); the weights are
+ * 1 - f_p1, f_p1 - f_p2, f_p2 - f_p3, f_p3.
+ * A vertex whose weight is exactly 0 is not read for the value -- a NaN elsewhere in the column stays out of it --, and
+ * hmg_grid_locate reports the element's first vertex in its place.  The gradient belongs to the whole element and reads all its
+ * vertices (only when it is asked for).  No reductions, no atomics: the same bits in every run and for every launch shape.
+ *
+ * hmg_grid_locate runs on the host (a grid without a context too): per point the cell, the dim + 1 vertices as 0-based
+ * HIERARCHICAL node ids -- rows of hmg_vec_download's matrix: value = sum_k weights[k] x_host[nodes[k], cell] --, the weights,
+ * and, where gweights is not NULL, the vectors g_k (dim each, vertex-major) with gradient = sum_k v_k g_k over the element's own
+ * vertices (nodes[] names them wherever all weights are positive).  Points without a cell: nodes -1, weights and gweights NaN.
+ * hmg_sample uploads the points, runs one kernel (one thread per point) and downloads what was asked for; each of values
+ * (npoints), gradients (dim per point) and cell (npoints) may be NULL, not all three.  hmg_sample_raster forms the points on the
+ * device, x(a, b) = fma(b, dv, fma(a, du, origin)) per component for 0 <= a < nu, 0 <= b < nv; outputs at index b * nu + a.
+ * device_column is the base address of a level vector of `level` (hmg_vec_device_ptr): it must be device memory with
+ * ld(level) * ncells doubles from it inside ONE allocation, or the call is refused before anything is launched (a wrong level
+ * or a pointer into the middle of a vector is a message, never a fault).  The calls take no hmg_vec: hmg_vec_device_ptr settles a
+ * pending r-update of that vector and marks it exposed, so sampling a grid's r, p or Ap keeps the eager tail of hmg_vcycle for
+ * that vector from then on; sampling x, which is what drivers do, changes nothing.
+ * The locator (a uniform bin grid over the bounding box of the current cells; per bin the cells that may meet it, ascending) is
+ * built at the first of these calls and again after hmg_grid_shrink; its device copy (setup memory, one allocation, plus one
+ * lattice table per 3D level used) at the first device call.  Points and results take one block of the context's pool of
+ * level-vector memory; the calls synchronise.  Any simplicial base mesh; 3D levels 1-7, 2D levels 1-11.
+ * hmg_ctx_counter: "sample_launches", "sample_kernel_ns" and "sample_download_ns" (the last call's kernel, by device events, and
+ * its downloads, by the host clock) per context; "sample_locator_builds", "sample_locator_bytes" and
+ * "sample_locator_max_candidates" (the longest list of a bin) count locators built in this process and describe the last one:
+ * process-wide like "device_allocs" and, unlike every other counter ("device_allocs" too), answered for a NULL context as well --
+ * a grid without a context has a locator and nothing else to ask.
+ * A raster of any shape up to 2^31 - 1 pixels is one launch: a workgroup takes 16 x 16 pixels, on a raster thinner than 16 pixels
+ * one way a tile as thin as the raster (a line of pixels: 256 x 1).
+ * Refused with a message, nothing launched and nothing changed: a partitioned grid; a level out of range; null points / origin /
+ * du / dv; npoints or nu * nv above 2^31 - 1 or negative (0: success, nothing written); all outputs NULL; and, for the two
+ * device calls, a grid without a context or a column that fails the check above. */
+int hmg_grid_locate(hmg_grid *grid, int level, int64_t npoints, const double *points /* point-major, dim each */,
+                    int32_t *cell /* npoints */, int32_t *nodes /* (dim+1) per point: 0-based HIERARCHICAL row ids */,
+                    double *weights /* (dim+1) per point */, double *gweights /* dim*(dim+1) per point, or NULL */);
+int hmg_sample(hmg_grid *grid, int level, const void *device_column /* base of a level vector: ld*Ne doubles */,
+               const double *xi /* dim, or NULL */, int64_t npoints, const double *points /* host */,
+               double *values, double *gradients, int32_t *cell /* host; each may be NULL */);
+int hmg_sample_raster(hmg_grid *grid, int level, const void *device_column, const double *xi,
+                      const double *origin, const double *du, const double *dv /* dim each */, int64_t nu, int64_t nv,
+                      double *values, double *gradients, int32_t *cell /* nu*nv, index b*nu + a */);
 
 /* ---- fused fast path ------------------------------------------------------------------------ */
 /* smoothing_steps!(steps, implicit, ops, curr, k)            (src/multigrid.jl:46-71) */

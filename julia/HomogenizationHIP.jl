@@ -380,6 +380,36 @@ function cell_extrema(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} =
                 nthr == 0 ? C_NULL : collect(Float64, thresholds), out))
     (out[1, :], out[2, :], round.(Int64, out[3:end, :]))
 end
+# Point samples of a level vector (hmg_grid_locate, hmg_sample, hmg_sample_raster; api.locate / sample / sample_raster): points is
+# dim x n.  locate (host, a grid without a context too): cell (n; -1: none), nodes ((dim+1) x n, 0-BASED hierarchical ids: add 1 for
+# rows of Matrix(v)), weights ((dim+1) x n), gweights (dim x (dim+1) x n).  sample / sample_raster: u = ξ⋅x + v, its gradient
+# (dim x n) and the cell, evaluated on the device from the vector as stored; the raster's pixel (a, b) is origin + a du + b dv at
+# index a + 1, b + 1 of nu x nv arrays.  They read v through device_ptr(v) (a pending r-update of v is settled, v counts as exposed).
+function locate(g::HipGrid{dim}, level::Integer, points::AbstractMatrix{Float64}) where {dim}
+    n = size(points, 2)
+    cell = zeros(Int32, n); nodes = zeros(Int32, dim + 1, n); w = zeros(Float64, dim + 1, n); gw = zeros(Float64, dim, dim + 1, n)
+    check(ccall((:hmg_grid_locate, LIB), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                g.h, level, n, Matrix{Float64}(points), cell, nodes, w, gw))
+    (cell, nodes, w, gw)
+end
+function sample(v::HipMatrix, points::AbstractMatrix{Float64}, ξ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    g = v.grid
+    d, n = size(points)
+    val = zeros(Float64, n); grad = zeros(Float64, d, n); cell = zeros(Int32, n)
+    check(ccall((:hmg_sample, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                g.h, v.level, device_ptr(v), ξ === nothing ? C_NULL : collect(Float64, ξ), n, Matrix{Float64}(points), val, grad, cell))
+    (value = val, gradient = grad, cell = cell)
+end
+function sample_raster(v::HipMatrix, origin::AbstractVector{Float64}, du::AbstractVector{Float64}, dv::AbstractVector{Float64},
+                       nu::Integer, nv::Integer, ξ::Union{Nothing,AbstractVector{Float64}} = nothing)
+    g = v.grid
+    d = length(origin)
+    val = zeros(Float64, nu, nv); grad = zeros(Float64, d, nu, nv); cell = zeros(Int32, nu, nv)
+    check(ccall((:hmg_sample_raster, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                g.h, v.level, device_ptr(v), ξ === nothing ? C_NULL : collect(Float64, ξ), collect(Float64, origin), collect(Float64, du),
+                collect(Float64, dv), nu, nv, val, grad, cell))
+    (value = val, gradient = grad, cell = cell)
+end
 # subsets are prefixes 1:n of the ∞-norm ordered cells (find_elements_in_radius, :32-43).  The first term's dot(∂ϕ, P) is
 # the entry of rhs_aξ∇v! for the same ξ: the caller's right-hand side b of outer step 0 is passed along.
 integrate_first_term(v₀::HipMatrix, b::HipMatrix, subset::AbstractUnitRange, ops::AnyL2PlusDivAGrad) =

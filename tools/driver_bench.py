@@ -25,6 +25,10 @@ energy density (one solve, the moment pass, then the pass over the fine elements
 ("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D; with --large-cells
 (the driver's keyword large_cells=True) 3D level 7 and 2D levels 9-11 too, through the window kernels of both passes: the line then
 carries "cell_moments_window_launches" and "cell_extrema_window_launches".
+--slice N: driver.dirichlet_homogenization on hypercube(n) with slices=[one axis-aligned N x N raster through the middle of the
+domain] (one solve, the moment pass, then hmg_sample_raster with the flux and the energy density per pixel): one line with the wall
+time of a run after --warmup untimed ones, the pixels inside the domain, the largest sampled energy density over the homogenized
+one and the counters "sample_kernel_ns", "sample_download_ns", "sample_locator_bytes", "sample_locator_max_candidates".
 --uniaxial: driver.uniaxial_homogenization_tensor on hypercube(n) (d solves on one grid, the two faces normal to e_k as the grid's
 Dirichlet set in front of solve k): one line with the wall time of a run after --warmup untimed ones, the cycles and the tensor.
 --blocks B: driver.block_homogenization_tensor(n, B) (the Dirichlet cell problems of all (n / B)^d blocks in d solves on one grid)
@@ -52,6 +56,8 @@ ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficie
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
 ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor or --extrema: per-cell passes of cells larger than the LDS")
 ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
+ap.add_argument("--slice", type=int, default=0, metavar="N", help="the Dirichlet driver with one axis-aligned N x N slice through the "
+                "middle of the domain: wall time, sampling counters")
 ap.add_argument("--uniaxial", action="store_true", help="the uniaxial tensor driver on hypercube(n): wall time, cycles, tensor")
 ap.add_argument("--blocks", type=int, default=0, metavar="B", help="block upscaling of hypercube(n) in blocks of B cubes per axis "
                 "against one Dirichlet tensor run per block")
@@ -66,6 +72,39 @@ else:
     sgrid = driver.generate_conductivity(a.dim, width, a.field_seed, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
+if a.slice:
+    if a.polycrystal:
+        principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
+        sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
+    else:
+        sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
+    xi = np.ones(a.dim) / np.sqrt(a.dim)
+    step = a.n / a.slice
+    origin = np.full(a.dim, 1.0 + 0.5 * step)                   # hypercube(n) is the box [1, 1 + n]^dim
+    if a.dim == 3:
+        origin[2] = 1.0 + 0.5 * a.n + 0.3 * step                # the middle of the box, off the lattice planes
+    du, dv = np.zeros(a.dim), np.zeros(a.dim)
+    du[0] = dv[1] = step
+    kw = dict(refinements=a.refinements, xi=xi, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate,
+              smoother=a.smoother, slices=[(origin, du, dv, a.slice, a.slice)])
+    for _ in range(a.warmup):
+        driver.dirichlet_homogenization(a.n, tag, **kw)
+    ctx.sync()
+    t0 = time.perf_counter()
+    r = driver.dirichlet_homogenization(a.n, tag, **kw)
+    ctx.sync()
+    wall = time.perf_counter() - t0
+    s = r["slices"][0]
+    print(json.dumps({"config": f"dirichlet_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}, "
+                                f"slices=[{a.slice} x {a.slice}])",
+                      "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
+                      "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
+                      "energy_form": r["energy_form"], "pixels": int(s["cell"].size), "pixels_inside": int((s["cell"] >= 0).sum()),
+                      "max_energy_density_over_mean": float(np.nanmax(s["energy_density"]) / r["energy_form"]),
+                      "sample_kernel_ns": ctx.counter("sample_kernel_ns"), "sample_download_ns": ctx.counter("sample_download_ns"),
+                      "sample_locator_bytes": ctx.counter("sample_locator_bytes"),
+                      "sample_locator_max_candidates": ctx.counter("sample_locator_max_candidates")}))
+    sys.exit(0)
 if a.extrema:
     if a.polycrystal:
         principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
