@@ -220,7 +220,9 @@ void coarse_pcg(hmg_grid *g)
             throw std::runtime_error("coarse PCG: no convergence to coarse_rtol within coarse_maxit iterations");
     }
     g->coarse_last_it = (int)pr.h[1];
-    g->coarse_budget = std::min(c->coarse_maxit, coarse_budget_for(c, g->coarse_last_it));
+    // (b = 0: every kernel returned at once and the count is 0, which says nothing about the next right-hand side -- a budget
+    // from it, four iterations, made the next solve a miss; that one counts its iterations instead)
+    if (pr.h[3] > 0.0) g->coarse_budget = std::min(c->coarse_maxit, coarse_budget_for(c, g->coarse_last_it));
 }
 
 }  // namespace

@@ -1317,6 +1317,7 @@ static inline int coarse_spmv_blocks(int64_t n)      // 16 lanes per row
 
 void launch_coarse_gather_rhs(const Launch &L, const CoarseDev &A, const double *u, double *b)
 {
+    if (A.n == 0) return;                          // (every node is constrained: no unknown, and a launch of no blocks is an error)
     hipLaunchKernelGGL(k_coarse_gather_rhs, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, L.stream, A.interior,
                        A.n, u, b);
     check_launch();
@@ -1324,6 +1325,7 @@ void launch_coarse_gather_rhs(const Launch &L, const CoarseDev &A, const double 
 void launch_coarse_scatter_sol(const Launch &L, const CoarseDev &A, int64_t nnodes, const double *x, double *u)
 {
     launch_fill(L, u, nnodes, 0.0);
+    if (A.n == 0) return;                          // (x = 0 on every node)
     hipLaunchKernelGGL(k_coarse_scatter_sol, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, L.stream, A.interior,
                        A.n, x, u);
     check_launch();

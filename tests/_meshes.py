@@ -19,7 +19,29 @@ def delaunay_mesh(O, dim, npts, seed):
     return O.Mesh(np.ascontiguousarray(pts[used]), np.sort(remap[cells], axis=1))
 
 
-CUBE_NODES = np.array([(0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1)],
+def fan_mesh(O, dim, ninner, nouter, seed):
+    """One centre node, `ninner` nodes on the unit circle / sphere around it and `nouter` on the one of radius 2, Delaunay as in
+    `delaunay_mesh`.  The inner nodes lie on one sphere with the centre inside it, so no simplex of inner nodes alone is Delaunay:
+    the centre is a neighbour of every one of them and its row of the level-1 matrix has ninner + 1 entries.  The outer nodes are
+    in convex position, so all of them lie on the boundary and the unknowns are the centre (node 0) and the inner nodes
+    (1 .. ninner).  No cell is dropped: tests/test_coarse_solve_host.py holds the smallest cell volume of the meshes in use."""
+    from scipy.spatial import Delaunay
+    rng = np.random.default_rng(seed)
+
+    def shell(n, radius):
+        if dim == 2:
+            phi = 2.0 * np.pi * (np.arange(n) + 0.6 * (rng.random(n) - 0.5)) / n
+            return radius * np.stack([np.cos(phi), np.sin(phi)], axis=1)
+        v = rng.standard_normal((n, 3))
+        return radius * v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    pts = np.concatenate([np.zeros((1, dim)), shell(ninner, 1.0), shell(nouter, 2.0)])
+    cells = np.sort(Delaunay(pts).simplices.astype(np.int64), axis=1)
+    assert np.unique(cells).size == pts.shape[0]
+    return O.Mesh(np.ascontiguousarray(pts), np.ascontiguousarray(cells))
+
+
+CUBE_NODES =np.array([(0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1)],
                       dtype=np.float64)
 CUBE_ELEMENTS = np.array([(1, 2, 3, 5), (2, 3, 4, 8), (3, 5, 7, 8), (2, 5, 6, 8), (2, 3, 5, 8)], dtype=np.int64) - 1
 
