@@ -152,7 +152,8 @@ class Context:
 
     def counter(self, name: str) -> int:
         """Diagnostic counters of the library by name, as include/hmg.h lists them at hmg_ctx_counter ("wave_launches": launches of
-        the one-wave-per-cell level-5 apply; "lazy_r_form" / "lazy_ap_form": what the last V-cycle left pending; "ap_rebuilt": pending
+        the one-wave-per-cell level-5 apply; "lazy_r_form" / "lazy_ap_form" / "lazy_x_form": what the last V-cycle left pending; "x_deferred" / "x_settled": V-cycles that
+        left x-updates pending and those a later call had to finish (option "lazy_x"); "ap_rebuilt": pending
         r-updates that had to form their Ap again first; ...).  -1 for an unknown name."""
         return int(self._lib.hmg_ctx_counter(self.h, name.encode()))
 

@@ -58,7 +58,8 @@ namespace hmg {
 // table terms held across the load phase, no products -- the same weights to the last bit (same products, same order, formed once)
 // LF (fused WC instantiations): the form of the load phase is known at compile time -- 1: one stream in one batch (CG step 0),
 // 2: two streams in one batch, nothing stored (a dead step), 3: the batched general form; 0: decided at run time;
-// 4 (RS): the local residual that carries THREE pending x-updates (ApplyArgs::x4: a fourth stream, batches of a third);
+// 4: a residual that carries THREE pending x-updates (ApplyArgs::x4: a fourth stream, batches of a third) -- RS: the down leg's local
+// residual, restricted in the epilogue; without RS: the first residual of a V-cycle that finishes the x of the cycle before it;
 // 5 (CG): the coarse column is (x + a p) + c (r + b p) of three coarse columns (ApplyArgs::xc_p, xc_r: the coarser level's post-smoother
 // left both its x-updates to this pass).  One form per
 // instantiation: the other forms' values do not compete for the 80 registers, and the dead step can take its rows behind the
@@ -280,9 +281,9 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         const double beta = x2c ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
         const double ax = xac || x3c ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
         const double c2 = x3c ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
-        // x4 (own instantiation, LF == 4): a third pending x-update in front of the two, x + dx4*p0 in the place of x -- the
+        // x4 (own instantiations, LF == 4): a third pending x-update in front of the two, x + dx4*p0 in the place of x -- the
         // roundings of x += a0*p0; x += ax*p1; p2 = r2 + beta*p1; x += c2*p2 done one after the other
-        constexpr bool X4 = FUSED && RS && LF == 4;
+        constexpr bool X4 = FUSED && LF == 4;
         const double *x4c = X4 && a.x4 ? a.x4 + cell * lv.ld : nullptr;
         const double dx4 = x4c ? a.scal[a.d_num] / a.scal[a.d_den] : 0.0;
         // FUSED, optional: the prolongation of the coarse-grid correction, xin = x + P xcoarse (interpolate_and_sum_to!,
@@ -1118,6 +1119,21 @@ static bool weight_cache_ok(const Launch &L, const LevelDev &lv, const MeshDev &
            (a.alpha == 1.0 || a.alpha == -1.0) && a.lambda == mesh.wc_lambda;
 }
 
+bool apply_carries_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double lambda, int updates)
+{
+    // the stored first residual r = b - A x with x's last two or three CG updates in its load phase: level 6's 512-thread shape, the
+    // whole column in the batched load phase; three updates through the one instantiation with the fourth stream (class weights
+    // from the cache)
+    const CellShape s = planned_cell_shape(L, lv);
+    if (s.roles != ROLE_ALL || s.rb != 6 || lv.nf > 13 * 512 || L.slab2_force) return false;
+    if (updates < 3) return true;
+    ApplyArgs a{};
+    a.alpha = -1.0;
+    a.lambda = lambda;
+    a.flags = 1;
+    return weight_cache_ok(L, lv, mesh, a);
+}
+
 static CellRole apply_cell_role(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a, const CellShape &s,
                                 bool fused)
 {
@@ -1132,6 +1148,8 @@ static CellRole apply_cell_role(const Launch &L, const LevelDev &lv, const MeshD
         r.lf = a.xc_p ? 5 : 0;
     else if (r.rs)
         r.lf = a.x4 ? 4 : 0;
+    else if (a.x4)
+        r.lf = 4;                  // (the carrying first residual: launch_apply_dim has checked its operands and the cache)
     else if (r.wc && !a.xacc && !a.x3 && !a.xcoarse && !a.rcoarse)
         // CG step 0; a dead step, or one that writes its direction elsewhere (no store may sit between the loads of a stream it aliases)
         r.lf = !a.x2 ? 1 : !a.xout || a.xout != a.x2 ? 2 : 0;
@@ -1213,9 +1231,10 @@ constexpr uint32_t cell_key(int nt, int spt, int rb, bool cg, bool rs, bool wc, 
 template <int DIM, bool FUSED, bool WD = false>
 static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const ApplyArgs &a)
 {
-    // a third pending x-update: the register-blocked local residual of level 6 alone has the stream (no other family is reached with it)
-    if (a.x4 && !(FUSED && DIM == 3 && !WD && a.x3 && a.x2 && a.xout && a.rcoarse && !a.xcoarse && !a.xacc && !(a.flags & 128) &&
-                  apply_defers3(L, lv)))
+    // a third pending x-update: the register-blocked residuals of level 6 alone have the stream (no other family is reached with it) --
+    // the local residual that restricts in its epilogue, and the stored first residual with its class weights from the cache
+    if (a.x4 && !(FUSED && DIM == 3 && !WD && a.x3 && a.x2 && a.xout && !a.xcoarse && !a.xacc && !(a.flags & 128) &&
+                  (a.rcoarse ? apply_defers3(L, lv) : a.src && a.out && apply_carries_x(L, lv, mesh, a.lambda, 3))))
         throw std::runtime_error("operator apply: a third pending x-update (x4) where no kernel carries it");
     // the coarse x with its last two updates pending: the in-image prolongation of level 6 alone combines the three coarse columns
     if ((a.xc_p || a.xc_r) && !(FUSED && DIM == 3 && !WD && a.xc_p && a.xc_r && a.xcoarse && (a.flags & 64) && !a.x2 && !a.xacc && !a.x3 &&
@@ -1256,6 +1275,7 @@ static void launch_apply_dim(const Launch &L, const LevelDev &lv, const MeshDev 
     HMG_CELL(R3,    512, 13, 6, false, false, true,  0);
     HMG_CELL(RF,    512, 13, 6, false, false, true,  1);
     HMG_CELL(RF,    512, 13, 6, false, false, true,  2);
+    HMG_CELL(RF,    512, 13, 6, false, false, true,  4);
     HMG_CELL(RF,    512, 13, 6, false, true,  false, 0);
     HMG_CELL(RF,    512, 13, 6, false, true,  false, 4);
     HMG_CELL(RF,    512, 13, 6, false, true,  true,  0);

@@ -284,6 +284,10 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "r_dropped") return ctx->r_dropped;              // ... and those that never had to be
     if (n == "lazy_ap_form") return ctx->last_ap_form;        // the last hmg_vcycle / hmg_fcg_step: 1 its record was left without a stored Ap (option lazy_ap)
     if (n == "ap_rebuilt") return ctx->ap_rebuilt;            // pending r-updates that had to run the last CG step's apply again first
+    if (n == "lazy_x_form") return ctx->last_x_form;          // the last hmg_vcycle: x-updates it left pending on its top level's x (0, 2, 3; option lazy_x)
+    if (n == "x_deferred") return ctx->x_deferred;            // V-cycles that left them pending
+    if (n == "x_settled") return ctx->x_settled;              // ... whose x a later call finished with the x-only tail (the others rode in the next first residual)
+    if (n == "x_settled_read") return ctx->x_settled_read;    // ... of them: by a call that was handed x or a vector the updates rest on
     if (n == "coarse_x_folds") return ctx->coarse_x_folds;
     if (n == "cell_moments_kernel_ns") return ctx->moments_kernel_ns;       // the last hmg_cell_moments: kernel alone
     if (n == "cell_moments_download_ns") return ctx->moments_download_ns;   // ... and the download of its per-cell sums
@@ -323,7 +327,7 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         {"coarse_probe", &hmg_ctx::coarse_probe}, {"fuse_cg", &hmg_ctx::fuse_cg_default}, {"fold_x", &hmg_ctx::fold_x},
         {"swap_rp", &hmg_ctx::swap_rp}, {"fold_prolong", &hmg_ctx::fold_prolong}, {"zero_entry", &hmg_ctx::zero_entry},
         {"fold_restrict", &hmg_ctx::fold_restrict}, {"lazy_dead", &hmg_ctx::lazy_dead}, {"lazy_pre", &hmg_ctx::lazy_pre}, {"fold_coarse_x", &hmg_ctx::fold_coarse_x}, {"fold_faces", &hmg_ctx::fold_faces},
-        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"lazy_r", &hmg_ctx::lazy_r}, {"lazy_ap", &hmg_ctx::lazy_ap}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
+        {"lean_post", &hmg_ctx::lean_post}, {"lazy_post", &hmg_ctx::lazy_post}, {"lazy_r", &hmg_ctx::lazy_r}, {"lazy_ap", &hmg_ctx::lazy_ap}, {"lazy_x", &hmg_ctx::lazy_x}, {"prolong_in_image", &hmg_ctx::prolong_in_image},
         {"comm_rehearsal", &hmg_ctx::comm_rehearsal}};
     for (const auto &f : flags)
         if (n == f.first) {

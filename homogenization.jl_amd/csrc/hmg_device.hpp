@@ -139,7 +139,7 @@ struct ApplyArgs {
     int a_num, a_den;
     const double *x3;      // optional (k_apply FUSED, with x2, without xacc): xin = (x + ax*x2) + c*(x3 + beta*x2),
     int c_num, c_den;      //   ax = scal[a_num]/scal[a_den], c = scal[c_num]/scal[c_den]: two CG x-updates at once
-    const double *x4;      // optional (x3 mode of the register-blocked k_apply that restricts in its epilogue -- apply_defers3() -- only):
+    const double *x4;      // optional (x3 mode of the register-blocked k_apply -- apply_defers3(), apply_carries_x() -- only):
     int d_num, d_den;      //   x + (scal[d_num]/scal[d_den]) * x4 takes the place of x, a third x-update in front of the two.  Every
                            //   other kernel family (k_apply_wave, k_apply_small, k_apply_slab / _slab2, k_apply_rows) refuses it
     const double *xcoarse; // optional (fused kernel, not the slab one): xin = x + P xcoarse first (prolongation of the
@@ -223,6 +223,9 @@ bool apply_restricts(const Launch &L, const LevelDev &lv);
 bool apply_folds_coarse_x(const Launch &L, const LevelDev &lv);
 // ... and can that residual carry three pending x-updates (ApplyArgs::x4)?  Level 6's 512-thread shape only.
 bool apply_defers3(const Launch &L, const LevelDev &lv);
+// ... and can the stored first residual r = b - A x (src, out, xout = x) carry the last `updates` (2 or 3) CG x-updates of the V-cycle
+// before it?  Level 6's 512-thread shape only; three of them with the class weights from the cache (one instantiation has the stream).
+bool apply_carries_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double lambda, int updates);
 // Fused CG pass, see k_apply<.., FUSED>: the kernel (possibly over a cell list, several launches) leaves
 // per-cell partial sums in mesh.blockpart; the reduce step turns them into scal[slot_pap] = sum mult*xin*out and
 // scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.mult / a.blockpart are filled in here, and a.scal where the caller left
@@ -290,7 +293,14 @@ void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDe
 // ... its x-updates alone (the r half stays pending); alpha_out[0] = scal[s_num]/scal[s_den], alpha_out[1] = 1.0,
 // alpha_out[2] = scal[b_num], alpha_out[3] = scal[b_den] (four doubles)
 void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
-                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out);
+                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out,
+                      const double *scal = nullptr);
+// ... left pending too (option lazy_x): the scalars it would read, saved to out[0..8) -- out[0..4) as launch_cg_x_tail leaves them,
+// out[4] / out[5] = scal[a_num], scal[a_den], out[6] / out[7] = scal[z_num], scal[z_den] (0, 1 unless `three`).  launch_cg_x_tail with
+// scal = out, the slots (0, 1; 4, 5; 2, 3; 6, 7) and a null alpha_out is then the launch not made here (scal: the bank it reads, default
+// the context's)
+void launch_cg_x_save(const Launch &L, int s_num, int s_den, int a_num, int a_den, int b_num, int b_den, bool three, int z_num, int z_den,
+                      double *out);
 // x += (scal[a_num]/scal[a_den]) p; with_p: p = r + (scal[s_num]/scal[s_den]) p
 void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, int a_num, int a_den,
                          int s_num, int s_den, int with_p);

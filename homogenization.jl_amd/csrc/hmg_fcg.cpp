@@ -170,7 +170,8 @@ int hmg_fcg_step(void *handle, hmg_vec *x, hmg_vec **states)
     hmg_vec *b_keep = top[1];
     top[1] = f->R;
     try {
-        vcycle(f->g, f->level, f->steps, f->steps_coarse, states, /*top=*/true, /*zero_guess=*/true);
+        // (with a direction to combine with, the first reader of z is the pass that forms z.q: it can take z's last updates)
+        vcycle(f->g, f->level, f->steps, f->steps_coarse, states, /*top=*/true, /*zero_guess=*/true, /*lazy_x=*/f->have_dir);
     } catch (...) {
         top[1] = b_keep;
         throw;
@@ -179,7 +180,13 @@ int hmg_fcg_step(void *handle, hmg_vec *x, hmg_vec **states)
     const double *zd = top[0]->d;                        // (read after the V-cycle, which exchanges device pointers of handles)
     const FcgLaunch F = launch_of(f);
     if (f->have_dir) {
-        launch_fcg_dot_zq(F, zd, qd, n);
+        const PendingX px = take_pending_x(f->g, top[0]);
+        if (px.form)
+            // z = x lacks its last two or three CG updates (option lazy_x): formed where z.q reads it, 48 B/DOF instead of 40 + 16
+            launch_fcg_dot_zq_x(F, top[0]->d, px.form == 3 ? f->g->top_spare.p : px.p->d, px.form == 3 ? px.p->d : nullptr, px.r->d,
+                                f->g->pend_alpha(), qd, n);
+        else
+            launch_fcg_dot_zq(F, zd, qd, n);
         scalar_sum(f->g, FB_ZQ, 1);
     }
     launch_fcg_direction(F, pd, zd, n, f->have_dir ? 0 : 1);

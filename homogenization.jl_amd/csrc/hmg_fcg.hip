@@ -39,6 +39,45 @@ k_fcg_dot_zq(const double *__restrict__ z, const double *__restrict__ q, int64_t
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+// ... where the V-cycle left z's last CG updates pending (option lazy_x): z = ((z [+ az p0]) + ax p1) + alpha (r2 + beta p1) formed
+// here -- k_cg_x_tail's arithmetic from the eight ratios it would have read (sc: launch_cg_x_save) --, stored, and used in the
+// dot product: 48 B/DOF (40 with two updates) instead of the tail's 40 (32) + 16.  XU == 2: three updates, p0 is read.
+template <int XU>
+__global__ void __launch_bounds__(FB)
+k_fcg_dot_zq_x(double *z, const double *__restrict__ p1, const double *__restrict__ p0, const double *__restrict__ r2,
+               const double *__restrict__ sc, const double *__restrict__ q, int64_t n, double *__restrict__ part)
+{
+    __shared__ double red[4];
+    const double alpha = sc[0] / sc[1];
+    const double ax = sc[4] / sc[5];
+    const double beta = sc[2] / sc[3];
+    const double az = XU == 2 ? sc[6] / sc[7] : 0.0;
+    const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
+    double acc = 0.0;
+    if (i < (n >> 1)) {
+        double2 zv = reinterpret_cast<double2 *>(z)[i];
+        const double2 pv = reinterpret_cast<const double2 *>(p1)[i], rv = reinterpret_cast<const double2 *>(r2)[i],
+                      qv = reinterpret_cast<const double2 *>(q)[i];
+        if (XU == 2) {
+            const double2 ov = reinterpret_cast<const double2 *>(p0)[i];
+            zv.x = axpy1(az, ov.x, zv.x);
+            zv.y = axpy1(az, ov.y, zv.y);
+        }
+        zv.x = xupd2(ax, beta, alpha, zv.x, pv.x, rv.x);
+        zv.y = xupd2(ax, beta, alpha, zv.y, pv.y, rv.y);
+        reinterpret_cast<double2 *>(z)[i] = zv;
+        acc = __builtin_fma(zv.x, qv.x, acc);
+        acc = __builtin_fma(zv.y, qv.y, acc);
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double zl = xupd2(ax, beta, alpha, XU == 2 ? axpy1(az, p0[n - 1], z[n - 1]) : z[n - 1], p1[n - 1], r2[n - 1]);
+        z[n - 1] = zl;
+        acc = __builtin_fma(zl, q[n - 1], acc);
+    }
+    const double s = block_sum(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
 // beta = -(z.q) / (p.q)_prev; a vanishing (p.q)_prev means the iteration had already arrived: the old direction is dropped
 __global__ void __launch_bounds__(FB)
 k_fcg_direction(double *p, const double *__restrict__ z, int64_t n, const double *__restrict__ bank, double *fs, int first)
@@ -178,6 +217,20 @@ void launch_fcg_dot_zq(const FcgLaunch &F, const double *z, const double *q, int
     const int64_t nb = fcg_blocks(n);
     check_blocks(nb);
     hipLaunchKernelGGL(k_fcg_dot_zq, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, q, n, F.part);
+    check_launch();
+    reduce<1>(F, nb, FB_ZQ);
+}
+
+void launch_fcg_dot_zq_x(const FcgLaunch &F, double *z, const double *p1, const double *p0, const double *r2, const double *saved,
+                         const double *q, int64_t n)
+{
+    if (!z || !p1 || !r2 || !saved || !q) throw std::runtime_error("flexible CG: pending updates of z without their vectors");
+    const int64_t nb = fcg_blocks(n);
+    check_blocks(nb);
+    if (p0)
+        hipLaunchKernelGGL(k_fcg_dot_zq_x<2>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, p1, p0, r2, saved, q, n, F.part);
+    else
+        hipLaunchKernelGGL(k_fcg_dot_zq_x<1>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, p1, p0, r2, saved, q, n, F.part);
     check_launch();
     reduce<1>(F, nb, FB_ZQ);
 }

@@ -568,14 +568,7 @@ k_cg_rupdate(const double *r, double *rout, const double *__restrict__ q, int64_
 struct XUSlots {
     int a_num, a_den, b_num, b_den, z_num, z_den;
 };
-// the two pending x-updates of a lazy last step, p_i formed on the fly: (x + ax p) + alpha (r + beta p).  One function for the
-// r-update that carries them and for the x-only tail (k_cg_x_tail): the roundings cannot drift apart.
-__device__ __forceinline__ double xupd2(double ax, double beta, double alpha, double xv, double pv, double rv)
-{
-    const double t1 = axpy1(ax, pv, xv);
-    const double p2 = axpy1(beta, pv, rv);
-    return axpy1(alpha, p2, t1);
-}
+// (the two pending x-updates themselves: xupd2() of hmg_stencil.hpp, shared with the flexible CG's kernel that forms z from them)
 template <int XU>
 __global__ void __launch_bounds__(SB)
 k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, int64_t n, const double *__restrict__ scal,
@@ -672,11 +665,29 @@ k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ 
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (n & 1) x[n - 1] = xupd2(ax, beta, alpha, XU == 2 ? axpy1(az, p0[n - 1], x[n - 1]) : x[n - 1], p[n - 1], r[n - 1]);
+        if (!alpha_out) return;                  // (run late from the saved scalars, k_cg_x_save: they hold all of this already)
         alpha_out[0] = alpha;
         alpha_out[1] = 1.0;
         alpha_out[2] = scal[xs.b_num];           // beta as the apply of this step read it: the same division forms it again
         alpha_out[3] = scal[xs.b_den];
     }
+}
+
+// What k_cg_x_tail reads from the scalar bank, saved instead of used (hmg_vcycle, option lazy_x: the x-updates stay pending as well):
+// out[0..4) as k_cg_x_tail leaves them, out[4] / out[5] numerator and denominator of ax, out[6] / out[7] of az (0 / 1 without a third
+// update).  k_cg_x_tail, or a residual that carries the updates in its load phase, run later with `out` as its scalars forms every
+// ratio by the same division of the same numbers, whatever the scalar bank holds by then.
+__global__ void k_cg_x_save(const double *__restrict__ scal, int s_num, int s_den, XUSlots xs, int three, double *out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    out[0] = scal[s_num] / scal[s_den];
+    out[1] = 1.0;
+    out[2] = scal[xs.b_num];
+    out[3] = scal[xs.b_den];
+    out[4] = scal[xs.a_num];
+    out[5] = scal[xs.a_den];
+    out[6] = three ? scal[xs.z_num] : 0.0;
+    out[7] = three ? scal[xs.z_den] : 1.0;
 }
 
 // x += alpha p (alpha = scal[a_num]/scal[a_den]) and, if with_p, p = r + beta p (beta = scal[s_num]/scal[s_den])
@@ -876,16 +887,27 @@ void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDe
 
 // the x-updates of launch_cg_rupdate_faces_x alone; alpha_out[0..4) = s_num/s_den, 1.0, scal[b_num], scal[b_den]
 void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
-                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out)
+                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out, const double *scal)
 {
-    if (!alpha_out || n <= 0) throw std::runtime_error("x-only tail without a place for its step length");
+    if ((!alpha_out && !scal) || n <= 0) throw std::runtime_error("x-only tail without a place for its step length");
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
     const XUSlots xs{a_num, a_den, b_num, b_den, z_num, z_den};
+    if (!scal) scal = L.scal;
     if (p0)
-        hipLaunchKernelGGL(k_cg_x_tail<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, L.scal, s_num, s_den, xs, alpha_out);
+        hipLaunchKernelGGL(k_cg_x_tail<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, scal, s_num, s_den, xs, alpha_out);
     else
-        hipLaunchKernelGGL(k_cg_x_tail<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, L.scal, s_num, s_den, xs, alpha_out);
+        hipLaunchKernelGGL(k_cg_x_tail<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, scal, s_num, s_den, xs, alpha_out);
+    check_launch();
+}
+
+// ... not run at all: what it would read from the scalar bank goes to out[0..8) (k_cg_x_save)
+void launch_cg_x_save(const Launch &L, int s_num, int s_den, int a_num, int a_den, int b_num, int b_den, bool three, int z_num, int z_den,
+                      double *out)
+{
+    if (!out) throw std::runtime_error("pending x-updates without a place for their scalars");
+    const XUSlots xs{a_num, a_den, b_num, b_den, three ? z_num : 0, three ? z_den : 0};
+    hipLaunchKernelGGL(k_cg_x_save, dim3(1), dim3(1), 0, L.stream, L.scal, s_num, s_den, xs, three ? 1 : 0, out);
     check_launch();
 }
 

@@ -226,6 +226,7 @@ struct hmg_ctx {
     bool fold_coarse_x = true;  // ... and the level below the finest leaves them to the finest level's first residual, which reads that x anyway (see coarse_x_folds())
     bool lazy_r = true;         // hmg_vcycle / hmg_fcg_step: the finest level's last r-update only finishes x; r_3 is formed when somebody reads it (PendingR)
     bool lazy_ap = true;        // ... and the CG step in front of it does not store A p_2 (three-update form): the record rebuilds it when r is read (PendingR::ap_stored)
+    bool lazy_x = true;         // ... and the x-updates of that launch stay pending too: the next hmg_vcycle's first residual forms x where it reads it (PendingX)
     int lazy_top = 2;           // ... on the finest level its last step leaves both x-updates to the r-update, 2: and the step before its own (see smooth_form())
     bool zero_entry = true;        // V-cycle: a coarse level's zero initial guess is never materialised (see zero_entry_ok())
     bool fold_restrict = true;     // V-cycle: the restriction rides in the epilogue of the local residual, which is then not stored
@@ -280,6 +281,10 @@ struct hmg_ctx {
     int64_t r_dropped = 0;                   // ... and those nobody read: overwritten by the next V-cycle, a copy or a fill, or destroyed
     int last_ap_form = 0;                    // 1: the last hmg_vcycle / hmg_fcg_step left that pending r without a stored Ap (option lazy_ap)
     int64_t ap_rebuilt = 0;                  // pending residuals whose Ap had to be formed first: the last CG step's apply, launched late
+    int last_x_form = 0;                     // x-updates the last hmg_vcycle left pending on its top level's x: 0, 2 or 3 (option lazy_x)
+    int64_t x_deferred = 0;                  // V-cycles that left them pending ...
+    int64_t x_settled = 0;                   // ... those of them a later call had to finish (the eager x-only tail, launched late; the others rode in a first residual)
+    int64_t x_settled_read = 0;              // ... of those: because a call was handed x or the direction it rests on
     int last_top_form = 0;                   // form the last finest-level post-smoother inside hmg_vcycle took: 0 plain, 1 two-update, 2 three-update
     // Level-vector memory handed back by hmg_vec_destroy, kept for the next hmg_vec_create of the same size: on this
     // platform hipMalloc of memory the process has freed before costs ~35 ms per GB (tools/dev/alloc_probe.hip: 6 x 10 GB
@@ -321,7 +326,21 @@ struct PendingR {
     bool ap_stored = true;      // false: Ap is still to be rebuilt (option lazy_ap)
     bool orphan_Ap = false;     // Ap's handle was destroyed while r still needs its memory: the record owns it until it closes
 };
-// (hmg_*_destroy may come from any thread, a finalizer's for one: it never launches.  Whoever touches the record holds the lifetime lock.)
+// (hmg_*_destroy may come from any thread, a finalizer's for one: it launches only where a vector goes that pending x-updates rest on.
+//  Whoever touches the records holds the lifetime lock.)
+
+// The x-updates of that last launch, not launched either (option lazy_x): x lacks  x += a0 p0 (form 3 only);  x += a1 p1;
+// x += a2 (r2 + b2 p1).  p1 is the p handle's memory (form 2) or the grid's spare vector (form 3, where the p handle holds p0), r2 the r
+// handle's -- so the record lives inside an unformed PendingR on the same r, which settles it before r changes -- and the ratios are the
+// eight doubles of hmg_grid::pend_alpha() (launch_cg_x_save).  The next hmg_vcycle on the same states forms x in the load phase of its
+// first residual (apply_carries_x: the x3 / x4 streams the down leg's local residual has), which writes x and r in one pass; every other
+// call that is handed x, p or r, or changes what they rest on, runs the x-only tail first (settle_x()).  The bits do not depend on the path.
+// form 0: x was finished at once because the caller read it after the cycle before (hmg_grid::x_reader, as r_reader); the record watches.
+struct PendingX {
+    hmg_vec *x = nullptr, *p = nullptr, *r = nullptr;
+    int level = 0;
+    int form = 0;
+};
 
 struct hmg_grid {
     int refs = 1;
@@ -338,10 +357,12 @@ struct hmg_grid {
     DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
     DevBuf<uint16_t> d_dmask, d_dupmask;
     DevBuf<uint8_t> d_mult;
-    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last four doubles: step length and beta of a pending r-update
+    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last eight doubles: step length and beta of a pending r-update, the ratios of pending x-updates
     PendingR pend;
+    PendingX pendx;
+    bool x_reader = false;                       // a caller's read settled pending x-updates and no V-cycle's x went unread since (see PendingX)
     bool r_reader = false;                       // a caller's read settled a record and none was dropped unread since (see PendingR)
-    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 4 : nullptr; }
+    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 8 : nullptr; }
     bool fuse_cg = true;
     DevBuf<double> d_coef;
     std::vector<double> sigma, coef;
@@ -477,15 +498,25 @@ inline const LevelDev &lev(const hmg_grid *g, int level)
 void materialize_r(hmg_grid *g, bool read = false);
 // a record that has its Ap still to rebuild (option lazy_ap) is settled before what the rebuild rests on changes: the operator, lambda,
 // the spare vector, the context's options.  Not a read.  A record that holds its Ap stays open.
+// ... and pending x-updates always (the spare vector, the kernel choice)
+void settle_x(hmg_grid *g, bool read = false);
+// the flexible CG's first pass over z forms them itself: the record on x, if it has updates to form, is handed over and closed (a
+// record that only watches stays: hmg_fcg_step is a reader of its V-cycle's x like any other, and the next lines say so)
+PendingX take_pending_x(hmg_grid *g, const hmg_vec *x);
 inline void settle_rebuild(hmg_grid *g)
 {
+    if (g && g->ctx && g->pendx.x) settle_x(g);
     if (g && g->ctx && g->pend.r && !g->pend.ap_stored) materialize_r(g);
 }
 // every entry point that is handed a vector goes through one of these three before it touches it:
 // the vector is read or partly written -- a pending r or Ap is settled first
+// (pending x-updates first, if v is x or a vector they rest on: forming r overwrites one of those)
 inline void settle(const hmg_vec *v)
 {
-    if (v && v->g && v->g->pend.r && (v == v->g->pend.r || v == v->g->pend.Ap)) materialize_r(v->g, /*read=*/true);
+    if (!v || !v->g) return;
+    const PendingX &px = v->g->pendx;
+    if (px.x && (v == px.x || v == px.p || v == px.r)) settle_x(v->g, /*read=*/v != px.r);
+    if (v->g->pend.r && (v == v->g->pend.r || v == v->g->pend.Ap)) materialize_r(v->g, /*read=*/true);
 }
 // every entry of the vector is about to be overwritten unread: a pending r is dropped, a pending Ap settled
 void settle_overwritten(const hmg_vec *v);
@@ -555,7 +586,8 @@ void ensure_smoother_diag(hmg_grid *g, int top, hmg_vec **states);
 void release_smoother_diag(hmg_grid *g);
 // zero_guess (top level only; below it always holds): x is to be taken as zero whatever it holds -- never written where the
 // smoother's form allows that (zero_entry_ok), filled first otherwise: the same bits either way
-void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top = true, bool zero_guess = false);
+// lazy_x: the caller is not the next reader of the top level's x (hmg_vcycle; hmg_fcg_step reads it at once)
+void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top = true, bool zero_guess = false, bool lazy_x = false);
 
 // ---- hmg_coarse.cpp ----
 void coarse_solve(hmg_grid *g, hmg_vec *b1, hmg_vec *x1);

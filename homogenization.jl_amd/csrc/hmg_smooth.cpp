@@ -262,6 +262,9 @@ struct SmoothForm {
                             // (zero_entry_ok): the first residual is the constrained copy of b, b - A 0 to the last bit
     bool lazy_r = false;    // (set by the caller, tails Top2 / Top3) the last launch finishes x only and leaves the r-update
                             // pending on the grid (lazy_r_ok())
+    bool lazy_x = false;    // (set by the caller, with lazy_r) ... and may leave x's updates pending as well (lazy_x_ok())
+    int carry_x = 0;        // (set by the caller, Role::Pre on the top level of hmg_vcycle) 2 / 3: x lacks the last two / three updates of
+                            // the V-cycle before, which ride in the first residual (PendingX, taken out of the grid by enter_top())
 };
 
 // What a pre-smoother leaves to its caller (tails DeadDefer, DeadDefer2 and DeadDefer3), or a post-smoother below the finest level
@@ -414,8 +417,8 @@ namespace {
 
 // r = b - A x, constraint, interface sum (src/multigrid.jl:50): the first residual of both smoothers, with the forms its caller
 // may ask for -- x a zero that is not in memory (f.x_zero), the coarse-grid correction riding in the load phase (xcoarse, cx)
-void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, const SmoothForm &f, const hmg_vec *xcoarse,
-                    const DeferredX *cx)
+void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, const hmg_vec *p, const SmoothForm &f,
+                    const hmg_vec *xcoarse, const DeferredX *cx)
 {
     const LevelDev &lv = lev(g, level);
     const Launch &L = g->ctx->L;
@@ -454,6 +457,28 @@ void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, 
                 a.c_den = cx->pap;
                 g->ctx->coarse_x_folds += 1;
             }
+            apply_then_sum(g, lv, a, true, -1, -1);
+        } else if (f.carry_x) {
+            // x still lacks the last CG updates of the V-cycle before this one (option lazy_x): formed in the load phase as the down
+            // leg's local residual forms them, from p0 (three updates: the p handle), p1 (the spare vector / the p handle) and r2 (still
+            // in r) with the ratios k_cg_x_save put aside, and written back -- 56 B/DOF instead of 40 + 24.  r goes over r2 in place:
+            // a workgroup reads its own cell's column of it alone, in the load phase, and stores behind the barrier after it.
+            need(f.carry_x == 2 || g->top_spare.p != nullptr, "pending x-updates have lost the spare vector they rest on");
+            a.x2 = f.carry_x == 3 ? g->top_spare.p : p->d;
+            a.x3 = r->d;
+            if (f.carry_x == 3) {
+                a.x4 = p->d;
+                a.d_num = 6;
+                a.d_den = 7;
+            }
+            a.a_num = 4;
+            a.a_den = 5;
+            a.s_num = 2;
+            a.s_den = 3;
+            a.c_num = 0;
+            a.c_den = 1;
+            a.xout = x->d;
+            a.scal = g->pend_alpha();
             apply_then_sum(g, lv, a, true, -1, -1);
         } else {
             apply_then_sum(g, lv, a, false, -1, -1);
@@ -549,6 +574,31 @@ bool lazy_ap_ok(const hmg_grid *g, const SmoothForm &f)
     return g->ctx->lazy_ap && f.tail == Tail::Top3 && f.lazy_r && !g->r_reader;
 }
 
+// May that launch leave the x-updates pending as well (option lazy_x)?  Under lazy_r_ok()'s conditions with x and p added (the spare
+// vector is the library's own), on a level whose first residual can carry them (apply_carries_x()).
+bool lazy_x_ok(const hmg_grid *g, int level, Tail tail, const hmg_vec *x, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap)
+{
+    if (!g->ctx->lazy_x || !g->fuse_cg) return false;
+    for (const hmg_vec *v : {x, p})
+        if (!v->own || v->exposed) return false;
+    if (x == r || x == p || x == Ap || p == r || p == Ap) return false;
+    return apply_carries_x(g->ctx->L, lev(g, level), g->md, g->lambda, tail == Tail::Top3 ? 3 : 2);
+}
+
+// form 0: x is finished (its reader memory is set); the record watches whether it is read again
+void open_pending_x(hmg_grid *g, int level, hmg_vec *x, hmg_vec *p, hmg_vec *r, int form)
+{
+    LifetimeLock lock(lifetime_mutex());
+    need(!g->pendx.x, "pending x-updates were not settled before the next ones");
+    g->pendx.x = x;
+    g->pendx.p = form ? p : nullptr;
+    g->pendx.r = form ? r : nullptr;
+    g->pendx.level = level;
+    g->pendx.form = form;
+    g->ctx->last_x_form = form;
+    if (form) g->ctx->x_deferred += 1;
+}
+
 DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
                  const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
 {
@@ -559,7 +609,8 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
     // (a record without a stored Ap rests on the spare vector, which these two tails write: on other vectors than the record's --
     //  hmg_vcycle_down / _up next to a V-cycle's states -- nothing else has settled it)
     if (f.tail == Tail::Top3 || f.tail == Tail::DeadDefer3) settle_rebuild(g);
-    first_residual(g, level, x, b, r, f, xcoarse, cx);
+    need(!f.carry_x || (!f.x_zero && !xcoarse), "pending x-updates where the first residual cannot carry them");
+    first_residual(g, level, x, b, r, p, f, xcoarse, cx);
     if (g->smoother == 1) {
         smooth_pcg(g, level, steps, x, r, p, Ap, f);
         return {};
@@ -698,8 +749,12 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.xout = a.xacc = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
         if (f.lazy_r && !g->r_reader) {
-            launch_cg_x_tail(L, r->d, n, cur, S_PAP2, x->d, p->d, other, S_PAP, cur, other, nullptr, 0, 0, g->pend_alpha());
+            if (f.lazy_x && !g->x_reader)
+                launch_cg_x_save(L, cur, S_PAP2, other, S_PAP, cur, other, false, 0, 0, g->pend_alpha());
+            else
+                launch_cg_x_tail(L, r->d, n, cur, S_PAP2, x->d, p->d, other, S_PAP, cur, other, nullptr, 0, 0, g->pend_alpha());
             open_pending(g, level, r, Ap, other, false);
+            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 2);
             return {};
         }
         launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, other, x->d, p->d, other, S_PAP, cur, other,
@@ -713,19 +768,27 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.xout = a.xacc = nullptr;
         a.s_num = S_RS3;
         a.s_den = cur;
+        auto x_tail3 = [&]() {     // the three x-updates now, or their ratios put aside (option lazy_x)
+            if (f.lazy_x && !g->x_reader)
+                launch_cg_x_save(L, S_RS3, S_PAP3, cur, S_PAP2, S_RS3, cur, true, other, S_PAP, g->pend_alpha());
+            else
+                launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
+        };
         if (lazy_ap_ok(g, f)) {
             // A p_2 has one reader, the pending r-update: the step delivers p_2.Ap_2 alone -- the pre-smoother's dead launch (16 instead
             // of 24 B/DOF, no interface sum) -- and the record forms Ap again if somebody reads r (materialize_r())
             a.out = nullptr;
             apply_then_sum(g, lv, a, true, S_PAP3, -1);
-            launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
+            x_tail3();
             open_pending(g, level, r, Ap, other, false, /*ap_stored=*/false);
+            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 3);
             return {};
         }
         apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
         if (f.lazy_r && !g->r_reader) {
-            launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
+            x_tail3();
             open_pending(g, level, r, Ap, other, false);
+            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 3);
             return {};
         }
         launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, S_RS3, S_PAP3, other, x->d, g->top_spare.p, cur, S_PAP2,
@@ -758,8 +821,10 @@ bool zero_entry_ok(const hmg_grid *g, int k, int steps)
 }
 
 // Returns the number of x-updates the pre-smoother left to the local residual (hmg_ctx_counter "lazy_pre_form").
-int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false, bool x_zero = false, int steps_next = -1)
+int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false, bool x_zero = false, int steps_next = -1,
+                int carry_x = 0)
 {
+    // carry_x: this level's x lacks the last x-updates of the V-cycle before (enter_top()): the pre-smoother's first residual has them
     // x_zero: this level's x is a zero nobody has written (see zero_entry_ok); steps_next: the CG steps the next coarser
     // level will take (inside hmg_vcycle; decides whether ITS zero initial guess has to be written)
     // inside (hmg_vcycle): nobody can read this level's r before the post-smoother's first residual overwrites it
@@ -771,6 +836,7 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
     SmoothForm form = smooth_form(g, k, steps, Role::Pre);
     need(!x_zero || form.tail == Tail::DeadDefer2, "zero initial guess: the pre-smoother does not defer both x-updates");
     form.x_zero = x_zero;
+    form.carry_x = carry_x;
     const DeferredX dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form);
     const int deferred = dx.rs < 0 ? 0 : dx.three_updates ? 3 : dx.two_updates ? 2 : 1;
     const bool skip_fill = inside && steps_next >= 0 && zero_entry_ok(g, k - 1, steps_next);
@@ -827,7 +893,7 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
 // cx: what level k - 1's post-smoother left of its x (hand_up); hand_up: may this level's post-smoother leave its own in turn?
 // lazy_r: the caller is hmg_vcycle / hmg_fcg_step on its top level and has settled the grid's pending record
 DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const DeferredX *cx = nullptr, bool hand_up = false,
-                    bool lazy_r = false)
+                    bool lazy_r = false, bool lazy_x = false)
 {
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
@@ -841,6 +907,7 @@ DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, cons
     SmoothForm form = smooth_form(g, k, steps, role);
     form.hand_up = hand_up && form.tail == Tail::DeadX2;
     form.lazy_r = lazy_r && (form.tail == Tail::Top2 || form.tail == Tail::Top3) && lazy_r_ok(g, cur[2], cur[3], cur[4]);
+    form.lazy_x = lazy_x && form.lazy_r && lazy_x_ok(g, k, form.tail, cur[0], cur[2], cur[3], cur[4]);
     return smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form, fold_p ? nxt[0] : nullptr, cx);
 }
 
@@ -860,7 +927,8 @@ bool coarse_x_folds(const hmg_grid *g, int k, int steps_below)
 }
 
 // hand_up: the level above finishes this level's x in its first residual (coarse_x_folds()); returns what is left to it
-DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool hand_up)
+DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool hand_up,
+                       int carry_x = 0, bool lazy_x = false)
 {
     // ref: src/multigrid.jl:73-119
     if (k == 1) {                                  // (the scatter of the level-1 solution overwrites every entry of x)
@@ -872,11 +940,11 @@ DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec 
     //  a zero guess on the top level (hmg_fcg_step) is written here on the same condition)
     const bool x_zero = (zero_guess || !top) && zero_entry_ok(g, k, steps);
     if (top && zero_guess && !x_zero) launch_fill(g->ctx->L, st[5 * (k - 1)]->d, vec_len(st[5 * (k - 1)]), 0.0);
-    const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse);
+    const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse, carry_x);
     if (top) g->ctx->last_pre_form = deferred;
     const DeferredX cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
-    if (top) g->ctx->last_top_form = g->ctx->last_r_form = g->ctx->last_ap_form = 0;
-    return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up, /*lazy_r=*/top);
+    if (top) g->ctx->last_top_form = g->ctx->last_r_form = g->ctx->last_ap_form = g->ctx->last_x_form = 0;
+    return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up, /*lazy_r=*/top, /*lazy_x=*/top && lazy_x);
 }
 
 }  // namespace
@@ -899,6 +967,7 @@ void close_pending(hmg_grid *g)
 
 void drop_pending(hmg_grid *g)
 {
+    settle_x(g);                                 // (pending x-updates read the r_2 that is about to go)
     if (!g->pend.formed) g->ctx->r_dropped += 1;
     g->r_reader = false;                         // nobody read it: the next V-cycle defers
     close_pending(g);
@@ -906,9 +975,73 @@ void drop_pending(hmg_grid *g)
 
 }  // namespace
 
+// The eager launch of pending x-updates, now: k_cg_x_tail on (x, p1, p0, r2) with the ratios put aside as its scalars.  Before
+// anything that forms or drops the pending r on the same vectors: the rebuild of Ap reads r_2 and the spare vector and writes Ap
+// alone, the r-update then overwrites r_2 -- x first, and both see their inputs.
+void settle_x(hmg_grid *g, bool read)
+{
+    LifetimeLock lock(lifetime_mutex());
+    const PendingX q = g->pendx;
+    if (!q.x) return;
+    if (q.form) {
+        HIPCHK(hipSetDevice(g->ctx->device));
+        const double *saved = g->pend_alpha();
+        need(saved != nullptr && (q.form == 2 || g->top_spare.p != nullptr), "pending x-updates have lost the spare vector they rest on");
+        if (q.form == 3)
+            launch_cg_x_tail(g->ctx->L, q.r->d, vec_len(q.x), 0, 1, q.x->d, g->top_spare.p, 4, 5, 2, 3, q.p->d, 6, 7, nullptr, saved);
+        else
+            launch_cg_x_tail(g->ctx->L, q.r->d, vec_len(q.x), 0, 1, q.x->d, q.p->d, 4, 5, 2, 3, nullptr, 0, 0, nullptr, saved);
+        g->ctx->x_settled += 1;
+        if (read) g->ctx->x_settled_read += 1;
+    }
+    g->pendx = PendingX{};
+    if (read) g->x_reader = true;                // (the next V-cycle finishes its x at once and watches again)
+}
+
+PendingX take_pending_x(hmg_grid *g, const hmg_vec *x)
+{
+    LifetimeLock lock(lifetime_mutex());
+    const PendingX q = g->pendx;
+    if (q.x == x && !q.form) {                   // (only watched: this reader costs nothing where the updates ride with it)
+        g->pendx = PendingX{};
+        g->x_reader = false;
+        return PendingX{};
+    }
+    if (q.x != x) {
+        settle_x(g);
+        return PendingX{};
+    }
+    need(g->pend_alpha() != nullptr && (q.form == 2 || g->top_spare.p != nullptr), "pending x-updates have lost the spare vector they rest on");
+    g->pendx = PendingX{};
+    return q;
+}
+
+namespace {
+
+// x is about to be overwritten unread, or goes: nothing is left to form
+void drop_x(hmg_grid *g)
+{
+    g->pendx = PendingX{};
+    g->x_reader = false;
+}
+
+// the x half of settle_overwritten() / pending_keeps(): x itself is dropped, a vector the updates rest on settles them
+void release_x(hmg_grid *g, const hmg_vec *v)
+{
+    const PendingX &q = g->pendx;
+    if (!q.x) return;
+    if (v == q.x)
+        drop_x(g);
+    else if (v == q.p || v == q.r)
+        settle_x(g);
+}
+
+}  // namespace
+
 void materialize_r(hmg_grid *g, bool read)
 {
     LifetimeLock lock(lifetime_mutex());
+    settle_x(g);
     const PendingR q = g->pend;
     if (!q.r) return;
     if (!q.formed) {
@@ -941,9 +1074,11 @@ void materialize_r(hmg_grid *g, bool read)
 
 void settle_overwritten(const hmg_vec *v)
 {
-    if (!v || !v->g || !v->g->pend.r) return;
+    if (!v || !v->g || (!v->g->pend.r && !v->g->pendx.x)) return;
     LifetimeLock lock(lifetime_mutex());
     hmg_grid *g = v->g;
+    release_x(g, v);
+    if (!g->pend.r) return;
     if (v == g->pend.Ap)
         materialize_r(g);
     else if (v == g->pend.r)
@@ -953,7 +1088,9 @@ void settle_overwritten(const hmg_vec *v)
 bool pending_keeps(hmg_vec *v)
 {
     hmg_grid *g = v->g;
-    if (!g || !g->pend.r) return false;
+    if (!g) return false;
+    release_x(g, v);                             // (a vector pending x-updates rest on: they are formed now, the one launch a destroy makes)
+    if (!g->pend.r) return false;
     if (v == g->pend.r)
         drop_pending(g);
     else if (v == g->pend.Ap) {
@@ -971,10 +1108,37 @@ namespace {
 // Entry of a V-cycle on the top level k: a record on the very r and Ap this cycle is about to overwrite (its first residual writes
 // every entry of r, src/multigrid.jl:50; Ap is scratch) is dropped; any other is settled, the x-only tail needs the grid's
 // step-length buffer for itself.
-void enter_top(hmg_grid *g, int k, hmg_vec **st)
+// Pending x-updates (option lazy_x) on this cycle's own x, p and r ride in its first residual: the record is taken out of the grid and
+// its form returned (0: nothing to carry).  Any other are settled; with zero_guess x is not read at all and they are dropped.  A record
+// that only watched x and is still open: nobody read x since, the reader memory goes.
+int enter_top(hmg_grid *g, int k, hmg_vec **st, bool zero_guess)
 {
+    int carry = 0;
+    if (g->pendx.x) {
+        LifetimeLock lock(lifetime_mutex());
+        const PendingX px = g->pendx;
+        bool same_x = k >= 2 && k == px.level;
+        for (int i = 0; i < 5 * k && same_x; ++i) {
+            const int at = i - 5 * (k - 1);
+            same_x = (st[i] == px.x) == (at == 0) && (!px.form || ((st[i] == px.r) == (at == 2) && (st[i] == px.p) == (at == 3)));
+        }
+        if (!px.form) {
+            if (same_x) g->x_reader = false;
+            g->pendx = PendingX{};
+        } else if (same_x && zero_guess)
+            drop_x(g);
+        else if (same_x && g->fuse_cg && g->smoother == 0 && g->ctx->lazy_x && px.r == g->pend.r && !g->pend.formed &&
+                 apply_carries_x(g->ctx->L, lev(g, k), g->md, g->lambda, px.form)) {
+            carry = px.form;
+            g->pendx = PendingX{};               // (r_2 stays where it is: the pending r on the same states is dropped below, never formed)
+        } else
+            settle_x(g);
+    }
     const PendingR &q = g->pend;
-    if (!q.r) return;
+    if (!q.r) {
+        need(!carry, "pending x-updates without the pending r they rest on");
+        return 0;
+    }
     bool same = k >= 2 && k == q.level;
     for (int i = 0; i < 5 * k && same; ++i) {
         const bool is_r = i == 5 * (k - 1) + 2, is_Ap = i == 5 * (k - 1) + 4;
@@ -982,16 +1146,22 @@ void enter_top(hmg_grid *g, int k, hmg_vec **st)
     }
     if (same)
         settle_overwritten(q.r);
-    else
+    else {
+        if (carry) {                             // (cannot happen: the x record shares its r with this one and saw the same states)
+            g->pendx = PendingX{st[5 * (k - 1)], st[5 * (k - 1) + 3], st[5 * (k - 1) + 2], k, carry};
+            carry = 0;
+        }
         materialize_r(g);
+    }
+    return carry;
 }
 
 }  // namespace
 
-void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess)
+void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool lazy_x)
 {
-    if (top) enter_top(g, k, st);
-    (void)vcycle_level(g, k, steps, steps_coarse, st, top, zero_guess, /*hand_up=*/false);
+    const int carry_x = top ? enter_top(g, k, st, zero_guess) : 0;
+    (void)vcycle_level(g, k, steps, steps_coarse, st, top, zero_guess, /*hand_up=*/false, carry_x, lazy_x);
 }
 
 }  // namespace hmg
@@ -1222,7 +1392,7 @@ int hmg_vcycle(hmg_grid *g, int top_level, int steps, int steps_coarse, hmg_vec 
     for (int l = 1; l <= top_level; ++l)
         for (int q = 0; q < 5; ++q) check_vec(g, l, states[5 * (l - 1) + q], "states[]", /*settle_pending=*/false);   // (vcycle() does)
     ensure_smoother_diag(g, top_level, states);
-    vcycle(g, top_level, steps, steps_coarse, states);
+    vcycle(g, top_level, steps, steps_coarse, states, /*top=*/true, /*zero_guess=*/false, /*lazy_x=*/true);
     HMG_END
 }
 

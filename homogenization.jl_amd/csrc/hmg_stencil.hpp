@@ -33,6 +33,16 @@ constexpr int WSZ_RB = 64; // ... of the register-blocked instantiations: only t
 // one-wave level-4 kernel rounded x += alpha p twice, k_cg_xp_update once).
 __device__ __forceinline__ double axpy1(double a, double x, double y) { return __builtin_fma(a, x, y); }   // a x + y
 
+// The two pending x-updates of a lazy last CG step, p_i formed on the fly: (x + ax p) + alpha (r + beta p).  One function for the
+// r-update that carries them (k_cg_rupdate_faces), the x-only tail (k_cg_x_tail) and the flexible CG's first pass over z
+// (k_fcg_dot_zq_x): the roundings cannot drift apart.
+__device__ __forceinline__ double xupd2(double ax, double beta, double alpha, double xv, double pv, double rv)
+{
+    const double t1 = axpy1(ax, pv, xv);
+    const double p2 = axpy1(beta, pv, rv);
+    return axpy1(alpha, p2, t1);
+}
+
 // A global store the compiler does not COUNT.  In a loop that requests the next item's loads before it stores the current item's
 // results, a compiler-visible store between a load and its first use on SOME control-flow path turns the wait for that load into a
 // vmcnt(0) -- the store's round trip to L2 (~2000 cycles) per item (measured on the level-7 kernel, profiles/r05_level7_phase_timing.txt).

@@ -35,8 +35,9 @@ void upload_mesh(hmg_grid *g)
 #else
     constexpr size_t BP = 2;
 #endif
-    // (+ 4: the step length of a pending r-update and its step's beta live behind the partials, hmg_grid::pend_alpha())
-    if (g->d_blockpart.n < (size_t)M.ncells * BP + 4) g->d_blockpart.alloc((size_t)M.ncells * BP + 4);
+    // (+ 8: the step length of a pending r-update, its step's beta and the other ratios of pending x-updates live behind the
+    //  partials, hmg_grid::pend_alpha())
+    if (g->d_blockpart.n < (size_t)M.ncells * BP + 8) g->d_blockpart.alloc((size_t)M.ncells * BP + 8);
     g->d_cells_cut.upload(K.cells_cut, s);
     g->d_cells_inner.upload(K.cells_inner, s);
     g->d_cell_perm.upload(K.cell_perm, s);

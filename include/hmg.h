@@ -111,7 +111,7 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *       was settled by a read takes the eager tail in its next cycle and only notes whether r is read again ("lazy_r_form" 0); the
  *       first cycle whose r goes unread brings the x-only tail back.  Only a call that is handed r or Ap counts as a read, not a
  *       setter that settles the record.
- *       The hmg_*_destroy calls never launch (they may come from a finalizer's thread): if Ap is destroyed while r is pending,
+ *       The hmg_*_destroy calls never launch (they may come from a finalizer's thread; the one exception is under "lazy_x"): if Ap is destroyed while r is pending,
  *       its memory stays with the grid until r has been formed or dropped (the grid itself outlives r anyway).  Until then that
  *       block is NOT in the pool of option "vec_pool": an hmg_vec_create that replaces the destroyed Ap at once allocates a new
  *       block ("device_allocs" + 1) and the device holds one more vector of that level for a while -- 10 GB at 1.3e9 entries.
@@ -132,6 +132,24 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *       hmg_grid_set_operator, hmg_grid_set_operator_tensor, hmg_grid_set_lambda and every hmg_ctx_set_option on the grid's
  *       context form it first as well (not a read).  The two-update form, partitioned grids and the other eager cases of
  *       "lazy_r" store Ap as before.  0: Ap is always stored.  hmg_ctx_counter "lazy_ap_form", "ap_rebuilt".
+ *   "lazy_x" 1: where "lazy_r" leaves that r-update pending, hmg_vcycle does not launch the x-only tail that remained either: x
+ *       lacks its last two (two-update form) or three CG updates, the grid notes on which vectors they rest (x; p_0 in p; p_1 in p
+ *       or the spare vector; r_2 in r) and puts their ratios aside (eight doubles of the grid's buffer), and the NEXT hmg_vcycle on
+ *       the same states forms x in the load phase of its first residual r = b - A x, which writes x and r in one pass: 56 B/DOF
+ *       instead of 40 + 24 and one launch less per cycle.  The same arithmetic in the same order: x, r and every value derived
+ *       from them are the same to the last bit.  Every other call that is handed x, p or r (downloads, uploads, norms, dot
+ *       products, axpy, fills, samples, integrals, per-cell moments / extrema / fields, hmg_smooth, hmg_vcycle_down / _up,
+ *       hmg_vcycle on another top level or other states, hmg_fcg_*), whatever forms or drops the pending r, and
+ *       hmg_grid_set_operator*, hmg_grid_set_lambda, hmg_ctx_set_option, hmg_grid_shrink, hmg_grid_set_smoother,
+ *       hmg_grid_reserve_spare(grid, 0), hmg_level_tune_placement and the exchange setters run the x-only tail first -- the launch
+ *       that was left out, from the ratios put aside.  So does hmg_vec_destroy of p or r (the one launch a destroy makes; x
+ *       destroyed or overwritten whole drops the updates).  A caller that reads x after every cycle would pay 40 + 56 B/DOF for
+ *       40 + 24: the grid remembers that a call was handed x and finishes x at once in its next cycles ("lazy_x_form" 0) until a
+ *       cycle's x goes unread, as "lazy_r" does for r.  hmg_fcg_step, once it has a direction, forms z = x in the pass that computes z.q
+ *       (48 B/DOF instead of 40 + 16); its first step after hmg_fcg_start gets a finished x.
+ *       Taken where the first residual has the streams: 3D level 6 (the 512-thread register-blocked apply; three updates with
+ *       the class weights from the cache); other top levels, and the eager cases of "lazy_r" with x and p added (wrapped, handed
+ *       out), keep the x-only tail.  0: always.  hmg_ctx_counter "lazy_x_form", "x_deferred", "x_settled", "x_settled_read".
  *   "fold_prolong" 1: the prolongation rides in the post-smoother's first residual.
  *   "prolong_in_image" 1: on level 6 that residual stages the coarse column at the even nodes of the LDS lattice image
  *       (three workgroups per CU stay resident); 0: in LDS of its own behind it.
@@ -173,7 +191,9 @@ int hmg_ctx_apply_timing_level(hmg_ctx *ctx, int level, int64_t *launches, doubl
    r-updates formed by a later call; "r_materialized_by_read": those of them formed because a call was handed r or Ap, the others
    by hmg_grid_shrink and the other setters, the placement tuner or a V-cycle on other vectors) and "r_dropped" (those that never had to be formed), "lazy_ap_form" (1: that
    pending r-update was left without a stored Ap, option "lazy_ap") and "ap_rebuilt" (pending r-updates that had to run the last CG step's apply again
-   before they could be formed), "coarse_x_folds" (residuals
+   before they could be formed), "lazy_x_form" (the x-updates the last hmg_vcycle left pending on its top level's x, option "lazy_x": 3, 2 or 0), "x_deferred"
+   (V-cycles that left some), "x_settled" (those of them a later call finished with the x-only tail; the others rode in the next V-cycle's first residual or
+   were dropped with x) and "x_settled_read" (of those: because a call was handed x or p), "coarse_x_folds" (residuals
    that finished the coarser level's x on the way, option "fold_coarse_x": one per hmg_vcycle from level 6), "fcg_bytes" (p, q and R of this context's
    hmg_fcg objects), "smoother_diag_bytes" (inverse diagonals held by this context's grids, see hmg_grid_set_smoother) and
    "smoother_diag_builds" (times a grid of this context formed them), the "sample_*" counters listed at hmg_sample (those of

@@ -505,7 +505,7 @@ function HipContext(device::Integer, stream::Ptr{Cvoid})                 # kerne
 end
 set_option!(c::HipContext, name::String, v::Float64) =
     check(ccall((:hmg_ctx_set_option_f64, LIB), Cint, (Ptr{Cvoid}, Cstring, Float64), c.h, name, v))
-# diagnostic counters by name (include/hmg.h, hmg_ctx_counter): "lazy_r_form", "lazy_ap_form", "r_materialized", "ap_rebuilt", "r_dropped", ...
+# diagnostic counters by name (include/hmg.h, hmg_ctx_counter): "lazy_r_form", "lazy_ap_form", "lazy_x_form", "x_deferred", "x_settled", "r_materialized", "ap_rebuilt", "r_dropped", ...
 counter(c::HipContext, name::String) = Int(ccall((:hmg_ctx_counter, LIB), Int64, (Ptr{Cvoid}, Cstring), c.h, name))
 stream(c::HipContext) = ccall((:hmg_ctx_stream, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), c.h)
 scalar_bank(c::HipContext) = ccall((:hmg_ctx_scalar_bank, LIB), Ptr{Cvoid}, (Ptr{Cvoid},), c.h)
