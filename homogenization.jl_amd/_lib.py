@@ -60,6 +60,8 @@ SIGNATURES = {
     "hmg_grid_set_smoother": (c_int, [vp, c_int]),
     "hmg_grid_smoother": (c_int, [vp]),
     "hmg_grid_smoother_diag": (c_int, [vp, c_int, vp]),
+    "hmg_grid_set_smoother_chebyshev": (c_int, [vp, c_f64, p_f64]),
+    "hmg_grid_smoother_bounds": (c_int, [vp, c_int, p_f64, p_f64]),
     "hmg_grid_ncells": (c_i64, [vp]),
     "hmg_grid_nnodes": (c_i64, [vp]),
     "hmg_grid_nlevels": (c_int, [vp]),

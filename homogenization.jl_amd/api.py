@@ -31,7 +31,7 @@ from . import _lib as L
 Tri64 = "Tri64"   # element-type tags (src/grid.jl:29-37)
 Tet64 = "Tet64"
 
-SMOOTHERS = {"cg": 0, "jacobi": 1}   # hmg_grid_set_smoother
+SMOOTHERS = {"cg": 0, "jacobi": 1, "chebyshev": 2}   # hmg_grid_set_smoother, hmg_grid_set_smoother_chebyshev
 
 
 def _dim_of(tag):
@@ -269,17 +269,38 @@ class ImplicitFineGrid:
         and raises if the memory is not there, False releases it (the reference's five vectors per level)."""
         L.check(self._lib.hmg_grid_reserve_spare(self.h, 1 if enable else 0))
 
-    def set_smoother(self, kind="cg"):
-        """The smoother of smoothing_steps / vcycle / FlexibleCG on this grid (include/hmg.h: hmg_grid_set_smoother): "cg" is the
-        reference's (default), "jacobi" is CG preconditioned by the inverse diagonal of the assembled operator.  "jacobi" reserves
-        one vector per level >= 2 and raises if the memory is not there; set it before the level vectors are created."""
+    def set_smoother(self, kind="cg", ratio=None, lambda_hi=None):
+        """The smoother of smoothing_steps / vcycle / FlexibleCG on this grid (include/hmg.h: hmg_grid_set_smoother,
+        hmg_grid_set_smoother_chebyshev): "cg" is the reference's (default), "jacobi" is CG preconditioned by the inverse diagonal
+        of the assembled operator, "chebyshev" a Chebyshev polynomial in that diagonal times the operator on
+        [lambda_hi / ratio, lambda_hi] (no dot products).  "jacobi" and "chebyshev" reserve one vector per level >= 2 and raise if
+        the memory is not there; set it before the level vectors are created.
+        ratio, lambda_hi ("chebyshev" only): None for the library's default ratio and its own rigorous bounds, or a ratio > 1 and
+        one bound per level (entry l - 1 for level l; <= 0: formed).  A partitioned grid needs a bound > 0 for every level >= 2."""
         if kind not in SMOOTHERS:
             raise ValueError(f"smoother must be one of {sorted(SMOOTHERS)}, not {kind!r}")
-        L.check(self._lib.hmg_grid_set_smoother(self.h, SMOOTHERS[kind]))
+        if kind != "chebyshev":
+            if ratio is not None or lambda_hi is not None:
+                raise ValueError('ratio and lambda_hi belong to smoother "chebyshev"')
+            L.check(self._lib.hmg_grid_set_smoother(self.h, SMOOTHERS[kind]))
+            return
+        hi = None
+        if lambda_hi is not None:
+            hi = np.ascontiguousarray(lambda_hi, dtype=np.float64).reshape(-1)
+            if hi.size != self.levels:
+                raise ValueError(f"lambda_hi must have one entry per level ({self.levels}), not {hi.size}")
+        L.check(self._lib.hmg_grid_set_smoother_chebyshev(self.h, 0.0 if ratio is None else float(ratio),
+                                                          hi.ctypes.data_as(L.p_f64) if hi is not None else None))
 
     def smoother(self) -> str:
         k = int(self._lib.hmg_grid_smoother(self.h))
         return {v: n for n, v in SMOOTHERS.items()}[k]
+
+    def smoother_bounds(self, level):
+        """(lambda_lo, lambda_hi) of a level as the "chebyshev" smoother uses them, formed first if stale (synchronises)."""
+        lo, hi = ctypes.c_double(), ctypes.c_double()
+        L.check(self._lib.hmg_grid_smoother_bounds(self.h, level, ctypes.byref(lo), ctypes.byref(hi)))
+        return lo.value, hi.value
 
     def coarse_setup(self):
         L.check(self._lib.hmg_coarse_setup(self.h))
@@ -784,13 +805,20 @@ def smoothing_steps(steps, implicit, ops, curr: LevelState, k: int):
     L.check(L.load().hmg_smooth(implicit.h, k, steps, curr.x.h, curr.b.h, curr.r.h, curr.p.h, curr.Ap.h))
 
 
-def set_smoother(implicit: ImplicitFineGrid, kind: str = "cg"):
-    """"cg" (the reference's smoother, default) or "jacobi" (CG preconditioned by the inverse diagonal)."""
-    implicit.set_smoother(kind)
+def set_smoother(implicit: ImplicitFineGrid, kind: str = "cg", **kw):
+    """"cg" (the reference's smoother, default), "jacobi" (CG preconditioned by the inverse diagonal) or "chebyshev" (a Chebyshev
+    polynomial in the inverse diagonal times the operator; keywords ratio, lambda_hi: ImplicitFineGrid.set_smoother)."""
+    implicit.set_smoother(kind, **kw)
+
+
+def smoother_bounds(implicit: ImplicitFineGrid, level: int):
+    """(lambda_lo, lambda_hi) of the level's "chebyshev" smoother."""
+    return implicit.smoother_bounds(level)
 
 
 def smoother_diag(implicit: ImplicitFineGrid, level: int, out: DeviceMatrix = None) -> DeviceMatrix:
-    """The level's inverse diagonal as the "jacobi" smoother uses it (0 on constrained nodes), formed first if it is stale."""
+    """The level's inverse diagonal as the "jacobi" and "chebyshev" smoothers use it (0 on constrained nodes), formed first if it is
+    stale."""
     out = DeviceMatrix(implicit, level) if out is None else out
     L.check(implicit._lib.hmg_grid_smoother_diag(implicit.h, level, out.h))
     return out

@@ -96,8 +96,6 @@ void vec_release(hmg_ctx *c, void *p, size_t bytes)
     (void)hipFree(p);
 }
 
-namespace {
-
 // scratch of the streaming reductions (one partial per 256-thread block = per 512 entries, see hmg_kernels.hip)
 void ensure_reduce_scratch(hmg_ctx *c, int64_t nentries)
 {
@@ -108,6 +106,8 @@ void ensure_reduce_scratch(hmg_ctx *c, int64_t nentries)
     c->L.rpart = c->rpart.p;
     c->L.rpart_cap = need_blocks;
 }
+
+namespace {
 
 void ctx_unref(hmg_ctx *ctx)
 {
@@ -276,6 +276,9 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "fcg_bytes") return ctx->fcg_bytes;
     if (n == "smoother_diag_bytes") return ctx->smoother_diag_bytes;
     if (n == "smoother_diag_builds") return ctx->smoother_diag_builds;
+    if (n == "smoother_bound_builds") return ctx->smoother_bound_builds;   // level bounds of the Chebyshev smoother formed on the device
+    if (n == "cheb_applies") return ctx->cheb_applies;        // operator applies inside Chebyshev smoothings (first residuals not counted)
+    if (n == "cheb_smoothings") return ctx->cheb_smoothings;  // Chebyshev smoothings of at least one step
     if (n == "lazy_top_form") return ctx->last_top_form;
     if (n == "lazy_pre_form") return ctx->last_pre_form;
     if (n == "lazy_r_form") return ctx->last_r_form;          // the last hmg_vcycle / hmg_fcg_step: 1 its top level's r-update is (or was) pending

@@ -80,6 +80,16 @@ struct LevelDev {
     const double *wcache;          // null: not available on this level
 };
 
+// entity class of a storage slot from the entity-major ranges (corners | edges | faces | interior): no addressing table, so
+// every level of both dimensions is served, 2D levels 9-11 included (the setup kernels of hmg_pcg.hip and hmg_cheb.hip)
+__device__ __forceinline__ int slot_class(const LevelDev &lv, int t)
+{
+    return t < lv.ncorner    ? 1 + lv.nface + lv.nedge + t
+           : t < lv.off_face ? 1 + lv.nface + (t - lv.off_edge) / lv.nei
+           : t < lv.off_int  ? 1 + (t - lv.off_face) / lv.nfi
+                             : 0;
+}
+
 // level-5 geometry k_apply_wave is compiled for (apply_wave_ok checks it against the level's tables, build_wave_tables lays
 // out the wave tables by it)
 constexpr int WM = 16, WNF = 969, WNFI = 105, WNEI = 15, WNCORNER = 4, WNBLK = 152, WNFC = 165, WR = 4;

@@ -262,6 +262,9 @@ struct hmg_ctx {
     int64_t fcg_bytes = 0;                   // p, q and R of this context's hmg_fcg objects (hmg_fcg.cpp)
     int64_t smoother_diag_bytes = 0;         // inverse diagonals held by this context's grids (hmg_grid_set_smoother)
     int64_t smoother_diag_builds = 0;        // times a grid of this context formed them (ensure_smoother_diag)
+    int64_t smoother_bound_builds = 0;       // level bounds of the Chebyshev smoother formed by this context's grids (ensure_smoother_diag)
+    int64_t cheb_applies = 0;                // operator applies launched inside Chebyshev smoothings (the first residual not counted)
+    int64_t cheb_smoothings = 0;             // Chebyshev smoothings of at least one step
     int64_t moments_kernel_ns = 0, moments_download_ns = 0;   // the last hmg_cell_moments: its kernel (device events) and the download of its sums (host clock)
     int64_t pair_moments_kernel_ns = 0, pair_moments_download_ns = 0;   // the last hmg_cell_pair_moments, likewise
     int64_t extrema_kernel_ns = 0;           // the last hmg_cell_extrema: its kernel (device events)
@@ -394,7 +397,11 @@ struct hmg_grid {
     bool top_spare_refused = false;
     // Jacobi-preconditioned CG smoother (hmg_grid_set_smoother): per level >= 2 the inverse of the assembled operator's diagonal,
     // 0 on constrained nodes -- a consistent level vector, reserved by the call (setup memory), formed by ensure_smoother_diag()
-    int smoother = 0;                            // 0: CG (src/multigrid.jl:46-71), 1: Jacobi-preconditioned CG
+    int smoother = 0;                            // 0: CG (src/multigrid.jl:46-71), 1: Jacobi-preconditioned CG, 2: Chebyshev-Jacobi
+    // Chebyshev-Jacobi smoother (hmg_grid_set_smoother_chebyshev): a polynomial in dinv o A on [hi / ratio, hi] per level >= 2
+    double cheb_ratio = 0.0;                     // lambda_hi / lambda_lo
+    std::vector<double> cheb_given;              // [nlevels] the caller's bounds (> 0: used as given, nothing is formed), or empty
+    std::vector<double> cheb_hi;                 // [nlevels] the bounds in use; formed with dinv and stale with it (dinv_level_ready)
     std::vector<std::unique_ptr<DevBuf<double>>> dinv;   // [nlevels], empty with smoother 0
     bool dinv_ready = false;                     // false: operator, lambda, domain, cut or exchange changed since they were formed
     std::vector<char> dinv_level_ready;          // [nlevels] formed since then (a level is formed where a call first smooths on it)
@@ -543,6 +550,8 @@ inline bool has_exchange(const hmg_grid *g) { return g->exchange || g->ex_begin 
 double *vec_alloc(hmg_ctx *c, size_t bytes);
 // ... and back into the pool (stream-ordered: what was enqueued on the context's stream before runs before the next owner's work)
 void vec_release(hmg_ctx *c, void *p, size_t bytes);
+// block partials of the streaming reductions for vectors of nentries entries (allocates where the context's are too few: setup)
+void ensure_reduce_scratch(hmg_ctx *c, int64_t nentries);
 // what hmg_vec_destroy does with a vector nobody needs any more: memory to the pool, the object, its reference to the grid
 void release_vec(hmg_vec *v);
 void grid_unref(hmg_grid *grid);

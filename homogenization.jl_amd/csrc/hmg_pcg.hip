@@ -24,15 +24,7 @@ namespace {
 
 constexpr int PB = 256;   // threads per block
 
-// entity class of a storage slot from the entity-major ranges (corners | edges | faces | interior): no addressing table, so
-// every level of both dimensions is served, 2D levels 9-11 included
-__device__ __forceinline__ int slot_class(const LevelDev &lv, int t)
-{
-    return t < lv.ncorner    ? 1 + lv.nface + lv.nedge + t
-           : t < lv.off_face ? 1 + lv.nface + (t - lv.off_edge) / lv.nei
-           : t < lv.off_int  ? 1 + (t - lv.off_face) / lv.nfi
-                             : 0;
-}
+// (the entity class of a storage slot: slot_class(), hmg_device.hpp)
 
 // The assembled diagonal is the interface sum of the cell-local ones.  A floating-point sum depends on the order of its terms, and
 // the order differs between an unpartitioned grid (all copies of a node in ascending cell order) and a partitioned one (every rank's

@@ -3,6 +3,7 @@
 // (hmg_smooth, hmg_vcycle*, hmg_level_tune_placement, hmg_grid_reserve_spare).
 #include "../../include/hmg.h"
 #include "hmg_objects.hpp"
+#include "hmg_cheb.hpp"
 #include "hmg_pcg.hpp"
 
 #include <algorithm>
@@ -291,9 +292,9 @@ SmoothForm smooth_form(const hmg_grid *g, int level, int steps, Role role)
     const bool lean = c->lean_post && (role == Role::PostTop || role == Role::PostBelow);
     const bool dead = role == Role::Pre || (lean && role == Role::PostBelow);
     SmoothForm f;
-    // (the Jacobi-preconditioned smoother has the tails of the unfused path and nothing else: no pointer exchange, no riding face
-    //  sums, no deferred x-updates)
-    if (!g->fuse_cg || g->smoother == 1) {
+    // (the Jacobi-preconditioned and the Chebyshev smoother have the tails of the unfused path and nothing else: no pointer
+    //  exchange, no riding face sums, no deferred x-updates)
+    if (!g->fuse_cg || g->smoother != 0) {
         f.tail = dead ? Tail::DeadXp : lean ? Tail::ScratchP : Tail::Full;
         return f;
     }
@@ -365,11 +366,30 @@ bool wants_top_spare(const hmg_grid *g, int level)
 
 // The inverse diagonals of the Jacobi-preconditioned smoother, level by level: the cell-local diagonal, its interface sum (on a
 // partitioned grid with the cut exchange -- every rank gets here in the same call), then the inversion off the constrained nodes.
+// A grid with an interface exchange or a partition: the maximum over the grid would need a maximum over the ranks, and the exchange
+// hooks only sum.
+static bool cheb_needs_given(const hmg_grid *g) { return g->part || has_exchange(g) || g->scalar_sum; }
+
+static bool cheb_all_given(const hmg_grid *g, const std::vector<double> &given)
+{
+    if (given.size() != (size_t)g->nlevels) return false;
+    for (int level = 2; level <= g->nlevels; ++level)
+        if (!(given[(size_t)level - 1] > 0.0)) return false;
+    return true;
+}
+
+static const char *const CHEB_PARTITIONED =
+    "Chebyshev smoother: on a partitioned grid (or one with an interface exchange) the bound of every level >= 2 must be given "
+    "(hmg_grid_set_smoother_chebyshev, lambda_hi): forming it needs a maximum over the ranks, which the exchange hooks do not have";
+
+// For kind 2 the level's bound lambda_hi is formed right behind its inverse diagonal, in the same scratch vector: the cell-local
+// absolute row sums, their interface sum, the maximum of dinv o s (one host read per level and generation), times CHEB_SAFETY.
 void ensure_smoother_diag(hmg_grid *g, int level, double *scratch)
 {
-    if (g->smoother != 1 || level < 2) return;
+    if (g->smoother == 0 || level < 2) return;
     need(g->has_op, "operator not set");
     need(g->dinv.size() == (size_t)g->nlevels && level <= g->nlevels, "Jacobi-preconditioned smoother: the inverse diagonals were not reserved");
+    if (g->smoother == 2 && cheb_needs_given(g) && !cheb_all_given(g, g->cheb_given)) throw std::runtime_error(CHEB_PARTITIONED);
     if (!g->dinv_ready) {                        // a new generation: nothing formed, nothing counted
         g->dinv_level_ready.assign((size_t)g->nlevels, 0);
         g->dinv_build_counted = false;
@@ -386,6 +406,20 @@ void ensure_smoother_diag(hmg_grid *g, int level, double *scratch)
         launch_diag_accum(g->ctx->L, lv, g->md, scratch, d, limb);
     }
     launch_dinv_finish(g->ctx->L, lv, g->md, d);
+    if (g->smoother == 2) {
+        g->cheb_hi.resize((size_t)g->nlevels, 0.0);
+        const double given = g->cheb_given.size() == (size_t)g->nlevels ? g->cheb_given[(size_t)level - 1] : 0.0;
+        double hi = given;
+        if (!(given > 0.0)) {
+            launch_operator_rowabs(g->ctx->L, lv, g->md, g->lambda, scratch);
+            interface_sum(g, lv, scratch);
+            launch_cheb_max(g->ctx->L, d, scratch, (int64_t)lv.ld * g->md.ncells, S_HOST);
+            hi = CHEB_SAFETY * read_scalar(g->ctx, S_HOST);
+            g->ctx->smoother_bound_builds += 1;
+            need(g->md.ncells == 0 || (std::isfinite(hi) && hi > 0.0), "Chebyshev smoother: the bound of this level is not a positive number");
+        }
+        g->cheb_hi[(size_t)level - 1] = hi;
+    }
     g->dinv_level_ready[(size_t)level - 1] = 1;
     if (!g->dinv_build_counted) {
         g->ctx->smoother_diag_builds += 1;
@@ -395,7 +429,7 @@ void ensure_smoother_diag(hmg_grid *g, int level, double *scratch)
 
 void ensure_smoother_diag(hmg_grid *g, int top, hmg_vec **states)
 {
-    if (g->smoother != 1) return;
+    if (g->smoother == 0) return;
     for (int level = 2; level <= top; ++level) ensure_smoother_diag(g, level, states[5 * (level - 1) + 4]->d);
 }
 
@@ -537,6 +571,45 @@ void smooth_pcg(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_v
     }
 }
 
+// The Chebyshev polynomial in dinv o A on [hi / ratio, hi] (hmg_grid_set_smoother_chebyshev), after first_residual():
+//   d = c0 dinv o r
+//   steps x { x += d;  Ad = A d, constraint, interface sum;  r -= Ad;  d = c1[k] d + c2[k] dinv o r }
+// The coefficients (ChebCoef, hmg_cheb.hpp) are host numbers formed here from the level's bound: no reduction, no sum over ranks, no
+// host round trip.  p holds d, Ap holds Ad; the apply is the plain one with the constraint.  Tails (smooth_form()): Full as above;
+// ScratchP ends with x += d, r -= Ad; DeadXp ends with x += d and launches no apply for its last step.
+void smooth_cheb(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_vec *p, hmg_vec *Ap, const SmoothForm &f)
+{
+    const LevelDev &lv = lev(g, level);
+    const Launch &L = g->ctx->L;
+    const int64_t n = vec_len(x);
+    need(g->dinv_ready && g->dinv.size() == (size_t)g->nlevels && g->dinv_level_ready[(size_t)level - 1] && g->dinv[(size_t)level - 1] &&
+             (g->dinv[(size_t)level - 1]->p || n == 0) && g->cheb_hi.size() == (size_t)g->nlevels,
+         "Chebyshev smoother: no inverse diagonal or no bound for this level");
+    need(f.tail == Tail::Full || f.tail == Tail::ScratchP || f.tail == Tail::DeadXp, "Chebyshev smoother: unknown tail");
+    const double *dinv = g->dinv[(size_t)level - 1]->p;
+    const double hi = g->cheb_hi[(size_t)level - 1];
+    ChebCoef c(hi / g->cheb_ratio, hi);
+    launch_cheb_start(L, p->d, r->d, dinv, n, c.c0);
+    if (steps > 0) g->ctx->cheb_smoothings += 1;
+    for (int i = 0; i < steps; ++i) {
+        const bool last = i == steps - 1;
+        if (last && f.tail == Tail::DeadXp) {
+            launch_cheb_tail(L, x->d, p->d, nullptr, nullptr, n);         // x += d: nothing else of this step is read
+            return;
+        }
+        apply(g, lv, 1.0, p->d, nullptr, Ap->d, 1);                       // Ad = A d, constraint
+        interface_sum(g, lv, Ap->d);
+        g->ctx->cheb_applies += 1;
+        if (last && f.tail == Tail::ScratchP) {
+            launch_cheb_tail(L, x->d, p->d, r->d, Ap->d, n);
+            return;
+        }
+        double c1, c2;
+        c.next(c1, c2);
+        launch_cheb_step(L, x->d, p->d, r->d, Ap->d, dinv, n, c1, c2);
+    }
+}
+
 // May the finest level's post-smoother inside hmg_vcycle leave its last r-update pending (option lazy_r)?  Not where the memory
 // can be read behind the library's back (caller-owned vectors, pointers handed out -- p too: it changes places with r), and not on
 // a partitioned grid, where the deferred sum over the ranks would be a collective at a place no rank can foresee.
@@ -613,6 +686,10 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
     first_residual(g, level, x, b, r, p, f, xcoarse, cx);
     if (g->smoother == 1) {
         smooth_pcg(g, level, steps, x, r, p, Ap, f);
+        return {};
+    }
+    if (g->smoother == 2) {
+        smooth_cheb(g, level, steps, x, r, p, Ap, f);
         return {};
     }
     int cur = S_RS, other = S_RS2;
@@ -811,7 +888,7 @@ bool zero_entry_ok(const hmg_grid *g, int k, int steps)
 {
     if (!g->ctx->zero_entry) return false;
     if (k == 1) return true;
-    if (g->smoother == 1) return false;          // (its zero guesses are written)
+    if (g->smoother != 0) return false;          // (their zero guesses are written)
     if (steps != 2 || smooth_form(g, k, steps, Role::Pre).tail != Tail::DeadDefer2) return false;
     // (register-blocked levels take that residual through the instantiation that also restricts in its epilogue -- the only one
     //  of theirs the zero-input form is compiled into)
@@ -918,7 +995,7 @@ DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, cons
 bool coarse_x_folds(const hmg_grid *g, int k, int steps_below)
 {
     const hmg_ctx *c = g->ctx;
-    if (k < 3 || g->smoother == 1 || !c->fold_coarse_x || !c->lazy_post || !c->fold_prolong || !c->lean_post || !g->fuse_cg || !c->prolong_in_image) return false;
+    if (k < 3 || g->smoother != 0 || !c->fold_coarse_x || !c->lazy_post || !c->fold_prolong || !c->lean_post || !g->fuse_cg || !c->prolong_in_image) return false;
     const LevelDev &lv = g->ld[(size_t)k - 1];
     if (!(apply_lds_bytes(lv) > 48 * 1024 && apply_lds_bytes(lv) <= 160 * 1024 &&
           apply_lds_bytes(lv) + sizeof(double) * (size_t)g->ld[(size_t)k - 2].nf <= 80 * 1024))
@@ -1185,40 +1262,110 @@ int hmg_grid_reserve_spare(hmg_grid *g, int enable)
 
 // The smoother of a grid: 0 = the reference's CG (default), 1 = CG preconditioned by the inverse diagonal of the assembled operator.
 // Kind 1 reserves one vector per level >= 2 here (setup memory; formed at the next call that smooths); kind 0 hands them back.
+// one vector per level >= 2 for the inverse diagonals of kinds 1 and 2, unless the grid holds them already
+static void reserve_smoother_diag(hmg_grid *g, const char *who)
+{
+    if (g->dinv.size() == (size_t)g->nlevels) return;
+    release_smoother_diag(g);
+    std::vector<std::unique_ptr<DevBuf<double>>> bufs((size_t)g->nlevels);
+    int64_t bytes = 0;
+    for (int level = 2; level <= g->nlevels; ++level) {
+        const size_t n = (size_t)g->ld[(size_t)level - 1].ld * (size_t)g->mesh_full.ncells;
+        bufs[(size_t)level - 1].reset(new DevBuf<double>);
+        try {
+            bufs[(size_t)level - 1]->alloc(n);
+        } catch (const std::exception &) {
+            (void)hipGetLastError();
+            throw std::runtime_error(std::string(who) + ": the inverse diagonal of level " + std::to_string(level) + " (" +
+                                     std::to_string((n * sizeof(double)) >> 20) + " MiB) does not fit the device memory; the smoother is unchanged");
+        }
+        bytes += (int64_t)(n * sizeof(double));
+    }
+    g->dinv = std::move(bufs);
+    g->ctx->smoother_diag_bytes += bytes;
+}
+
 int hmg_grid_set_smoother(hmg_grid *g, int kind)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
     need(g->ctx != nullptr, "this grid was created without a device context (host tables only)");
-    need(kind == 0 || kind == 1, "smoother kind must be 0 (CG) or 1 (Jacobi-preconditioned CG)");
+    need(kind == 0 || kind == 1, "smoother kind must be 0 (CG) or 1 (Jacobi-preconditioned CG); kind 2, the Chebyshev-Jacobi smoother, "
+                                 "takes its parameters through hmg_grid_set_smoother_chebyshev");
     HIPCHK(hipSetDevice(g->ctx->device));
     materialize_r(g);                            // (the Jacobi smoother forms its diagonal in the Ap of the next call)
-    if (kind == 1 && g->dinv.size() != (size_t)g->nlevels) {
-        release_smoother_diag(g);
-        std::vector<std::unique_ptr<DevBuf<double>>> bufs((size_t)g->nlevels);
-        int64_t bytes = 0;
-        for (int level = 2; level <= g->nlevels; ++level) {
-            const size_t n = (size_t)g->ld[(size_t)level - 1].ld * (size_t)g->mesh_full.ncells;
-            bufs[(size_t)level - 1].reset(new DevBuf<double>);
-            try {
-                bufs[(size_t)level - 1]->alloc(n);
-            } catch (const std::exception &) {
-                (void)hipGetLastError();
-                throw std::runtime_error("hmg_grid_set_smoother: the inverse diagonal of level " + std::to_string(level) + " (" +
-                                         std::to_string((n * sizeof(double)) >> 20) + " MiB) does not fit the device memory; the smoother is unchanged");
-            }
-            bytes += (int64_t)(n * sizeof(double));
-        }
-        g->dinv = std::move(bufs);
-        g->ctx->smoother_diag_bytes += bytes;
-    }
+    if (kind == 1) reserve_smoother_diag(g, "hmg_grid_set_smoother");
     if (kind == 0) {
         release_smoother_diag(g);
         // (a vector of the finest level created from now on brings the spare direction vector of the CG forms as it always did)
     }
     g->smoother = kind;
+    g->cheb_ratio = 0.0;
+    g->cheb_given.clear();
+    g->cheb_hi.clear();
     g->dinv_ready = false;
     g->op_epoch += 1;                            // an hmg_fcg object's direction belongs to the old preconditioner
+    HMG_END
+}
+
+// Kind 2: the Chebyshev polynomial in dinv o A on [lambda_hi / ratio, lambda_hi].  Reserves the inverse diagonals as kind 1 does; the
+// bounds that are not given are formed with them (ensure_smoother_diag).
+int hmg_grid_set_smoother_chebyshev(hmg_grid *g, double ratio, const double *lambda_hi)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only)");
+    need(std::isfinite(ratio) && (ratio <= 0.0 || ratio > 1.0), "hmg_grid_set_smoother_chebyshev: ratio must be a finite number > 1 (<= 0: the default)");
+    std::vector<double> given;
+    if (lambda_hi) {
+        given.assign(lambda_hi, lambda_hi + g->nlevels);
+        for (double &v : given) {
+            need(!std::isnan(v) && v < HUGE_VAL, "hmg_grid_set_smoother_chebyshev: lambda_hi must hold finite numbers (<= 0: the bound is formed)");
+            if (!(v > 0.0)) v = 0.0;
+        }
+    }
+    if (cheb_needs_given(g) && !cheb_all_given(g, given)) throw std::runtime_error(CHEB_PARTITIONED);   // (before anything changes)
+    HIPCHK(hipSetDevice(g->ctx->device));
+    materialize_r(g);                            // (the diagonal and the bound are formed in the Ap of the next call)
+    reserve_smoother_diag(g, "hmg_grid_set_smoother_chebyshev");
+    g->smoother = 2;
+    g->cheb_ratio = ratio > 1.0 ? ratio : CHEB_DEFAULT_RATIO;
+    g->cheb_given = std::move(given);
+    g->cheb_hi.clear();
+    g->dinv_ready = false;
+    g->op_epoch += 1;                            // an hmg_fcg object's direction belongs to the old preconditioner
+    HMG_END
+}
+
+// lambda_lo and lambda_hi of a level as the Chebyshev smoother uses them; forms the inverse diagonal and the bound first where they are
+// stale, with a scratch vector from the context's pool.  Synchronises: not for the inside of a V-cycle.
+int hmg_grid_smoother_bounds(hmg_grid *g, int level, double *lambda_lo, double *lambda_hi)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only)");
+    need(g->smoother == 2, "hmg_grid_smoother_bounds: the grid's smoother has no bounds (hmg_grid_set_smoother_chebyshev)");
+    need(level >= 2 && level <= g->nlevels, "level out of range (2..nlevels: level 1 has no smoother)");
+    hmg_ctx *c = g->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (!(g->dinv_ready && g->dinv_level_ready[(size_t)level - 1])) {
+        materialize_r(g);
+        const size_t bytes = sizeof(double) * (size_t)g->ld[(size_t)level - 1].ld * (size_t)std::max<int64_t>(g->mesh_full.ncells, 1);
+        ensure_reduce_scratch(c, (int64_t)(bytes / sizeof(double)));   // (no vector of this level need exist yet)
+        double *scratch = vec_alloc(c, bytes);
+        try {
+            ensure_smoother_diag(g, level, scratch);
+            HIPCHK(hipStreamSynchronize(c->stream));
+        } catch (...) {
+            (void)hipStreamSynchronize(c->stream);
+            vec_release(c, scratch, bytes);
+            throw;
+        }
+        vec_release(c, scratch, bytes);
+    }
+    const double hi = g->cheb_hi[(size_t)level - 1];
+    if (lambda_hi) *lambda_hi = hi;
+    if (lambda_lo) *lambda_lo = hi / g->cheb_ratio;
     HMG_END
 }
 
@@ -1228,7 +1375,7 @@ int hmg_grid_smoother_diag(hmg_grid *g, int level, hmg_vec *out)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
-    need(g->smoother == 1, "hmg_grid_smoother_diag: the grid's smoother has no diagonal (hmg_grid_set_smoother(grid, 1))");
+    need(g->smoother != 0, "hmg_grid_smoother_diag: the grid's smoother has no diagonal (hmg_grid_set_smoother(grid, 1), hmg_grid_set_smoother_chebyshev)");
     need(level >= 2 && level <= g->nlevels, "level out of range (2..nlevels: level 1 has no smoother)");
     check_vec(g, level, out, "out");
     ensure_smoother_diag(g, level, out->d);

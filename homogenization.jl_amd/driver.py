@@ -231,7 +231,9 @@ def checkerboard_homogenization(n: int = 4, eltype=Tri64, refinements: int = 2, 
     method's p, q, R.  At tolerances far above rounding the two forms stop at iterates that differ by about the tolerance.
     `smoother` = "jacobi": the V-cycle's smoother is CG preconditioned by the inverse diagonal of the assembled operator
     (api.set_smoother; one more vector per level >= 2) instead of the reference's CG ("cg").  Fewer cycles at high contrast, about
-    1.5 times the traffic per cycle; combines freely with `accelerate`; reported in timings["smoother"]."""
+    1.5 times the traffic per cycle; combines freely with `accelerate`; reported in timings["smoother"].
+    `smoother` = "chebyshev": a Chebyshev polynomial in that inverse diagonal times the operator, with the library's own bound per
+    level and its default ratio -- no dot products, one apply fewer per smoothing inside the V-cycle; the same memory as "jacobi"."""
     import time
     t_start = time.perf_counter()
     save_dir = "."
@@ -543,7 +545,7 @@ def checkerboard_hypercube_multigrid(n: int, eltype=Tet64, refinements: int = 2,
     (src/examples/homogenized_coefficients.jl:509-571): -div(a grad u) = 1 with zero Dirichlet data (lambda = 0),
     `max_cycles` V-cycles with 3 smoothing steps; `refinements` is the number of grids.  Seeded like the other
     driver; `save` = level (or (level, directory)) writes checkerboard_full_<refinements>.vtu with point data "x";
-    `smoother` = "cg" (the reference's) or "jacobi" (api.set_smoother).
+    `smoother` = "cg" (the reference's), "jacobi" or "chebyshev" (api.set_smoother).
     Returns (rs, state of the finest level, implicit grid)."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None

@@ -118,7 +118,7 @@ int hmg_ctx_release_memory(hmg_ctx *ctx);
  *       A host that recycles state vectors between V-cycles reads or destroys r first, or keeps Ap.
  *       Needs the "lazy_top" forms; the eager tail runs where the memory can be read behind the library's back (r, p or Ap
  *       wrapped by hmg_vec_wrap, or handed out once by hmg_vec_device_ptr), on a partitioned grid (the deferred sum over the ranks
- *       would be a collective at a place no rank can foresee) and with smoother kind 1.  0: the eager tail always.
+ *       would be a collective at a place no rank can foresee) and with smoother kinds 1 and 2.  0: the eager tail always.
  *       hmg_ctx_counter "lazy_r_form", "r_materialized", "r_materialized_by_read", "r_dropped".
  *   "lazy_ap" 1: where "lazy_r" leaves the r-update of the three-update form pending (three steps or more, the spare vector
  *       reserved), the CG step in front of it does not store Ap = A p_2 either: it delivers p_2.Ap_2 for the step length (the
@@ -267,8 +267,32 @@ int hmg_grid_reserve_spare(hmg_grid *grid, int enable);
  * operator for an hmg_fcg object (hmg_fcg_step then asks for hmg_fcg_start).  A grid without a device context is refused. */
 int hmg_grid_set_smoother(hmg_grid *grid, int kind);
 int hmg_grid_smoother(const hmg_grid *grid);           /* the kind; -1 for a null grid */
-/* out = dinv of the level (2..nlevels), formed first if it is stale; kind 1 only */
+/* out = dinv of the level (2..nlevels), formed first if it is stale; kinds 1 and 2 */
 int hmg_grid_smoother_diag(hmg_grid *grid, int level, hmg_vec *out);
+/* Kind 2, the Chebyshev-Jacobi smoother: a Chebyshev polynomial in dinv o A on [lambda_lo, lambda_hi], lambda_lo = lambda_hi / ratio,
+ * with kind 1's dinv.  No dot product, so no reduction and no sum over ranks inside a smoothing; a fixed linear operator.
+ *     theta = (hi + lo) / 2;  delta = (hi - lo) / 2;  sigma1 = theta / delta;  rho_0 = 1 / sigma1
+ *     r = b - A x, constraint, interface sum;  d = (1 / theta) dinv o r
+ *     steps x { x += d;  Ad = A d, constraint, interface sum;  r -= Ad;
+ *               rho_{k+1} = 1 / (2 sigma1 - rho_k);  d = (rho_{k+1} rho_k) d + (2 rho_{k+1} / delta) dinv o r }
+ * hmg_smooth leaves the next d in p and A d in Ap.  Inside a V-cycle a smoother whose x alone is read ends with x += d and launches no
+ * apply for its last step: `steps` steps cost steps - 1 applies behind the first residual (hmg_ctx_counter "cheb_applies" counts
+ * them, "cheb_smoothings" the smoothings of at least one step).
+ * lambda_hi of a level must be an upper bound of the largest eigenvalue of dinv o A on the free nodes; an estimate that falls short
+ * makes the V-cycle diverge.  Where none is given the library forms, with dinv and stale with it,
+ *     lambda_hi = 1.02 * max over free slots i of dinv_i * (interface sum of s_i),   s_i = the absolute row sum of the cell's own
+ *                 lambda M + K_sigma at slot i
+ * which is at least the Gershgorin bound of the assembled matrix and at most 1.02 (dim + 1): one more kernel, interface sum and
+ * maximum per level, and one host read (hmg_ctx_counter "smoother_bound_builds" counts the levels formed).
+ * ratio <= 0: the default, 30; otherwise it must be finite and > 1.  lambda_hi: NULL, or nlevels entries,
+ * entry l - 1 for level l; an entry > 0 is used as given (no factor, nothing formed), an entry <= 0 asks for the formed bound.
+ * A partitioned grid, or one with an interface exchange, is accepted only with entries > 0 for every level >= 2 (the maximum over the
+ * ranks would need a hook the exchange does not have); without them the call fails and changes nothing.
+ * Memory, staleness, hmg_fcg objects, pending updates and hmg_grid_set_smoother(grid, 0 | 1) afterwards: as for kind 1. */
+int hmg_grid_set_smoother_chebyshev(hmg_grid *grid, double ratio, const double *lambda_hi);
+/* lambda_lo and lambda_hi of a level (2..nlevels) as kind 2 uses them; forms dinv and the bound first if they are stale (scratch
+ * from the context's pool) and synchronises the stream: not for the inside of a V-cycle.  Either pointer may be NULL. */
+int hmg_grid_smoother_bounds(hmg_grid *grid, int level, double *lambda_lo, double *lambda_hi);
 int64_t hmg_grid_ncells(const hmg_grid *grid);
 int64_t hmg_grid_nnodes(const hmg_grid *grid);
 int hmg_grid_nlevels(const hmg_grid *grid);

@@ -184,11 +184,23 @@ Base.copyto!(d::HipMatrix, s::HipMatrix) = (check(ccall((:hmg_vec_copy, LIB), Ci
 # The smoother of smoothing_steps! / vcycle! / the flexible CG on this grid (include/hmg.h: hmg_grid_set_smoother): :cg is the
 # reference's (default), :jacobi is CG preconditioned by the inverse diagonal of the assembled operator.  :jacobi reserves one vector
 # per level >= 2 (an error if the device memory is not there): set it before the level vectors are created.
-const SMOOTHERS = Dict(:cg => 0, :jacobi => 1)
-set_smoother!(g::HipGrid, kind::Symbol = :cg) =
-    check(ccall((:hmg_grid_set_smoother, LIB), Cint, (Ptr{Cvoid}, Cint), g.h, SMOOTHERS[kind]))
-smoother(g::HipGrid) = (k = ccall((:hmg_grid_smoother, LIB), Cint, (Ptr{Cvoid},), g.h); k == 1 ? :jacobi : :cg)
-# the level's inverse diagonal as the :jacobi smoother uses it (0 on constrained nodes), formed first if it is stale
+# :chebyshev is a Chebyshev polynomial in that inverse diagonal times the operator on [lambda_hi / ratio, lambda_hi] (no dot products;
+# hmg_grid_set_smoother_chebyshev): ratio <= 0 takes the library's default, lambda_hi is nothing (the library forms a rigorous bound
+# per level) or one bound per level, entries <= 0 formed.  A partitioned grid needs a bound > 0 for every level >= 2.
+const SMOOTHERS = Dict(:cg => 0, :jacobi => 1, :chebyshev => 2)
+function set_smoother!(g::HipGrid, kind::Symbol = :cg; ratio::Real = 0.0, lambda_hi::Union{Nothing,Vector{Float64}} = nothing)
+    kind == :chebyshev || return check(ccall((:hmg_grid_set_smoother, LIB), Cint, (Ptr{Cvoid}, Cint), g.h, SMOOTHERS[kind]))
+    hi = lambda_hi === nothing ? Ptr{Float64}(C_NULL) : pointer(lambda_hi)
+    GC.@preserve lambda_hi check(ccall((:hmg_grid_set_smoother_chebyshev, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Float64}), g.h, Float64(ratio), hi))
+end
+smoother(g::HipGrid) = (k = ccall((:hmg_grid_smoother, LIB), Cint, (Ptr{Cvoid},), g.h); k == 2 ? :chebyshev : k == 1 ? :jacobi : :cg)
+# (lambda_lo, lambda_hi) of a level as the :chebyshev smoother uses them, formed first if stale (synchronises)
+function smoother_bounds(g::HipGrid, level::Integer)
+    lo, hi = Ref{Float64}(0.0), Ref{Float64}(0.0)
+    check(ccall((:hmg_grid_smoother_bounds, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Float64}, Ref{Float64}), g.h, level, lo, hi))
+    (lo[], hi[])
+end
+# the level's inverse diagonal as the :jacobi and :chebyshev smoothers use it (0 on constrained nodes), formed first if it is stale
 smoother_diag!(out::HipMatrix, g::HipGrid, level::Integer) =
     (check(ccall((:hmg_grid_smoother_diag, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}), g.h, level, out.h)); out)
 # rand!(x) (src/examples/homogenized_coefficients.jl:246): seeded and layout independent on the device

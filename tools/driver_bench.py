@@ -3,7 +3,8 @@
   python tools/driver_bench.py --n 1 --dim 3 --refinements 4 --tolerance 1e-5 [--no-cpu] [--accelerate] [--contrast 100] [--smoother jacobi]
 --accelerate: the V-cycle preconditions a flexible CG iteration (driver.checkerboard_homogenization(accelerate=True)); the CPU
 oracle has the stationary iteration only, so --accelerate implies --no-cpu.
---smoother jacobi: the V-cycle's smoother is the Jacobi-preconditioned CG (driver keyword smoother="jacobi"); the CPU oracle has the
+--smoother jacobi | chebyshev: the V-cycle's smoother is the Jacobi-preconditioned CG or the Chebyshev-Jacobi polynomial (driver keyword
+smoother=); the CPU oracle has the
 reference's smoother only, so it implies --no-cpu as well.
 --tensor [--repeats R] [--warmup W]: the full homogenized tensor.  One run of driver.checkerboard_homogenization_tensor (d corrector
 solves, one setup) against the d (d + 1) / 2 runs of the scalar driver that polarising by hand takes (xi = e_i and
@@ -48,7 +49,7 @@ ap.add_argument("--refinements", type=int, default=4)
 ap.add_argument("--tolerance", type=float, default=1e-5)
 ap.add_argument("--no-cpu", action="store_true")
 ap.add_argument("--accelerate", action="store_true")
-ap.add_argument("--smoother", choices=("cg", "jacobi"), default="cg")
+ap.add_argument("--smoother", choices=("cg", "jacobi", "chebyshev"), default="cg")
 ap.add_argument("--contrast", type=float, default=9.0, help="sigma takes the values 1 and this")
 ap.add_argument("--tensor", action="store_true", help="one tensor run against d (d + 1) / 2 scalar runs")
 ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
