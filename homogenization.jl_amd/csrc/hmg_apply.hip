@@ -278,14 +278,14 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
         // x3 mode (two pending CG x-updates folded into a residual): xin = (x + ax*p1) + c2*(r2 + beta*p1), x2 = p1,
         // x3 = r2; the same three roundings as x += ax*p1; p2 = r2 + beta*p1; x += c2*p2 done one after the other
         const double *x3c = FUSED && a.x3 ? a.x3 + cell * lv.ld : nullptr;
-        const double beta = x2c ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
-        const double ax = xac || x3c ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
-        const double c2 = x3c ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
+        const double beta = x2c ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0;
+        const double ax = xac || x3c ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0;
+        const double c2 = x3c ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0;
         // x4 (own instantiations, LF == 4): a third pending x-update in front of the two, x + dx4*p0 in the place of x -- the
         // roundings of x += a0*p0; x += ax*p1; p2 = r2 + beta*p1; x += c2*p2 done one after the other
         constexpr bool X4 = FUSED && LF == 4;
         const double *x4c = X4 && a.x4 ? a.x4 + cell * lv.ld : nullptr;
-        const double dx4 = x4c ? a.scal[a.d_num] / a.scal[a.d_den] : 0.0;
+        const double dx4 = x4c ? a.scal[a.d.num] / a.scal[a.d.den] : 0.0;
         // FUSED, optional: the prolongation of the coarse-grid correction, xin = x + P xcoarse (interpolate_and_sum_to!,
         // src/interpolation.jl:64-74: identity rows += 1.0 c[a], midpoints += 0.5 c[a], += 0.5 c[b] in the CSC
         // column order), from the cell's coarse column staged in LDS behind the lattice image
@@ -315,9 +315,9 @@ k_apply(LevelDev lv, const double *__restrict__ coef, const uint16_t *__restrict
             // (x + cxa*p) + cxc*(r + cxb*p), the three roundings of k_cg_x2_update
             constexpr bool CX = cgather && LF == 5;
             const double *cpc = CX ? a.xc_p + cell * a.ldc : nullptr, *crc = CX ? a.xc_r + cell * a.ldc : nullptr;
-            const double cxa = CX ? to_sgpr(a.scal[a.a_num] / a.scal[a.a_den]) : 0.0;
-            const double cxb = CX ? to_sgpr(a.scal[a.s_num] / a.scal[a.s_den]) : 0.0;
-            const double cxc = CX ? to_sgpr(a.scal[a.c_num] / a.scal[a.c_den]) : 0.0;
+            const double cxa = CX ? to_sgpr(a.scal[a.a.num] / a.scal[a.a.den]) : 0.0;
+            const double cxb = CX ? to_sgpr(a.scal[a.s.num] / a.scal[a.s.den]) : 0.0;
+            const double cxc = CX ? to_sgpr(a.scal[a.c.num] / a.scal[a.c.den]) : 0.0;
             double cv2[NC], cp2[CX ? NC : 1], cr2[CX ? NC : 1];
             int cl2[NC];
 #pragma unroll
@@ -801,9 +801,9 @@ k_apply_slab(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
     double *xoc = FUSED && a.xout ? a.xout + cell * lv.ld : nullptr;
     double *xac = FUSED && a.xacc ? a.xacc + cell * lv.ld : nullptr;
     const double *x3c = FUSED && a.x3 ? a.x3 + cell * lv.ld : nullptr;   // two pending x-updates, see k_apply
-    const double beta = to_sgpr(x2c ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0);
-    const double ax = to_sgpr(xac || x3c ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0);
-    const double c2 = to_sgpr(x3c ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0);
+    const double beta = to_sgpr(x2c ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0);
+    const double ax = to_sgpr(xac || x3c ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0);
+    const double c2 = to_sgpr(x3c ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0);
     const uint32_t dm = (a.flags & 1) ? dmask[cell] : 0u;
     const double *sc = a.src ? a.src + cell * lv.ld : nullptr;
     double *oc = a.out ? a.out + cell * (a.out_ld ? a.out_ld : (int64_t)lv.ld) : nullptr;

@@ -55,9 +55,9 @@ k_apply_rows(LevelDev lv, const double *__restrict__ coef, const uint16_t *__res
     double *xac = FUSED && a.xacc ? a.xacc + cell * lv.ld : nullptr;
     const double *x3c = FUSED && a.x3 ? a.x3 + cell * lv.ld : nullptr;   // two pending x-updates, see k_apply
     const bool xzero = FUSED && (a.flags & 128);                          // x is zero and is not read (x3 form only)
-    const double beta = to_sgpr(x2c ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0);
-    const double ax = to_sgpr(xac || x3c ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0);
-    const double c2 = to_sgpr(x3c ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0);
+    const double beta = to_sgpr(x2c ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0);
+    const double ax = to_sgpr(xac || x3c ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0);
+    const double c2 = to_sgpr(x3c ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0);
     const uint32_t dm = (a.flags & 1) ? dmask[cell] : 0u;
     const double *sc = a.src ? a.src + cell * lv.ld : nullptr;
     double *oc = a.out ? a.out + cell * (a.out_ld ? a.out_ld : (int64_t)lv.ld) : nullptr;

@@ -256,9 +256,9 @@ k_apply_slab2(LevelDev lv, const double *__restrict__ coef, const uint16_t *__re
         // LOADERS.  Rows of 512 slots: row j of step f = (cell, slab) holds entries (j R + e) 256 + rt of the slab's load list; the
         // rows of all steps of all this workgroup's cells are ONE stream, walked by three cursors a fixed distance apart.
         // ------------------------------------------------------------------------------------------------------------------
-        const double beta = to_sgpr(FUSED && NS >= 2 ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0);
-        const double ax = to_sgpr(FUSED && NS == 3 ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0);
-        const double c2 = to_sgpr(FUSED && a.x3 ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0);
+        const double beta = to_sgpr(FUSED && NS >= 2 ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0);
+        const double ax = to_sgpr(FUSED && NS == 3 ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0);
+        const double c2 = to_sgpr(FUSED && a.x3 ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0);
         const bool x3mode = FUSED && NS == 3 && a.x3 != nullptr;
         const bool xzero = FUSED && (a.flags & 128);
         const double *xa_base = NS == 3 ? (a.x3 ? a.x3 : a.xacc) : nullptr;

@@ -67,9 +67,9 @@ k_apply_small(LevelDev lv, const uint16_t *__restrict__ dmask, const int32_t *__
     const bool neg = a.alpha < 0.0;
     double beta = 0.0, ax = 0.0, c2 = 0.0;
     if constexpr (FUSED) {
-        beta = a.x2 ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
-        ax = a.xacc || a.x3 ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
-        c2 = a.x3 ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
+        beta = a.x2 ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0;
+        ax = a.xacc || a.x3 ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0;
+        c2 = a.x3 ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0;
     }
     const bool xzero = FUSED && (a.flags & 128);
     const int64_t G = gridDim.x;
@@ -241,9 +241,9 @@ k_apply_pack(LevelDev lv, const uint16_t *__restrict__ dmask, const int32_t *__r
     const bool neg = a.alpha < 0.0;
     double beta = 0.0, ax = 0.0, c2 = 0.0;
     if constexpr (FUSED) {
-        beta = a.x2 ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
-        ax = a.xacc || a.x3 ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
-        c2 = a.x3 ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
+        beta = a.x2 ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0;
+        ax = a.xacc || a.x3 ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0;
+        c2 = a.x3 ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0;
     }
     const bool xzero = FUSED && (a.flags & 128);
     const int64_t G = gridDim.x, nquad = (a.nwork + 3) >> 2;

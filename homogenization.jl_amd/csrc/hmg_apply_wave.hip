@@ -148,9 +148,9 @@ k_apply_wave(LevelDev lv, const uint16_t *__restrict__ dmask, const int32_t *__r
     const bool v15 = lane + 960 < WNF;
     double beta = 0.0, ax = 0.0, c2 = 0.0;
     if constexpr (FUSED) {
-        beta = a.x2 ? a.scal[a.s_num] / a.scal[a.s_den] : 0.0;
-        ax = a.xacc || a.x3 ? a.scal[a.a_num] / a.scal[a.a_den] : 0.0;
-        c2 = a.x3 ? a.scal[a.c_num] / a.scal[a.c_den] : 0.0;
+        beta = a.x2 ? a.scal[a.s.num] / a.scal[a.s.den] : 0.0;
+        ax = a.xacc || a.x3 ? a.scal[a.a.num] / a.scal[a.a.den] : 0.0;
+        c2 = a.x3 ? a.scal[a.c.num] / a.scal[a.c.den] : 0.0;
     }
     // (one opaque zero per USE: a shared one lets the backend form every `word | zero` at the top of the cell and keep
     //  them all -- the table twice)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace hmg {
@@ -140,29 +141,60 @@ struct MeshDev {
     SlabTables slab;             // set per level before an apply of a level whose cell exceeds the LDS
 };
 
+// scalar bank slots (device doubles)
+// (S_DONE / S_ITER / S_CRR: device-side state of the coarse PCG -- converged flag, iterations done, last r.r;
+//  slots 12..15: host sums of hmg_comm_sum_host; S_RS3 / S_PAP3: the third pair of a smoother that defers three x-updates --
+//  the bank is 16 doubles by contract (hmg_ctx_set_scalar_bank), so they share S_C1, which the coarse PCG leaves alone, and S_TMP, a
+//  temporary of calls that cannot run inside a smoother)
+enum { S_RS = 0, S_PAP = 1, S_RS2 = 2, S_TMP = 3, S_C0 = 4, S_C1 = 5, S_C2 = 6, S_C3 = 7, S_PAP2 = 8, S_DONE = 9, S_ITER = 10,
+       S_CRR = 11, S_HOST = 12, S_COUNT = 16,
+       S_RS3 = S_C1, S_PAP3 = S_TMP };
+
+struct Ratio { int num, den; };     // scal[num] / scal[den]
+
+// CG x-updates that a smoother left undone, for a later launch to finish:
+//   x lacks  [x += first p0;]  x += prev p1;  x += last (r2 + beta p1)        (count 3 / 2)
+//   x lacks  x += last p1                                                      (count 1)
+// with the roundings of the updates made one after the other (xupd2() of hmg_stencil.hpp).
+struct XUpdates {
+    int count = 0;                                        // 0: nothing is pending
+    Ratio last{-1, -1}, prev{-1, -1}, beta{-1, -1}, first{-1, -1};
+    const double *p0 = nullptr, *p1 = nullptr, *r2 = nullptr;
+    const double *scal = nullptr;                         // where the ratios are read; null: the scalar bank
+};
+
+// The ratios of pending updates put aside, so that they outlive the scalar bank's slots: XS_COUNT doubles behind a grid's block partials
+// (hmg_grid::pend_alpha()), written by k_cg_x_tail (the first four) or k_cg_x_save (all).  The step length is stored formed, with a 1.0
+// behind it, the others as numerator and denominator: whoever reads the block as its `scal` forms every ratio by the division that the
+// launch not made would have done.
+enum { XS_ALPHA = 0, XS_ONE = 1, XS_BETA_NUM = 2, XS_BETA_DEN = 3, XS_PREV_NUM = 4, XS_PREV_DEN = 5, XS_FIRST_NUM = 6, XS_FIRST_DEN = 7,
+       XS_COUNT = 8 };
+constexpr Ratio XS_LAST{XS_ALPHA, XS_ONE}, XS_BETA{XS_BETA_NUM, XS_BETA_DEN}, XS_PREV{XS_PREV_NUM, XS_PREV_DEN},
+    XS_FIRST{XS_FIRST_NUM, XS_FIRST_DEN};
+
 struct ApplyArgs {
     double alpha, lambda;
-    const double *x;       // input column; with x2: xin = x + beta * x2, beta = scal[s_num] / scal[s_den]
+    const double *x;       // input column; with x2: xin = x + beta * x2, beta = s
     const double *x2;
     double *xout;          // optional: xin written back (p-update / p = r)
-    double *xacc;          // optional: xacc += (scal[a_num] / scal[a_den]) * x2  (the previous step's x-update)
-    int a_num, a_den;
-    const double *x3;      // optional (k_apply FUSED, with x2, without xacc): xin = (x + ax*x2) + c*(x3 + beta*x2),
-    int c_num, c_den;      //   ax = scal[a_num]/scal[a_den], c = scal[c_num]/scal[c_den]: two CG x-updates at once
+    double *xacc;          // optional: xacc += a * x2  (the previous step's x-update)
+    Ratio a;
+    const double *x3;      // optional (k_apply FUSED, with x2, without xacc): xin = (x + a*x2) + c*(x3 + beta*x2):
+    Ratio c;               //   two CG x-updates at once
     const double *x4;      // optional (x3 mode of the register-blocked k_apply -- apply_defers3(), apply_carries_x() -- only):
-    int d_num, d_den;      //   x + (scal[d_num]/scal[d_den]) * x4 takes the place of x, a third x-update in front of the two.  Every
+    Ratio d;               //   x + d * x4 takes the place of x, a third x-update in front of the two.  Every
                            //   other kernel family (k_apply_wave, k_apply_small, k_apply_slab / _slab2, k_apply_rows) refuses it
     const double *xcoarse; // optional (fused kernel, not the slab one): xin = x + P xcoarse first (prolongation of the
     int64_t ldc;           //   coarse-grid correction; column stride ldc), written back through xout
     const double *xc_p, *xc_r;   // optional (with xcoarse and flags bit 6, register-blocked k_apply -- apply_folds_coarse_x() -- only): the
-                           //   coarse column is (xcoarse + (scal[a_num]/scal[a_den]) xc_p) + (scal[c_num]/scal[c_den]) (xc_r +
-                           //   (scal[s_num]/scal[s_den]) xc_p), the coarser level's last two CG x-updates; every other family refuses them
+                           //   coarse column is (xcoarse + a xc_p) + c (xc_r + s xc_p), the coarser level's last two CG x-updates;
+                           //   every other family refuses them
     const double *src;     // optional: out = src + alpha * A * xin
     double *out;
     double *rcoarse;       // optional (k_apply RS instantiation): restrict_to!(rcoarse, P, out) in the epilogue -- column stride
     int64_t ldrc;          //   ldrc; `out` itself may then be null (the cell-local residual is not stored at all)
-    const double *scal;
-    int s_num, s_den;
+    const double *scal;    // where the ratios a, c, d, s are read
+    Ratio s;
     double *blockpart;
     const uint8_t *mult;
     int flags;             // bit 0: Dirichlet constraint on out; bit 1: mass term only; bit 2 (slab kernel): weights =
@@ -178,6 +210,10 @@ struct ApplyArgs {
     int64_t nwork;         // set by the launcher: work items (cells) of this launch -- one-wave workgroups loop over them
     const int32_t *cell_class;  // set by the launcher (WC instantiations): the cell's class in the class-weight cache
 };
+// (a kernel argument: the ratios lie where the pairs of ints they replaced lay)
+static_assert(sizeof(ApplyArgs) == 240 && offsetof(ApplyArgs, a) == 48 && offsetof(ApplyArgs, c) == 64 && offsetof(ApplyArgs, d) == 80 &&
+                  offsetof(ApplyArgs, s) == 160,
+              "ApplyArgs layout");
 
 struct CoarseDev {
     int64_t n;
@@ -185,15 +221,6 @@ struct CoarseDev {
     const double *val, *diag;
     const int32_t *interior;     // n
 };
-
-// scalar bank slots (device doubles)
-// (S_DONE / S_ITER / S_CRR: device-side state of the coarse PCG -- converged flag, iterations done, last r.r;
-//  slots 12..15: host sums of hmg_comm_sum_host; S_RS3 / S_PAP3: the third pair of a smoother that defers three x-updates --
-//  the bank is 16 doubles by contract (hmg_ctx_set_scalar_bank), so they share S_C1, which the coarse PCG leaves alone, and S_TMP, a
-//  temporary of calls that cannot run inside a smoother)
-enum { S_RS = 0, S_PAP = 1, S_RS2 = 2, S_TMP = 3, S_C0 = 4, S_C1 = 5, S_C2 = 6, S_C3 = 7, S_PAP2 = 8, S_DONE = 9, S_ITER = 10,
-       S_CRR = 11, S_HOST = 12, S_COUNT = 16,
-       S_RS3 = S_C1, S_PAP3 = S_TMP };
 
 struct Launch {
     hipStream_t stream;
@@ -239,7 +266,7 @@ bool apply_carries_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, d
 // Fused CG pass, see k_apply<.., FUSED>: the kernel (possibly over a cell list, several launches) leaves
 // per-cell partial sums in mesh.blockpart; the reduce step turns them into scal[slot_pap] = sum mult*xin*out and
 // scal[slot_rr] = sum xin*xin (slot_rr < 0: not wanted).  a.mult / a.blockpart are filled in here, and a.scal where the caller left
-// it null (the bank; a caller's own a.scal is where the kernel reads its s_num / s_den ... from, the sums go to the bank either way).
+// it null (the bank; a caller's own a.scal is where the kernel reads its ratios from, the sums go to the bank either way).
 void launch_apply_fused_kernel(const Launch &L, const LevelDev &lv, const MeshDev &mesh, ApplyArgs a);
 void launch_apply_fused_reduce(const Launch &L, const MeshDev &mesh, int slot_pap, int slot_rr);
 // scal[slot] = partials[0] + ... + partials[n - 1], one block in a fixed order (k_finalize, hmg_kernels.hip); the caller checks the launch
@@ -287,38 +314,30 @@ void launch_dot(const Launch &L, const double *x, const double *y, int64_t n, in
 void launch_norm2_unique(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *x, int slot);
 // p = r; scal[slot] = r.r
 void launch_copy_dot(const Launch &L, double *p, const double *r, int64_t n, int slot);
-// alpha = scal[s_num]/scal[s_den]; x += alpha p; r -= alpha q; scal[s_out] = r.r
-void launch_cg_update(const Launch &L, double *x, double *r, const double *p, const double *q, int64_t n,
-                      int s_num, int s_den, int s_out);
-// alpha = scal[s_num]/scal[s_den]; r -= alpha q; scal[s_out] = r.r
-void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const double *q, int64_t n, int s_num, int s_den,
-                       int s_out);
+// x += alpha p; r -= alpha q; scal[s_out] = r.r
+void launch_cg_update(const Launch &L, double *x, double *r, const double *p, const double *q, int64_t n, Ratio alpha, int s_out);
+// r -= alpha q; scal[s_out] = r.r
+void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const double *q, int64_t n, Ratio alpha, int s_out);
 // the same with the face part of q's interface sum taken on the fly (q unsummed on the shared faces)
-// (scal: where s_num / s_den are read, default the bank; the r.r goes to the bank's s_out either way)
+// (scal: where alpha is read, default the bank; the r.r goes to the bank's s_out either way)
 void launch_cg_rupdate_faces(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                             const double *q, int64_t n, int s_num, int s_den, int s_out, const double *scal = nullptr);
-void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                               const double *q, int64_t n, int s_num, int s_den, int s_out, double *x, const double *p, int a_num,
-                               int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den);
-// ... its x-updates alone (the r half stays pending); alpha_out[0] = scal[s_num]/scal[s_den], alpha_out[1] = 1.0,
-// alpha_out[2] = scal[b_num], alpha_out[3] = scal[b_den] (four doubles)
-void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
-                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out,
-                      const double *scal = nullptr);
-// ... left pending too (option lazy_x): the scalars it would read, saved to out[0..8) -- out[0..4) as launch_cg_x_tail leaves them,
-// out[4] / out[5] = scal[a_num], scal[a_den], out[6] / out[7] = scal[z_num], scal[z_den] (0, 1 unless `three`).  launch_cg_x_tail with
-// scal = out, the slots (0, 1; 4, 5; 2, 3; 6, 7) and a null alpha_out is then the launch not made here (scal: the bank it reads, default
-// the context's)
-void launch_cg_x_save(const Launch &L, int s_num, int s_den, int a_num, int a_den, int b_num, int b_den, bool three, int z_num, int z_den,
-                      double *out);
-// x += (scal[a_num]/scal[a_den]) p; with_p: p = r + (scal[s_num]/scal[s_den]) p
-void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, int a_num, int a_den,
-                         int s_num, int s_den, int with_p);
-// x = (x + (scal[a_num]/scal[a_den]) p) + (scal[c_num]/scal[c_den]) (r + (scal[b_num]/scal[b_den]) p)
-void launch_cg_x2_update(const Launch &L, double *x, const double *p, const double *r, int64_t n, int a_num, int a_den, int b_num,
-                         int b_den, int c_num, int c_den);
-// beta = scal[s_num]/scal[s_den]; p = r + beta p
-void launch_cg_pupdate(const Launch &L, double *p, const double *r, int64_t n, int s_num, int s_den);
+                             const double *q, int64_t n, Ratio alpha, int s_out, const double *scal = nullptr);
+// ... with the two or three pending x-updates u of a lazy last step finished on the way: r = u.r2, alpha = u.last (read from the bank)
+void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double *rout, const double *q, int64_t n,
+                               int s_out, double *x, const XUpdates &u);
+// ... its x-updates alone (the r half stays pending); alpha_out, where not null, receives the first four doubles of the saved block
+// (XS_ALPHA .. XS_BETA_DEN)
+void launch_cg_x_tail(const Launch &L, double *x, int64_t n, const XUpdates &u, double *alpha_out);
+// ... left pending too (option lazy_x): the scalars it would read from the bank, saved to out[0 .. XS_COUNT) (first: 0 / 1 with two
+// updates).  launch_cg_x_tail with the block as u.scal, the ratios XS_LAST, XS_PREV, XS_BETA, XS_FIRST and a null alpha_out is then
+// the launch not made here
+void launch_cg_x_save(const Launch &L, const XUpdates &u, double *out);
+// x += alpha p; with_p: p = r + beta p
+void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, Ratio alpha, Ratio beta, int with_p);
+// both updates of u (count 2) in one pass: x = (x + prev p1) + last (r2 + beta p1)
+void launch_cg_x2_update(const Launch &L, double *x, int64_t n, const XUpdates &u);
+// p = r + beta p
+void launch_cg_pupdate(const Launch &L, double *p, const double *r, int64_t n, Ratio beta);
 
 void launch_gather_base(const Launch &L, const MeshDev &mesh, int ld1, const double *v1, double *u);
 void launch_scatter_base(const Launch &L, const MeshDev &mesh, int ld1, const double *u, double *v1);

@@ -183,8 +183,7 @@ int hmg_fcg_step(void *handle, hmg_vec *x, hmg_vec **states)
         const PendingX px = take_pending_x(f->g, top[0]);
         if (px.form)
             // z = x lacks its last two or three CG updates (option lazy_x): formed where z.q reads it, 48 B/DOF instead of 40 + 16
-            launch_fcg_dot_zq_x(F, top[0]->d, px.form == 3 ? f->g->top_spare.p : px.p->d, px.form == 3 ? px.p->d : nullptr, px.r->d,
-                                f->g->pend_alpha(), qd, n);
+            launch_fcg_dot_zq_x(F, top[0]->d, saved_updates(f->g, px), qd, n);
         else
             launch_fcg_dot_zq(F, zd, qd, n);
         scalar_sum(f->g, FB_ZQ, 1);

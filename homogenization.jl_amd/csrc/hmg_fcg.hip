@@ -40,7 +40,7 @@ k_fcg_dot_zq(const double *__restrict__ z, const double *__restrict__ q, int64_t
 }
 
 // ... where the V-cycle left z's last CG updates pending (option lazy_x): z = ((z [+ az p0]) + ax p1) + alpha (r2 + beta p1) formed
-// here -- k_cg_x_tail's arithmetic from the eight ratios it would have read (sc: launch_cg_x_save) --, stored, and used in the
+// here -- k_cg_x_tail's arithmetic from the saved block it would have read (sc: launch_cg_x_save, hmg_device.hpp XS_*) --, stored, and used in the
 // dot product: 48 B/DOF (40 with two updates) instead of the tail's 40 (32) + 16.  XU == 2: three updates, p0 is read.
 template <int XU>
 __global__ void __launch_bounds__(FB)
@@ -48,10 +48,10 @@ k_fcg_dot_zq_x(double *z, const double *__restrict__ p1, const double *__restric
                const double *__restrict__ sc, const double *__restrict__ q, int64_t n, double *__restrict__ part)
 {
     __shared__ double red[4];
-    const double alpha = sc[0] / sc[1];
-    const double ax = sc[4] / sc[5];
-    const double beta = sc[2] / sc[3];
-    const double az = XU == 2 ? sc[6] / sc[7] : 0.0;
+    const double alpha = sc[XS_ALPHA] / sc[XS_ONE];
+    const double ax = sc[XS_PREV_NUM] / sc[XS_PREV_DEN];
+    const double beta = sc[XS_BETA_NUM] / sc[XS_BETA_DEN];
+    const double az = XU == 2 ? sc[XS_FIRST_NUM] / sc[XS_FIRST_DEN] : 0.0;
     const int64_t i = (int64_t)blockIdx.x * FB + threadIdx.x;
     double acc = 0.0;
     if (i < (n >> 1)) {
@@ -221,16 +221,17 @@ void launch_fcg_dot_zq(const FcgLaunch &F, const double *z, const double *q, int
     reduce<1>(F, nb, FB_ZQ);
 }
 
-void launch_fcg_dot_zq_x(const FcgLaunch &F, double *z, const double *p1, const double *p0, const double *r2, const double *saved,
-                         const double *q, int64_t n)
+void launch_fcg_dot_zq_x(const FcgLaunch &F, double *z, const XUpdates &u, const double *q, int64_t n)
 {
-    if (!z || !p1 || !r2 || !saved || !q) throw std::runtime_error("flexible CG: pending updates of z without their vectors");
+    // (the kernel reads the saved block at its own places: u is what saved_updates() makes of a record)
+    if (!z || !u.p1 || !u.r2 || !u.scal || !q || (u.count == 3) != (u.p0 != nullptr))
+        throw std::runtime_error("flexible CG: pending updates of z without their vectors");
     const int64_t nb = fcg_blocks(n);
     check_blocks(nb);
-    if (p0)
-        hipLaunchKernelGGL(k_fcg_dot_zq_x<2>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, p1, p0, r2, saved, q, n, F.part);
+    if (u.p0)
+        hipLaunchKernelGGL(k_fcg_dot_zq_x<2>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, u.p1, u.p0, u.r2, u.scal, q, n, F.part);
     else
-        hipLaunchKernelGGL(k_fcg_dot_zq_x<1>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, p1, p0, r2, saved, q, n, F.part);
+        hipLaunchKernelGGL(k_fcg_dot_zq_x<1>, dim3((unsigned)nb), dim3(FB), 0, F.stream, z, u.p1, u.p0, u.r2, u.scal, q, n, F.part);
     check_launch();
     reduce<1>(F, nb, FB_ZQ);
 }

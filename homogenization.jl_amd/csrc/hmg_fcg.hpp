@@ -2,9 +2,7 @@
 // (hmg_fcg.cpp) and its kernels (hmg_fcg.hip) share.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "hmg_device.hpp"
 
 namespace hmg {
 
@@ -27,10 +25,9 @@ struct FcgLaunch {
 int64_t fcg_blocks(int64_t n);                       // blocks of a streaming launch over n doubles
 // bank[FB_ZQ] = z.q
 void launch_fcg_dot_zq(const FcgLaunch &F, const double *z, const double *q, int64_t n);
-// ... with z's last CG updates still pending (option lazy_x; hmg_objects.hpp: PendingX): z = ((z [+ az p0]) + ax p1) + alpha (r2 +
-// beta p1) is formed, stored and used; saved[0..8): the ratios as launch_cg_x_save left them; p0 null: two updates
-void launch_fcg_dot_zq_x(const FcgLaunch &F, double *z, const double *p1, const double *p0, const double *r2, const double *saved,
-                         const double *q, int64_t n);
+// ... with z's last two or three CG updates still pending (option lazy_x; hmg_objects.hpp: PendingX): z with the updates u is formed,
+// stored and used; u: saved_updates() of the record, its ratios read from the saved block u.scal as launch_cg_x_save left them
+void launch_fcg_dot_zq_x(const FcgLaunch &F, double *z, const XUpdates &u, const double *q, int64_t n);
 // first != 0: p = z, fs[F_BETA] = 0;  else beta = -bank[FB_ZQ] / fs[F_PQ], p = z + beta p, fs[F_BETA] = beta
 void launch_fcg_direction(const FcgLaunch &F, double *p, const double *z, int64_t n, int first);
 // bank[FB_PQ] = p.q, bank[FB_PR] = p.R

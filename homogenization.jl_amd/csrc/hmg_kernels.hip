@@ -566,8 +566,9 @@ k_cg_rupdate(const double *r, double *rout, const double *__restrict__ q, int64_
 // roundings of  x += alpha_{i-1} p_{i-1};  p_i = r_i + beta p_{i-1};  x += alpha_i p_i  one after the other (k_cg_x2_update).
 // XU == 2: a third pending update comes first, x += az p0 (the step before wrote its direction next to p0 instead of over it).
 struct XUSlots {
-    int a_num, a_den, b_num, b_den, z_num, z_den;
+    Ratio a, b, z;
 };
+static_assert(sizeof(XUSlots) == 6 * sizeof(int), "XUSlots is a kernel argument: six ints");
 // (the two pending x-updates themselves: xupd2() of hmg_stencil.hpp, shared with the flexible CG's kernel that forms z from them)
 template <int XU>
 __global__ void __launch_bounds__(SB)
@@ -578,9 +579,9 @@ k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, 
 {
     __shared__ double red[4];
     const double alpha = scal[s_num] / scal[s_den];
-    const double ax = XU ? scal[xs.a_num] / scal[xs.a_den] : 0.0;
-    const double beta = XU ? scal[xs.b_num] / scal[xs.b_den] : 0.0;
-    const double az = XU == 2 ? scal[xs.z_num] / scal[xs.z_den] : 0.0;
+    const double ax = XU ? scal[xs.a.num] / scal[xs.a.den] : 0.0;
+    const double beta = XU ? scal[xs.b.num] / scal[xs.b.den] : 0.0;
+    const double az = XU == 2 ? scal[xs.z.num] / scal[xs.z.den] : 0.0;
     auto xupd = [&](double xv, double pv, double rv) { return xupd2(ax, beta, alpha, xv, pv, rv); };
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     double acc = 0.0;
@@ -636,9 +637,9 @@ k_cg_rupdate_faces(const double *r, double *rout, const double *__restrict__ q, 
 
 // The x half of k_cg_rupdate_faces<XU> alone (XU = 1, 2), for a caller that leaves the r half pending (hmg_vcycle, option lazy_r):
 // reads x, p (, p0) and r, writes x -- no q, no partner gather, no r store, no reduction.  The step length it formed goes to
-// alpha_out[0] with a 1.0 behind it: k_cg_rupdate_faces<0> run later with alpha_out as its scalars (slots 0 / 1) forms the same
-// alpha, whatever the scalar bank holds by then.  alpha_out[2] / alpha_out[3]: numerator and denominator of this step's beta, for a
-// caller that did not store Ap either (option lazy_ap) and runs the step's apply again with alpha_out as its scalars.
+// alpha_out[XS_ALPHA] with a 1.0 behind it: k_cg_rupdate_faces<0> run later with alpha_out as its scalars (the ratio XS_LAST) forms the
+// same alpha, whatever the scalar bank holds by then.  alpha_out[XS_BETA_NUM / _DEN]: numerator and denominator of this step's beta, for
+// a caller that did not store Ap either (option lazy_ap) and runs the step's apply again with alpha_out as its scalars (XS_BETA).
 template <int XU>
 __global__ void __launch_bounds__(SB)
 k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ p0, const double *__restrict__ r, int64_t n,
@@ -646,9 +647,9 @@ k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ 
 {
     static_assert(XU == 1 || XU == 2, "one or two stored directions");
     const double alpha = scal[s_num] / scal[s_den];
-    const double ax = scal[xs.a_num] / scal[xs.a_den];
-    const double beta = scal[xs.b_num] / scal[xs.b_den];
-    const double az = XU == 2 ? scal[xs.z_num] / scal[xs.z_den] : 0.0;
+    const double ax = scal[xs.a.num] / scal[xs.a.den];
+    const double beta = scal[xs.b.num] / scal[xs.b.den];
+    const double az = XU == 2 ? scal[xs.z.num] / scal[xs.z.den] : 0.0;
     const int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x;
     if (i < (n >> 1)) {
         double2 xv = reinterpret_cast<double2 *>(x)[i];
@@ -666,28 +667,28 @@ k_cg_x_tail(double *x, const double *__restrict__ p, const double *__restrict__ 
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         if (n & 1) x[n - 1] = xupd2(ax, beta, alpha, XU == 2 ? axpy1(az, p0[n - 1], x[n - 1]) : x[n - 1], p[n - 1], r[n - 1]);
         if (!alpha_out) return;                  // (run late from the saved scalars, k_cg_x_save: they hold all of this already)
-        alpha_out[0] = alpha;
-        alpha_out[1] = 1.0;
-        alpha_out[2] = scal[xs.b_num];           // beta as the apply of this step read it: the same division forms it again
-        alpha_out[3] = scal[xs.b_den];
+        alpha_out[XS_ALPHA] = alpha;
+        alpha_out[XS_ONE] = 1.0;
+        alpha_out[XS_BETA_NUM] = scal[xs.b.num]; // beta as the apply of this step read it: the same division forms it again
+        alpha_out[XS_BETA_DEN] = scal[xs.b.den];
     }
 }
 
 // What k_cg_x_tail reads from the scalar bank, saved instead of used (hmg_vcycle, option lazy_x: the x-updates stay pending as well):
-// out[0..4) as k_cg_x_tail leaves them, out[4] / out[5] numerator and denominator of ax, out[6] / out[7] of az (0 / 1 without a third
-// update).  k_cg_x_tail, or a residual that carries the updates in its load phase, run later with `out` as its scalars forms every
+// the whole saved block (hmg_device.hpp: XS_ALPHA ... XS_FIRST_DEN) -- its first four doubles as k_cg_x_tail leaves them, then numerator
+// and denominator of ax and of az (0 / 1 without a third update).  k_cg_x_tail, or a residual that carries the updates in its load phase, run later with `out` as its scalars forms every
 // ratio by the same division of the same numbers, whatever the scalar bank holds by then.
 __global__ void k_cg_x_save(const double *__restrict__ scal, int s_num, int s_den, XUSlots xs, int three, double *out)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    out[0] = scal[s_num] / scal[s_den];
-    out[1] = 1.0;
-    out[2] = scal[xs.b_num];
-    out[3] = scal[xs.b_den];
-    out[4] = scal[xs.a_num];
-    out[5] = scal[xs.a_den];
-    out[6] = three ? scal[xs.z_num] : 0.0;
-    out[7] = three ? scal[xs.z_den] : 1.0;
+    out[XS_ALPHA] = scal[s_num] / scal[s_den];
+    out[XS_ONE] = 1.0;
+    out[XS_BETA_NUM] = scal[xs.b.num];
+    out[XS_BETA_DEN] = scal[xs.b.den];
+    out[XS_PREV_NUM] = scal[xs.a.num];
+    out[XS_PREV_DEN] = scal[xs.a.den];
+    out[XS_FIRST_NUM] = three ? scal[xs.z.num] : 0.0;
+    out[XS_FIRST_DEN] = three ? scal[xs.z.den] : 1.0;
 }
 
 // x += alpha p (alpha = scal[a_num]/scal[a_den]) and, if with_p, p = r + beta p (beta = scal[s_num]/scal[s_den])
@@ -832,110 +833,114 @@ void launch_copy_dot(const Launch &L, double *p, const double *r, int64_t n, int
     check_launch();
     reduce_finish(L, nb, slot);
 }
-void launch_cg_update(const Launch &L, double *x, double *r, const double *p, const double *q, int64_t n, int s_num,
-                      int s_den, int s_out)
+void launch_cg_update(const Launch &L, double *x, double *r, const double *p, const double *q, int64_t n, Ratio alpha, int s_out)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, r, p, q, n, L.scal, s_num, s_den,
+    hipLaunchKernelGGL(k_cg_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, r, p, q, n, L.scal, alpha.num, alpha.den,
                        reduce_target(L, nb));
     check_launch();
     reduce_finish(L, nb, s_out);
 }
-void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const double *q, int64_t n, int s_num, int s_den,
-                       int s_out)
+void launch_cg_rupdate(const Launch &L, const double *r, double *rout, const double *q, int64_t n, Ratio alpha, int s_out)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_rupdate, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, L.scal, s_num, s_den,
+    hipLaunchKernelGGL(k_cg_rupdate, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, L.scal, alpha.num, alpha.den,
                        reduce_target(L, nb));
     check_launch();
     reduce_finish(L, nb, s_out);
 }
 
 void launch_cg_rupdate_faces(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                             const double *q, int64_t n, int s_num, int s_den, int s_out, const double *scal)
+                             const double *q, int64_t n, Ratio alpha, int s_out, const double *scal)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_rupdate_faces<0>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, scal ? scal : L.scal, s_num, s_den,
-                       reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi,
-                       (double *)nullptr, (const double *)nullptr, (const double *)nullptr, XUSlots{0, 0, 0, 0, 0, 0});
+    hipLaunchKernelGGL(k_cg_rupdate_faces<0>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, scal ? scal : L.scal, alpha.num,
+                       alpha.den, reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi,
+                       (double *)nullptr, (const double *)nullptr, (const double *)nullptr, XUSlots{});
     check_launch();
     reduce_finish(L, nb, s_out);
 }
 
-// ... with the pending x-updates of a lazy last step: x = ((x [+ (z_num/z_den) p0]) + (a_num/a_den) p) + (s_num/s_den) (r + (b_num/b_den) p)
-void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, const double *r, double *rout,
-                               const double *q, int64_t n, int s_num, int s_den, int s_out, double *x, const double *p, int a_num,
-                               int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den)
+// The kernels' view of two or three pending x-updates: p = u.p1, p0 = u.p0 (three), r = u.r2, alpha = u.last, and these slots
+static XUSlots xu_slots(const XUpdates &u)
+{
+    if ((u.count != 2 && u.count != 3) || !u.p1 || !u.r2 || (u.count == 3) != (u.p0 != nullptr))
+        throw std::runtime_error("pending x-updates without their vectors");
+    return XUSlots{u.prev, u.beta, u.count == 3 ? u.first : Ratio{0, 0}};
+}
+
+// ... with the pending x-updates of a lazy last step: x = ((x [+ first p0]) + prev p1) + last (r2 + beta p1)
+void launch_cg_rupdate_faces_x(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double *rout, const double *q, int64_t n,
+                               int s_out, double *x, const XUpdates &u)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    const XUSlots xs{a_num, a_den, b_num, b_den, z_num, z_den};
-    if (p0)
-        hipLaunchKernelGGL(k_cg_rupdate_faces<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, L.scal, s_num, s_den,
-                           reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi, x, p,
-                           p0, xs);
+    const XUSlots xs = xu_slots(u);
+    if (u.scal) throw std::runtime_error("an r-update reads its step length from the scalar bank");
+    if (u.p0)
+        hipLaunchKernelGGL(k_cg_rupdate_faces<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, u.r2, rout, q, n, L.scal, u.last.num, u.last.den,
+                           reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi, x, u.p1,
+                           u.p0, xs);
     else
-        hipLaunchKernelGGL(k_cg_rupdate_faces<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, r, rout, q, n, L.scal, s_num, s_den,
-                           reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi, x, p,
-                           p0, xs);
+        hipLaunchKernelGGL(k_cg_rupdate_faces<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, u.r2, rout, q, n, L.scal, u.last.num, u.last.den,
+                           reduce_target(L, nb), mesh.face_partner, lv.ld, 1.0 / (double)lv.ld, lv.off_face, lv.off_int, lv.nfi, x, u.p1,
+                           u.p0, xs);
     check_launch();
     reduce_finish(L, nb, s_out);
 }
 
-// the x-updates of launch_cg_rupdate_faces_x alone; alpha_out[0..4) = s_num/s_den, 1.0, scal[b_num], scal[b_den]
-void launch_cg_x_tail(const Launch &L, const double *r, int64_t n, int s_num, int s_den, double *x, const double *p, int a_num,
-                      int a_den, int b_num, int b_den, const double *p0, int z_num, int z_den, double *alpha_out, const double *scal)
+// the x-updates of launch_cg_rupdate_faces_x alone
+void launch_cg_x_tail(const Launch &L, double *x, int64_t n, const XUpdates &u, double *alpha_out)
 {
-    if ((!alpha_out && !scal) || n <= 0) throw std::runtime_error("x-only tail without a place for its step length");
+    if ((!alpha_out && !u.scal) || n <= 0) throw std::runtime_error("x-only tail without a place for its step length");
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    const XUSlots xs{a_num, a_den, b_num, b_den, z_num, z_den};
-    if (!scal) scal = L.scal;
-    if (p0)
-        hipLaunchKernelGGL(k_cg_x_tail<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, scal, s_num, s_den, xs, alpha_out);
+    const XUSlots xs = xu_slots(u);
+    const double *scal = u.scal ? u.scal : L.scal;
+    if (u.p0)
+        hipLaunchKernelGGL(k_cg_x_tail<2>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, u.p1, u.p0, u.r2, n, scal, u.last.num, u.last.den, xs,
+                           alpha_out);
     else
-        hipLaunchKernelGGL(k_cg_x_tail<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, p0, r, n, scal, s_num, s_den, xs, alpha_out);
+        hipLaunchKernelGGL(k_cg_x_tail<1>, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, u.p1, u.p0, u.r2, n, scal, u.last.num, u.last.den, xs,
+                           alpha_out);
     check_launch();
 }
 
-// ... not run at all: what it would read from the scalar bank goes to out[0..8) (k_cg_x_save)
-void launch_cg_x_save(const Launch &L, int s_num, int s_den, int a_num, int a_den, int b_num, int b_den, bool three, int z_num, int z_den,
-                      double *out)
+// ... not run at all: what it would read from the scalar bank goes to out[0 .. XS_COUNT) (k_cg_x_save)
+void launch_cg_x_save(const Launch &L, const XUpdates &u, double *out)
 {
-    if (!out) throw std::runtime_error("pending x-updates without a place for their scalars");
-    const XUSlots xs{a_num, a_den, b_num, b_den, three ? z_num : 0, three ? z_den : 0};
-    hipLaunchKernelGGL(k_cg_x_save, dim3(1), dim3(1), 0, L.stream, L.scal, s_num, s_den, xs, three ? 1 : 0, out);
+    if (!out || u.scal) throw std::runtime_error("pending x-updates without a place for their scalars");
+    hipLaunchKernelGGL(k_cg_x_save, dim3(1), dim3(1), 0, L.stream, L.scal, u.last.num, u.last.den, xu_slots(u), u.count == 3 ? 1 : 0, out);
     check_launch();
 }
 
-void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, int a_num, int a_den,
-                         int s_num, int s_den, int with_p)
+void launch_cg_xp_update(const Launch &L, double *x, double *p, const double *r, int64_t n, Ratio alpha, Ratio beta, int with_p)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_xp_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, r, n, L.scal, a_num, a_den, s_num,
-                       s_den, with_p);
+    hipLaunchKernelGGL(k_cg_xp_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, r, n, L.scal, alpha.num, alpha.den, beta.num,
+                       beta.den, with_p);
     check_launch();
 }
 
-void launch_cg_x2_update(const Launch &L, double *x, const double *p, const double *r, int64_t n, int a_num, int a_den, int b_num,
-                         int b_den, int c_num, int c_den)
+void launch_cg_x2_update(const Launch &L, double *x, int64_t n, const XUpdates &u)
 {
+    if (u.count != 2 || !u.p1 || !u.r2 || u.scal) throw std::runtime_error("the one-pass x-update takes two pending updates from the scalar bank");
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_x2_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, p, r, n, L.scal, a_num, a_den, b_num, b_den,
-                       c_num, c_den);
+    hipLaunchKernelGGL(k_cg_x2_update, dim3((unsigned)nb), dim3(SB), 0, L.stream, x, u.p1, u.r2, n, L.scal, u.prev.num, u.prev.den,
+                       u.beta.num, u.beta.den, u.last.num, u.last.den);
     check_launch();
 }
 
-void launch_cg_pupdate(const Launch &L, double *p, const double *r, int64_t n, int s_num, int s_den)
+void launch_cg_pupdate(const Launch &L, double *p, const double *r, int64_t n, Ratio beta)
 {
     const int64_t nb = stream_blocks(n);
     check_grid(nb);
-    hipLaunchKernelGGL(k_cg_pupdate, dim3((unsigned)nb), dim3(SB), 0, L.stream, p, r, n, L.scal, s_num, s_den);
+    hipLaunchKernelGGL(k_cg_pupdate, dim3((unsigned)nb), dim3(SB), 0, L.stream, p, r, n, L.scal, beta.num, beta.den);
     check_launch();
 }
 

@@ -3,7 +3,8 @@
 //
 //   hmg_context.cpp  lifetimes of contexts, grids and vectors, device memory and the level-vector pool, options, counters
 //   hmg_upload.cpp   grid creation: kernel tables to the device (or, on a host-only grid, into the checksum), operator, queries
-//   hmg_smooth.cpp   operator apply with its sums, CG smoother, V-cycle, placement tuner
+//   hmg_smooth.cpp   operator apply with its sums, the three smoothers, V-cycle, placement tuner
+//   hmg_pending.cpp  the records of a V-cycle's last r-update and x-updates left pending: opened, settled, carried, dropped
 //   hmg_coarse.cpp   level-1 system, its PCG and the probes budgeted solves leave behind
 //   hmg_comm.cpp     cut exchange, the RCCL communicator and the exchange settings of a grid
 //   hmg_fcg.cpp      flexible CG around the V-cycle
@@ -307,8 +308,9 @@ struct hmg_ctx {
     std::vector<struct hmg_grid *> pend_grids;
 };
 
-// The last r-update of a V-cycle, not launched yet (option lazy_r): r still holds r_2, Ap the unsummed A p_2, alpha[0] / alpha[1]
-// the step length.  Forming it is launch_cg_rupdate_faces on (r, r, Ap) with alpha[] as its scalars and its r.r into `slot` --
+// The last r-update of a V-cycle, not launched yet (option lazy_r): r still holds r_2, Ap the unsummed A p_2, the saved block
+// (hmg_device.hpp, hmg_grid::pend_alpha()) the step length.  Forming it is launch_cg_rupdate_faces on (r, r, Ap) with the block as its
+// scalars, the ratio XS_LAST and its r.r into `slot` --
 // the launch the eager tail makes (materialize_r()).  Open on unpartitioned grids and library-owned, never exposed vectors only.
 // A caller that reads r after every cycle (a driver that watches the residual norm) would pay for the split: 40 + 26 B/DOF instead of
 // 58.  So the grid remembers whether the last V-cycle's r was read (hmg_grid::r_reader): if it was, the next tail runs the eager
@@ -316,7 +318,7 @@ struct hmg_ctx {
 // that is dropped unread clears the flag and the next V-cycle defers again.  The bits do not depend on the path.
 // Option lazy_ap (three-update form): the last CG step ran in the dead form -- p_2.Ap_2 for the step length, nothing stored -- and Ap
 // holds no A p_2 (ap_stored = false).  Forming r then starts with the launch the eager tail would have made: the fused apply on x = r
-// (still r_2), x2 = the spare vector (still p_1), beta_2 = alpha[2] / alpha[3] as k_cg_x_tail saved it, out = Ap, the edge / node
+// (still r_2), x2 = the spare vector (still p_1), beta_2 = the block's XS_BETA as k_cg_x_tail saved it, out = Ap, the edge / node
 // interface sum, p.Ap into S_PAP3.  Such a record rests on the spare vector, the operator (sigma, lambda, masks, class-weight cache)
 // and the kernel choice as well: whatever changes one of them settles the record first (hmg_grid_set_operator*, _set_lambda,
 // hmg_ctx_set_option through hmg_ctx::pend_grids, a smoother that is about to write the spare vector).  Ap's memory is the column to
@@ -334,8 +336,8 @@ struct PendingR {
 
 // The x-updates of that last launch, not launched either (option lazy_x): x lacks  x += a0 p0 (form 3 only);  x += a1 p1;
 // x += a2 (r2 + b2 p1).  p1 is the p handle's memory (form 2) or the grid's spare vector (form 3, where the p handle holds p0), r2 the r
-// handle's -- so the record lives inside an unformed PendingR on the same r, which settles it before r changes -- and the ratios are the
-// eight doubles of hmg_grid::pend_alpha() (launch_cg_x_save).  The next hmg_vcycle on the same states forms x in the load phase of its
+// handle's -- so the record lives inside an unformed PendingR on the same r, which settles it before r changes -- and the ratios are those
+// of the saved block (launch_cg_x_save): saved_updates() says all of this as an XUpdates.  The next hmg_vcycle on the same states forms x in the load phase of its
 // first residual (apply_carries_x: the x3 / x4 streams the down leg's local residual has), which writes x and r in one pass; every other
 // call that is handed x, p or r, or changes what they rest on, runs the x-only tail first (settle_x()).  The bits do not depend on the path.
 // form 0: x was finished at once because the caller read it after the cycle before (hmg_grid::x_reader, as r_reader); the record watches.
@@ -360,12 +362,12 @@ struct hmg_grid {
     DevBuf<int32_t> d_cells, d_face_pairs, d_face_partner, d_edge_ptr, d_edge_ent, d_node_ptr, d_node_ent, d_node_first;
     DevBuf<uint16_t> d_dmask, d_dupmask;
     DevBuf<uint8_t> d_mult;
-    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last eight doubles: step length and beta of a pending r-update, the ratios of pending x-updates
+    DevBuf<double> d_blockpart;                  // per-cell reduction partials; its last XS_COUNT doubles: the saved block (hmg_device.hpp) of a pending r-update and of pending x-updates
     PendingR pend;
     PendingX pendx;
     bool x_reader = false;                       // a caller's read settled pending x-updates and no V-cycle's x went unread since (see PendingX)
     bool r_reader = false;                       // a caller's read settled a record and none was dropped unread since (see PendingR)
-    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - 8 : nullptr; }
+    double *pend_alpha() const { return d_blockpart.p ? d_blockpart.p + d_blockpart.n - XS_COUNT : nullptr; }
     bool fuse_cg = true;
     DevBuf<double> d_coef;
     std::vector<double> sigma, coef;
@@ -499,7 +501,18 @@ inline const LevelDev &lev(const hmg_grid *g, int level)
     return g->ld[level - 1];
 }
 
-// ---- the pending r-update of a grid (hmg_smooth.cpp) ----
+// ---- hmg_pending.cpp ----
+// The pending records of a grid (PendingR, PendingX above).  When the finest level's post-smoother inside hmg_vcycle may leave them:
+bool lazy_r_ok(const hmg_grid *g, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap);
+bool lazy_ap_ok(const hmg_grid *g);
+bool lazy_x_ok(const hmg_grid *g, int level, int updates, const hmg_vec *x, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap);
+// ... and how (slot: where the r-update's r.r goes; form: the x-updates left, 0 for a record that only watches)
+void open_pending(hmg_grid *g, int level, hmg_vec *r, hmg_vec *Ap, int slot, bool formed, bool ap_stored = true);
+void open_pending_x(hmg_grid *g, int level, hmg_vec *x, hmg_vec *p, hmg_vec *r, int form);
+// what a PendingX record with updates to form says is pending: its vectors and the ratios of the grid's saved block
+XUpdates saved_updates(const hmg_grid *g, const PendingX &record);
+// entry of a V-cycle on top level k with the states st: settles or drops the records; returns the x-updates its first residual is to carry
+XUpdates enter_top(hmg_grid *g, int k, hmg_vec **st, bool zero_guess);
 // forms it now, if there is one: afterwards vectors and scalar bank are what the eager tail leaves.  read: the caller is about to
 // read r or Ap (settle()) -- only that is remembered as a read (hmg_grid::r_reader); a setter that settles the record is not one
 void materialize_r(hmg_grid *g, bool read = false);
@@ -507,8 +520,8 @@ void materialize_r(hmg_grid *g, bool read = false);
 // the spare vector, the context's options.  Not a read.  A record that holds its Ap stays open.
 // ... and pending x-updates always (the spare vector, the kernel choice)
 void settle_x(hmg_grid *g, bool read = false);
-// the flexible CG's first pass over z forms them itself: the record on x, if it has updates to form, is handed over and closed (a
-// record that only watches stays: hmg_fcg_step is a reader of its V-cycle's x like any other, and the next lines say so)
+// the flexible CG's first pass over z forms them itself: the record on x, if it has updates to form, is handed over (saved_updates() reads
+// it) and closed (a record that only watches stays: hmg_fcg_step is a reader of its V-cycle's x like any other, and the next lines say so)
 PendingX take_pending_x(hmg_grid *g, const hmg_vec *x);
 inline void settle_rebuild(hmg_grid *g)
 {
@@ -581,6 +594,9 @@ void set_slab(hmg_grid *g, const LevelDev &lv);
 void apply(hmg_grid *g, const LevelDev &lv, double alpha, const double *x, const double *src, double *out, int mask);
 void restrict_level(hmg_grid *g, int level_fine, const double *rf, double *bc);
 void interface_sum(hmg_grid *g, const LevelDev &lv, double *x, bool faces = true);
+// the apply with the interface sum of its output and, fused, its reductions into the bank's slot_pap / slot_rr (< 0: not wanted)
+void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, int slot_pap, int slot_rr, bool sum_out = true,
+                    bool faces = true);
 // sum over the ranks of scal[slot .. slot + count) through the grid's scalar_sum callback (nothing on an unpartitioned grid)
 void scalar_sum(hmg_grid *g, int slot, int count);
 bool reserve_top_spare(hmg_grid *g, bool must);

@@ -256,20 +256,19 @@ void launch_pcg_start(const Launch &L, double *p, const double *r, const double 
     reduce(L, nb, s_out);
 }
 
-void launch_pcg_rupdate(const Launch &L, double *r, const double *q, const double *dinv, int64_t n, int s_num, int s_den, int s_out)
+void launch_pcg_rupdate(const Launch &L, double *r, const double *q, const double *dinv, int64_t n, Ratio alpha, int s_out)
 {
     const int64_t nb = blocks_of(n);
-    hipLaunchKernelGGL(k_pcg_rupdate, dim3((unsigned)nb), dim3(PB), 0, L.stream, r, q, dinv, n, L.scal, s_num, s_den,
+    hipLaunchKernelGGL(k_pcg_rupdate, dim3((unsigned)nb), dim3(PB), 0, L.stream, r, q, dinv, n, L.scal, alpha.num, alpha.den,
                        partials_of(L, nb));
     check_launch();
     reduce(L, nb, s_out);
 }
 
-void launch_pcg_xp(const Launch &L, double *x, double *p, const double *r, const double *dinv, int64_t n, int a_num, int a_den,
-                   int b_num, int b_den)
+void launch_pcg_xp(const Launch &L, double *x, double *p, const double *r, const double *dinv, int64_t n, Ratio alpha, Ratio beta)
 {
     const int64_t nb = blocks_of(n);
-    hipLaunchKernelGGL(k_pcg_xp, dim3((unsigned)nb), dim3(PB), 0, L.stream, x, p, r, dinv, n, L.scal, a_num, a_den, b_num, b_den);
+    hipLaunchKernelGGL(k_pcg_xp, dim3((unsigned)nb), dim3(PB), 0, L.stream, x, p, r, dinv, n, L.scal, alpha.num, alpha.den, beta.num, beta.den);
     check_launch();
 }
 

@@ -18,10 +18,9 @@ void launch_diag_accum(const Launch &L, const LevelDev &lv, const MeshDev &mesh,
 void launch_dinv_finish(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double *d);
 // p = dinv o r; scal[s_out] = r . p
 void launch_pcg_start(const Launch &L, double *p, const double *r, const double *dinv, int64_t n, int s_out);
-// alpha = scal[s_num] / scal[s_den]; r -= alpha q; scal[s_out] = r . (dinv o r)
-void launch_pcg_rupdate(const Launch &L, double *r, const double *q, const double *dinv, int64_t n, int s_num, int s_den, int s_out);
-// alpha = scal[a_num] / scal[a_den], beta = scal[b_num] / scal[b_den]; x += alpha p; p = dinv o r + beta p
-void launch_pcg_xp(const Launch &L, double *x, double *p, const double *r, const double *dinv, int64_t n, int a_num, int a_den,
-                   int b_num, int b_den);
+// r -= alpha q; scal[s_out] = r . (dinv o r)
+void launch_pcg_rupdate(const Launch &L, double *r, const double *q, const double *dinv, int64_t n, Ratio alpha, int s_out);
+// x += alpha p; p = dinv o r + beta p
+void launch_pcg_xp(const Launch &L, double *x, double *p, const double *r, const double *dinv, int64_t n, Ratio alpha, Ratio beta);
 
 }  // namespace hmg

@@ -136,14 +136,15 @@ void agree_on_cut(hmg_grid *g)
     g->cut_agreed_ready = true;
 }
 
+}  // namespace
+
 // out = (src ? src : 0) + alpha*A*xin with the Dirichlet constraint, followed by the interface sum of
 // `out` (local + across ranks).  fused: the CG extras of k_apply<.., FUSED> (xin = x + beta*x2 written to
 // xout, scal[slot_pap] = sum mult*xin*out, scal[slot_rr] = sum xin*xin), summed over ranks.
 // On a partitioned grid the cells that own a copy of a cut entity go first; their cut DOFs are packed and
 // the sum over ranks is started, then the remaining cells and interface entities are processed while it
 // is in flight.
-void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, int slot_pap, int slot_rr,
-                    bool sum_out = true, bool faces = true)
+void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, int slot_pap, int slot_rr, bool sum_out, bool faces)
 {
     hmg_ctx *c = g->ctx;
     const Launch &L = c->L;
@@ -230,11 +231,13 @@ void apply_then_sum(hmg_grid *g, const LevelDev &lv, ApplyArgs a, bool fused, in
     cut_pack(g, lv, a.out, 1);
 }
 
+namespace {
+
 // Who runs a smoother, and so what of its state is read afterwards: inside a V-cycle the reference overwrites part of it
 // unread (src/multigrid.jl:46-50,100-115).  With option lean_post = 0 the post-smoothers leave what Plain leaves.
 enum class Role {
     Plain,       // hmg_smooth: x, r, p and Ap as the reference leaves them
-    Pre,         // vcycle_down: x only, and its last x-update(s) may be handed back (DeferredX)
+    Pre,         // vcycle_down: x only, and its last x-update(s) may be handed back (XUpdates)
     PostTop,     // vcycle_up on the finest level: x and r; p and Ap are scratch
     PostBelow,   // vcycle_up below the finest level: x only
 };
@@ -264,25 +267,43 @@ struct SmoothForm {
     bool lazy_r = false;    // (set by the caller, tails Top2 / Top3) the last launch finishes x only and leaves the r-update
                             // pending on the grid (lazy_r_ok())
     bool lazy_x = false;    // (set by the caller, with lazy_r) ... and may leave x's updates pending as well (lazy_x_ok())
-    int carry_x = 0;        // (set by the caller, Role::Pre on the top level of hmg_vcycle) 2 / 3: x lacks the last two / three updates of
+    XUpdates carry_x;       // (set by the caller, Role::Pre on the top level of hmg_vcycle) x lacks the last two / three updates of
                             // the V-cycle before, which ride in the first residual (PendingX, taken out of the grid by enter_top())
 };
 
-// What a pre-smoother leaves to its caller (tails DeadDefer, DeadDefer2 and DeadDefer3), or a post-smoother below the finest level
-// to the level above (tail DeadX2 with hand_up: the two-update form, with the vectors that hold p1 and r2).
-struct DeferredX {
-    int rs = -1;         // >= 0: x += (scal[rs] / scal[pap]) * p_last is still to be done
-    int pap = S_PAP;
-    // lazy form (two_updates): p_last itself was not formed either.  With p1 = the p handle, r2 = the r handle:
-    //   x += (scal[a_num]/scal[a_den]) p1;  p2 = r2 + (scal[b_num]/scal[b_den]) p1;  x += (scal[rs]/scal[pap]) p2
-    bool two_updates = false;
-    int a_num = -1, a_den = -1, b_num = -1, b_den = -1;
-    // three updates (Tail::DeadDefer3): in front of those two x += (scal[d_num]/scal[d_den]) p0, p0 = the p handle; p1 is then
-    // the grid's spare vector
-    bool three_updates = false;
-    int d_num = -1, d_den = -1;
-    const double *p = nullptr, *r = nullptr;   // (hand_up)
-};
+// What smooth() returns: the x-updates a pre-smoother leaves to its caller (tails DeadDefer, DeadDefer2 and DeadDefer3: one, two, three),
+// or a post-smoother below the finest level to the level above (tail DeadX2 with hand_up: two).  Two host functions, and nothing else,
+// turn an XUpdates into the arguments of an apply:
+
+// ... of a load phase that finishes this level's x on the way (written back): x2 / x3 / x4 are p1 / r2 / p0
+void finish_x_in_load(ApplyArgs &a, const XUpdates &u, double *x)
+{
+    a.xout = x;
+    a.scal = u.scal;
+    a.x2 = u.p1;
+    if (u.count == 1) {
+        a.s = u.last;
+        return;
+    }
+    a.x3 = u.r2;
+    a.a = u.prev;
+    a.s = u.beta;
+    a.c = u.last;
+    if (u.count == 3) {
+        a.x4 = u.p0;
+        a.d = u.first;
+    }
+}
+
+// ... of a first residual that finishes the coarser level's x where its column is staged (two updates)
+void finish_coarse_x_staged(ApplyArgs &a, const XUpdates &u)
+{
+    a.xc_p = u.p1;
+    a.xc_r = u.r2;
+    a.a = u.prev;
+    a.s = u.beta;
+    a.c = u.last;
+}
 
 // Every context option that shapes the smoother is read here, before the first launch.
 SmoothForm smooth_form(const hmg_grid *g, int level, int steps, Role role)
@@ -451,8 +472,8 @@ namespace {
 
 // r = b - A x, constraint, interface sum (src/multigrid.jl:50): the first residual of both smoothers, with the forms its caller
 // may ask for -- x a zero that is not in memory (f.x_zero), the coarse-grid correction riding in the load phase (xcoarse, cx)
-void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, const hmg_vec *p, const SmoothForm &f,
-                    const hmg_vec *xcoarse, const DeferredX *cx)
+void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, const SmoothForm &f, const hmg_vec *xcoarse,
+                    const XUpdates *cx)
 {
     const LevelDev &lv = lev(g, level);
     const Launch &L = g->ctx->L;
@@ -477,42 +498,21 @@ void first_residual(hmg_grid *g, int level, hmg_vec *x, hmg_vec *b, hmg_vec *r, 
             a.xout = x->d;
             // (cells that fill a third of the LDS: no room for the coarse column next to three resident images)
             if (g->ctx->prolong_in_image && apply_lds_bytes(lv) > 48 * 1024) a.flags |= 64;
-            if (cx && cx->rs >= 0) {
+            if (cx && cx->count) {
                 // the coarse x still lacks its last two CG updates: done per coarse entry where the column is staged (24 instead of
                 // 32 + 8 B per coarse DOF, one launch fewer)
-                need(cx->two_updates && cx->p && cx->r && (a.flags & 64), "pending coarse x-updates where the residual cannot carry them");
-                a.xc_p = cx->p;
-                a.xc_r = cx->r;
-                a.a_num = cx->a_num;
-                a.a_den = cx->a_den;
-                a.s_num = cx->b_num;
-                a.s_den = cx->b_den;
-                a.c_num = cx->rs;
-                a.c_den = cx->pap;
+                need(cx->count == 2 && cx->p1 && cx->r2 && (a.flags & 64), "pending coarse x-updates where the residual cannot carry them");
+                finish_coarse_x_staged(a, *cx);
                 g->ctx->coarse_x_folds += 1;
             }
             apply_then_sum(g, lv, a, true, -1, -1);
-        } else if (f.carry_x) {
+        } else if (f.carry_x.count) {
             // x still lacks the last CG updates of the V-cycle before this one (option lazy_x): formed in the load phase as the down
             // leg's local residual forms them, from p0 (three updates: the p handle), p1 (the spare vector / the p handle) and r2 (still
-            // in r) with the ratios k_cg_x_save put aside, and written back -- 56 B/DOF instead of 40 + 24.  r goes over r2 in place:
-            // a workgroup reads its own cell's column of it alone, in the load phase, and stores behind the barrier after it.
-            need(f.carry_x == 2 || g->top_spare.p != nullptr, "pending x-updates have lost the spare vector they rest on");
-            a.x2 = f.carry_x == 3 ? g->top_spare.p : p->d;
-            a.x3 = r->d;
-            if (f.carry_x == 3) {
-                a.x4 = p->d;
-                a.d_num = 6;
-                a.d_den = 7;
-            }
-            a.a_num = 4;
-            a.a_den = 5;
-            a.s_num = 2;
-            a.s_den = 3;
-            a.c_num = 0;
-            a.c_den = 1;
-            a.xout = x->d;
-            a.scal = g->pend_alpha();
+            // in r) with the ratios k_cg_x_save put aside (saved_updates()), and written back -- 56 B/DOF instead of 40 + 24.  r goes over
+            // r2 in place: a workgroup reads its own cell's column of it alone, in the load phase, and stores behind the barrier after it.
+            need(f.carry_x.count == 2 || g->top_spare.p != nullptr, "pending x-updates have lost the spare vector they rest on");
+            finish_x_in_load(a, f.carry_x, x->d);
             apply_then_sum(g, lv, a, true, -1, -1);
         } else {
             apply_then_sum(g, lv, a, false, -1, -1);
@@ -558,15 +558,15 @@ void smooth_pcg(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_v
         const bool last = i == steps - 1;
         if (last && f.tail != Tail::Full) {
             if (f.tail == Tail::ScratchP) {
-                launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, cur, S_PAP, other);   // alpha = rz / p.Ap
+                launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, {cur, S_PAP}, other);   // alpha = rz / p.Ap
                 scalar_sum(g, other, 1);
             }
-            launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rz / p.Ap) p
+            launch_cg_xp_update(L, x->d, p->d, r->d, n, {cur, S_PAP}, {cur, other}, 0);   // x += (rz / p.Ap) p
             return;
         }
-        launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, cur, S_PAP, other);       // alpha = rz / p.Ap; rz'
+        launch_pcg_rupdate(L, r->d, Ap->d, dinv, n, {cur, S_PAP}, other);     // alpha = rz / p.Ap; rz'
         scalar_sum(g, other, 1);
-        launch_pcg_xp(L, x->d, p->d, r->d, dinv, n, cur, S_PAP, other, cur);  // beta = rz' / rz
+        launch_pcg_xp(L, x->d, p->d, r->d, dinv, n, {cur, S_PAP}, {other, cur});  // beta = rz' / rz
         std::swap(cur, other);
     }
 }
@@ -610,70 +610,8 @@ void smooth_cheb(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *r, hmg_
     }
 }
 
-// May the finest level's post-smoother inside hmg_vcycle leave its last r-update pending (option lazy_r)?  Not where the memory
-// can be read behind the library's back (caller-owned vectors, pointers handed out -- p too: it changes places with r), and not on
-// a partitioned grid, where the deferred sum over the ranks would be a collective at a place no rank can foresee.
-bool lazy_r_ok(const hmg_grid *g, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap)
-{
-    if (!g->ctx->lazy_r || g->smoother != 0 || g->part || has_exchange(g) || g->scalar_sum) return false;
-    for (const hmg_vec *v : {r, p, Ap})
-        if (!v->own || v->exposed) return false;
-    return r != Ap && g->pend_alpha() != nullptr && vec_len(r) > 0;
-}
-
-// formed: the eager launch has run (the caller reads r after every cycle, hmg_grid::r_reader); the record only watches
-// ap_stored = false: the last CG step ran in the dead form, Ap is rebuilt when the record is settled (option lazy_ap)
-void open_pending(hmg_grid *g, int level, hmg_vec *r, hmg_vec *Ap, int slot, bool formed, bool ap_stored = true)
-{
-    LifetimeLock lock(lifetime_mutex());
-    need(!g->pend.r, "a pending r-update was not settled before the next one");
-    need(ap_stored || !formed, "a formed r-update without its Ap");
-    g->pend.r = r;
-    g->pend.Ap = Ap;
-    g->pend.level = level;
-    g->pend.slot = slot;
-    g->pend.formed = formed;
-    g->pend.ap_stored = ap_stored;
-    g->ctx->last_r_form = formed ? 0 : 1;
-    g->ctx->last_ap_form = ap_stored ? 0 : 1;
-    auto &open = g->ctx->pend_grids;
-    if (std::find(open.begin(), open.end(), g) == open.end()) open.push_back(g);
-}
-
-// Can the last step of the three-update form run without storing A p_2 (option lazy_ap)?  Where the record is opened unformed, and
-// the dead launch is the one every fused apply family has (Tail::DeadDefer2 takes it on every level: x, x2, no out, no xout, no xacc).
-bool lazy_ap_ok(const hmg_grid *g, const SmoothForm &f)
-{
-    return g->ctx->lazy_ap && f.tail == Tail::Top3 && f.lazy_r && !g->r_reader;
-}
-
-// May that launch leave the x-updates pending as well (option lazy_x)?  Under lazy_r_ok()'s conditions with x and p added (the spare
-// vector is the library's own), on a level whose first residual can carry them (apply_carries_x()).
-bool lazy_x_ok(const hmg_grid *g, int level, Tail tail, const hmg_vec *x, const hmg_vec *r, const hmg_vec *p, const hmg_vec *Ap)
-{
-    if (!g->ctx->lazy_x || !g->fuse_cg) return false;
-    for (const hmg_vec *v : {x, p})
-        if (!v->own || v->exposed) return false;
-    if (x == r || x == p || x == Ap || p == r || p == Ap) return false;
-    return apply_carries_x(g->ctx->L, lev(g, level), g->md, g->lambda, tail == Tail::Top3 ? 3 : 2);
-}
-
-// form 0: x is finished (its reader memory is set); the record watches whether it is read again
-void open_pending_x(hmg_grid *g, int level, hmg_vec *x, hmg_vec *p, hmg_vec *r, int form)
-{
-    LifetimeLock lock(lifetime_mutex());
-    need(!g->pendx.x, "pending x-updates were not settled before the next ones");
-    g->pendx.x = x;
-    g->pendx.p = form ? p : nullptr;
-    g->pendx.r = form ? r : nullptr;
-    g->pendx.level = level;
-    g->pendx.form = form;
-    g->ctx->last_x_form = form;
-    if (form) g->ctx->x_deferred += 1;
-}
-
-DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap,
-                 const SmoothForm &f, const hmg_vec *xcoarse = nullptr, const DeferredX *cx = nullptr)
+XUpdates smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_vec *r, hmg_vec *p, hmg_vec *Ap, const SmoothForm &f,
+                const hmg_vec *xcoarse = nullptr, const XUpdates *cx = nullptr)
 {
     // ref: src/multigrid.jl:46-71
     const LevelDev &lv = lev(g, level);
@@ -682,8 +620,8 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
     // (a record without a stored Ap rests on the spare vector, which these two tails write: on other vectors than the record's --
     //  hmg_vcycle_down / _up next to a V-cycle's states -- nothing else has settled it)
     if (f.tail == Tail::Top3 || f.tail == Tail::DeadDefer3) settle_rebuild(g);
-    need(!f.carry_x || (!f.x_zero && !xcoarse), "pending x-updates where the first residual cannot carry them");
-    first_residual(g, level, x, b, r, p, f, xcoarse, cx);
+    need(!f.carry_x.count || (!f.x_zero && !xcoarse), "pending x-updates where the first residual cannot carry them");
+    first_residual(g, level, x, b, r, f, xcoarse, cx);
     if (g->smoother == 1) {
         smooth_pcg(g, level, steps, x, r, p, Ap, f);
         return {};
@@ -703,13 +641,13 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
             scalar_sum(g, S_PAP, 1);
             const bool last = i == steps - 1;
             if (last && f.tail == Tail::DeadXp) {
-                launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rs / p.Ap) p
+                launch_cg_xp_update(L, x->d, p->d, r->d, n, {cur, S_PAP}, {cur, other}, 0);   // x += (rs / p.Ap) p
                 return {};
             }
-            launch_cg_update(L, x->d, r->d, p->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs/pAp
+            launch_cg_update(L, x->d, r->d, p->d, Ap->d, n, {cur, S_PAP}, other);   // alpha = rs/pAp
             scalar_sum(g, other, 1);
             if (last && f.tail == Tail::ScratchP) return {};
-            launch_cg_pupdate(L, p->d, r->d, n, other, cur);                   // beta = rs'/rs
+            launch_cg_pupdate(L, p->d, r->d, n, {other, cur});                 // beta = rs'/rs
             std::swap(cur, other);
         }
         return {};
@@ -728,11 +666,9 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         a.x2 = i == 0 ? nullptr : p->d;                                   // p = r  /  p = r + beta p, beta = rs'/rs
         a.xout = i == 0 && f.swap_rp ? nullptr : p->d;                   // (swap_rp: r_0 itself becomes p_0)
         a.xacc = i == 0 ? nullptr : x->d;                                 // x += alpha_{i-1} p_{i-1}
-        a.a_num = other;                                                  // rs_{i-1} (after the swap below)
-        a.a_den = S_PAP;                                                  // p_{i-1}.Ap_{i-1}: still the old value here
+        a.a = {other, S_PAP};                                             // rs_{i-1} (after the swap below) / p_{i-1}.Ap_{i-1}: still the old value here
         a.out = Ap->d;
-        a.s_num = cur;
-        a.s_den = other;
+        a.s = {cur, other};
         a.flags = 1;
         return a;
     };
@@ -750,9 +686,9 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
             r_in = p->d;
         }
         if (ride)
-            launch_cg_rupdate_faces(L, lv, g->md, r_in, r->d, Ap->d, n, cur, S_PAP, other);
+            launch_cg_rupdate_faces(L, lv, g->md, r_in, r->d, Ap->d, n, {cur, S_PAP}, other);
         else
-            launch_cg_rupdate(L, r_in, r->d, Ap->d, n, cur, S_PAP, other);   // alpha = rs / p.Ap
+            launch_cg_rupdate(L, r_in, r->d, Ap->d, n, {cur, S_PAP}, other);   // alpha = rs / p.Ap
         scalar_sum(g, other, 1);
         std::swap(cur, other);
     };
@@ -765,13 +701,52 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
             a.xout = g->top_spare.p;
             a.xacc = nullptr;
             apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
-            launch_cg_rupdate_faces(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, S_RS3);
+            launch_cg_rupdate_faces(L, lv, g->md, r->d, r->d, Ap->d, n, {cur, S_PAP2}, S_RS3);
             scalar_sum(g, S_RS3, 1);
             continue;
         }
         step(i, f.ride);
     }
     if (f.tail == Tail::Top2 || f.tail == Tail::Top3) g->ctx->last_top_form = f.tail == Tail::Top3 ? 2 : 1;
+    // The x-updates a tail leaves undone, as the scalar bank and the vectors stand behind its last apply.  One or two: rs_{i-1} in `other`,
+    // rs_i in `cur`, p.Ap_{i-1} in S_PAP, p.Ap_i in S_PAP2 (two; S_PAP with one), p_{i-1} in p.  Three: rs_{i-2} in `other`, rs_{i-1} in
+    // `cur`, rs_i in S_RS3, p.Ap_{i-2} in S_PAP, p.Ap_{i-1} in S_PAP2, p.Ap_i in S_PAP3, p_{i-2} in p, p_{i-1} in the spare vector.
+    auto pending = [&](int count) {
+        XUpdates u;
+        u.count = count;
+        u.r2 = r->d;
+        u.p1 = count == 3 ? g->top_spare.p : p->d;
+        if (count == 1) u.last = {cur, S_PAP};
+        if (count == 2) {
+            u.prev = {other, S_PAP};       // alpha_{i-1}
+            u.beta = {cur, other};         // beta_i
+            u.last = {cur, S_PAP2};        // alpha_i
+        }
+        if (count == 3) {
+            u.p0 = p->d;
+            u.first = {other, S_PAP};      // alpha_{i-2}
+            u.prev = {cur, S_PAP2};
+            u.beta = {S_RS3, cur};
+            u.last = {S_RS3, S_PAP3};
+        }
+        return u;
+    };
+    // The end of the finest level's tails Top2 / Top3, behind the last apply: the updates u of x and the r-update, in one launch, or x
+    // alone and the r-update left pending (lazy_r), or the ratios of u put aside and both left pending (lazy_x)
+    auto top_tail = [&](const XUpdates &u, bool ap_stored) {
+        if (f.lazy_r && !g->r_reader) {
+            if (f.lazy_x && !g->x_reader)
+                launch_cg_x_save(L, u, g->pend_alpha());
+            else
+                launch_cg_x_tail(L, x->d, n, u, g->pend_alpha());
+            open_pending(g, level, r, Ap, other, false, ap_stored);
+            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : u.count);
+            return;
+        }
+        launch_cg_rupdate_faces_x(L, lv, g->md, r->d, Ap->d, n, other, x->d, u);
+        scalar_sum(g, other, 1);
+        if (f.lazy_r) open_pending(g, level, r, Ap, other, true);
+    };
     ApplyArgs a = args(last);
     switch (f.tail) {
     case Tail::Full:
@@ -779,100 +754,58 @@ DeferredX smooth(hmg_grid *g, int level, int steps, hmg_vec *x, hmg_vec *b, hmg_
         step(last, f.ride && f.tail == Tail::ScratchP);
         // x += alpha_last p (alpha_last = rs_{s-1} / p.Ap: `other` holds rs_{s-1} after the swap) and, Full only, the
         // reference's last p-update p = r + (rs_s / rs_{s-1}) p
-        launch_cg_xp_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, f.tail == Tail::Full ? 1 : 0);
+        launch_cg_xp_update(L, x->d, p->d, r->d, n, {other, S_PAP}, {cur, other}, f.tail == Tail::Full ? 1 : 0);
         return {};
     case Tail::DeadXp:
     case Tail::DeadDefer:
         a.out = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP, last == 0 ? cur : -1, true, true);
         if (last == 0 && f.swap_rp) exchange_rp();
-        if (f.tail == Tail::DeadDefer) return DeferredX{cur};
-        launch_cg_xp_update(L, x->d, p->d, r->d, n, cur, S_PAP, cur, other, 0);   // x += (rs / p.Ap) p
+        if (f.tail == Tail::DeadDefer) return pending(1);
+        launch_cg_xp_update(L, x->d, p->d, r->d, n, {cur, S_PAP}, {cur, other}, 0);   // x += (rs / p.Ap) p
         return {};
     case Tail::DeadDefer2:
-    case Tail::DeadX2:
+    case Tail::DeadX2: {
         // p_i is formed in LDS only, for the apply and the p.Ap reduction: neither p nor x nor Ap is written.  p.Ap of this
         // step goes to its own slot: S_PAP still holds the previous step's, which the first of the two x-updates needs.
         a.out = a.xout = a.xacc = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP2, -1);
-        if (f.tail == Tail::DeadX2 && f.hand_up) {
-            DeferredX d{cur, S_PAP2, true, other, S_PAP, cur, other};
-            d.p = p->d;
-            d.r = r->d;
-            return d;
-        }
-        if (f.tail == Tail::DeadX2) {
-            launch_cg_x2_update(L, x->d, p->d, r->d, n, other, S_PAP, cur, other, cur, S_PAP2);
+        const XUpdates u = pending(2);
+        if (f.tail == Tail::DeadX2 && !f.hand_up) {
+            launch_cg_x2_update(L, x->d, n, u);
             return {};
         }
-        return DeferredX{cur, S_PAP2, true, other, S_PAP, cur, other};   // alpha_i; alpha_{i-1} = rs_{i-1} / p.Ap_{i-1}, beta_i
-    case Tail::DeadDefer3:
-        // the dead step after a step that wrote its direction into the spare vector (slots as for Top3): reads r and the spare,
-        // writes nothing; x += alpha_{i-2} p_{i-2}, x += alpha_{i-1} p_{i-1} and x += alpha_i (r_i + beta_i p_{i-1}) are the caller's
-        a.x2 = g->top_spare.p;
+        return u;                          // to the local residual (DeadDefer2) or the level above (hand_up)
+    }
+    case Tail::DeadDefer3: {
+        // the dead step after a step that wrote its direction into the spare vector: reads r and the spare, writes nothing;
+        // x += alpha_{i-2} p_{i-2}, x += alpha_{i-1} p_{i-1} and x += alpha_i (r_i + beta_i p_{i-1}) are the caller's
+        const XUpdates u = pending(3);
+        a.x2 = u.p1;
         a.out = a.xout = a.xacc = nullptr;
-        a.s_num = S_RS3;
-        a.s_den = cur;
+        a.s = u.beta;
         apply_then_sum(g, lv, a, true, S_PAP3, -1);
-        {
-            DeferredX d{S_RS3, S_PAP3, true, cur, S_PAP2, S_RS3, cur};
-            d.three_updates = true;
-            d.d_num = other;
-            d.d_den = S_PAP;
-            return d;
-        }
+        return u;
+    }
     case Tail::Top2:
         // (p.Ap of this step to its own slot: S_PAP keeps the previous step's for the first of the two x-updates)
         a.xout = a.xacc = nullptr;
         apply_then_sum(g, lv, a, true, S_PAP2, -1, true, false);
-        if (f.lazy_r && !g->r_reader) {
-            if (f.lazy_x && !g->x_reader)
-                launch_cg_x_save(L, cur, S_PAP2, other, S_PAP, cur, other, false, 0, 0, g->pend_alpha());
-            else
-                launch_cg_x_tail(L, r->d, n, cur, S_PAP2, x->d, p->d, other, S_PAP, cur, other, nullptr, 0, 0, g->pend_alpha());
-            open_pending(g, level, r, Ap, other, false);
-            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 2);
-            return {};
-        }
-        launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, cur, S_PAP2, other, x->d, p->d, other, S_PAP, cur, other,
-                                  nullptr, 0, 0);
-        scalar_sum(g, other, 1);
-        if (f.lazy_r) open_pending(g, level, r, Ap, other, true);
+        top_tail(pending(2), true);
         return {};
-    case Tail::Top3:
-        // rs_{i-2} in `other`, rs_{i-1} in `cur`, rs_i in S_RS3;  p.Ap_{i-2} in S_PAP, p.Ap_{i-1} in S_PAP2;  p_{i-2} in p, p_{i-1} in the spare
-        a.x2 = g->top_spare.p;
+    case Tail::Top3: {
+        const XUpdates u = pending(3);
+        a.x2 = u.p1;
         a.xout = a.xacc = nullptr;
-        a.s_num = S_RS3;
-        a.s_den = cur;
-        auto x_tail3 = [&]() {     // the three x-updates now, or their ratios put aside (option lazy_x)
-            if (f.lazy_x && !g->x_reader)
-                launch_cg_x_save(L, S_RS3, S_PAP3, cur, S_PAP2, S_RS3, cur, true, other, S_PAP, g->pend_alpha());
-            else
-                launch_cg_x_tail(L, r->d, n, S_RS3, S_PAP3, x->d, g->top_spare.p, cur, S_PAP2, S_RS3, cur, p->d, other, S_PAP, g->pend_alpha());
-        };
-        if (lazy_ap_ok(g, f)) {
-            // A p_2 has one reader, the pending r-update: the step delivers p_2.Ap_2 alone -- the pre-smoother's dead launch (16 instead
-            // of 24 B/DOF, no interface sum) -- and the record forms Ap again if somebody reads r (materialize_r())
-            a.out = nullptr;
-            apply_then_sum(g, lv, a, true, S_PAP3, -1);
-            x_tail3();
-            open_pending(g, level, r, Ap, other, false, /*ap_stored=*/false);
-            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 3);
-            return {};
-        }
-        apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
-        if (f.lazy_r && !g->r_reader) {
-            x_tail3();
-            open_pending(g, level, r, Ap, other, false);
-            if (f.lazy_x) open_pending_x(g, level, x, p, r, g->x_reader ? 0 : 3);
-            return {};
-        }
-        launch_cg_rupdate_faces_x(L, lv, g->md, r->d, r->d, Ap->d, n, S_RS3, S_PAP3, other, x->d, g->top_spare.p, cur, S_PAP2,
-                                  S_RS3, cur, p->d, other, S_PAP);
-        scalar_sum(g, other, 1);
-        if (f.lazy_r) open_pending(g, level, r, Ap, other, true);
+        a.s = u.beta;
+        // A p_2 has one reader, the r-update: where that stays pending the step delivers p_2.Ap_2 alone -- the pre-smoother's dead launch
+        // (16 instead of 24 B/DOF, no interface sum) -- and the record forms Ap again if somebody reads r (materialize_r())
+        const bool ap_stored = !(f.lazy_r && lazy_ap_ok(g));
+        if (!ap_stored) a.out = nullptr;
+        apply_then_sum(g, lv, a, true, S_PAP3, -1, true, /*faces=*/!ap_stored);
+        top_tail(u, ap_stored);
         return {};
+    }
     }
     return {};
 }
@@ -899,7 +832,7 @@ bool zero_entry_ok(const hmg_grid *g, int k, int steps)
 
 // Returns the number of x-updates the pre-smoother left to the local residual (hmg_ctx_counter "lazy_pre_form").
 int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false, bool x_zero = false, int steps_next = -1,
-                int carry_x = 0)
+                const XUpdates &carry_x = {})
 {
     // carry_x: this level's x lacks the last x-updates of the V-cycle before (enter_top()): the pre-smoother's first residual has them
     // x_zero: this level's x is a zero nobody has written (see zero_entry_ok); steps_next: the CG steps the next coarser
@@ -914,10 +847,10 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
     need(!x_zero || form.tail == Tail::DeadDefer2, "zero initial guess: the pre-smoother does not defer both x-updates");
     form.x_zero = x_zero;
     form.carry_x = carry_x;
-    const DeferredX dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form);
-    const int deferred = dx.rs < 0 ? 0 : dx.three_updates ? 3 : dx.two_updates ? 2 : 1;
+    const XUpdates dx = smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form);
+    const int deferred = dx.count;
     const bool skip_fill = inside && steps_next >= 0 && zero_entry_ok(g, k - 1, steps_next);
-    if (dx.rs >= 0) {
+    if (deferred) {
         // local residual with the pre-smoother's pending x-update(s) folded into its load phase (x written back),
         // r = b - A x: 40 B/DOF instead of 24 + 24; in the lazy form the dead step wrote neither x nor p (16 B/DOF
         // instead of 40) and this pass reads r as well (48 B/DOF)
@@ -925,26 +858,9 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
         a.alpha = -1.0;
         a.lambda = g->lambda;
         a.x = cur[0]->d;
-        a.x2 = dx.three_updates ? g->top_spare.p : cur[3]->d;
-        a.xout = cur[0]->d;
-        if (dx.three_updates) {        // (49 B/DOF: x, p0, p1, r and b in, x and the restricted column out)
+        if (deferred == 3)             // (49 B/DOF: x, p0, p1, r and b in, x and the restricted column out)
             need(g->ctx->fold_restrict && apply_defers3(L, lev(g, k)), "three pending x-updates where the local residual cannot carry them");
-            a.x4 = cur[3]->d;
-            a.d_num = dx.d_num;
-            a.d_den = dx.d_den;
-        }
-        if (dx.two_updates) {
-            a.x3 = cur[2]->d;
-            a.a_num = dx.a_num;
-            a.a_den = dx.a_den;
-            a.s_num = dx.b_num;
-            a.s_den = dx.b_den;
-            a.c_num = dx.rs;
-            a.c_den = dx.pap;
-        } else {
-            a.s_num = dx.rs;
-            a.s_den = dx.pap;
-        }
+        finish_x_in_load(a, dx, cur[0]->d);
         a.src = cur[1]->d;
         a.out = cur[2]->d;
         a.flags = 1 | (x_zero ? 128 : 0);
@@ -969,8 +885,8 @@ int vcycle_down(hmg_grid *g, int k, int steps, hmg_vec **st, bool inside = false
 // level, PostBelow below it).
 // cx: what level k - 1's post-smoother left of its x (hand_up); hand_up: may this level's post-smoother leave its own in turn?
 // lazy_r: the caller is hmg_vcycle / hmg_fcg_step on its top level and has settled the grid's pending record
-DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const DeferredX *cx = nullptr, bool hand_up = false,
-                    bool lazy_r = false, bool lazy_x = false)
+XUpdates vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, const XUpdates *cx = nullptr, bool hand_up = false,
+                   bool lazy_r = false, bool lazy_x = false)
 {
     hmg_vec **cur = st + 5 * (k - 1);
     hmg_vec **nxt = st + 5 * (k - 2);
@@ -979,12 +895,12 @@ DeferredX vcycle_up(hmg_grid *g, int k, int steps, hmg_vec **st, Role role, cons
     // coarse column in LDS next to the lattice image (two workgroups per CU must still fit), else a separate pass
     const bool fold_p = g->ctx->fold_prolong && g->fuse_cg && apply_lds_bytes(lev(g, k)) <= 160 * 1024 &&
                         apply_lds_bytes(lev(g, k)) + sizeof(double) * (size_t)lev(g, k - 1).nf <= 80 * 1024;
-    need(!(cx && cx->rs >= 0) || fold_p, "pending coarse x-updates without the folded prolongation");
+    need(!(cx && cx->count) || fold_p, "pending coarse x-updates without the folded prolongation");
     if (!fold_p) launch_prolong_add(L, lev(g, k), lev(g, k - 1), g->md.ncells, nxt[0]->d, cur[0]->d);
     SmoothForm form = smooth_form(g, k, steps, role);
     form.hand_up = hand_up && form.tail == Tail::DeadX2;
     form.lazy_r = lazy_r && (form.tail == Tail::Top2 || form.tail == Tail::Top3) && lazy_r_ok(g, cur[2], cur[3], cur[4]);
-    form.lazy_x = lazy_x && form.lazy_r && lazy_x_ok(g, k, form.tail, cur[0], cur[2], cur[3], cur[4]);
+    form.lazy_x = lazy_x && form.lazy_r && lazy_x_ok(g, k, form.tail == Tail::Top3 ? 3 : 2, cur[0], cur[2], cur[3], cur[4]);
     return smooth(g, k, steps, cur[0], cur[1], cur[2], cur[3], cur[4], form, fold_p ? nxt[0] : nullptr, cx);
 }
 
@@ -1004,8 +920,8 @@ bool coarse_x_folds(const hmg_grid *g, int k, int steps_below)
 }
 
 // hand_up: the level above finishes this level's x in its first residual (coarse_x_folds()); returns what is left to it
-DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool hand_up,
-                       int carry_x = 0, bool lazy_x = false)
+XUpdates vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool hand_up,
+                      const XUpdates &carry_x = {}, bool lazy_x = false)
 {
     // ref: src/multigrid.jl:73-119
     if (k == 1) {                                  // (the scatter of the level-1 solution overwrites every entry of x)
@@ -1019,225 +935,16 @@ DeferredX vcycle_level(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec 
     if (top && zero_guess && !x_zero) launch_fill(g->ctx->L, st[5 * (k - 1)]->d, vec_len(st[5 * (k - 1)]), 0.0);
     const int deferred = vcycle_down(g, k, steps, st, /*inside=*/true, x_zero, steps_coarse, carry_x);
     if (top) g->ctx->last_pre_form = deferred;
-    const DeferredX cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
+    const XUpdates cx = vcycle_level(g, k - 1, steps_coarse, steps_coarse, st, false, false, coarse_x_folds(g, k, steps_coarse));
     if (top) g->ctx->last_top_form = g->ctx->last_r_form = g->ctx->last_ap_form = g->ctx->last_x_form = 0;
     return vcycle_up(g, k, steps, st, top ? Role::PostTop : Role::PostBelow, &cx, hand_up, /*lazy_r=*/top, /*lazy_x=*/top && lazy_x);
 }
 
 }  // namespace
 
-// The eager launch, now: launch_cg_rupdate_faces<0> on (r, r, Ap) with the stored step length (alpha / 1.0 is alpha) and its r.r
-// into the slot the eager tail would have written.  (No sum over ranks: the record opens on unpartitioned grids only.)
-namespace {
-
-// the record is settled or dropped: an Ap it had to keep alive goes now
-void close_pending(hmg_grid *g)
-{
-    hmg_vec *orphan = g->pend.orphan_Ap ? g->pend.Ap : nullptr;
-    g->pend = PendingR{};
-    if (g->ctx) {
-        auto &open = g->ctx->pend_grids;
-        open.erase(std::remove(open.begin(), open.end(), g), open.end());
-    }
-    if (orphan) release_vec(orphan);
-}
-
-void drop_pending(hmg_grid *g)
-{
-    settle_x(g);                                 // (pending x-updates read the r_2 that is about to go)
-    if (!g->pend.formed) g->ctx->r_dropped += 1;
-    g->r_reader = false;                         // nobody read it: the next V-cycle defers
-    close_pending(g);
-}
-
-}  // namespace
-
-// The eager launch of pending x-updates, now: k_cg_x_tail on (x, p1, p0, r2) with the ratios put aside as its scalars.  Before
-// anything that forms or drops the pending r on the same vectors: the rebuild of Ap reads r_2 and the spare vector and writes Ap
-// alone, the r-update then overwrites r_2 -- x first, and both see their inputs.
-void settle_x(hmg_grid *g, bool read)
-{
-    LifetimeLock lock(lifetime_mutex());
-    const PendingX q = g->pendx;
-    if (!q.x) return;
-    if (q.form) {
-        HIPCHK(hipSetDevice(g->ctx->device));
-        const double *saved = g->pend_alpha();
-        need(saved != nullptr && (q.form == 2 || g->top_spare.p != nullptr), "pending x-updates have lost the spare vector they rest on");
-        if (q.form == 3)
-            launch_cg_x_tail(g->ctx->L, q.r->d, vec_len(q.x), 0, 1, q.x->d, g->top_spare.p, 4, 5, 2, 3, q.p->d, 6, 7, nullptr, saved);
-        else
-            launch_cg_x_tail(g->ctx->L, q.r->d, vec_len(q.x), 0, 1, q.x->d, q.p->d, 4, 5, 2, 3, nullptr, 0, 0, nullptr, saved);
-        g->ctx->x_settled += 1;
-        if (read) g->ctx->x_settled_read += 1;
-    }
-    g->pendx = PendingX{};
-    if (read) g->x_reader = true;                // (the next V-cycle finishes its x at once and watches again)
-}
-
-PendingX take_pending_x(hmg_grid *g, const hmg_vec *x)
-{
-    LifetimeLock lock(lifetime_mutex());
-    const PendingX q = g->pendx;
-    if (q.x == x && !q.form) {                   // (only watched: this reader costs nothing where the updates ride with it)
-        g->pendx = PendingX{};
-        g->x_reader = false;
-        return PendingX{};
-    }
-    if (q.x != x) {
-        settle_x(g);
-        return PendingX{};
-    }
-    need(g->pend_alpha() != nullptr && (q.form == 2 || g->top_spare.p != nullptr), "pending x-updates have lost the spare vector they rest on");
-    g->pendx = PendingX{};
-    return q;
-}
-
-namespace {
-
-// x is about to be overwritten unread, or goes: nothing is left to form
-void drop_x(hmg_grid *g)
-{
-    g->pendx = PendingX{};
-    g->x_reader = false;
-}
-
-// the x half of settle_overwritten() / pending_keeps(): x itself is dropped, a vector the updates rest on settles them
-void release_x(hmg_grid *g, const hmg_vec *v)
-{
-    const PendingX &q = g->pendx;
-    if (!q.x) return;
-    if (v == q.x)
-        drop_x(g);
-    else if (v == q.p || v == q.r)
-        settle_x(g);
-}
-
-}  // namespace
-
-void materialize_r(hmg_grid *g, bool read)
-{
-    LifetimeLock lock(lifetime_mutex());
-    settle_x(g);
-    const PendingR q = g->pend;
-    if (!q.r) return;
-    if (!q.formed) {
-        HIPCHK(hipSetDevice(g->ctx->device));
-        if (!q.ap_stored) {
-            // the apply of the last CG step as the eager tail launches it: p_2 = r_2 + beta_2 p_1 formed in LDS, Ap = A p_2 with the
-            // edge / node interface sum, p.Ap into S_PAP3 again -- beta_2 from the numbers the x-only tail saved behind the step length
-            need(g->top_spare.p != nullptr && g->pend_alpha() != nullptr, "a pending r-update has lost the spare vector it rests on");
-            const LevelDev &lv = lev(g, q.level);
-            ApplyArgs a{};
-            a.alpha = 1.0;
-            a.lambda = g->lambda;
-            a.x = q.r->d;
-            a.x2 = g->top_spare.p;
-            a.out = q.Ap->d;
-            a.scal = g->pend_alpha();
-            a.s_num = 2;
-            a.s_den = 3;
-            a.flags = 1;
-            apply_then_sum(g, lv, a, true, S_PAP3, -1, true, false);
-            g->ctx->ap_rebuilt += 1;
-        }
-        launch_cg_rupdate_faces(g->ctx->L, lev(g, q.level), g->md, q.r->d, q.r->d, q.Ap->d, vec_len(q.r), 0, 1, q.slot, g->pend_alpha());
-        g->ctx->r_materialized += 1;
-        if (read) g->ctx->r_materialized_read += 1;
-    }
-    close_pending(g);
-    if (read) g->r_reader = true;                // (the next V-cycle forms its r at once and watches again)
-}
-
-void settle_overwritten(const hmg_vec *v)
-{
-    if (!v || !v->g || (!v->g->pend.r && !v->g->pendx.x)) return;
-    LifetimeLock lock(lifetime_mutex());
-    hmg_grid *g = v->g;
-    release_x(g, v);
-    if (!g->pend.r) return;
-    if (v == g->pend.Ap)
-        materialize_r(g);
-    else if (v == g->pend.r)
-        drop_pending(g);
-}
-
-bool pending_keeps(hmg_vec *v)
-{
-    hmg_grid *g = v->g;
-    if (!g) return false;
-    release_x(g, v);                             // (a vector pending x-updates rest on: they are formed now, the one launch a destroy makes)
-    if (!g->pend.r) return false;
-    if (v == g->pend.r)
-        drop_pending(g);
-    else if (v == g->pend.Ap) {
-        if (!g->pend.formed) {
-            g->pend.orphan_Ap = true;
-            return true;
-        }
-        close_pending(g);                        // (a record that only watches needs no Ap)
-    }
-    return false;
-}
-
-namespace {
-
-// Entry of a V-cycle on the top level k: a record on the very r and Ap this cycle is about to overwrite (its first residual writes
-// every entry of r, src/multigrid.jl:50; Ap is scratch) is dropped; any other is settled, the x-only tail needs the grid's
-// step-length buffer for itself.
-// Pending x-updates (option lazy_x) on this cycle's own x, p and r ride in its first residual: the record is taken out of the grid and
-// its form returned (0: nothing to carry).  Any other are settled; with zero_guess x is not read at all and they are dropped.  A record
-// that only watched x and is still open: nobody read x since, the reader memory goes.
-int enter_top(hmg_grid *g, int k, hmg_vec **st, bool zero_guess)
-{
-    int carry = 0;
-    if (g->pendx.x) {
-        LifetimeLock lock(lifetime_mutex());
-        const PendingX px = g->pendx;
-        bool same_x = k >= 2 && k == px.level;
-        for (int i = 0; i < 5 * k && same_x; ++i) {
-            const int at = i - 5 * (k - 1);
-            same_x = (st[i] == px.x) == (at == 0) && (!px.form || ((st[i] == px.r) == (at == 2) && (st[i] == px.p) == (at == 3)));
-        }
-        if (!px.form) {
-            if (same_x) g->x_reader = false;
-            g->pendx = PendingX{};
-        } else if (same_x && zero_guess)
-            drop_x(g);
-        else if (same_x && g->fuse_cg && g->smoother == 0 && g->ctx->lazy_x && px.r == g->pend.r && !g->pend.formed &&
-                 apply_carries_x(g->ctx->L, lev(g, k), g->md, g->lambda, px.form)) {
-            carry = px.form;
-            g->pendx = PendingX{};               // (r_2 stays where it is: the pending r on the same states is dropped below, never formed)
-        } else
-            settle_x(g);
-    }
-    const PendingR &q = g->pend;
-    if (!q.r) {
-        need(!carry, "pending x-updates without the pending r they rest on");
-        return 0;
-    }
-    bool same = k >= 2 && k == q.level;
-    for (int i = 0; i < 5 * k && same; ++i) {
-        const bool is_r = i == 5 * (k - 1) + 2, is_Ap = i == 5 * (k - 1) + 4;
-        same = (st[i] == q.r) == is_r && (st[i] == q.Ap) == is_Ap;
-    }
-    if (same)
-        settle_overwritten(q.r);
-    else {
-        if (carry) {                             // (cannot happen: the x record shares its r with this one and saw the same states)
-            g->pendx = PendingX{st[5 * (k - 1)], st[5 * (k - 1) + 3], st[5 * (k - 1) + 2], k, carry};
-            carry = 0;
-        }
-        materialize_r(g);
-    }
-    return carry;
-}
-
-}  // namespace
-
 void vcycle(hmg_grid *g, int k, int steps, int steps_coarse, hmg_vec **st, bool top, bool zero_guess, bool lazy_x)
 {
-    const int carry_x = top ? enter_top(g, k, st, zero_guess) : 0;
+    const XUpdates carry_x = top ? enter_top(g, k, st, zero_guess) : XUpdates{};
     (void)vcycle_level(g, k, steps, steps_coarse, st, top, zero_guess, /*hand_up=*/false, carry_x, lazy_x);
 }
 

@@ -35,9 +35,9 @@ void upload_mesh(hmg_grid *g)
 #else
     constexpr size_t BP = 2;
 #endif
-    // (+ 8: the step length of a pending r-update, its step's beta and the other ratios of pending x-updates live behind the
+    // (+ XS_COUNT: the step length of a pending r-update, its step's beta and the other ratios of pending x-updates live behind the
     //  partials, hmg_grid::pend_alpha())
-    if (g->d_blockpart.n < (size_t)M.ncells * BP + 8) g->d_blockpart.alloc((size_t)M.ncells * BP + 8);
+    if (g->d_blockpart.n < (size_t)M.ncells * BP + XS_COUNT) g->d_blockpart.alloc((size_t)M.ncells * BP + XS_COUNT);
     g->d_cells_cut.upload(K.cells_cut, s);
     g->d_cells_inner.upload(K.cells_inner, s);
     g->d_cell_perm.upload(K.cell_perm, s);
