@@ -52,18 +52,23 @@ k_operator_rowabs(LevelDev lv, int64_t ncells, const double *__restrict__ coef, 
     s[e] = sum;
 }
 
+// The maximum that keeps a NaN: fmax drops one, and a bound folded with it comes back finite from an operator that is not (the
+// host's check of the bound could then never fire).  A NaN operand gives a NaN whatever the order of the fold; without one these are
+// fmax's bits (the terms are >= 0: no signed zeros to tell apart).
+__device__ __forceinline__ double max_nan(double a, double b) { return (a > b || a != a) ? a : b; }
+
 // all threads of the block call; result valid in thread 0.  red: >= blockDim / 64 doubles of LDS
 __device__ __forceinline__ double block_max(double v, double *red)
 {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_down(v, o, 64));
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) red[w] = v;
     __syncthreads();
     double m = 0.0;
     if (threadIdx.x == 0) {
         const int nw = (blockDim.x + 63) >> 6;
-        for (int i = 0; i < nw; ++i) m = fmax(m, red[i]);
+        for (int i = 0; i < nw; ++i) m = max_nan(m, red[i]);
     }
     __syncthreads();
     return m;
@@ -77,9 +82,9 @@ k_cheb_max(const double *__restrict__ dinv, const double *__restrict__ s, int64_
     double m = 0.0;
     if (i < (n >> 1)) {
         const double2 dv = reinterpret_cast<const double2 *>(dinv)[i], sv = reinterpret_cast<const double2 *>(s)[i];
-        m = fmax(dv.x * sv.x, dv.y * sv.y);
+        m = max_nan(dv.x * sv.x, dv.y * sv.y);
     }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) m = fmax(m, dinv[n - 1] * s[n - 1]);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) m = max_nan(m, dinv[n - 1] * s[n - 1]);
     const double b = block_max(m, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = b;
 }
@@ -91,7 +96,7 @@ __global__ void __launch_bounds__(PB) k_cheb_max_fold(const double *__restrict__
     const int64_t per = (nb + gridDim.x - 1) / gridDim.x;
     const int64_t b0 = (int64_t)blockIdx.x * per, b1 = b0 + per < nb ? b0 + per : nb;
     double m = 0.0;
-    for (int64_t b = b0 + threadIdx.x; b < b1; b += PB) m = fmax(m, part[b]);
+    for (int64_t b = b0 + threadIdx.x; b < b1; b += PB) m = max_nan(m, part[b]);
     const double r = block_max(m, red);
     if (threadIdx.x == 0) out[blockIdx.x] = r;
 }

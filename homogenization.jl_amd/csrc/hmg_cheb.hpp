@@ -31,7 +31,7 @@ struct ChebCoef {
 // s[slot, cell] = sum over the taps of | sum_t ctab[class(slot)][tap][t] * scale_t(cell) |: the absolute row sum of the cell's own
 // lambda M + K_sigma at that slot (the products of launch_operator_diag, over all taps instead of the centre one); 0 in the padding
 void launch_operator_rowabs(const Launch &L, const LevelDev &lv, const MeshDev &mesh, double lambda, double *s);
-// scal[slot] = max over the n entries of dinv[e] * s[e] (0 for n = 0): block partials, then a fixed-order fold
+// scal[slot] = max over the n entries of dinv[e] * s[e] (0 for n = 0; NaN if a term is NaN): block partials, then a fixed-order fold
 void launch_cheb_max(const Launch &L, const double *dinv, const double *s, int64_t n, int slot);
 // d = c0 * (dinv o r)
 void launch_cheb_start(const Launch &L, double *d, const double *r, const double *dinv, int64_t n, double c0);

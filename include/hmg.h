@@ -282,8 +282,13 @@ int hmg_grid_smoother_diag(hmg_grid *grid, int level, hmg_vec *out);
  * makes the V-cycle diverge.  Where none is given the library forms, with dinv and stale with it,
  *     lambda_hi = 1.02 * max over free slots i of dinv_i * (interface sum of s_i),   s_i = the absolute row sum of the cell's own
  *                 lambda M + K_sigma at slot i
- * which is at least the Gershgorin bound of the assembled matrix and at most 1.02 (dim + 1): one more kernel, interface sum and
- * maximum per level, and one host read (hmg_ctx_counter "smoother_bound_builds" counts the levels formed).
+ * which is at least 1.02 times the Gershgorin bound of the assembled matrix on the free rows (|sum_c a^c_ij| <= sum_c |a^c_ij|), hence an
+ * upper bound of the largest eigenvalue.  It has no ceiling of its own: with the default Dirichlet set it stayed below 1.02 (dim + 1) on
+ * every mesh tried, but with the constraint lifted (hmg_grid_set_dirichlet_faces, nfaces = 0) a 2D grid of 8 perturbed cells, sigma in
+ * {1, 100}, gives 6.39 > 3.06.  It depends on the operator, on lambda, on the domain and on the Dirichlet set (constrained rows leave the
+ * maximum) and is formed again after a change of any of them.  A level without a free entry has the maximum 0 and is refused ("the bound
+ * of this level is not a positive number"), as is one whose operator holds a NaN or an infinity (the maximum keeps a NaN).  One more
+ * kernel, interface sum and maximum per level, and one host read (hmg_ctx_counter "smoother_bound_builds" counts the levels formed).
  * ratio <= 0: the default, 30; otherwise it must be finite and > 1.  lambda_hi: NULL, or nlevels entries,
  * entry l - 1 for level l; an entry > 0 is used as given (no factor, nothing formed), an entry <= 0 asks for the formed bound.
  * A partitioned grid, or one with an interface exchange, is accepted only with entries > 0 for every level >= 2 (the maximum over the

@@ -15,11 +15,19 @@ tests/_pcg_smoother_form.py (the oracle's operator tables).  The bound comes fro
 Tails (the names of smooth_form() in csrc/hmg_smooth.cpp): "full" as above (p holds the next d), "scratch_p" ends with x += d, r -= Ad,
 "dead_xp" ends with x += d alone -- no apply for the last step.
 
+Both operator objects are served: the oracle's L2PlusDivAGrad (diagonal sigma) and tests/_tensor_sigma_form.py's TensorOp (a full
+symmetric tensor per cell, P = J^-1 sigma J^-T from its coefficient_rows, its mul and local_residual) -- with a TensorOp the
+inverse diagonals are _tensor_sigma_form.inverse_diagonal's and the level-1 solve _tensor_sigma_form.make_base_level's.  The
+constraint is the operator's own, whichever face set it was built from (tests/_dirichlet_faces_form.py: oracle_constraint).  A
+level without a free entry (dinv = 0 everywhere) has the bound 0 and no interval: the smoother is not stated there.
+
 `ChebGlobalForm` is tests/_global_form.py's GlobalForm (global vectors, assembled matrices) with 1 / A.diagonal() on the interior
 nodes; it takes the interval as numbers.  In both, the V-cycle is the reference's (src/multigrid.jl:73-119): `steps` is not
 forwarded, level 1 is solved directly."""
 import numpy as np
 
+import _tensor_sigma_form as T
+from _dirichlet_faces_form import FaceSetForm, all_faces, default_faces, oracle_constraint
 from _global_form import GlobalForm
 from _pcg_smoother_form import first_copy_residual_norm, inverse_diagonal
 
@@ -32,28 +40,53 @@ CONVERGENCE_FACTOR = 0.765
 CONVERGENCE_PIN = CONVERGENCE_FACTOR + 0.03
 
 
+def _is_tensor(A):
+    return isinstance(A, T.TensorOp)
+
+
+def _scaled_P(O, base, A):
+    """(|J|, |J| P) per cell, P = J^-1 sigma J^-T: (Ne,), (Ne, dim, dim)"""
+    dim = base.dim
+    if _is_tensor(A):
+        rows = T.coefficient_rows(O, base, A.sig)                # |J| P, upper triangle by rows, then |J|
+        iu = np.triu_indices(dim)
+        dP = np.empty((base.nelements(), dim, dim))
+        dP[:, iu[0], iu[1]] = rows[:, :iu[0].size]
+        dP[:, iu[1], iu[0]] = rows[:, :iu[0].size]
+        return rows[:, iu[0].size], dP
+    _, Jinv, det = O.cell_geometry(base)
+    return det, det[:, None, None] * np.einsum("eki,ek,ekj->eij", Jinv, A.sigmas, Jinv)
+
+
+def _mul(O, alpha, base, A, x, y):
+    return T.mul(O, alpha, base, A, x, y) if _is_tensor(A) else O.mul(alpha, base, A, x, y)
+
+
+def _local_residual(O, implicit, A, curr, k):
+    return T.local_residual(O, implicit, A, curr, k) if _is_tensor(A) else O.local_residual(implicit, A, curr, k)
+
+
 def cell_local_rowabs(O, implicit, A, chunk=64):
     """Nf x Ne: the absolute row sums of every cell's own lambda M + K_sigma.  One sparse matrix per distinct coefficient row:
     the terms share one sparsity pattern (the union), a coefficient row weighs their values, the row sums are one sparse product."""
     import scipy.sparse as sp
     base = implicit.base
     dim = base.dim
-    _, Jinv, det = O.cell_geometry(base)
-    P = np.einsum("eki,ek,ekj->eij", Jinv, A.sigmas, Jinv)
+    det, dP = _scaled_P(O, base, A)
     terms = [A.mass.tocoo()] + [A.diffusion_terms[a][b].tocoo() for a in range(dim) for b in range(dim)]
-    coef = np.column_stack([A.lam * det] + [det * P[:, a, b] for a in range(dim) for b in range(dim)])       # Ne x (1 + dim^2)
+    coef = np.column_stack([A.lam * det] + [dP[:, a, b] for a in range(dim) for b in range(dim)])            # Ne x (1 + dim^2)
     nf = A.mass.shape[0]
     keys = [t.row.astype(np.int64) * nf + t.col for t in terms]
     pattern = np.unique(np.concatenate(keys))
-    T = np.zeros((len(terms), pattern.size))
+    vals = np.zeros((len(terms), pattern.size))
     for q, (t, k) in enumerate(zip(terms, keys)):
-        np.add.at(T[q], np.searchsorted(pattern, k), t.data)
+        np.add.at(vals[q], np.searchsorted(pattern, k), t.data)
     to_row = sp.csr_matrix((np.ones(pattern.size), (np.arange(pattern.size), pattern // nf)), shape=(pattern.size, nf))
     rows, inverse = np.unique(coef, axis=0, return_inverse=True)
     inverse = np.asarray(inverse).reshape(-1)
     s = np.empty((rows.shape[0], nf))
     for i in range(0, rows.shape[0], chunk):
-        s[i:i + chunk] = (to_row.T @ np.abs(rows[i:i + chunk] @ T).T).T
+        s[i:i + chunk] = (to_row.T @ np.abs(rows[i:i + chunk] @ vals).T).T
     return np.asfortranarray(s[inverse].T)
 
 
@@ -69,7 +102,8 @@ def bounds_local(O, implicit, ops, grids, dinvs):
 
 
 def inverse_diagonals(O, implicit, ops, grids):
-    return [None] + [inverse_diagonal(O, implicit, ops[k - 1], k) for k in range(2, grids + 1)]
+    return [None] + [(T.inverse_diagonal if _is_tensor(ops[k - 1]) else inverse_diagonal)(O, implicit, ops[k - 1], k)
+                     for k in range(2, grids + 1)]
 
 
 def coefficients(lo, hi, steps):
@@ -87,7 +121,7 @@ def coefficients(lo, hi, steps):
 
 def smoothing_steps_cheb(O, steps, implicit, A, curr, k, dinv, lo, hi, tail="full"):
     c0, cs = coefficients(lo, hi, steps)
-    O.local_residual(implicit, A, curr, k)
+    _local_residual(O, implicit, A, curr, k)
     O.broadcast_interfaces(curr.r, implicit, k)
     curr.p[...] = c0 * (dinv * curr.r)
     for i in range(steps):
@@ -96,7 +130,7 @@ def smoothing_steps_cheb(O, steps, implicit, A, curr, k, dinv, lo, hi, tail="ful
         if last and tail == "dead_xp":
             return
         curr.Ap.fill(0.0)
-        O.mul(1.0, implicit.base, A, curr.p, curr.Ap)
+        _mul(O, 1.0, implicit.base, A, curr.p, curr.Ap)
         O.apply_constraint(curr.Ap, k, A.constraint, implicit)
         O.broadcast_interfaces(curr.Ap, implicit, k)
         curr.r -= curr.Ap
@@ -115,7 +149,7 @@ def vcycle_cheb(O, implicit, base_level, ops, levels, k, steps, dinvs, his, rati
     P = implicit.reference.interops[k - 2]
     hi = his[k - 1]
     smoothing_steps_cheb(O, steps, implicit, ops[k - 1], curr, k, dinvs[k - 1], hi / ratio, hi)
-    O.local_residual(implicit, ops[k - 1], curr, k)
+    _local_residual(O, implicit, ops[k - 1], curr, k)
     O.restrict_to(nxt.b, P, curr.r)
     nxt.x.fill(0.0)
     vcycle_cheb(O, implicit, base_level, ops, levels, k - 1, 2, dinvs, his, ratio)       # `steps` is not forwarded (src/multigrid.jl:109)
@@ -194,3 +228,41 @@ class ChebGlobalForm(GlobalForm):
             d = rho_next * rho * d + (2 * rho_next / delta) * (dinv * r)
             rho = rho_next
         return x, r
+
+
+class ChebFaceSetForm(FaceSetForm, ChebGlobalForm):
+    """ChebGlobalForm whose constrained nodes are those lying on a chosen face of the base mesh (FaceSetForm: geometry only),
+    with one conductivity row per base cell."""
+
+
+FACE_SET_CASES = {3: (20, 4), 2: (19, 5)}        # dim: (seed, levels) on hypercube(dim, 2), sigma in {1, 100}, lambda 0.7, perturbed by 0.2
+
+
+def face_sets(mesh):
+    """The constrained sets the bound is followed through, chosen on the lattice (before the nodes move): the default one (the
+    outer boundary), none at all, every face of every cell."""
+    return {"default": default_faces(mesh.elements), "empty": np.zeros((0, mesh.dim), dtype=np.int64),
+            "every": all_faces(mesh.elements)[0]}
+
+
+class FaceSetCase:
+    """The oracle's side of one of FACE_SET_CASES, as tests/test_gpu_dirichlet_faces.py's Case draws it (nodes moved first, then
+    sigma, from one generator); under(faces): operators, inverse diagonals and bounds with that set's constraint."""
+
+    def __init__(self, O, dim, lam=0.7, perturb=0.2):
+        self.O, self.dim, self.lam = O, dim, lam
+        seed, self.levels = FACE_SET_CASES[dim]
+        self.mesh = O.hypercube(dim, 2)
+        self.sets = face_sets(self.mesh)
+        rng = np.random.default_rng(seed)
+        self.mesh.nodes = self.mesh.nodes + perturb * (rng.random(self.mesh.nodes.shape) - 0.5)
+        self.sig = rng.choice([1.0, 100.0], size=(self.mesh.nelements(), dim))
+        self.impl = O.ImplicitFineGrid.create(self.mesh, self.levels)
+        self.tables = [(O.build_local_diffusion_operators(l), O.mass_matrix(l)) for l in self.impl.reference.levels]
+
+    def under(self, faces):
+        O = self.O
+        cons = oracle_constraint(O, self.mesh, faces)
+        ops = [O.L2PlusDivAGrad(d, m, cons, self.lam, self.sig) for d, m in self.tables]
+        dinvs = inverse_diagonals(O, self.impl, ops, self.levels)
+        return cons, ops, dinvs, bounds_local(O, self.impl, ops, self.levels, dinvs)

@@ -44,6 +44,18 @@ def plane_faces(nodes, elements, axis, value):
     return f[np.all(np.abs(np.asarray(nodes)[f][:, :, axis] - value) <= 1e-12, axis=1)]
 
 
+def sides(m, axis):
+    x = m.nodes[:, axis]
+    return np.concatenate([plane_faces(m.nodes, m.elements, axis, x.min()), plane_faces(m.nodes, m.elements, axis, x.max())])
+
+
+def mid_plane_and_sides(m):
+    """an internal plane normal to the first axis -- every face of it lies between two cells -- and the two outer sides normal to
+    the last: most of the outer boundary is free"""
+    lo, hi = m.nodes[:, 0].min(), m.nodes[:, 0].max()
+    return np.concatenate([plane_faces(m.nodes, m.elements, 0, 0.5 * (lo + hi)), sides(m, m.dim - 1)])
+
+
 def block_boundary_faces(nodes, elements, block):
     """faces on the planes x_a = min_a + j * block of every axis a (the outer boundary among them)"""
     nodes = np.asarray(nodes, dtype=np.float64)
@@ -123,6 +135,6 @@ def on_faces(points, nodes, faces):
 class FaceSetForm(GlobalForm):
     """GlobalForm whose constrained nodes, on every refined mesh, are those lying on a chosen face of the base mesh"""
 
-    def __init__(self, O, base, sgrid, lam, implicit, grids, dim, faces):
-        super().__init__(O, base, sgrid, lam, implicit, grids, dim)
+    def __init__(self, O, base, sgrid, lam, implicit, grids, dim, faces, cond=None):
+        super().__init__(O, base, sgrid, lam, implicit, grids, dim, cond=cond)
         self.inner = [~on_faces(m.nodes, base.nodes, faces) for m in self.meshes]

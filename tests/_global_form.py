@@ -10,7 +10,9 @@ import numpy as np
 
 
 class GlobalForm:
-    def __init__(self, O, base, sgrid, lam, implicit, grids, dim):
+    def __init__(self, O, base, sgrid, lam, implicit, grids, dim, cond=None):
+        """cond: (Ne, dim) per base cell in the place of `sgrid` (any base mesh, a perturbed one included: nodes are matched after
+        rounding to 1 / 4096) -- a refined element takes its parent's row, red refinement keeps a parent's children together."""
         import scipy.sparse as sp
         self.O, self.grids, self.dim = O, grids, dim
         w = np.array([1, 1 << 20, 1 << 40][:dim])
@@ -20,7 +22,8 @@ class GlobalForm:
             m = O.refine_uniformly(base, times=l) if l else base
             m.elements = O.sort_element_nodes(m.elements)
             self.meshes.append(m)
-            self.A.append(O.assemble_checkerboard(m, O.conductivity_per_element(m, sgrid, (0.0,) * dim), lam).tocsr())
+            sig = O.conductivity_per_element(m, sgrid, (0.0,) * dim) if cond is None else np.repeat(cond, (2 ** dim) ** l, axis=0)
+            self.A.append(O.assemble_checkerboard(m, sig, lam).tocsr())
             mask = np.zeros(m.nnodes(), dtype=bool)
             mask[O.list_interior_nodes(m)] = True
             self.inner.append(mask)

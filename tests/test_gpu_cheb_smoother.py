@@ -37,6 +37,8 @@ def _check_bounds(p, g, ctx, levels_checked, ratio=DEFAULT_RATIO):
         print(f"level {lev}: lambda_hi {hi:.12f}, statement {want:.12f}, relative difference {abs(hi - want) / want:.2e}")
         assert abs(hi - want) <= 1e-11 * want, (lev, hi, want)
         assert lo == hi / ratio
+        # not a property of the bound: of the default Dirichlet set on the meshes this helper is called with.  With the constraint
+        # lifted the 2D case of tests/test_gpu_cheb_smoother_cross.py gives 6.39 > 3.06 (tests/test_cheb_smoother_statement.py)
         assert hi <= 1.02 * (p.mesh.dim + 1) * (1 + 1e-12)
     n0 = ctx.counter("smoother_bound_builds")
     again = [hmg.smoother_bounds(g, lev) for lev in levels_checked]

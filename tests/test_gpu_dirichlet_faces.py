@@ -14,8 +14,8 @@ import homogenization_jl_amd as hmg
 from homogenization_jl_amd import driver
 from homogenization_jl_amd._lib import HmgError
 
-from _dirichlet_faces_form import (FaceSetForm, block_boundary_faces, default_faces, interior_faces, one_based,
-                                   oracle_base_level, oracle_constraint, plane_faces)
+from _dirichlet_faces_form import (FaceSetForm, block_boundary_faces, default_faces, interior_faces, mid_plane_and_sides,  # noqa: F401
+                                   one_based, oracle_base_level, oracle_constraint, plane_faces, sides)
 from _fcg_form import fcg_global
 
 pytestmark = pytest.mark.gpu
@@ -34,18 +34,6 @@ def ctx():
     c = hmg.Context(0)
     yield c
     c.close()
-
-
-def sides(m, axis):
-    x = m.nodes[:, axis]
-    return np.concatenate([plane_faces(m.nodes, m.elements, axis, x.min()), plane_faces(m.nodes, m.elements, axis, x.max())])
-
-
-def mid_plane_and_sides(m):
-    """an internal plane normal to the first axis -- every face of it lies between two cells -- and the two outer sides normal to
-    the last: most of the outer boundary is free"""
-    lo, hi = m.nodes[:, 0].min(), m.nodes[:, 0].max()
-    return np.concatenate([plane_faces(m.nodes, m.elements, 0, 0.5 * (lo + hi)), sides(m, m.dim - 1)])
 
 
 class Case:
@@ -192,11 +180,13 @@ def test_2d_levels_5_and_9(oracle, ctx, levels, counter):
 
 
 @pytest.mark.parametrize("fused", [1, 0])
-@pytest.mark.parametrize("smoother", ["cg", "jacobi"])
+@pytest.mark.parametrize("smoother", ["cg", "jacobi", "chebyshev"])
 @pytest.mark.parametrize("dim", [3, 2])
 def test_smoothing_steps(oracle, ctx, dim, smoother, fused):
-    """hmg_smooth, three steps on every level of a small grid, both smoothers, with and without the fused CG pass: x, r, p to
-    1e-10.  The Jacobi smoother's inverse diagonal is 0 on the constrained nodes, the internal plane's among them."""
+    """hmg_smooth, three steps on every level of a small grid, the three smoothers, with and without the fused CG pass: x, r, p to
+    1e-10.  The Jacobi smoother's inverse diagonal is 0 on the constrained nodes, the internal plane's among them; the Chebyshev
+    smoother's bound (1e-11) and steps are the statement's under the case's constraint."""
+    from _cheb_smoother_form import DEFAULT_RATIO, lambda_hi_local, smoothing_steps_cheb
     from _pcg_smoother_form import inverse_diagonal, smoothing_steps_jacobi
     O = oracle
     m = O.hypercube(dim, 2)
@@ -207,12 +197,18 @@ def test_smoothing_steps(oracle, ctx, dim, smoother, fused):
         dst = hmg.LevelState(c.g, lev)
         dst.x.from_host(st.x)
         dst.b.from_host(st.b)
-        if smoother == "jacobi":
+        if smoother != "cg":
             dinv = inverse_diagonal(O, c.impl, c.op(lev), lev)
             got = hmg.smoother_diag(c.g, lev).to_host()
             assert relerr(got, dinv) <= TOL
             np.testing.assert_array_equal(got == 0.0, dinv == 0.0)
+        if smoother == "jacobi":
             smoothing_steps_jacobi(O, 3, c.impl, c.op(lev), st, lev, dinv)
+        elif smoother == "chebyshev":
+            hi = lambda_hi_local(O, c.impl, c.op(lev), lev, dinv)
+            got = hmg.smoother_bounds(c.g, lev)[1]
+            assert abs(got - hi) <= TOL * hi, (lev, got, hi)
+            smoothing_steps_cheb(O, 3, c.impl, c.op(lev), st, lev, dinv, hi / DEFAULT_RATIO, hi)
         else:
             O.smoothing_steps(3, c.impl, c.op(lev), st, lev)
         hmg.smoothing_steps(3, c.g, c.A, dst, lev)
@@ -349,7 +345,7 @@ def test_exact_savings_are_exact_one_by_one(ctx, dim, n, levels):
         g.close()
 
 
-@pytest.mark.parametrize("smoother", ["cg", "jacobi"])
+@pytest.mark.parametrize("smoother", ["cg", "jacobi", "chebyshev"])
 def test_back_to_the_default_set_gives_the_bits_of_a_grid_that_never_left_it(ctx, smoother):
     """set(custom), a V-cycle, set(-1), coarse_setup, V-cycles: x and r of a grid that never saw the call, bit for bit; the device
     masks live where they lived ("device_allocs" constant across the setter) and the tables are the default ones again."""
@@ -419,7 +415,8 @@ def _laminate(dim, n):
     return layers, np.broadcast_to(layers.reshape((n,) + (1,) * (dim - 1) + (dim,)), (n,) * dim + (dim,)).copy()
 
 
-@pytest.mark.parametrize("dim,smoother,accelerate", [(2, "cg", False), (3, "jacobi", True)])
+@pytest.mark.parametrize("dim,smoother,accelerate", [(2, "cg", False), (3, "jacobi", True), (2, "chebyshev", False),
+                                                     (3, "chebyshev", True)])
 def test_uniaxial_driver_is_exact_for_a_laminate(ctx, dim, smoother, accelerate):
     """Layers normal to e_1: "tensor" is diag(harmonic mean of sigma_11, arithmetic means of the others), in the energy and in the
     flux form.  Solver-limited: 1e-8, the bound tests/test_gpu_pcg_smoother.py holds its driver to against the direct solve, with

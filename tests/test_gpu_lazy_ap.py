@@ -385,7 +385,7 @@ def test_flexible_cg(ctx, problems, levels):
 
 
 # ---- 7. the forms that keep the stored Ap --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("why", ["top2-nospare", "two-steps", "2d", "jacobi", "synthetic-cut", "wrapped", "r-reader"])
+@pytest.mark.parametrize("why", ["top2-nospare", "two-steps", "2d", "jacobi", "chebyshev", "synthetic-cut", "wrapped", "r-reader"])
 def test_fallbacks_keep_todays_form(ctx, problems, why):
     """Without the spare vector (Top2), with two smoothing steps, in 2D, with the Jacobi smoother, on a partitioned grid, with a
     caller-owned r and for a caller that reads r after every cycle the last step stores Ap as before: lazy_ap_form = 0, nothing is
@@ -436,15 +436,15 @@ def test_fallbacks_keep_todays_form(ctx, problems, why):
         return out
 
     try:
-        if why == "jacobi":
-            P.g.set_smoother("jacobi")
+        if why in ("jacobi", "chebyshev"):
+            P.g.set_smoother(why)
         if why == "top2-nospare":
             P.g.reserve_spare(False)
         res = _modes(c, run, modes=("lazy_ap=0", "on"))
         assert np.isfinite(res[0][3]) and res[0][3] > 0.0
         _all_equal(res, why)
     finally:
-        if why == "jacobi":
+        if why in ("jacobi", "chebyshev"):
             P.g.set_smoother("cg")
         if why == "top2-nospare":
             P.g.reserve_spare(True)

@@ -557,7 +557,7 @@ def test_flexible_cg_never_forms_r(ctx, problems):
 
 # ---- 4. eager fall-backs --------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
-@pytest.mark.parametrize("why", ["wrapped", "exposed", "jacobi", "partitioned"])
+@pytest.mark.parametrize("why", ["wrapped", "exposed", "jacobi", "chebyshev", "partitioned"])
 def test_eager_fallbacks(ctx, problems, why):
     """Where the memory of r can be read behind the library's back, on a partitioned grid and with the Jacobi smoother the eager
     tail runs whatever the option says: lazy_r_form = 0, nothing is ever formed late, and the results are those of lazy_r = 0."""
@@ -594,11 +594,11 @@ def test_eager_fallbacks(ctx, problems, why):
         return out
 
     try:
-        if why == "jacobi":
-            P.g.set_smoother("jacobi")
+        if why in ("jacobi", "chebyshev"):
+            P.g.set_smoother(why)
         _equal(*_both(ctx, run), why)
     finally:
-        if why == "jacobi":
+        if why in ("jacobi", "chebyshev"):
             P.g.set_smoother("cg")
         _close(*keep)
         if why == "partitioned":

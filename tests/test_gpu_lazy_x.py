@@ -267,7 +267,7 @@ def test_a_caller_that_reads_x_after_every_cycle(ctx, problems):
 
 
 # ---- 4. where nothing is deferred ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("why", ["wrapped-x", "wrapped-p", "handed-out", "synthetic-cut", "jacobi"])
+@pytest.mark.parametrize("why", ["wrapped-x", "wrapped-p", "handed-out", "synthetic-cut", "jacobi", "chebyshev"])
 def test_refusals(ctx, problems, why):
     import torch
     levels = 6
@@ -304,13 +304,13 @@ def test_refusals(ctx, problems, why):
         return _observed(st)
 
     try:
-        if why == "jacobi":
-            P.g.set_smoother("jacobi")
+        if why in ("jacobi", "chebyshev"):
+            P.g.set_smoother(why)
         res = _with(c, OFF_ON, run)
         assert np.isfinite(res[0][-1]) and res[0][-1] > 0.0
         _all_equal(res, why)
     finally:
-        if why == "jacobi":
+        if why in ("jacobi", "chebyshev"):
             P.g.set_smoother("cg")
         _close(*keep)
         if why == "synthetic-cut":

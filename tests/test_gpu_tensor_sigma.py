@@ -167,15 +167,17 @@ def test_right_hand_side_integrals_and_level_1_solve(request, ctx, which):
     g.close()
 
 
-@pytest.mark.parametrize("smoother", ["cg", "jacobi"])
+@pytest.mark.parametrize("smoother", ["cg", "jacobi", "chebyshev"])
 @pytest.mark.parametrize("which", ["cube", "square"])
 def test_vcycles(request, ctx, which, smoother):
-    """three smoothing steps, two V-cycles: x 1e-9, r 1e-8; "jacobi": the inverse diagonal first, 1e-11"""
+    """three smoothing steps, two V-cycles: x 1e-9, r 1e-8; "jacobi" and "chebyshev": the inverse diagonal first, 1e-11;
+    "chebyshev": the bound of every level 1e-11, the cycles those of tests/_cheb_smoother_form.py over the tensor operator"""
+    import _cheb_smoother_form as C
     prob = request.getfixturevalue(which)
     O, top = prob.O, prob.grids
     g, A = device(ctx, prob, smoother)
-    dinvs = None
-    if smoother == "jacobi":
+    dinvs = his = None
+    if smoother != "cg":
         dinvs = prob.dinvs()
         for level in range(2, top + 1):
             got = hmg.smoother_diag(g, level).to_host()
@@ -183,6 +185,12 @@ def test_vcycles(request, ctx, which, smoother):
             print(f"level {level}: inverse diagonal {err:.2e}")
             assert err <= 1e-11, (level, err)
             np.testing.assert_array_equal(got == 0.0, dinvs[level - 1] == 0.0)
+    if smoother == "chebyshev":
+        his = C.bounds_local(O, prob.implicit, prob.ops, top, dinvs)
+        for level in range(2, top + 1):
+            hi = hmg.smoother_bounds(g, level)[1]
+            print(f"level {level}: bound {hi:.12f}, statement {his[level - 1]:.12f}")
+            assert abs(hi - his[level - 1]) <= 1e-11 * his[level - 1], (level, hi, his[level - 1])
     rng = np.random.default_rng(6)
     x0, b0 = prob.rand(rng, top), prob.rand(rng, top)
     prob.start(x0, b0)
@@ -191,7 +199,10 @@ def test_vcycles(request, ctx, which, smoother):
     dst[-1].b.from_host(b0)
     bl = hmg.BaseLevel(g)
     for cyc in range(2):
-        prob.cycle(3, dinvs)
+        if smoother == "chebyshev":
+            C.vcycle_cheb(O, prob.implicit, prob.base_level, prob.ops, prob.states, top, 3, dinvs, his)
+        else:
+            prob.cycle(3, dinvs if smoother == "jacobi" else None)
         hmg.vcycle(g, bl, [A] * top, dst, top, 3)
         ex, er = relerr(dst[-1].x.to_host(), prob.states[-1].x), relerr(dst[-1].r.to_host(), prob.states[-1].r)
         print(f"{which} {smoother} cycle {cyc + 1}: x {ex:.2e} r {er:.2e}")
