@@ -45,6 +45,8 @@ SIGNATURES = {
     "hmg_cell_pair_moments_count": (c_int, [vp]),
     "hmg_cell_extrema": (c_int, [vp, vp, p_f64, p_f64, c_int, p_f64, p_f64]),
     "hmg_grid_fine_elements": (c_i64, [vp, c_int]),
+    "hmg_cell_extrema_where": (c_int, [vp, vp, p_f64, p_f64, c_int, p_f64, p_f64, p_i32]),
+    "hmg_grid_element_vertices": (c_int, [vp, c_int, c_i64, p_i32, p_i32]),
     "hmg_grid_locate": (c_int, [vp, c_int, c_i64, p_f64, p_i32, p_i32, p_f64, p_f64]),
     "hmg_sample": (c_int, [vp, c_int, vp, p_f64, c_i64, p_f64, p_f64, p_f64, p_i32]),
     "hmg_sample_raster": (c_int, [vp, c_int, vp, p_f64, p_f64, p_f64, p_f64, c_i64, c_i64, p_f64, p_f64, p_i32]),

@@ -667,7 +667,37 @@ def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None
     (form = global_form[implicit.local_cells]; a form of global length is refused), while the operator's sigma is the global field.
     qmax and qmin of a cell are NaN exactly when q_T is NaN on one of its elements (a NaN in the cell's column, inf - inf); an
     infinite q_T is a value; a NaN element is counted for no threshold; other cells are untouched.
-    What to do with the results: fields.exceedance_volume, fields.concentration.  No counterpart in the reference."""
+    What to do with the results: fields.exceedance_volume, fields.concentration; cell_extrema_where also says where the extrema
+    sit.  No counterpart in the reference."""
+    return _cell_extrema(v, implicit, xi, form, thresholds, False)
+
+
+def cell_extrema_where(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None, thresholds=None):
+    """cell_extrema, and which fine element holds each extremum (hmg_cell_extrema_where): (qmax, qmin, counts, where_max,
+    where_min).  The first three are cell_extrema's for the same arguments, bit for bit.  where_max, where_min (Ne, d + 1) int32:
+    the vertices of the element that attains the maximum (minimum) of the cell, as 0-based HIERARCHICAL node ids -- rows of
+    `DeviceMatrix.to_host()`, the convention of `locate` -- in the element's own order p, p + pi1, p + pi1 + pi2, p + s.  Among
+    elements of equal value (==) the one with the lowest code slot(p) * 8 + k is reported (slot: table "hier2slot"; k: the bit of
+    table_i32 "elem_mask"), so the ints are the same for every launch shape, kernel family and run.  A cell whose extrema are NaN
+    has -1 in both rows; an infinite value has a location.  The same single pass of 8 B/DOF; served and refused as cell_extrema
+    (option "cell_extrema_windows", partitioned and shrunk grids).  Counters: "cell_extrema_where_launches",
+    "cell_extrema_where_kernel_ns".  fields.element_centroids turns the vertices into points, fields.hot_spots ranks them."""
+    return _cell_extrema(v, implicit, xi, form, thresholds, True)
+
+
+def element_vertices(implicit: ImplicitFineGrid, level: int, codes):
+    """The vertices of the fine elements of `level` named by codes slot(p) * 8 + k (hmg_grid_element_vertices; host only, a grid
+    without a context too): (n, d + 1) int32, 0-based hierarchical node ids in the element's order p, p + pi1, p + pi1 + pi2, p + s.
+    A code whose slot is out of range or whose bit k of the slot's "elem_mask" is clear is refused."""
+    lib = L.load()
+    d = implicit.base.dim
+    c = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+    nodes = np.zeros((c.shape[0], d + 1), dtype=np.int32)
+    L.check(lib.hmg_grid_element_vertices(implicit.h, int(level), c.shape[0], c.ctypes.data_as(L.p_i32), nodes.ctypes.data_as(L.p_i32)))
+    return nodes
+
+
+def _cell_extrema(v, implicit, xi, form, thresholds, located):
     lib = L.load()
     d = implicit.base.dim
     ne = implicit.ncells()
@@ -697,8 +727,15 @@ def cell_extrema(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None
     if nthr:
         tp = thr.ctypes.data_as(L.p_f64)
     out = np.zeros((ne, 2 + nthr), dtype=np.float64)
-    L.check(lib.hmg_cell_extrema(implicit.h, v.h, xp, fp, nthr, tp, out.ctypes.data_as(L.p_f64)))
-    return np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]), np.rint(out[:, 2:]).astype(np.int64)
+    if located:
+        where = np.zeros((ne, 2, d + 1), dtype=np.int32)
+        L.check(lib.hmg_cell_extrema_where(implicit.h, v.h, xp, fp, nthr, tp, out.ctypes.data_as(L.p_f64), where.ctypes.data_as(L.p_i32)))
+    else:
+        L.check(lib.hmg_cell_extrema(implicit.h, v.h, xp, fp, nthr, tp, out.ctypes.data_as(L.p_f64)))
+    res = (np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1]), np.rint(out[:, 2:]).astype(np.int64))
+    if located:
+        res += (np.ascontiguousarray(where[:, 0]), np.ascontiguousarray(where[:, 1]))
+    return res
 
 
 def _points_of(implicit, points):

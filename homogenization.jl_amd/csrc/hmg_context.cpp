@@ -299,6 +299,8 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_moments_window_launches") return ctx->moments_window_launches;   // launches of the window kernels (option "cell_moments_windows")
     if (n == "cell_moments_windows") return ctx->moments_windows;                   // ... and that option's value (a caller that sets it for one pass restores it)
     if (n == "cell_extrema_kernel_ns") return ctx->extrema_kernel_ns;               // the last hmg_cell_extrema: kernel alone
+    if (n == "cell_extrema_where_kernel_ns") return ctx->extrema_where_kernel_ns;   // the last hmg_cell_extrema_where: kernel alone
+    if (n == "cell_extrema_where_launches") return ctx->extrema_where_launches;     // launches of the located kernels, either family
     if (n == "cell_extrema_window_launches") return ctx->extrema_window_launches;   // launches of its window kernels (option "cell_extrema_windows")
     if (n == "cell_extrema_windows") return ctx->extrema_windows;                   // ... and that option's value
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;    // as the RCCL communicator was created; 0: none

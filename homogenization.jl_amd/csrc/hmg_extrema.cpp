@@ -64,7 +64,42 @@ bool invert(int dim, const double A[3][3], double inv[3][3])
     return true;
 }
 
+// permutations of the basis in lexicographic order: bit k of the element mask
+const int PERM3[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+const int PERM2[2][3] = {{0, 1, 0}, {1, 0, 0}};
+
 }  // namespace
+
+// Codes slot(p) * 8 + k -> the element's vertices p, p + pi1, p + pi1 + pi2, p + s as hierarchical node ids, pi the permutation
+// bit k names (include/hmg.h: hmg_grid_element_vertices; the one decode of hmg_cell_extrema_where's kernel results too).
+// The lattice -> slot table is formed per call from slot_ijk: (m + 1)^dim ints, next to nothing beside the call's own work.
+void element_vertices(const LevelTables &T, const ElementTables &E, int64_t n, const int32_t *codes, int32_t *nodes, const char *who)
+{
+    const int dim = T.dim, nv = dim + 1, nperm = dim == 3 ? 6 : 2, m1 = T.m + 1;
+    auto idx = [&](int i, int j, int k) { return ((size_t)k * m1 + j) * m1 + i; };
+    std::vector<int32_t> slot_at((size_t)m1 * m1 * (dim == 3 ? m1 : 1), -1);
+    for (int q = 0; q < T.nf; ++q) slot_at[idx(T.slot_ijk[3 * q], T.slot_ijk[3 * q + 1], T.slot_ijk[3 * q + 2])] = q;
+    for (int64_t e = 0; e < n; ++e) {
+        const int32_t code = codes[e];
+        const int64_t slot = code >> 3;
+        const int k = code & 7;
+        if (code < 0 || slot >= T.nf)
+            throw std::runtime_error(std::string(who) + ": code " + std::to_string(code) + " (entry " + std::to_string(e) +
+                                     ") names slot " + std::to_string(slot) + "; level " + std::to_string(T.level) + " has slots 0 to " +
+                                     std::to_string(T.nf - 1));
+        if (k >= nperm || !((E.mask[slot] >> k) & 1u))
+            throw std::runtime_error(std::string(who) + ": code " + std::to_string(code) + " (entry " + std::to_string(e) +
+                                     ") names element " + std::to_string(k) + " of slot " + std::to_string(slot) +
+                                     ", whose bit of \"elem_mask\" is clear: no fine element of level " + std::to_string(T.level));
+        int x[3] = {T.slot_ijk[3 * slot], T.slot_ijk[3 * slot + 1], T.slot_ijk[3 * slot + 2]};
+        nodes[e * nv] = T.slot2hier[slot];
+        const int *pi = dim == 3 ? PERM3[k] : PERM2[k];
+        for (int r = 0; r < dim; ++r) {
+            for (int a = 0; a < dim; ++a) x[a] += E.dirs[(size_t)pi[r] * dim + a];
+            nodes[e * nv + r + 1] = T.slot2hier[slot_at[idx(x[0], x[1], x[2])]];   // (inside the cell: build_element_tables checked)
+        }
+    }
+}
 
 ElementTables build_element_tables(const LevelTables &T)
 {
@@ -118,9 +153,6 @@ ElementTables build_element_tables(const LevelTables &T)
             E.taps[q] = taps[q];
         }
     }
-    // permutations of the basis in lexicographic order
-    static const int PERM3[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-    static const int PERM2[2][3] = {{0, 1, 0}, {1, 0, 0}};
     auto perm = [&](int k) { return dim == 3 ? PERM3[k] : PERM2[k]; };
 
     // ---- the mask, from the element list ----
@@ -221,21 +253,31 @@ int64_t hmg_grid_fine_elements(const hmg_grid *g, int level)
     return (int64_t)1 << (g->dim * (level - 1));
 }
 
-int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr, const double *thresholds, double *out)
+}  // extern "C"
+
+namespace {
+
+// hmg_cell_extrema (located = false) and hmg_cell_extrema_where: one text of the checks, the rows and the launch; `who` names the
+// call in every message.  where: host, 2 (dim + 1) ints per cell.
+void cell_extrema_call(const std::string &who, bool located, hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr,
+                       const double *thresholds, double *out, int32_t *where)
 {
-    HMG_TRY
-    need(g != nullptr, "null grid");
-    need(out != nullptr, "hmg_cell_extrema: null output array");
-    need(g->ctx != nullptr, "hmg_cell_extrema: this grid was created without a device context (host tables only): no compute path exists on the CPU");
-    need(v != nullptr, "hmg_cell_extrema: null vector");
-    need(v->g == g, "hmg_cell_extrema: vector belongs to another grid");
+    auto need = [&](bool c, const char *msg) {
+        if (!c) throw std::runtime_error(who + ": " + msg);
+    };
+    hmg::need(g != nullptr, "null grid");
+    need(out != nullptr, "null output array");
+    need(!located || where != nullptr, "null where array");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    need(v != nullptr, "null vector");
+    need(v->g == g, "vector belongs to another grid");
     if (nthr < 0 || nthr > EX_MAX_THRESHOLDS)
-        throw std::runtime_error("hmg_cell_extrema: " + std::to_string(nthr) + " thresholds; 0 to 8 are served");
-    need(nthr == 0 || thresholds != nullptr, "hmg_cell_extrema: null thresholds");
+        throw std::runtime_error(who + ": " + std::to_string(nthr) + " thresholds; 0 to 8 are served");
+    need(nthr == 0 || thresholds != nullptr, "null thresholds");
     ExtremaThresholds thr;
     for (int j = 0; j < EX_MAX_THRESHOLDS; ++j) {
         thr.t[j] = j < nthr ? thresholds[j] : HUGE_VAL;
-        if (j < nthr && !std::isfinite(thr.t[j])) throw std::runtime_error("hmg_cell_extrema: threshold " + std::to_string(j) + " is not finite");
+        if (j < nthr && !std::isfinite(thr.t[j])) throw std::runtime_error(who + ": threshold " + std::to_string(j) + " is not finite");
     }
     check_vec(g, v->level, v, "v");
     const LevelDev &lv = lev(g, v->level);
@@ -247,7 +289,7 @@ int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *fo
     const int mode = g->ctx->extrema_windows;
     const bool window = mode != 0 && can && (mode == 2 || !fits);
     if (!window && !fits)
-        throw std::runtime_error("hmg_cell_extrema: one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
+        throw std::runtime_error(who + ": one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
                                  " nodes) does not fit the LDS; the per-cell extrema serve " +
                                  (dim == 3 ? "3D levels up to 6" : "2D levels up to 8") +
                                  (can ? "; the context option \"cell_extrema_windows\" = 1 takes larger cells through the window kernels"
@@ -257,17 +299,17 @@ int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *fo
     if (form)
         for (int64_t q = 0; q < nc * nq; ++q)
             if (!std::isfinite(form[q]))
-                throw std::runtime_error("hmg_cell_extrema: the form of cell " + std::to_string(q / nq) + " is not finite");
+                throw std::runtime_error(who + ": the form of cell " + std::to_string(q / nq) + " is not finite");
     if (xi)
-        for (int a = 0; a < dim; ++a) need(std::isfinite(xi[a]), "hmg_cell_extrema: xi is not finite");
-    if (nc == 0) return 0;
+        for (int a = 0; a < dim; ++a) need(std::isfinite(xi[a]), "xi is not finite");
+    if (nc == 0) return;
     const ElementTables &E = g->fields.elem.at(v->level - 1);
 
     // ---- one row per cell: Q~ = M^T Q M, xi~ = M^-1 xi, M = m Jinv B^-T ----
     double Bm[3][3] = {{0}}, Binv[3][3];
     for (int b = 0; b < dim; ++b)
         for (int a = 0; a < dim; ++a) Bm[a][b] = E.dirs[(size_t)b * dim + a];        // columns a, b, c
-    need(invert(dim, Bm, Binv), "hmg_cell_extrema: the lattice basis is singular");
+    need(invert(dim, Bm, Binv), "the lattice basis is singular");
     std::vector<double> rows((size_t)nc * nrow);
     const double scale = (double)lv.m;
     std::atomic<bool> singular{false};
@@ -309,44 +351,97 @@ int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *fo
             }
         }
     });
-    need(!singular, "hmg_cell_extrema: a cell's geometry is singular");
+    need(!singular, "a cell's geometry is singular");
 
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
     const uint8_t *d_mask = device_mask(g, v->level);
     const size_t nout = (size_t)(2 + nthr) * (size_t)nc;
     const size_t row_bytes = sizeof(double) * rows.size(), out_bytes = sizeof(double) * nout;
+    const size_t code_bytes = sizeof(int32_t) * 2 * (size_t)nc;
     double *d_rows = vec_alloc(c, row_bytes), *d_out = nullptr;
+    int32_t *d_codes = nullptr;
+    std::vector<int32_t> codes(located ? 2 * (size_t)nc : 0);
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     try {
         d_out = vec_alloc(c, out_bytes);
+        if (located) d_codes = (int32_t *)vec_alloc(c, code_bytes);
         HIPCHK(hipEventCreate(&ev0));
         HIPCHK(hipEventCreate(&ev1));
         HIPCHK(hipMemcpyAsync(d_rows, rows.data(), row_bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipEventRecord(ev0, c->stream));
         if (window) {
-            launch_cell_extrema_window(c->L, lv, st, nc, v->d, d_mask, d_rows, thr, nthr, d_out);
+            launch_cell_extrema_window(c->L, lv, st, nc, v->d, d_mask, d_rows, thr, nthr, d_out, d_codes);
             c->extrema_window_launches += 1;
         } else
-            launch_cell_extrema(c->L, lv, nc, v->d, d_mask, d_rows, thr, nthr, d_out);
+            launch_cell_extrema(c->L, lv, nc, v->d, d_mask, d_rows, thr, nthr, d_out, d_codes);
+        if (located) c->extrema_where_launches += 1;
         HIPCHK(hipEventRecord(ev1, c->stream));
         HIPCHK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (located) HIPCHK(hipMemcpyAsync(codes.data(), d_codes, code_bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         float ms = 0.0f;
         HIPCHK(hipEventElapsedTime(&ms, ev0, ev1));
-        c->extrema_kernel_ns = (int64_t)((double)ms * 1e6);
+        (located ? c->extrema_where_kernel_ns : c->extrema_kernel_ns) = (int64_t)((double)ms * 1e6);
     } catch (...) {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         (void)hipStreamSynchronize(c->stream);       // (the rows' host copy goes out of scope)
         vec_release(c, d_rows, row_bytes);
         if (d_out) vec_release(c, d_out, out_bytes);
+        if (d_codes) vec_release(c, (double *)d_codes, code_bytes);
         throw;
     }
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
     vec_release(c, d_rows, row_bytes);
     vec_release(c, d_out, out_bytes);
+    if (!located) return;
+    vec_release(c, (double *)d_codes, code_bytes);
+    // the kernel's codes -> vertices: -1 (the cell's extrema are NaN) stays -1 in all its entries, every other code is decoded
+    const int nv = dim + 1;
+    const LevelTables &T = g->lt.at(v->level - 1);
+    std::vector<int32_t> valid, pos;
+    for (size_t q = 0; q < codes.size(); ++q)
+        if (codes[q] >= 0) {
+            valid.push_back(codes[q]);
+            pos.push_back((int32_t)q);
+        }
+    std::vector<int32_t> verts(valid.size() * nv);
+    element_vertices(T, E, (int64_t)valid.size(), valid.data(), verts.data(), who.c_str());
+    std::fill(where, where + codes.size() * nv, -1);
+    for (size_t q = 0; q < pos.size(); ++q) std::copy(&verts[q * nv], &verts[q * nv] + nv, where + (size_t)pos[q] * nv);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hmg_cell_extrema(hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr, const double *thresholds, double *out)
+{
+    HMG_TRY
+    cell_extrema_call("hmg_cell_extrema", false, g, v, xi, form, nthr, thresholds, out, nullptr);
+    HMG_END
+}
+
+int hmg_cell_extrema_where(hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr, const double *thresholds,
+                           double *out, int32_t *where)
+{
+    HMG_TRY
+    cell_extrema_call("hmg_cell_extrema_where", true, g, v, xi, form, nthr, thresholds, out, where);
+    HMG_END
+}
+
+int hmg_grid_element_vertices(const hmg_grid *g, int level, int64_t n, const int32_t *codes, int32_t *nodes)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    if (level < 1 || level > g->nlevels)
+        throw std::runtime_error("hmg_grid_element_vertices: level " + std::to_string(level) + " out of range 1 to " + std::to_string(g->nlevels));
+    need(n >= 0, "hmg_grid_element_vertices: a negative number of codes");
+    if (n == 0) return 0;
+    need(codes != nullptr && nodes != nullptr, "hmg_grid_element_vertices: null array");
+    element_vertices(g->lt.at(level - 1), g->fields.elem.at(level - 1), n, codes, nodes, "hmg_grid_element_vertices");
     HMG_END
 }
 

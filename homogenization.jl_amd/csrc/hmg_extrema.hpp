@@ -13,6 +13,8 @@ namespace hmg {
 constexpr int EX_TAP_A = 11, EX_TAP_B = 8, EX_TAP_C = 4, EX_TAP_AB = 5, EX_TAP_AC = 13, EX_TAP_BC = 10, EX_TAP_S = 1;   // 3D
 constexpr int EX2_TAP_A = 5, EX2_TAP_B = 4, EX2_TAP_S = 1;                                                             // 2D
 constexpr int EX_MAX_THRESHOLDS = 8;
+// hmg_cell_extrema_where: an element's code is slot(p) * 8 + k, k its bit of the element mask; a thread that saw no element holds
+constexpr int EX_NO_CODE = 0x7fffffff;
 
 struct ExtremaThresholds {
     double t[EX_MAX_THRESHOLDS];
@@ -23,13 +25,19 @@ inline int cell_extrema_nrow(int dim) { return dim * (dim + 1) / 2 + dim; }
 
 // LDS of one workgroup: the lattice image with its guard, per wave a maximum, a minimum and the counters
 size_t cell_extrema_lds_bytes(const LevelDev &lv);
+// ... of the located form (codes given): per wave two codes more
+size_t cell_extrema_where_lds_bytes(const LevelDev &lv);
 // the levels served: those whose cell fits the LDS with the image (3D up to 6, 2D up to 8)
 bool cell_extrema_ok(const LevelDev &lv);
 // out[c][0] = max, out[c][1] = min of q over the fine elements of cell c, out[c][2 + j] = number of elements with q > thr.t[j],
 // j < nthr, for the first ncells columns of v (column stride lv.ld).  elem_mask: one byte per slot (ElementTables::mask);
 // rows: cell_extrema_nrow(dim) numbers per cell.  The same bits in every run and for every grid size.
+// codes = nullptr: the kernels of hmg_cell_extrema.  codes given (device, 2 ints per cell): the located instantiations of the
+// same bodies -- out has the same bits, and codes[c][0], codes[c][1] name the elements that hold the maximum and the minimum as
+// slot(p) * 8 + k (p the element's lowest vertex, k its bit of the mask), among equal values (==) the lowest code; -1, -1 where
+// the cell's extrema are NaN.  The same ints in every run, for every grid size and from either kernel family.
 void launch_cell_extrema(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const uint8_t *elem_mask,
-                         const double *rows, const ExtremaThresholds &thr, int nthr, double *out);
+                         const double *rows, const ExtremaThresholds &thr, int nthr, double *out, int *codes = nullptr);
 
 // Cells larger than the LDS (hmg_extrema_window.hip): the same results in the same rows from a rolling window of the LDS -- slabs of
 // k-planes in 3D (st: the level's SlabTables, the lists of k_apply_slab), bands of lattice rows in 2D (closed forms, st unused).
@@ -39,6 +47,7 @@ bool cell_extrema_window_ok(const LevelDev &lv, const SlabTables &st);
 // out[c][0 .. 2 + nthr) for the first ncells columns; throws on a level it cannot address, on nthr outside 0 .. 8, on null bases and
 // on more than 2^31 - 1 cells before any launch; the same bits in every run and for every number of cells
 void launch_cell_extrema_window(const Launch &L, const LevelDev &lv, const SlabTables &st, int64_t ncells, const double *v,
-                                const uint8_t *elem_mask, const double *rows, const ExtremaThresholds &thr, int nthr, double *out);
+                                const uint8_t *elem_mask, const double *rows, const ExtremaThresholds &thr, int nthr, double *out,
+                                int *codes = nullptr);
 
 }  // namespace hmg

@@ -37,25 +37,35 @@ constexpr int EW_NW = EW_NT / 64;
 constexpr int EW_MV = 5;             // values per thread of the slab form's window move (two planes of level 7: 4225 nodes)
 constexpr int EW_HB = 4;             // loads in flight per thread in the load phases
 constexpr int EW_RED = 2 * EW_NW + EW_NW * EX_MAX_THRESHOLDS / 2;   // doubles in front of the window: red [16][2], redc [16][8] ints
+constexpr int EW_REDW = EW_NW;       // located forms: doubles more in front of the window, redw [16][2] ints
 static_assert(RW_NT == EW_NT, "the row bands are those of a 1024-thread workgroup");
 
-__global__ void __launch_bounds__(EW_NT)
-k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *__restrict__ elem_mask,
-                    const double *__restrict__ rows, ExtremaThresholds thr, int nthr, double *__restrict__ out)
+// The bodies of the kernels below.  W = ExtremaWhere is the located form (hmg_cell_extrema_where): the codes slot * 8 + k of the
+// elements that hold maximum and minimum stay in two registers across slabs / bands, like the extrema, and are folded with them,
+// once per cell; every value is formed and picked as in the other form, which this parameter leaves as it was.
+template <class W>
+__device__ __forceinline__ void cell_extrema_slab_body(const LevelDev &lv, const double *v, const SlabTables &st,
+                                                       const uint8_t *__restrict__ elem_mask, const double *__restrict__ rows,
+                                                       const ExtremaThresholds &thr, int nthr, double *__restrict__ out,
+                                                       int *__restrict__ codes)
 {
     constexpr int DIM = 3, NQ = 6, NROW = NQ + DIM, NT = EW_NT, HB = EW_HB, MV = EW_MV;
+    constexpr bool WHERE = std::is_same<W, ExtremaWhere>::value;
     extern __shared__ double smem[];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lv.m;
     double *red = smem;                       // [NW][2]: maximum, minimum
     int *redc = (int *)(red + 2 * EW_NW);     // [NW][EX_MAX_THRESHOLDS]
-    double *img = smem + EW_RED;              // st.lds_nodes doubles: [planes k0-1 .. k1 | zero guard]
+    int *redw = (int *)(smem + EW_RED);       // located form: [NW][2] codes
+    double *img = smem + EW_RED + (WHERE ? EW_REDW : 0);   // st.lds_nodes doubles: [planes k0-1 .. k1 | zero guard]
     const int64_t cell = blockIdx.x;
     const double *vc = v + cell * lv.ld;
     double Q[NQ], X[DIM];
     extrema_row<DIM>(rows + cell * NROW, Q, X);
     ExtremaAcc acc;
     acc.reset();
+    W wh;
+    if constexpr (WHERE) wh.reset();
     auto plane_off = [&](int k) {   // PO(k) = number of lattice nodes in planes < k
         if (k <= 0) return 0;
         if (k > m + 1) k = m + 1;
@@ -121,6 +131,7 @@ k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *
             const int e = it * NT + tid;
             const uint32_t pw = p0;
             const unsigned mk = ms;
+            const int slot = s0;
             p0 = p1;
             s0 = s1;
             ms = elem_mask[s0];
@@ -129,7 +140,10 @@ k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *
             if (e < cp_surf && mk != 0) {                           // (mk == 0: no element has its lowest vertex here)
                 int L, len, A, B, cls, k;
                 decode32w(pw, m, L, len, A, B, cls, k);
-                extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc);
+                if constexpr (WHERE)
+                    extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc, slot, &wh);
+                else
+                    extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc);
             }
         }
         const int n_int = cp_cnt - cp_surf;
@@ -138,6 +152,7 @@ k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *
             const int e = it * NT + tid;
             const uint32_t pw = q0;
             const unsigned mk = mi;
+            const int slot = t0;
             q0 = q1;
             t0 = t1;
             mi = elem_mask[t0];
@@ -146,12 +161,34 @@ k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *
             if (e < n_int && mk != 0) {
                 int L, len, A, B;
                 decode_lattice(pw, m, L, len, A, B);
-                extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc);
+                if constexpr (WHERE)
+                    extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc, slot, &wh);
+                else
+                    extrema_node<DIM>(xs, L, len, A, B, lo, whi, mk, Q, X, thr, nthr, acc);
             }
         }
         lo_prev = lo;
     }
-    extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell);
+    if constexpr (WHERE)
+        extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell, &wh, redw, codes);
+    else
+        extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell);
+}
+
+__global__ void __launch_bounds__(EW_NT)
+k_cell_extrema_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *__restrict__ elem_mask,
+                    const double *__restrict__ rows, ExtremaThresholds thr, int nthr, double *__restrict__ out)
+{
+    cell_extrema_slab_body<ExtremaNoWhere>(lv, v, st, elem_mask, rows, thr, nthr, out, nullptr);
+}
+
+// the located form of k_cell_extrema_slab
+__global__ void __launch_bounds__(EW_NT)
+k_extrema_where_slab(LevelDev lv, const double *v, SlabTables st, const uint8_t *__restrict__ elem_mask,
+                     const double *__restrict__ rows, ExtremaThresholds thr, int nthr, double *__restrict__ out,
+                     int *__restrict__ codes)
+{
+    cell_extrema_slab_body<ExtremaWhere>(lv, v, st, elem_mask, rows, thr, nthr, out, codes);
 }
 
 // Row of lattice position L (0 <= L < nf), as rows_row_of, without its loops.  RO(j) <= L is j^2 - b j + 2 L >= 0, b = 2 m + 3, so
@@ -178,23 +215,28 @@ __device__ __forceinline__ int rows_slot_at(int m, int L, int j, int nei, int of
     return rows_slot(m, i, j, nei, off_int, cls);
 }
 
-__global__ void __launch_bounds__(EW_NT)
-k_cell_extrema_rows(LevelDev lv, const double *v, const uint8_t *__restrict__ elem_mask, const double *__restrict__ rows,
-                    ExtremaThresholds thr, int nthr, double *__restrict__ out)
+template <class W>
+__device__ __forceinline__ void cell_extrema_rows_body(const LevelDev &lv, const double *v, const uint8_t *__restrict__ elem_mask,
+                                                       const double *__restrict__ rows, const ExtremaThresholds &thr, int nthr,
+                                                       double *__restrict__ out, int *__restrict__ codes)
 {
     constexpr int DIM = 2, NQ = 3, NROW = NQ + DIM, NT = EW_NT, HB = EW_HB;
+    constexpr bool WHERE = std::is_same<W, ExtremaWhere>::value;
     extern __shared__ double smem[];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lv.m, nei = lv.nei, off_int = lv.off_int;
     double *red = smem;                       // [NW][2]: maximum, minimum
     int *redc = (int *)(red + 2 * EW_NW);     // [NW][EX_MAX_THRESHOLDS]
-    double *img = smem + EW_RED;              // RW_WIN doubles: [rows j0-1 .. j1 | zero guard]
+    int *redw = (int *)(smem + EW_RED);       // located form: [NW][2] codes
+    double *img = smem + EW_RED + (WHERE ? EW_REDW : 0);   // RW_WIN doubles: [rows j0-1 .. j1 | zero guard]
     const int64_t cell = blockIdx.x;
     const double *vc = v + cell * lv.ld;
     double Q[NQ], X[DIM];
     extrema_row<DIM>(rows + cell * NROW, Q, X);
     ExtremaAcc acc;
     acc.reset();
+    W wh;
+    if constexpr (WHERE) wh.reset();
 
     int lo_prev = 0;
     for (int j0 = 0, j1 = 0; j0 <= m; j0 = j1) {
@@ -243,29 +285,57 @@ k_cell_extrema_rows(LevelDev lv, const double *v, const uint8_t *__restrict__ el
         // rows [j0, j1): the node's row and its mask are formed one trip ahead of use (a trip behind the band's end repeats its last
         // node: every mask load is unconditional and inside the level's mask)
         const int e0 = rows_ro(m, j0), ecnt = rows_ro(m, j1) - e0;
-        auto node_at = [&](int e, int &L, int &j, unsigned &mk) {
+        auto node_at = [&](int e, int &L, int &j, unsigned &mk, int &slot) {
             L = e0 + min(e, ecnt - 1);
             j = rows_row_near(m, L);
-            mk = elem_mask[rows_slot_at(m, L, j, nei, off_int)];
+            slot = rows_slot_at(m, L, j, nei, off_int);
+            mk = elem_mask[slot];
         };
-        int Ln, jn;
+        int Ln, jn, sn;                                             // (sn: the located form alone reads it)
         unsigned mkn;
-        node_at(tid, Ln, jn, mkn);
+        node_at(tid, Ln, jn, mkn, sn);
         __syncthreads();
         for (int q0 = 0; q0 < ecnt; q0 += NT) {
             const int e = q0 + tid, L = Ln, j = jn;
             const unsigned mk = mkn;
-            node_at(e + NT, Ln, jn, mkn);
-            if (e < ecnt && mk != 0) extrema_node<DIM>(xs, L, m + 1 - j, 0, 0, lo, whi, mk, Q, X, thr, nthr, acc);
+            const int slot = sn;
+            node_at(e + NT, Ln, jn, mkn, sn);
+            if (e < ecnt && mk != 0) {
+                if constexpr (WHERE)
+                    extrema_node<DIM>(xs, L, m + 1 - j, 0, 0, lo, whi, mk, Q, X, thr, nthr, acc, slot, &wh);
+                else
+                    extrema_node<DIM>(xs, L, m + 1 - j, 0, 0, lo, whi, mk, Q, X, thr, nthr, acc);
+            }
         }
         lo_prev = lo;
     }
-    extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell);
+    if constexpr (WHERE)
+        extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell, &wh, redw, codes);
+    else
+        extrema_fold<EW_NW>(acc, nthr, wave, red, redc, out, cell);
 }
 
-size_t slab_lds_bytes(const SlabTables &st) { return sizeof(double) * ((size_t)EW_RED + (size_t)st.lds_nodes); }
+__global__ void __launch_bounds__(EW_NT)
+k_cell_extrema_rows(LevelDev lv, const double *v, const uint8_t *__restrict__ elem_mask, const double *__restrict__ rows,
+                    ExtremaThresholds thr, int nthr, double *__restrict__ out)
+{
+    cell_extrema_rows_body<ExtremaNoWhere>(lv, v, elem_mask, rows, thr, nthr, out, nullptr);
+}
 
-constexpr size_t rows_lds_bytes() { return sizeof(double) * ((size_t)EW_RED + (size_t)RW_WIN); }
+// the located form of k_cell_extrema_rows
+__global__ void __launch_bounds__(EW_NT)
+k_extrema_where_rows(LevelDev lv, const double *v, const uint8_t *__restrict__ elem_mask, const double *__restrict__ rows,
+                     ExtremaThresholds thr, int nthr, double *__restrict__ out, int *__restrict__ codes)
+{
+    cell_extrema_rows_body<ExtremaWhere>(lv, v, elem_mask, rows, thr, nthr, out, codes);
+}
+
+size_t slab_lds_bytes(const SlabTables &st, bool where = false)
+{
+    return sizeof(double) * ((size_t)EW_RED + (where ? EW_REDW : 0) + (size_t)st.lds_nodes);
+}
+
+constexpr size_t rows_lds_bytes(bool where = false) { return sizeof(double) * ((size_t)EW_RED + (where ? EW_REDW : 0) + (size_t)RW_WIN); }
 
 // the layout and packed-word ranges k_cell_extrema_slab relies on (those of the slab moment kernel, without its class table)
 bool slab_ok(const LevelDev &lv, const SlabTables &st)
@@ -273,7 +343,7 @@ bool slab_ok(const LevelDev &lv, const SlabTables &st)
     if (!st.head || !st.ld_word || !st.cp_word || !st.cp_slot || st.nslab < 1 || st.lds_nodes <= 0) return false;
     // the packed words (L and the slot in 16 bits each, i, j, k in 7 bits each) hold this level's values; two planes fit the move
     if (lv.m < 1 || lv.m > 127 || lv.nf > 0x10000 || (lv.m + 1) * (lv.m + 1) > EW_MV * EW_NT) return false;
-    return slab_lds_bytes(st) <= LDS_PER_CU;
+    return slab_lds_bytes(st, true) <= LDS_PER_CU;          // (either form: both serve the same levels)
 }
 
 // ... and k_cell_extrema_rows (those of the row-band moment kernel: the storage order rows_slot assumes, the window of the widest band)
@@ -282,7 +352,7 @@ bool rows_ok(const LevelDev &lv)
     if (lv.ncorner != 3 || lv.nedge != 3 || lv.nface != 0) return false;
     if (lv.m < 2 || lv.m > 1024 || lv.nei != lv.m - 1 || lv.off_int != 3 + 3 * lv.nei || lv.nf != rows_ro(lv.m, lv.m + 1)) return false;
     if (rows_ro(lv.m, 3) + RW_GUARD > RW_WIN || 2 * (lv.m + 1) > RW_MV * RW_NT) return false;
-    return 2 * rows_lds_bytes() <= LDS_PER_CU;
+    return 2 * rows_lds_bytes(true) <= LDS_PER_CU;          // (either form)
 }
 
 template <class K, class... Args>
@@ -302,7 +372,8 @@ bool cell_extrema_window_ok(const LevelDev &lv, const SlabTables &st)
 }
 
 void launch_cell_extrema_window(const Launch &L, const LevelDev &lv, const SlabTables &st, int64_t ncells, const double *v,
-                                const uint8_t *elem_mask, const double *rows, const ExtremaThresholds &thr, int nthr, double *out)
+                                const uint8_t *elem_mask, const double *rows, const ExtremaThresholds &thr, int nthr, double *out,
+                                int *codes)
 {
     if (lv.dim != 2 && lv.dim != 3) throw std::runtime_error("cell extrema (window): not a 2D or 3D level");
     if (!cell_extrema_window_ok(lv, st))
@@ -312,8 +383,12 @@ void launch_cell_extrema_window(const Launch &L, const LevelDev &lv, const SlabT
     if (!v || !elem_mask || !rows || !out) throw std::runtime_error("cell extrema (window): null device pointer");
     if (ncells <= 0) return;
     if (ncells > 0x7fffffffLL) throw std::runtime_error("cell extrema (window): too many cells for one launch");
-    if (lv.dim == 3)
+    if (lv.dim == 3 && codes)
+        launch_cells(k_extrema_where_slab, slab_lds_bytes(st, true), L, ncells, lv, v, st, elem_mask, rows, thr, nthr, out, codes);
+    else if (lv.dim == 3)
         launch_cells(k_cell_extrema_slab, slab_lds_bytes(st), L, ncells, lv, v, st, elem_mask, rows, thr, nthr, out);
+    else if (codes)
+        launch_cells(k_extrema_where_rows, rows_lds_bytes(true), L, ncells, lv, v, elem_mask, rows, thr, nthr, out, codes);
     else
         launch_cells(k_cell_extrema_rows, rows_lds_bytes(), L, ncells, lv, v, elem_mask, rows, thr, nthr, out);
 }

@@ -142,6 +142,10 @@ struct ElementTables {
 // (slot, bit) are not exactly that list, where their number is not 2^(dim (level - 1)), or where the taps are not those the
 // kernel was written for (hmg_extrema.hpp).
 ElementTables build_element_tables(const LevelTables &T);
+// n codes slot(p) * 8 + k -> nodes[(dim + 1) * n]: the element's vertices p, p + pi1, p + pi1 + pi2, p + s as 0-based hierarchical
+// node ids, pi the permutation bit k of the mask names.  Throws, naming `who` and the first offender, on a slot out of range or a
+// clear mask bit.  Host tables only.
+void element_vertices(const LevelTables &T, const ElementTables &E, int64_t n, const int32_t *codes, int32_t *nodes, const char *who);
 
 // ---------------------------------------------------------------------------------------------
 // Base-mesh tables.

@@ -269,6 +269,8 @@ struct hmg_ctx {
     int64_t moments_kernel_ns = 0, moments_download_ns = 0;   // the last hmg_cell_moments: its kernel (device events) and the download of its sums (host clock)
     int64_t pair_moments_kernel_ns = 0, pair_moments_download_ns = 0;   // the last hmg_cell_pair_moments, likewise
     int64_t extrema_kernel_ns = 0;           // the last hmg_cell_extrema: its kernel (device events)
+    int64_t extrema_where_kernel_ns = 0;     // the last hmg_cell_extrema_where, likewise: a counter of its own, so that one process times both
+    int64_t extrema_where_launches = 0;      // launches of the located kernels (hmg_ctx_counter "cell_extrema_where_launches")
     int64_t sample_launches = 0;             // launches of k_sample (hmg_sample, hmg_sample_raster)
     int64_t sample_kernel_ns = 0, sample_download_ns = 0;   // the last of those calls: its kernel (device events), its downloads (host clock)
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window

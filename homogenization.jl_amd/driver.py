@@ -643,7 +643,8 @@ def _large_cells(ctx, on: bool):
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                              fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
-                             large_cells: bool = False, extrema: bool = False, thresholds=None, slices=None):
+                             large_cells: bool = False, extrema: bool = False, thresholds=None, slices=None,
+                             locations: bool = False):
     """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
     a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
     moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
@@ -667,6 +668,11 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     "min_energy_density" (Ne each: the extrema of grad u . sigma_c grad u in every cell), "concentration" = peak / energy_form and,
     with `thresholds` (up to 8 multiples of energy_form), "exceedance" (Ne, nthr): the volume of every cell on which the energy
     density exceeds each; they are in the returned dict with or without `fields`, and with `save` in the file.
+    `locations` (with `extrema`): the same pass also says where (api.cell_extrema_where; every other entry keeps its bits):
+    "peak_location" and "min_location" (Ne, dim), the centroids of the fine elements that hold each cell's extrema (NaN for a cell
+    whose extrema are NaN), and "hot_spots", the ten cells of highest peak, highest first (fields.hot_spots): a dict of "cell",
+    "value", "point" and "sampled" -- the energy density of u sampled at each point on the device (api.sample), which is the
+    value again up to rounding; with `save` the peaks also go to `save`_peaks.vtu as a point cloud (vtk.export_points).
     `slices`: a list of rasters (origin, du, dv, nu, nv) -- pixel (a, b) at origin + a du + b dv --; u = xi.x + v is sampled on each
     from the converged corrector on the device (api.sample_raster; any top level) and "slices" in the returned dict is a list of
     dicts with "value", "cell" (nv, nu), "gradient", "flux" (nv, nu, dim) and "energy_density" (nv, nu), NaN / -1 outside the
@@ -707,12 +713,26 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     peaks = {}
     if extrema:
         thr = np.zeros(0) if thresholds is None else np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        call = api.cell_extrema_where if locations else api.cell_extrema
         with _large_cells(ctx, large_cells):
-            qmax, qmin, counts = api.cell_extrema(xv, implicit, xi, cell_fields.energy_form(cond), thr * out["energy_form"])
+            qmax, qmin, counts, *where = call(xv, implicit, xi, cell_fields.energy_form(cond), thr * out["energy_form"])
         peaks = {"peak_energy_density": qmax, "min_energy_density": qmin,
                  "concentration": cell_fields.concentration(qmax, out["energy_form"])}
         if thr.size:
             peaks["exceedance"] = cell_fields.exceedance_volume(counts, vol, api.fine_elements(implicit, total_grids))
+        if locations:
+            cells = np.arange(qmax.shape[0])
+            peaks["peak_location"] = cell_fields.element_centroids(implicit, total_grids, cells, where[0])
+            peaks["min_location"] = cell_fields.element_centroids(implicit, total_grids, cells, where[1])
+            hc, hv, hp = cell_fields.hot_spots(qmax, where[0], implicit, total_grids, k=10)
+            here = ~np.isnan(hp).any(axis=1)
+            sampled = np.full(hc.shape[0], np.nan)
+            if here.any():
+                s = api.sample(xv, implicit, hp[here], xi=xi, value=False)
+                sampled[here] = cell_fields.sample_energy_density(cond, s["cell"], s["gradient"])
+            out["hot_spots"] = {"cell": hc, "value": hv, "point": hp, "sampled": sampled}
+            if save is not None:
+                vtk.export_points(f"{save}_peaks", peaks["peak_location"], {"peak_energy_density": qmax, "cell": cells})
         out.update(peaks)
     if slices is not None:
         out["slices"] = []

@@ -185,3 +185,48 @@ def line_points(p0, p1, n):
         raise ValueError("a line takes at least its two ends")
     t = np.linspace(0.0, 1.0, int(n))[:, None]
     return (1.0 - t) * p0 + t * p1
+
+
+def element_points(implicit, level, cells, nodes):
+    """Physical coordinates of named vertices of fine elements: cells (n,) coarse cell ids, nodes (n, d + 1) 0-based hierarchical
+    node ids of `level` (api.cell_extrema_where's where_max / where_min, api.locate's nodes) -> (n, d + 1, d).  Formed from the
+    base mesh's corners of those cells and the level's reference positions of those vertices only -- never the whole fine grid.
+    A vertex id of -1 (a cell without a location: NaN extrema) gives NaN."""
+    base = implicit.base
+    d = base.dim
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1)
+    nodes = np.asarray(nodes, dtype=np.int64)
+    if nodes.ndim != 2 or nodes.shape[0] != cells.shape[0]:
+        raise ValueError(f"nodes {nodes.shape} does not fit {cells.shape[0]} cells")
+    nf = implicit.nf(level)
+    if cells.size and (cells.min() < 0 or cells.max() >= implicit.ncells()):
+        raise ValueError("a cell id is not a current cell of the grid")
+    if nodes.size and (nodes.min() < -1 or nodes.max() >= nf):
+        raise ValueError(f"a node id is not a node of level {level}")
+    m = 2 ** (level - 1)
+    h2s = implicit.table_i32("hier2slot", level)
+    ijk = implicit.table_i32("slot_ijk", level).reshape(-1, 3)
+    ok = nodes >= 0
+    ref = ijk[h2s[np.where(ok, nodes, 0)]][..., :d].astype(np.float64) / m        # (n, d + 1, d) reference coordinates
+    X = np.asarray(base.nodes, dtype=np.float64)[np.asarray(base.elements)[cells] - 1]   # (n, d + 1, d) corners
+    J = X[:, 1:, :] - X[:, :1, :]
+    out = X[:, :1, :] + np.einsum("nva,nac->nvc", ref, J)
+    out[~ok] = np.nan
+    return out
+
+
+def element_centroids(implicit, level, cells, nodes):
+    """The centroids of those elements, (n, d): interior points of the elements (api.locate finds the element again)."""
+    return element_points(implicit, level, cells, nodes).mean(axis=1)
+
+
+def hot_spots(qmax, where_max, implicit, level, k=10):
+    """The k cells with the highest qmax (api.cell_extrema_where), highest first, equal values by ascending cell id, NaN last:
+    (cells (k,) int64, values (k,), centroids (k, d) of the elements that hold them)."""
+    q = np.asarray(qmax, dtype=np.float64).reshape(-1)
+    w = np.asarray(where_max)
+    if w.ndim != 2 or w.shape[0] != q.shape[0]:
+        raise ValueError(f"where_max {w.shape} does not fit {q.shape[0]} cells")
+    key = np.where(np.isnan(q), -np.inf, q)
+    order = np.lexsort((np.arange(q.shape[0]), np.isnan(q), -key))[:max(int(k), 0)]
+    return order.astype(np.int64), q[order], element_centroids(implicit, level, order, w[order])

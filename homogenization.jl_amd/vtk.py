@@ -13,7 +13,7 @@ import base64
 
 import numpy as np
 
-_VTK_TYPE = {3: 5, 4: 10}     # triangle, tetrahedron
+_VTK_TYPE = {1: 1, 3: 5, 4: 10}     # vertex, triangle, tetrahedron
 _NAMES = {np.dtype("float64"): "Float64", np.dtype("int64"): "Int64", np.dtype("uint8"): "UInt8",
           np.dtype("int32"): "Int32"}
 
@@ -189,3 +189,21 @@ def export_slice(name, origin, du, dv, sampled):
     a = np.arange(nu, dtype=np.float64)[None, :, None]
     b = np.arange(nv, dtype=np.float64)[:, None, None]
     return write_vts(name, origin + a * du + b * dv, sampled)
+
+
+def export_points(name, points, point_data=None):
+    """A point cloud as a .vtu of vertex cells: points (n, dim), point_data name -> (n,) / (n, c).  The peaks of
+    api.cell_extrema_where (fields.element_centroids) open in ParaView next to export_cell_fields' mesh.  Points with a NaN
+    coordinate (cells without a location) are left out, with their data."""
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] not in (2, 3):
+        raise ValueError(f"points must have shape (n, dim), not {points.shape}")
+    keep = ~np.isnan(points).any(axis=1)
+    data = {}
+    for key, a in (point_data or {}).items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape[0] != points.shape[0] or a.ndim > 2:
+            raise ValueError(f"point data {key!r}: {a.shape} does not fit {points.shape[0]} points")
+        data[key] = a[keep]
+    pts = points[keep]
+    return write_vtu(name, pts, np.arange(pts.shape[0], dtype=np.int64)[:, None], point_data=data)

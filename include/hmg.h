@@ -459,6 +459,38 @@ int hmg_cell_extrema(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NUL
                      double *out /* host, (2 + nthr)*ncells */);
 int64_t hmg_grid_fine_elements(const hmg_grid *grid, int level);   /* 2^(dim (level-1)); host-only grid too; -1: null grid or bad level */
 
+/* ---- ... and WHERE: the fine elements that hold the maximum and the minimum ---------------------------------------------
+ * hmg_cell_extrema_where is hmg_cell_extrema with one more result.  out is what hmg_cell_extrema writes for the same arguments,
+ * bit for bit: the values come from the same evaluation and are picked by the same comparisons, whatever the locations are.
+ * where[c * 2 (dim + 1) ..]: the dim + 1 vertices of the element that attains max_T q_T of cell c, then the dim + 1 vertices of
+ * the element that attains min_T q_T.  Vertices are 0-based HIERARCHICAL node ids -- rows of hmg_vec_download's matrix, the
+ * convention of hmg_grid_locate's nodes -- in the element's own order p, p + pi1, p + pi1 + pi2, p + s (2D: p, p + pi1, p + s): p
+ * the lexicographically lowest vertex in the lattice coordinates "slot_ijk", pi the permutation of the lattice basis a, b, c
+ * ("elem_dirs") that the element's bit k of "elem_mask" names, s = a + b + c.  3D k = 0 .. 5: (a,b,c), (a,c,b), (b,a,c), (b,c,a),
+ * (c,a,b), (c,b,a); 2D k = 0, 1: (a,b), (b,a).
+ * Ties: elements tie when their values are equal (==: +0 and -0 tie, and then out may carry the sign of another element of the
+ * tie than the one reported, as hmg_cell_extrema's does).  Among tied elements the one with the LOWEST CODE slot(p) * 8 + k is
+ * reported, slot(p) the storage slot of p (table "hier2slot").  The rule refers to nothing but the values and the grid's tables:
+ * the same ints for every launch shape, number of cells, kernel family ("cell_extrema_windows") and run.
+ * NaN: a cell whose extrema are NaN (the rule of hmg_cell_extrema) has -1 in all 2 (dim + 1) entries; other cells are not
+ * touched.  An infinite q_T is a value like any other and has a location.  Level 1: one element per cell, both locations are it.
+ * The same single pass: 8 B/DOF and one launch, the codes ride next to the running extrema in registers and through the folds;
+ * 8 bytes more per cell come back, and the host turns the codes into vertices with hmg_grid_element_vertices' decode.
+ * Served and refused exactly as hmg_cell_extrema -- the option "cell_extrema_windows" (3D level 7, 2D levels 9-11), partitioned
+ * grids (local cells, where indexed by local cell), shrunk grids (current cells), every argument check, in messages that name
+ * this call -- and a null where is refused too.  hmg_ctx_counter "cell_extrema_where_launches" counts its launches (a window
+ * launch counts in "cell_extrema_window_launches" as well), "cell_extrema_where_kernel_ns" is the last call's kernel time;
+ * "cell_extrema_kernel_ns" stays that of the last hmg_cell_extrema.
+ *
+ * hmg_grid_element_vertices: n codes slot * 8 + k of `level` -> nodes[(dim + 1) * n], the vertices as above.  Host tables only: it
+ * works on a grid without a device context.  A code whose slot is out of range (negative codes too) or whose bit k of the slot's
+ * mask is clear is refused with a message naming the first such code; nothing is promised about nodes then.  n = 0: success. */
+int hmg_cell_extrema_where(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
+                           const double *form /* nq*ncells, or NULL */, int nthr, const double *thresholds /* nthr, or NULL */,
+                           double *out /* host, (2 + nthr)*ncells */, int32_t *where /* host, 2*(dim+1)*ncells */);
+int hmg_grid_element_vertices(const hmg_grid *grid, int level, int64_t n, const int32_t *codes /* n */,
+                              int32_t *nodes /* (dim+1)*n: 0-based HIERARCHICAL row ids */);
+
 /* ---- sampling a level vector at points and on raster slices (no counterpart in the reference) --------------------------
  * For a point x of physical space, a level and a level vector v of that level, as stored (no interface sum, no mask):
  *   cell      the current coarse cell (the prefix after hmg_grid_shrink) that contains x: all barycentric coordinates of x in it

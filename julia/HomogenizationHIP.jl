@@ -392,6 +392,31 @@ function cell_extrema(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} =
                 nthr == 0 ? C_NULL : collect(Float64, thresholds), out))
     (out[1, :], out[2, :], round.(Int64, out[3:end, :]))
 end
+# ... and where (hmg_cell_extrema_where; api.cell_extrema_where): the same three results, bit for bit, and the vertices of the fine
+# elements that hold each cell's maximum and minimum, (dim+1) x Ne each, 0-BASED hierarchical node ids (add 1 for rows of Matrix(v);
+# the convention of locate) in the element's own order p, p+π₁, p+π₁+π₂, p+s.  Among elements of equal value the one with the lowest
+# code slot(p)*8 + k is reported: the same ints for every launch shape, kernel family and run.  A cell whose extrema are NaN has -1.
+# element_vertices (hmg_grid_element_vertices; host, a grid without a context too) turns such codes into vertices, (dim+1) x n.
+grid_dim(::HipGrid{dim}) where {dim} = dim
+function cell_extrema_where(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                            form::Union{Nothing,AbstractMatrix{Float64}} = nothing, thresholds::AbstractVector{Float64} = Float64[])
+    g = v.grid
+    nthr = length(thresholds)
+    nv = grid_dim(g) + 1
+    out = zeros(Float64, 2 + nthr, ncells(g))
+    where = zeros(Int32, nv, 2, ncells(g))
+    check(ccall((:hmg_cell_extrema_where, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), form === nothing ? C_NULL : Matrix{Float64}(form), nthr,
+                nthr == 0 ? C_NULL : collect(Float64, thresholds), out, where))
+    (out[1, :], out[2, :], round.(Int64, out[3:end, :]), where[:, 1, :], where[:, 2, :])
+end
+function element_vertices(g::HipGrid{dim}, level::Integer, codes::AbstractVector{<:Integer}) where {dim}
+    c = collect(Int32, codes)
+    nodes = zeros(Int32, dim + 1, length(c))
+    check(ccall((:hmg_grid_element_vertices, LIB), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Int32}), g.h, level, length(c), c, nodes))
+    nodes
+end
 # Point samples of a level vector (hmg_grid_locate, hmg_sample, hmg_sample_raster; api.locate / sample / sample_raster): points is
 # dim x n.  locate (host, a grid without a context too): cell (n; -1: none), nodes ((dim+1) x n, 0-BASED hierarchical ids: add 1 for
 # rows of Matrix(v)), weights ((dim+1) x n), gweights (dim x (dim+1) x n).  sample / sample_raster: u = ξ⋅x + v, its gradient

@@ -26,6 +26,9 @@ energy density (one solve, the moment pass, then the pass over the fine elements
 ("cell_moments_kernel_ns", "cell_extrema_kernel_ns").  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D; with --large-cells
 (the driver's keyword large_cells=True) 3D level 7 and 2D levels 9-11 too, through the window kernels of both passes: the line then
 carries "cell_moments_window_launches" and "cell_extrema_window_launches".
+--locations (with --extrema): the driver's keyword locations=True -- the pass also reports which fine element holds each cell's
+peak (hmg_cell_extrema_where); the ten hottest spots are printed in front of the line (cell, peak over the homogenized energy
+density, position, the energy density sampled there), and the line carries "cell_extrema_where_kernel_ns" instead.
 --slice N: driver.dirichlet_homogenization on hypercube(n) with slices=[one axis-aligned N x N raster through the middle of the
 domain] (one solve, the moment pass, then hmg_sample_raster with the flux and the energy density per pixel): one line with the wall
 time of a run after --warmup untimed ones, the pixels inside the domain, the largest sampled energy density over the homogenized
@@ -57,6 +60,7 @@ ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficie
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
 ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor or --extrema: per-cell passes of cells larger than the LDS")
 ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
+ap.add_argument("--locations", action="store_true", help="with --extrema: where the peaks sit; prints the ten hottest spots")
 ap.add_argument("--slice", type=int, default=0, metavar="N", help="the Dirichlet driver with one axis-aligned N x N slice through the "
                 "middle of the domain: wall time, sampling counters")
 ap.add_argument("--uniaxial", action="store_true", help="the uniaxial tensor driver on hypercube(n): wall time, cycles, tensor")
@@ -114,7 +118,8 @@ if a.extrema:
         sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
     xi = np.ones(a.dim) / np.sqrt(a.dim)
     kw = dict(refinements=a.refinements, xi=xi, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate,
-              smoother=a.smoother, extrema=True, thresholds=[1.0, 2.0, 4.0], fields=True, large_cells=a.large_cells)
+              smoother=a.smoother, extrema=True, thresholds=[1.0, 2.0, 4.0], fields=True, large_cells=a.large_cells,
+              locations=a.locations)
     for _ in range(a.warmup):
         driver.dirichlet_homogenization(a.n, tag, **kw)
     ctx.sync()
@@ -122,15 +127,23 @@ if a.extrema:
     r = driver.dirichlet_homogenization(a.n, tag, **kw)
     ctx.sync()
     wall = time.perf_counter() - t0
+    if a.locations:
+        h = r["hot_spots"]
+        for c, val, pt, smp in zip(h["cell"], h["value"], h["point"], h["sampled"]):
+            print(f"hot spot: cell {int(c):7d}  peak / mean {val / r['energy_form']:10.4f}  at ({', '.join(f'{x:.6f}' for x in pt)})  "
+                  f"sampled there / mean {smp / r['energy_form']:10.4f}")
     print(json.dumps({"config": f"dirichlet_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}, "
-                                f"extrema=True{', large_cells=True' if a.large_cells else ''})",
+                                f"extrema=True{', large_cells=True' if a.large_cells else ''}"
+                                f"{', locations=True' if a.locations else ''})",
                       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
                       "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
                       "energy_form": r["energy_form"], "max_concentration": float(r["concentration"].max()),
                       "min_energy_density_over_mean": float(r["min_energy_density"].min() / r["energy_form"]),
                       "exceedance_fraction_at_1_2_4": (r["exceedance"].sum(axis=0) / r["volume"]).tolist(),
                       "cell_moments_kernel_ns": ctx.counter("cell_moments_kernel_ns"),
-                      "cell_extrema_kernel_ns": ctx.counter("cell_extrema_kernel_ns"), "large_cells": a.large_cells,
+                      ("cell_extrema_where_kernel_ns" if a.locations else "cell_extrema_kernel_ns"):
+                          ctx.counter("cell_extrema_where_kernel_ns" if a.locations else "cell_extrema_kernel_ns"),
+                      "large_cells": a.large_cells,
                       "cell_moments_window_launches": ctx.counter("cell_moments_window_launches"),
                       "cell_extrema_window_launches": ctx.counter("cell_extrema_window_launches")}))
     sys.exit(0)
