@@ -58,6 +58,9 @@ SIGNATURES = {
     "hmg_grid_shrink": (c_int, [vp, c_i64, c_i64]),
     "hmg_grid_set_dirichlet_faces": (c_int, [vp, c_i64, p_i64]),
     "hmg_grid_dirichlet_faces": (c_i64, [vp, p_i64, c_i64]),
+    "hmg_grid_create_periodic": (c_int, [vp, c_int, c_int, c_i64, p_f64, c_i64, p_i64, p_f64, pp]),
+    "hmg_grid_set_mean_free": (c_int, [vp, c_int]),
+    "hmg_grid_mean_free": (c_int, [vp]),
     "hmg_grid_reserve_spare": (c_int, [vp, c_int]),
     "hmg_grid_set_smoother": (c_int, [vp, c_int]),
     "hmg_grid_smoother": (c_int, [vp]),
@@ -128,6 +131,8 @@ SIGNATURES = {
     "hmg_grid_use_comm": (c_int, [vp]),
     "hmg_checkerboard_mesh_size": (c_int, [c_int, p_i64, p_i64, p_i64]),
     "hmg_checkerboard_mesh": (c_int, [c_int, p_i64, p_f64, c_int, c_int, p_f64, p_i64]),
+    "hmg_periodic_mesh_size": (c_int, [c_int, p_i64, p_i64, p_i64]),
+    "hmg_periodic_mesh": (c_int, [c_int, p_i64, p_f64, p_i64]),
     "hmg_block_owner": (c_int, [c_int, c_i64, p_f64, c_i64, p_i64, p_i64, c_f64, p_f64, p_i32]),
     "hmg_conductivity_per_element": (c_int, [c_int, c_i64, p_f64, c_i64, p_i64, p_i64, p_f64, p_f64, p_f64]),
     "hmg_grid_create_partition": (c_int, [vp, c_int, c_int, c_i64, p_f64, c_i64, p_i64, p_i32, c_int, c_int, pp]),

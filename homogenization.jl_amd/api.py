@@ -44,10 +44,28 @@ class Mesh:
     each row ascending (src/implicit_fine_grid.jl:14)."""
     nodes: np.ndarray
     elements: np.ndarray
+    period: np.ndarray | None = None
+    """box length per axis of a mesh on a torus (hmg_grid_create_periodic): the elements name torus nodes, `nodes` holds one
+    representative position each; None: an ordinary mesh"""
 
     @property
     def dim(self):
         return self.nodes.shape[1]
+
+    def cell_corners(self, cells=None):
+        """Corner positions of the cells (all, or those of an index array), (n, dim + 1, dim).  On a torus the corners are unwrapped
+        relative to the cell's first corner by the minimal image, p0 + (p - p0 - period rint((p - p0) / period)) -- the library's
+        rule --, so a cell that straddles the box comes out in one piece, possibly past the far side."""
+        el = np.asarray(self.elements, dtype=np.int64)
+        if cells is not None:
+            el = el[cells if isinstance(cells, slice) else np.asarray(cells)]
+        x = np.asarray(self.nodes, dtype=np.float64)[el - 1]
+        if self.period is None:
+            return x
+        per = np.asarray(self.period, dtype=np.float64)
+        d = x - x[:, :1, :]
+        d -= per * np.rint(d / per)
+        return x[:, :1, :] + d
 
 
 def pack_sigmas(sigmas, ncells, dim):
@@ -184,9 +202,17 @@ class ImplicitFineGrid:
         nodes = np.ascontiguousarray(base.nodes, dtype=np.float64)
         cells = np.ascontiguousarray(base.elements, dtype=np.int64)
         h = ctypes.c_void_p()
-        L.check(self._lib.hmg_grid_create(ctx.h if ctx else None, base.dim, levels, nodes.shape[0],
-                                          nodes.ctypes.data_as(L.p_f64), cells.shape[0],
-                                          cells.ctypes.data_as(L.p_i64), ctypes.byref(h)))
+        if getattr(base, "period", None) is not None:   # a grid on a torus (include/hmg.h: hmg_grid_create_periodic)
+            per = np.ascontiguousarray(base.period, dtype=np.float64).reshape(-1)
+            if per.size != base.dim:
+                raise ValueError(f"period must have one entry per axis ({base.dim}), not {per.size}")
+            L.check(self._lib.hmg_grid_create_periodic(ctx.h if ctx else None, base.dim, levels, nodes.shape[0],
+                                                       nodes.ctypes.data_as(L.p_f64), cells.shape[0],
+                                                       cells.ctypes.data_as(L.p_i64), per.ctypes.data_as(L.p_f64), ctypes.byref(h)))
+        else:
+            L.check(self._lib.hmg_grid_create(ctx.h if ctx else None, base.dim, levels, nodes.shape[0],
+                                              nodes.ctypes.data_as(L.p_f64), cells.shape[0],
+                                              cells.ctypes.data_as(L.p_i64), ctypes.byref(h)))
         self.h = h
         self._fin = weakref.finalize(self, self._lib.hmg_grid_destroy, h)   # (vectors keep the grid alive, the grid the ctx)
 
@@ -263,6 +289,16 @@ class ImplicitFineGrid:
         out = np.zeros((n, self.base.dim), dtype=np.int64)
         self._lib.hmg_grid_dirichlet_faces(self.h, out.ctypes.data_as(L.p_i64), out.size)
         return out
+
+    def set_mean_free(self, on=True):
+        """Solve a level-1 system that has the constants in its kernel -- lambda = 0 and no constrained node -- on their complement
+        instead of refusing it (include/hmg.h: hmg_grid_set_mean_free): the mean leaves the right-hand side before the level-1 PCG
+        and the solution after it, on the device.  A solution is then fixed up to a constant.  Default: on for periodic grids
+        only.  The level-1 system is due again afterwards and a FlexibleCG needs a new `start`."""
+        L.check(self._lib.hmg_grid_set_mean_free(self.h, 1 if on else 0))
+
+    def mean_free(self) -> bool:
+        return int(self._lib.hmg_grid_mean_free(self.h)) == 1
 
     def reserve_spare(self, enable=True):
         """The sixth finest-level vector of the default V-cycle form (include/hmg.h: hmg_grid_reserve_spare): True reserves it now

@@ -66,7 +66,9 @@ void coarse_setup(hmg_grid *g)
 {
     need(g->has_op, "hmg_grid_set_operator must be called first");
     const MeshTables &M = g->part ? g->part->global : g->cur();
-    if (g->lambda == 0.0 && std::find(M.node_on_boundary.begin(), M.node_on_boundary.end(), (uint8_t)1) == M.node_on_boundary.end())
+    // (the constants are in the kernel: solved on their complement where the grid says so, hmg_grid_set_mean_free)
+    g->coarse_singular = g->lambda == 0.0 && std::find(M.node_on_boundary.begin(), M.node_on_boundary.end(), (uint8_t)1) == M.node_on_boundary.end();
+    if (g->coarse_singular && !g->mean_free)
         throw std::runtime_error("hmg_coarse_setup: no node is constrained (hmg_grid_set_dirichlet_faces with an empty set) and "
                                  "lambda = 0: the level-1 matrix is singular");
     assemble_coarse_matrix(M, g->part ? g->sigma_global.data() : g->sigma.data(), g->sig_n, g->lambda, g->cm);
@@ -225,6 +227,17 @@ void coarse_pcg(hmg_grid *g)
     if (pr.h[3] > 0.0) g->coarse_budget = std::min(c->coarse_maxit, coarse_budget_for(c, g->coarse_last_it));
 }
 
+// The solve on the range of a matrix with the constants in its kernel: the mean leaves the right-hand side in front of the PCG --
+// whose b.b, and with it the stopping rule, is then that of the projected right-hand side -- and the solution behind it.  Both in
+// the stream: the blind iterations and the probe between them are what they are for a regular matrix.
+void coarse_pcg_on_range(hmg_grid *g)
+{
+    if (!g->coarse_singular) return coarse_pcg(g);
+    launch_coarse_remove_mean(g->ctx->L, g->cd, g->c_b.p);
+    coarse_pcg(g);
+    launch_coarse_remove_mean(g->ctx->L, g->cd, g->c_x.p);
+}
+
 }  // namespace
 
 // Called wherever the API has just synchronised the context's stream: probes that have landed by then are judged at once,
@@ -256,14 +269,14 @@ void coarse_solve(hmg_grid *g, hmg_vec *b1, hmg_vec *x1)
         launch_gather_owned(L, g->md, g->d_nodes_g.p, g->d_owned.p, lv.ld, b1->d, g->ex_buf);
         if (g->exchange(g->ex_user, g->ex_buf, ng) != 0) throw std::runtime_error("exchange callback failed");
         launch_coarse_gather_rhs(L, g->cd, g->ex_buf, g->c_b.p);
-        coarse_pcg(g);
+        coarse_pcg_on_range(g);
         launch_coarse_scatter_sol(L, g->cd, ng, g->c_x.p, g->c_u.p);
         launch_scatter_cells(L, g->d_cells_gnode.p, g->md.ncells, g->dim + 1, lv.ld, g->c_u.p, x1->d);
         return;
     }
     launch_gather_base(L, g->md, lv.ld, b1->d, g->c_u.p);
     launch_coarse_gather_rhs(L, g->cd, g->c_u.p, g->c_b.p);
-    coarse_pcg(g);
+    coarse_pcg_on_range(g);
     launch_coarse_scatter_sol(L, g->cd, g->md.nnodes, g->c_x.p, g->c_u.p);
     launch_scatter_base(L, g->md, lv.ld, g->c_u.p, x1->d);
 }

@@ -355,6 +355,8 @@ void launch_fill_random(const Launch &L, const LevelDev &lv, int64_t ncells, dou
 // preconditioned-CG pieces (Jacobi / Chebyshev) for the level-1 system
 void launch_coarse_gather_rhs(const Launch &L, const CoarseDev &A, const double *u, double *b);
 void launch_coarse_scatter_sol(const Launch &L, const CoarseDev &A, int64_t nnodes, const double *x, double *u);
+// v[0 .. A.n) -= its plain mean (one block, a fixed order of additions): the level-1 system with the constants in its kernel
+void launch_coarse_remove_mean(const Launch &L, const CoarseDev &A, double *v);
 void launch_coarse_init(const Launch &L, const CoarseDev &A, const double *b, double *x, double *r, double *z,
                         double *p, double zscale = 1.0, double *dcheb = nullptr);   // x=0,r=b,z=r/d,p=z, scal[S_C0]=r.z, scal[S_C2]=b.b, S_DONE = S_ITER = 0
 // polynomial (Chebyshev) preconditioner of the level-1 PCG, see k_coarse_cheb: with dcheb the init / update kernels leave

@@ -8,6 +8,7 @@
 // in "class" form (one coefficient row per entity of the reference simplex).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <thread>
@@ -185,12 +186,42 @@ struct MeshTables {
     // (point sampling does not read jinv: inverse_jacobian in hmg_sample.cpp inverts J again in long double -- the two inverses
     //  differ in the last bits, by up to eps times the cell's condition number)
     std::vector<double> detj, jinv;
+
+    // box length per axis of a grid on a torus (hmg_grid_create_periodic); all zeros: not periodic.  The cells name torus nodes,
+    // so every interface table above is what it is on any mesh -- opposite sides of the box are shared faces --, and coords holds
+    // one representative position per node: geometry is read through cell_edge_vectors() only.
+    double period[3] = {0.0, 0.0, 0.0};
+    bool periodic() const { return period[0] != 0.0 || period[1] != 0.0 || period[2] != 0.0; }
 };
+
+// d[q][a] = position of vertex q of cell c relative to its first vertex, by the minimal image on a torus:
+// p - p0 - period rint((p - p0) / period) per axis; with period 0 the plain difference p - p0 (the bits every table had before
+// there were tori).  d[0] is zero.
+inline void cell_edge_vectors(const MeshTables &M, int64_t c, double (&d)[4][3])
+{
+    const int dim = M.dim, N = dim + 1;
+    const int32_t *el = &M.cells[c * N];
+    const double *p0 = &M.coords[(size_t)el[0] * dim];
+    for (int q = 0; q < N; ++q) {
+        const double *p = &M.coords[(size_t)el[q] * dim];
+        for (int a = 0; a < 3; ++a) {
+            double v = a < dim ? p[a] - p0[a] : 0.0;
+            if (a < dim && M.period[a] != 0.0) v -= M.period[a] * std::rint(v / M.period[a]);
+            d[q][a] = v;
+        }
+    }
+}
 
 // cells_1based: (dim+1) x ncells, 1-based, each column ascending (reference contract,
 // src/implicit_fine_grid.jl:14).
 void build_mesh_tables(int dim, int64_t nnodes, const double *coords, int64_t ncells,
                        const int64_t *cells_1based, MeshTables &out);
+
+// The same on a torus of box lengths period[dim] (> 0, finite): the cells name torus nodes, coords holds one position per node.
+// Throws, naming the first offending cell, where an unwrapped edge component reaches half a period (the image is ambiguous:
+// fewer than three cells along that axis), besides what build_mesh_tables refuses.
+void build_mesh_tables_periodic(int dim, int64_t nnodes, const double *coords, int64_t ncells, const int64_t *cells_1based,
+                                const double *period, MeshTables &out);
 
 // Recomputes Dirichlet masks / boundary flags for the mesh restricted to the first
 // `ncells_prefix` cells (domain shrink, ref: src/examples/homogenized_coefficients.jl:309-316),

@@ -1121,6 +1121,29 @@ k_coarse_scatter_sol(const int32_t *__restrict__ interior, int64_t n, const doub
     if (i < n) u[interior[i]] = x[i];
 }
 
+// The level-1 matrix with the constants in its kernel (torus, lambda = 0: hmg_grid_set_mean_free): v <- v - mean(v), the
+// orthogonal projection onto its range, on the right-hand side in front of the PCG and on the solution behind it.  One
+// workgroup: thread t sums entries t, t + 1024, ... in ascending order, the wave and block sums are block_sum's -- the order of
+// additions is fixed by n alone, so every run gives the same bits.  Two passes: the first leaves a mean of rounding size
+// (eps |v|), which against a right-hand side that is almost a constant would be an inconsistent component the PCG cannot reduce;
+// the second takes that out as well.  A level-1 system is at most a few 10^5 unknowns: n / 1024 loads per thread, a few
+// microseconds next to the tens of launches of the solve between the two calls.
+__global__ void __launch_bounds__(1024) k_coarse_remove_mean(double *v, int64_t n)
+{
+    __shared__ double red[16];
+    __shared__ double mean;
+    for (int pass = 0; pass < 2; ++pass) {
+        double a = 0.0;
+        for (int64_t i = threadIdx.x; i < n; i += 1024) a += v[i];
+        const double s = block_sum(a, red);
+        if (threadIdx.x == 0) mean = s / (double)n;
+        __syncthreads();
+        const double m = mean;
+        for (int64_t i = threadIdx.x; i < n; i += 1024) v[i] -= m;   // (a thread's own entries: nothing to wait for)
+        __syncthreads();                                               // (mean is rewritten in the next pass)
+    }
+}
+
 __global__ void __launch_bounds__(256)
 k_coarse_init(CoarseDev A, const double *__restrict__ b, double *x, double *r, double *z, double *p, double *part0,
               double *part1, double zscale, double *dcheb)
@@ -1355,6 +1378,12 @@ void launch_coarse_scatter_sol(const Launch &L, const CoarseDev &A, int64_t nnod
     if (A.n == 0) return;                          // (x = 0 on every node)
     hipLaunchKernelGGL(k_coarse_scatter_sol, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, L.stream, A.interior,
                        A.n, x, u);
+    check_launch();
+}
+void launch_coarse_remove_mean(const Launch &L, const CoarseDev &A, double *v)
+{
+    if (A.n == 0) return;
+    hipLaunchKernelGGL(k_coarse_remove_mean, dim3(1), dim3(1024), 0, L.stream, v, A.n);
     check_launch();
 }
 void launch_coarse_init(const Launch &L, const CoarseDev &A, const double *b, double *x, double *r, double *z, double *p,

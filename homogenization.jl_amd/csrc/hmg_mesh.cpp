@@ -93,14 +93,12 @@ struct Geo {
 
 Geo cell_geo(const MeshTables &M, int64_t c)
 {
-    const int dim = M.dim, N = dim + 1;
-    const int32_t *el = &M.cells[c * N];
+    const int dim = M.dim;
     Geo g{};
-    const double *p0 = &M.coords[(size_t)el[0] * dim];
-    for (int col = 0; col < dim; ++col) {
-        const double *p = &M.coords[(size_t)el[col + 1] * dim];
-        for (int a = 0; a < dim; ++a) g.J[a][col] = p[a] - p0[a];
-    }
+    double d[4][3];
+    cell_edge_vectors(M, c, d);
+    for (int col = 0; col < dim; ++col)
+        for (int a = 0; a < dim; ++a) g.J[a][col] = d[col + 1][a];
     double inv[3][3] = {{0}};
     if (dim == 2) {
         double det = g.J[0][0] * g.J[1][1] - g.J[0][1] * g.J[1][0];
@@ -166,6 +164,7 @@ void build_from_cells0(MeshTables &M, EntLists *keep = nullptr)
     std::unordered_set<uint64_t> bedges;
     auto ekey = [&](int32_t a, int32_t b) { return (uint64_t)a * (uint64_t)M.nnodes + (uint64_t)b; };
 
+    int32_t over = -1;   // (torus: the first cell that is a third copy of a face / 2D edge)
     if (dim == 3) {
         auto faces = list_entities(M, 2);
         for_groups(faces, [&](size_t i, size_t j) {
@@ -182,9 +181,12 @@ void build_from_cells0(MeshTables &M, EntLists *keep = nullptr)
                 M.dupmask[faces[i + 1].cell] |= bit_face(faces[i + 1].lid);
                 set_mult(faces[i].cell, faces[i].lid, 2);
                 set_mult(faces[i + 1].cell, faces[i + 1].lid, 2);
-            } else
+            } else if (!M.periodic())
                 throw std::runtime_error("base mesh: a face is shared by more than two cells");
+            else
+                for (size_t q = i + 2; q < j; ++q) over = over < 0 ? faces[q].cell : std::min(over, faces[q].cell);
         });
+        if (over >= 0) throw std::runtime_error("periodic base mesh: a face is shared by more than two cells (cell " + std::to_string(over) + ")");
         if (keep) keep->faces.swap(faces);
         // pairs in ascending order of their first cell: consecutive wavefronts of the face kernel then walk the level
         // vector front to back (the key order above follows the node numbering instead)
@@ -207,8 +209,10 @@ void build_from_cells0(MeshTables &M, EntLists *keep = nullptr)
         if (dim == 2)
             for_groups(edges, [&](size_t i, size_t j) {
                 if (j - i == 1) bedges.insert(ekey(edges[i].key[0], edges[i].key[1]));
-                if (j - i > 2) throw std::runtime_error("base mesh: an edge is shared by more than two triangles");
+                if (j - i > 2 && !M.periodic()) throw std::runtime_error("base mesh: an edge is shared by more than two triangles");
+                for (size_t q = i + 2; q < j; ++q) over = over < 0 ? edges[q].cell : std::min(over, edges[q].cell);
             });
+        if (over >= 0) throw std::runtime_error("periodic base mesh: an edge is shared by more than two triangles (cell " + std::to_string(over) + ")");
         for_groups(edges, [&](size_t i, size_t j) {
             bool bnd = bedges.count(ekey(edges[i].key[0], edges[i].key[1])) != 0;
             if (bnd) {
@@ -265,6 +269,9 @@ void build_from_cells0(MeshTables &M, EntLists *keep = nullptr)
                 for (int a = 0; a < dim; ++a) M.jinv[(size_t)c * dim * dim + a + dim * b] = g.Jinv[a][b];
         }
     });
+    if (bad[0] && M.periodic())
+        for (int64_t c = 0; c < M.ncells; ++c)
+            if (!(M.detj[c] > 0.0)) throw std::runtime_error("periodic base mesh: degenerate cell " + std::to_string(c));
     if (bad[0]) throw std::runtime_error("base mesh: degenerate cell");
 }
 
@@ -297,6 +304,42 @@ static void build_mesh_tables_keep(int dim, int64_t nnodes, const double *coords
         M.cells[q] = (int32_t)v;
     }
     build_from_cells0(M, keep);
+}
+
+void build_mesh_tables_periodic(int dim, int64_t nnodes, const double *coords, int64_t ncells, const int64_t *cells_1based,
+                                const double *period, MeshTables &M)
+{
+    if (dim != 2 && dim != 3) throw std::runtime_error("dim must be 2 or 3");
+    for (int a = 0; a < dim; ++a)
+        if (!(period[a] > 0.0) || !std::isfinite(period[a]))
+            throw std::runtime_error("periodic base mesh: the period of axis " + std::to_string(a) + " must be positive and finite");
+    if (ncells <= 0 || nnodes <= 0) throw std::runtime_error("empty base mesh");
+    if (ncells >= (int64_t(1) << 27)) throw std::runtime_error("too many cells for one device partition");
+    const int N = dim + 1;
+    M = MeshTables();
+    M.dim = dim;
+    M.nnodes = nnodes;
+    M.ncells = ncells;
+    for (int a = 0; a < dim; ++a) M.period[a] = period[a];
+    M.coords.assign(coords, coords + (size_t)nnodes * dim);
+    M.cells.resize((size_t)ncells * N);
+    for (int64_t q = 0; q < ncells * N; ++q) {
+        int64_t v = cells_1based[q] - 1;
+        if (v < 0 || v >= nnodes) throw std::runtime_error("base mesh: node index out of range (cells are 1-based)");
+        M.cells[q] = (int32_t)v;
+    }
+    // the minimal image must be the only candidate: every component of every edge of a cell strictly inside half a period
+    for (int64_t c = 0; c < ncells; ++c) {
+        double d[4][3];
+        cell_edge_vectors(M, c, d);
+        for (int q = 0; q < N; ++q)
+            for (int r = q + 1; r < N; ++r)
+                for (int a = 0; a < dim; ++a)
+                    if (!(std::fabs(d[r][a] - d[q][a]) < 0.5 * period[a]))
+                        throw std::runtime_error("periodic base mesh: cell " + std::to_string(c) + " has an edge that spans half the period of axis " +
+                                                 std::to_string(a) + " or more: its image is ambiguous (a torus needs at least three cells per axis)");
+    }
+    build_from_cells0(M, nullptr);
 }
 
 void restrict_mesh_tables(const MeshTables &full, int64_t ncells_prefix, int64_t nnodes_prefix,

@@ -395,6 +395,8 @@ struct hmg_grid {
     CoarseMatrix cm;
     CoarseDev cd{};
     bool coarse_ready = false;
+    bool mean_free = false;                      // hmg_grid_set_mean_free: a level-1 matrix with the constants in its kernel is solved on their complement ...
+    bool coarse_singular = false;                // ... and the matrix coarse_setup assembled last is one (lambda = 0, no constrained node)
     DevBuf<int32_t> c_rowptr, c_colidx, c_interior;
     DevBuf<double> c_val, c_diag, c_b, c_x, c_r, c_z, c_p, c_q, c_u, c_z2, c_d;   // (c_z2, c_d: Chebyshev preconditioner)
     DevBuf<double> top_spare;           // second direction vector of the finest level's post-smoother (smooth(), lazy_top = 2)

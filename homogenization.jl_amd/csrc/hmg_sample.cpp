@@ -280,6 +280,8 @@ void prepare(hmg_grid *g, int level, const char *call)
 {
     need(g != nullptr, "null grid");
     if (g->part) throw std::runtime_error(std::string(call) + ": partitioned grids are not served (sample on an unpartitioned grid)");
+    // (the locator reads M.coords of a cell's nodes as they stand: on a torus they may sit on opposite sides of the box)
+    if (g->cur().periodic()) throw std::runtime_error(std::string(call) + ": periodic grids are not served (point location on a torus is not built)");
     if (level < 1 || level > g->nlevels)
         throw std::runtime_error(std::string(call) + ": level " + std::to_string(level) + " out of range (1 to " + std::to_string(g->nlevels) + ")");
 }

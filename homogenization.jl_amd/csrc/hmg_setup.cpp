@@ -180,6 +180,65 @@ int hmg_checkerboard_mesh(int dim, const int64_t *shape, const double *origin, i
     return 0;
 }
 
+// The same cubes on a torus: corner i + 1 along an axis is node (i + 1) mod shape, so the last cube of a row shares its far side
+// with the first.  Nodes sit at their multi-index (last coordinate fastest), cube q -- first index slowest, as above -- owns the
+// cells per q .. per q + per - 1 in the order of CUBE_TETS / SQUARE_TRIS, every tuple sorted by torus id.
+int hmg_periodic_mesh_size(int dim, const int64_t *shape, int64_t *nnodes, int64_t *ncells)
+{
+    try {
+        if ((dim != 2 && dim != 3) || !shape || !nnodes || !ncells) throw std::runtime_error("bad argument");
+        int64_t nn = 1, nc = dim == 3 ? 6 : 2;
+        for (int a = 0; a < dim; ++a) {
+            if (shape[a] < 3)
+                throw std::runtime_error("periodic mesh: every axis needs at least 3 cubes (with fewer a cell meets its own image)");
+            nn *= shape[a];
+            nc *= shape[a];
+        }
+        *nnodes = nn;
+        *ncells = nc;
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+    return 0;
+}
+
+int hmg_periodic_mesh(int dim, const int64_t *shape, double *coords, int64_t *cells)
+{
+    try {
+        int64_t nn, nc;
+        if (hmg_periodic_mesh_size(dim, shape, &nn, &nc) != 0) throw std::runtime_error(last_error());
+        if (!coords || !cells) throw std::runtime_error("null argument");
+        const int N = dim + 1, ncorner = 1 << dim, per = dim == 3 ? 6 : 2;
+        int64_t cstride[3] = {1, 1, 1};
+        for (int a = dim - 2; a >= 0; --a) cstride[a] = cstride[a + 1] * shape[a + 1];
+        parallel_for(nn, [&](int64_t a0, int64_t a1) {
+            for (int64_t q = a0; q < a1; ++q) {
+                int64_t idx[3] = {0, 0, 0}, r = q;      // the node's multi-index is the cube's with the same number
+                for (int a = dim - 1; a >= 0; --a) {
+                    idx[a] = r % shape[a];
+                    r /= shape[a];
+                }
+                for (int a = 0; a < dim; ++a) coords[q * dim + a] = (double)idx[a];
+                int64_t ids[8];
+                for (int c = 0; c < ncorner; ++c) {
+                    int64_t node = 0;
+                    for (int a = 0; a < dim; ++a) node += ((idx[a] + ((c >> a) & 1)) % shape[a]) * cstride[a];
+                    ids[c] = node;
+                }
+                for (int t = 0; t < per; ++t) {
+                    int64_t *out = cells + (q * per + t) * N;
+                    for (int l = 0; l < N; ++l) out[l] = ids[dim == 3 ? CUBE_TETS[t][l] : SQUARE_TRIS[t][l]];
+                    sort_small(out, N);
+                    for (int l = 0; l < N; ++l) out[l] += 1;      // 1-based, ascending tuples
+                }
+            }
+        });
+    } catch (const std::exception &e) {
+        return fail(e);
+    }
+    return 0;
+}
+
 int hmg_conductivity_per_element(int dim, int64_t nnodes, const double *coords, int64_t ncells, const int64_t *cells,
                                  const int64_t *grid_shape, const double *sigma_grid, const double *offset, double *sigma)
 {

@@ -378,7 +378,7 @@ extern "C" {
 // part: the grid is this rank's share, by `owner`, of the mesh (cut_owner: rehearsal partitions only, else null)
 static int create_grid(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords, int64_t ncells,
                        const int64_t *cells, bool part, const int32_t *owner, const int32_t *cut_owner, int rank, int nranks,
-                       hmg_grid **out)
+                       hmg_grid **out, const double *period = nullptr)
 {
     HMG_TRY
     need(coords && cells && out && (owner || !part), "null argument");
@@ -404,6 +404,9 @@ static int create_grid(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const
         if (cut_owner) g->part_cut_owner.assign(cut_owner, cut_owner + ncells);
         g->part_nnodes = nnodes;
         g->part_ncells = ncells;
+    } else if (period) {
+        build_mesh_tables_periodic(dim, nnodes, coords, ncells, cells, period, g->mesh_full);
+        g->mean_free = true;                     // (no node is constrained: with lambda = 0 the level-1 matrix has the constants in its kernel)
     } else {
         build_mesh_tables(dim, nnodes, coords, ncells, cells, g->mesh_full);
     }
@@ -422,6 +425,16 @@ int hmg_grid_create(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const do
                     const int64_t *cells, hmg_grid **out)
 {
     return create_grid(ctx, dim, nlevels, nnodes, coords, ncells, cells, false, nullptr, nullptr, 0, 1, out);
+}
+
+int hmg_grid_create_periodic(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords, int64_t ncells,
+                             const int64_t *cells, const double *period, hmg_grid **out)
+{
+    if (!period) {
+        last_error() = "hmg_grid_create_periodic: null period";
+        return 1;
+    }
+    return create_grid(ctx, dim, nlevels, nnodes, coords, ncells, cells, false, nullptr, nullptr, 0, 1, out, period);
 }
 
 int hmg_grid_create_partition(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords, int64_t ncells,
@@ -515,6 +528,7 @@ int hmg_grid_shrink(hmg_grid *g, int64_t ncells_prefix, int64_t nnodes_prefix)
 {
     HMG_TRY
     need(g != nullptr, "null grid");
+    need(!g->mesh_full.periodic(), "hmg_grid_shrink: a periodic grid has no prefix domains (a prefix of a torus is no torus)");
     need(!g->dir_custom, "hmg_grid_shrink: the grid holds a caller's Dirichlet faces (hmg_grid_set_dirichlet_faces); restore the "
                          "default set first (nfaces = -1)");
     if (g->ctx) materialize_r(g);                // (a pending r-update belongs to the cells and face partners of the grid as it is)
@@ -593,6 +607,25 @@ int hmg_grid_set_dirichlet_faces(hmg_grid *g, int64_t nfaces, const int64_t *fac
     g->coarse_ready = false;
     HMG_END
 }
+
+// The level-1 matrix with the constants in its kernel is solved on their complement (coarse_pcg_on_range) instead of being refused.
+// Towards what is cached the flag is part of the operator, as the constrained set is.
+int hmg_grid_set_mean_free(hmg_grid *g, int on)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(on == 0 || on == 1, "hmg_grid_set_mean_free: on must be 0 or 1");
+    if (g->ctx) {
+        HIPCHK(hipSetDevice(g->ctx->device));
+        materialize_r(g);                        // (settles pending x-updates first)
+    }
+    g->mean_free = on != 0;
+    g->op_epoch += 1;
+    g->coarse_ready = false;
+    HMG_END
+}
+
+int hmg_grid_mean_free(const hmg_grid *g) { return g ? (g->mean_free ? 1 : 0) : -1; }
 
 int64_t hmg_grid_dirichlet_faces(const hmg_grid *g, int64_t *out, int64_t cap)
 {

@@ -781,20 +781,15 @@ def dirichlet_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, 
     `save` (a file name) writes the coarse mesh with the cell fields of every pair k <= l, "pair_kl" and "energy_kl" = sigma_c :
     S_{u_k u_l}(c) (vtk.export_cell_fields).  Memory beyond `dirichlet_homogenization`: d finest-level vectors.  No counterpart
     in the reference."""
-    return _tensor_run("dirichlet_homogenization_tensor", None, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance,
-                       smoother, accelerate, fields, save, cond, smoothing_steps, max_cycles, large_cells)
+    base, cond = _hypercube_problem(n, eltype, sigma_grid, seed, values, cond)
+    return _tensor_run("dirichlet_homogenization_tensor", None, base, cond, refinements, ctx, tolerance,
+                       smoother, accelerate, fields, save, smoothing_steps, max_cycles, large_cells)
 
 
-def _tensor_run(who, faces, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance, smoother, accelerate, fields, save,
-                cond, smoothing_steps, max_cycles, large_cells):
-    """The d corrector solves and moment passes behind `dirichlet_homogenization_tensor` and the drivers that differ from it in
-    the constrained set only.  faces: None -- the grid's default set, no call --, a function base -> one face array, set once
-    before the solves, or base -> a list of d of them, set in front of solve k.  A set of the caller's is taken back behind the
-    solves, also when one raises."""
+def _hypercube_problem(n, eltype, sigma_grid, seed, values, cond):
+    """Base mesh and conductivity per cell of the drivers on `hypercube(eltype, n)`: `cond` as given, else `sigma_grid` -- default:
+    the seeded checkerboard of `values` -- looked up at the cell centres."""
     dim = api._dim_of(eltype)
-    own_ctx = ctx is None
-    if own_ctx:
-        ctx = api.Context(0)
     base = hypercube(eltype, n)
     if cond is None:
         if sigma_grid is None:
@@ -802,6 +797,20 @@ def _tensor_run(who, faces, n, eltype, refinements, ctx, sigma_grid, seed, value
         cond = conductivity_per_element(base, sigma_grid, (0.0,) * dim)
     else:
         cond = np.ascontiguousarray(cond, dtype=np.float64)
+    return base, cond
+
+
+def _tensor_run(who, faces, base, cond, refinements, ctx, tolerance, smoother, accelerate, fields, save, smoothing_steps,
+                max_cycles, large_cells):
+    """The d corrector solves and moment passes behind `dirichlet_homogenization_tensor` and the drivers that differ from it in
+    the base mesh and the constrained set only.  base, cond: the mesh (a torus where `base.period` is set) and the conductivity
+    per cell.  faces: None -- the grid's default set, no call --, a function base -> one face array, set once
+    before the solves, or base -> a list of d of them, set in front of solve k.  A set of the caller's is taken back behind the
+    solves, also when one raises."""
+    dim = base.dim
+    own_ctx = ctx is None
+    if own_ctx:
+        ctx = api.Context(0)
     face_sets = None if faces is None else faces(base)
     total_grids = refinements + 1
     implicit = api.ImplicitFineGrid(ctx, base, total_grids)
@@ -871,6 +880,53 @@ def _tensor_run(who, faces, n, eltype, refinements, ctx, sigma_grid, seed, value
     return out
 
 
+def periodic_mesh(eltype, shape) -> Mesh:
+    """`shape` unit cubes on a torus (include/hmg.h: hmg_periodic_mesh), the Kuhn split of `checkerboard_mesh`: node ids with the
+    last coordinate fastest, taken modulo `shape`; cube q (C order of its multi-index) owns cells 6q .. 6q + 5 (2D: 2q, 2q + 1), so
+    a per-cube field maps to cells by `np.repeat` without any coordinate.  An int is a cube.  Every axis needs 3 cubes or more.
+    `Mesh.period` = shape; the nodes sit at their multi-index, and a cell that wraps names nodes on opposite sides of the box
+    (`Mesh.cell_corners` unwraps it)."""
+    import ctypes
+    from . import _lib as L
+    dim = api._dim_of(eltype)
+    shp = np.ascontiguousarray(np.broadcast_to(np.asarray(shape, dtype=np.int64), (dim,)))
+    lib = L.load()
+    nn, ne = ctypes.c_int64(), ctypes.c_int64()
+    L.check(lib.hmg_periodic_mesh_size(dim, shp.ctypes.data_as(L.p_i64), ctypes.byref(nn), ctypes.byref(ne)))
+    nodes = np.zeros((nn.value, dim))
+    cells = np.zeros((ne.value, dim + 1), dtype=np.int64)
+    L.check(lib.hmg_periodic_mesh(dim, shp.ctypes.data_as(L.p_i64), nodes.ctypes.data_as(L.p_f64), cells.ctypes.data_as(L.p_i64)))
+    return Mesh(nodes, cells, shp.astype(np.float64))
+
+
+def periodic_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None, seed: int = 0,
+                                   values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
+                                   fields: bool = False, save=None, smoothing_steps: int = 3, max_cycles: int = 200,
+                                   large_cells: bool = False):
+    """The homogenized tensor of the PERIODIC cell problem -- its definition for periodic media, and for random media the boundary
+    condition with the smallest boundary-layer error: on the torus of n^d unit cubes (`periodic_mesh`, n >= 3) find v_k periodic
+    with a(v_k, w) = -int sigma e_k . grad w for all periodic w (lambda = 0, no constrained node), then "tensor" and "tensor_flux"
+    from the per-cell moments of u_k = e_k.x + v_k as in `dirichlet_homogenization_tensor`, whose keywords (without `cond`) and
+    returned dict these are.  `sigma_grid`: one tensor per unit cube, (n,) * dim + (dim,) diagonals or + (dim, dim) full symmetric
+    tensors; default: the seeded checkerboard of `values`.  The operator has the constants in its kernel: the level-1 solve works on
+    their complement (`ImplicitFineGrid.set_mean_free`, the default of a periodic grid), the finer levels need nothing, and a
+    corrector is fixed up to a constant -- nothing is normalised, every quantity returned depends on gradients only.  The space of
+    `dirichlet_homogenization_tensor` on the same `sigma_grid` is a subspace of the periodic one, so this diagonal is at most
+    that one's.  The tensor does not depend on where the period starts (in 3D up to the discretisation: the cells that wrap
+    choose their interior diagonals differently).  No counterpart in the reference."""
+    dim = api._dim_of(eltype)
+    base = periodic_mesh(eltype, n)
+    if sigma_grid is None:
+        sigma_grid = generate_conductivity(dim, n, seed, values)
+    sg = np.asarray(sigma_grid, dtype=np.float64)
+    if sg.shape not in ((n,) * dim + (dim,), (n,) * dim + (dim, dim)):
+        raise ValueError(f"sigma_grid must have shape {(n,) * dim + (dim,)} or {(n,) * dim + (dim, dim)}, not {sg.shape}")
+    per_cube = base.elements.shape[0] // n ** dim
+    cond = np.ascontiguousarray(np.repeat(sg.reshape((n ** dim,) + sg.shape[dim:]), per_cube, axis=0))
+    return _tensor_run("periodic_homogenization_tensor", None, base, cond, refinements, ctx, tolerance, smoother, accelerate,
+                       fields, save, smoothing_steps, max_cycles, large_cells)
+
+
 def faces_on_plane(base: Mesh, axis: int, value: float):
     """The faces of a base mesh (3D: triangles, 2D: edges) all of whose nodes have coordinate `axis` equal to `value` (to 1e-9 of
     the mesh's extent): an (nfaces, dim) array of 1-based node ids for `ImplicitFineGrid.set_dirichlet_faces`."""
@@ -909,8 +965,9 @@ def uniaxial_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *
         x = np.asarray(base.nodes, dtype=np.float64)
         return [np.concatenate([faces_on_plane(base, k, x[:, k].min()), faces_on_plane(base, k, x[:, k].max())])
                 for k in range(base.dim)]
-    return _tensor_run("uniaxial_homogenization_tensor", sides, n, eltype, refinements, ctx, sigma_grid, seed, values, tolerance,
-                       smoother, accelerate, fields, save, cond, smoothing_steps, max_cycles, large_cells)
+    base, cond = _hypercube_problem(n, eltype, sigma_grid, seed, values, cond)
+    return _tensor_run("uniaxial_homogenization_tensor", sides, base, cond, refinements, ctx, tolerance,
+                       smoother, accelerate, fields, save, smoothing_steps, max_cycles, large_cells)
 
 
 def block_homogenization_tensor(n: int, block: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None,
@@ -929,9 +986,9 @@ def block_homogenization_tensor(n: int, block: int, eltype=Tri64, refinements: i
     dim = api._dim_of(eltype)
     if block < 1 or n % block:
         raise ValueError(f"block must divide n = {n}")
-    run = _tensor_run("block_homogenization_tensor", lambda base: block_faces(base, block), n, eltype, refinements, ctx,
-                      sigma_grid, seed, values, tolerance, smoother, accelerate, True, save, cond, smoothing_steps, max_cycles,
-                      large_cells)
+    base, cond = _hypercube_problem(n, eltype, sigma_grid, seed, values, cond)
+    run = _tensor_run("block_homogenization_tensor", lambda base: block_faces(base, block), base, cond, refinements, ctx,
+                      tolerance, smoother, accelerate, True, save, smoothing_steps, max_cycles, large_cells)
     base, cond, vol, pairs, means = run["base"], run["cond"], run["volumes"], run["pairs"], run["means"]
     nb = n // block
     centers = _centers(base)

@@ -23,10 +23,17 @@ def _cond(cond, ne, d):
     return s
 
 
+def _corners(base, cells):
+    """Corner positions (n, d + 1, d) of some cells of a base mesh: api.Mesh.cell_corners, which unwraps the cells of a torus; a
+    mesh-like object without it has no period."""
+    if hasattr(base, "cell_corners"):
+        return np.asarray(base.cell_corners(cells), dtype=np.float64)
+    return np.asarray(base.nodes, dtype=np.float64)[np.asarray(base.elements)[cells] - 1]
+
+
 def cell_volumes(base, ncells=None):
     """|c| of the first `ncells` cells of a base mesh (api.Mesh: elements 1-based)."""
-    els = np.asarray(base.elements)[:ncells] - 1
-    p = np.asarray(base.nodes, dtype=np.float64)[els]                 # (Ne, d+1, d)
+    p = _corners(base, slice(None, ncells))                          # (Ne, d+1, d)
     d = p.shape[2]
     return np.abs(np.linalg.det(p[:, 1:, :] - p[:, :1, :])) / math.factorial(d)
 
@@ -208,7 +215,7 @@ def element_points(implicit, level, cells, nodes):
     ijk = implicit.table_i32("slot_ijk", level).reshape(-1, 3)
     ok = nodes >= 0
     ref = ijk[h2s[np.where(ok, nodes, 0)]][..., :d].astype(np.float64) / m        # (n, d + 1, d) reference coordinates
-    X = np.asarray(base.nodes, dtype=np.float64)[np.asarray(base.elements)[cells] - 1]   # (n, d + 1, d) corners
+    X = _corners(base, cells)                                                            # (n, d + 1, d) corners
     J = X[:, 1:, :] - X[:, :1, :]
     out = X[:, :1, :] + np.einsum("nva,nac->nvc", ref, J)
     out[~ok] = np.nan

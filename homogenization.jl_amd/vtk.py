@@ -84,6 +84,22 @@ def read_vtu(path):
     return out
 
 
+def _corners(base, ne):
+    """corners (ne, dim + 1, dim) of the first ne cells; the cells of a torus (api.Mesh.period) unwrapped"""
+    if getattr(base, "period", None) is not None:
+        return base.cell_corners(np.arange(ne))
+    return base.nodes[base.elements[:ne] - 1]
+
+
+def _points_and_cells(base, ne):
+    """The first ne cells of a base mesh as write_vtu takes them.  A mesh on a torus goes out with its corners duplicated per cell,
+    each cell unwrapped (api.Mesh.cell_corners): with shared points a cell that straddles the box would be drawn across it."""
+    if getattr(base, "period", None) is None:
+        return base.nodes, base.elements[:ne] - 1
+    X = _corners(base, ne)
+    return X.reshape(-1, X.shape[2]), np.arange(X.shape[0] * X.shape[1], dtype=np.int64).reshape(X.shape[0], X.shape[1])
+
+
 def construct_full_grid(implicit, level: int):
     """All cells of refinement level `level` as one explicit mesh; interface nodes are duplicated per coarse cell
     (node n of coarse cell e has index e * Nf + n, n in the reference's hierarchical order).
@@ -96,7 +112,7 @@ def construct_full_grid(implicit, level: int):
     ijk = implicit.table_i32("slot_ijk", level).reshape(-1, 3)[h2s][:, :dim].astype(np.float64) / m   # (nf, dim)
     ref_cells = implicit.table_i32("ref_cells", level).reshape(-1, dim + 1).astype(np.int64)
     ne = implicit.ncells()                                  # (a shrunk domain is a prefix of the base cells)
-    X = base.nodes[base.elements[:ne] - 1]                  # (ne, dim+1, dim)
+    X = _corners(base, ne)                                  # (ne, dim+1, dim); a torus: unwrapped
     J = X[:, 1:, :] - X[:, :1, :]                           # rows: X_a - X_0
     nodes = (X[:, :1, :] + np.einsum("na,eac->enc", ijk, J)).reshape(-1, dim)
     cells = (ref_cells[None, :, :] + (np.arange(ne, dtype=np.int64) * nf)[:, None, None]).reshape(-1, dim + 1)
@@ -110,7 +126,7 @@ def export_domain(base, cond, name="checkerboard"):
     if a.ndim == 3:
         iu = np.triu_indices(a.shape[1])
         a = np.ascontiguousarray(a[:, iu[0], iu[1]])
-    return write_vtu(name, base.nodes, base.elements - 1, cell_data={"a": a})
+    return write_vtu(name, *_points_and_cells(base, base.elements.shape[0]), cell_data={"a": a})
 
 
 def export_cell_fields(base, fields: dict, name="cell_fields"):
@@ -133,7 +149,7 @@ def export_cell_fields(base, fields: dict, name="cell_fields"):
         raise ValueError("no cell field given")
     if ne > base.elements.shape[0]:
         raise ValueError(f"{ne} values for {base.elements.shape[0]} cells")
-    return write_vtu(name, base.nodes, base.elements[:ne] - 1, cell_data=data)
+    return write_vtu(name, *_points_and_cells(base, ne), cell_data=data)
 
 
 def export_unknown(implicit, x, k: int, level: int, name=None, field="v"):

@@ -243,6 +243,33 @@ int hmg_grid_set_dirichlet_faces(hmg_grid *grid, int64_t nfaces, const int64_t *
 /* the current set (sorted ids within a face, faces in lexicographic order), at most cap ids into out (which may be NULL);
  * returns the number of faces, -1 for a null grid */
 int64_t hmg_grid_dirichlet_faces(const hmg_grid *grid, int64_t *out, int64_t cap);
+/* A grid on a torus (no counterpart in the reference): the cells name TORUS nodes -- 1-based, every tuple strictly ascending,
+ * a node once per cell --, coords holds one representative position per node and period[a] > 0 is the length of the box along
+ * axis a.  Periodicity is topology: every interface table is derived from the node ids alone, so opposite sides of the box are
+ * shared faces like any other, no face belongs to one cell, no node is constrained (hmg_grid_dirichlet_faces returns 0) and no
+ * kernel differs.  Geometry is read through one rule: a cell's vertices relative to its first vertex by the minimal image,
+ *     p - p0 - period rint((p - p0) / period)   per axis.
+ * Refused, naming the first offending cell, and nothing is created: an edge of a cell with an unwrapped component of
+ * period / 2 or more (the image is ambiguous: fewer than three cells along that axis), a face shared by more than two cells, a
+ * degenerate cell; and a period that is not positive and finite.  The grid takes hmg_grid_set_operator*, _set_lambda,
+ * _set_dirichlet_faces (a plane of fixed potential inside the torus: any faces of the mesh; nfaces = -1 is the empty set here),
+ * the smoothers, hmg_fcg_*, the right-hand sides, integrals and per-cell fields.  It refuses, with "periodic" in the message,
+ * hmg_grid_shrink, hmg_grid_locate, hmg_sample and hmg_sample_raster; there is no partitioned form.  hmg_grid_mean_free is 1. */
+int hmg_grid_create_periodic(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords /* dim*nnodes */,
+                             int64_t ncells, const int64_t *cells /* (dim+1)*ncells, 1-based */, const double *period /* dim */,
+                             hmg_grid **out);
+/* The level-1 system with the constants in its kernel.  With the flag on, lambda = 0 and no constrained node, hmg_coarse_setup
+ * assembles the singular matrix instead of refusing, and hmg_coarse_solve (hence every V-cycle) takes the plain mean over the
+ * level-1 nodes out of its right-hand side before the PCG -- the matrix's range is the complement of the constants -- and out of
+ * its solution after it: on the device, in the stream, in a fixed order of additions (the same bits in every run), inside the
+ * budget / probe scheme as it stands; the stopping rule is coarse_rtol of the projected right-hand side.  The finer levels need
+ * nothing: the smoothers add residual-derived directions only, and the constants of a level are the prolongation of those of
+ * level 1.  A solution is then fixed up to a constant; gradients, fluxes and energies do not depend on it.  With lambda > 0 or
+ * a constrained node the matrix is regular and the flag changes nothing.  Default: 0 on grids of hmg_grid_create* (whose refusal
+ * of the singular matrix stays), 1 on periodic grids.  Towards what is cached the call is hmg_grid_set_dirichlet_faces: pending
+ * records are settled, the level-1 system is assembled again, hmg_fcg_step asks for hmg_fcg_start. */
+int hmg_grid_set_mean_free(hmg_grid *grid, int on);
+int hmg_grid_mean_free(const hmg_grid *grid);   /* 0 / 1; -1 for a null grid */
 /* The reference's LevelState holds five vectors per level (src/multigrid.jl:18-25).  With option "lazy_top" = 2 (the default) the
  * finest level's post-smoother inside hmg_vcycle uses a SIXTH vector of that level's size (+20 % on the finest level's footprint)
  * to save 8 B/DOF of traffic per V-cycle.  It belongs to the grid and is setup, not hot-path, memory: reserved automatically when
@@ -723,6 +750,12 @@ int hmg_grid_create_partition_rehearsal(hmg_ctx *ctx, int dim, int nlevels, int6
 int hmg_checkerboard_mesh_size(int dim, const int64_t *shape, int64_t *nnodes, int64_t *ncells);
 int hmg_checkerboard_mesh(int dim, const int64_t *shape, const double *origin, int transposed_lookup, int ordered,
                           double *coords /* dim*nnodes */, int64_t *cells /* (dim+1)*ncells */);
+/* shape[] unit cubes on a torus (for hmg_grid_create_periodic with period = shape), the same split into 6 tetrahedra / 2
+ * triangles: node ids with the last coordinate fastest, taken modulo shape, nodes at their multi-index; cube q (first index
+ * slowest) owns cells 6q .. 6q + 5 (2D: 2q, 2q + 1) in the order of hmg_checkerboard_mesh, so a per-cube conductivity maps to
+ * cells without any coordinate; every tuple sorted ascending, 1-based.  shape[a] >= 3. */
+int hmg_periodic_mesh_size(int dim, const int64_t *shape, int64_t *nnodes, int64_t *ncells);
+int hmg_periodic_mesh(int dim, const int64_t *shape, double *coords /* dim*nnodes */, int64_t *cells /* (dim+1)*ncells */);
 /* conductivity_per_element(mesh, sigma, offset) (src/examples/homogenized_coefficients.jl:494-503): sigma[c] =
  * sigma_grid[trunc(centre_c + offset) - 1]; sigma_grid: grid_shape[0] x .. x grid_shape[dim-1] x dim, C order */
 int hmg_conductivity_per_element(int dim, int64_t nnodes, const double *coords, int64_t ncells, const int64_t *cells,

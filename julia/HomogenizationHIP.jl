@@ -78,6 +78,26 @@ function HipGrid(ctx::HipContext, implicit::ImplicitFineGrid{dim}) where {dim}
               HipGrid{dim}(h[], ctx, implicit, nlevels(implicit), nothing, NaN))
 end
 
+# The same grid on a torus (include/hmg.h: hmg_grid_create_periodic; no counterpart in the reference): the elements of the base
+# mesh name torus nodes, its nodes are one representative position each, period is the box length per axis.  No node is
+# constrained; with lambda = 0 the level-1 solve works on the complement of the constants (mean_free), and a solution is fixed up
+# to a constant.
+function HipGrid(ctx::HipContext, implicit::ImplicitFineGrid{dim}, period::Vector{Float64}) where {dim}
+    base = base_mesh(implicit)
+    coords, cells = flat_nodes(base), flat_cells(base)
+    length(period) == dim || error("period: one box length per axis")
+    h = Ref{Ptr{Cvoid}}()
+    check(ccall((:hmg_grid_create_periodic, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Int64, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                ctx.h, dim, nlevels(implicit), nnodes(base), coords, nelements(base), cells, period, h))
+    finalizer(g -> ccall((:hmg_grid_destroy, LIB), Cint, (Ptr{Cvoid},), g.h),
+              HipGrid{dim}(h[], ctx, implicit, nlevels(implicit), nothing, NaN))
+end
+# the level-1 system with the constants in its kernel is solved on their complement (default: periodic grids only)
+set_mean_free!(g::HipGrid, on::Bool = true) =
+    (check(ccall((:hmg_grid_set_mean_free, LIB), Cint, (Ptr{Cvoid}, Cint), g.h, on ? 1 : 0)); g)
+mean_free(g::HipGrid) = ccall((:hmg_grid_mean_free, LIB), Cint, (Ptr{Cvoid},), g.h) == 1
+
 # one rank's share of a global base mesh (dist.PartitionedGrid): owner[c] = rank that owns coarse cell c
 function HipGrid(ctx::HipContext, implicit::ImplicitFineGrid{dim}, owner::Vector{Int32}, rank::Integer, nranks::Integer) where {dim}
     base = base_mesh(implicit)
@@ -666,6 +686,14 @@ function checkerboard_mesh(dim::Integer, shape::Vector{Int64}, origin::Vector{Fl
     coords, cells = zeros(Float64, dim * nn[]), zeros(Int64, (dim + 1) * ne[])
     check(ccall((:hmg_checkerboard_mesh, LIB), Cint, (Cint, Ptr{Int64}, Ptr{Float64}, Cint, Cint, Ptr{Float64}, Ptr{Int64}),
                 dim, shape, origin, transposed_lookup ? 1 : 0, ordered ? 1 : 0, coords, cells))
+    (reshape(coords, dim, :), reshape(cells, dim + 1, :))
+end
+# shape[] unit cubes on a torus (period = shape): node ids modulo shape, cube q owns cells 6q+1 .. 6q+6 (2D: 2q+1, 2q+2) of the result
+function periodic_mesh(dim::Integer, shape::Vector{Int64})
+    nn, ne = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:hmg_periodic_mesh_size, LIB), Cint, (Cint, Ptr{Int64}, Ref{Int64}, Ref{Int64}), dim, shape, nn, ne))
+    coords, cells = zeros(Float64, dim * nn[]), zeros(Int64, (dim + 1) * ne[])
+    check(ccall((:hmg_periodic_mesh, LIB), Cint, (Cint, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}), dim, shape, coords, cells))
     (reshape(coords, dim, :), reshape(cells, dim + 1, :))
 end
 function conductivity_per_element(dim::Integer, coords::Matrix{Float64}, cells::Matrix{Int64}, grid_shape::Vector{Int64},

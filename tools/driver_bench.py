@@ -35,6 +35,8 @@ time of a run after --warmup untimed ones, the pixels inside the domain, the lar
 one and the counters "sample_kernel_ns", "sample_download_ns", "sample_locator_bytes", "sample_locator_max_candidates".
 --uniaxial: driver.uniaxial_homogenization_tensor on hypercube(n) (d solves on one grid, the two faces normal to e_k as the grid's
 Dirichlet set in front of solve k): one line with the wall time of a run after --warmup untimed ones, the cycles and the tensor.
+--periodic: driver.periodic_homogenization_tensor on periodic_mesh(n) (d solves of the periodic cell problem on a torus of n^d unit
+cubes, n >= 3, lambda = 0, the level-1 solve on the complement of the constants): the same line.
 --blocks B: driver.block_homogenization_tensor(n, B) (the Dirichlet cell problems of all (n / B)^d blocks in d solves on one grid)
 against the same number of dirichlet_homogenization_tensor(B) runs on the blocks' own meshes, in one process: the two wall times
 after --warmup untimed rounds of both, their ratio and the largest relative difference of a block's tensor."""
@@ -64,6 +66,7 @@ ap.add_argument("--locations", action="store_true", help="with --extrema: where 
 ap.add_argument("--slice", type=int, default=0, metavar="N", help="the Dirichlet driver with one axis-aligned N x N slice through the "
                 "middle of the domain: wall time, sampling counters")
 ap.add_argument("--uniaxial", action="store_true", help="the uniaxial tensor driver on hypercube(n): wall time, cycles, tensor")
+ap.add_argument("--periodic", action="store_true", help="the periodic tensor driver on the torus periodic_mesh(n): wall time, cycles, tensor")
 ap.add_argument("--blocks", type=int, default=0, metavar="B", help="block upscaling of hypercube(n) in blocks of B cubes per axis "
                 "against one Dirichlet tensor run per block")
 ap.add_argument("--repeats", type=int, default=3)
@@ -147,7 +150,7 @@ if a.extrema:
                       "cell_moments_window_launches": ctx.counter("cell_moments_window_launches"),
                       "cell_extrema_window_launches": ctx.counter("cell_extrema_window_launches")}))
     sys.exit(0)
-if a.uniaxial or a.blocks:
+if a.uniaxial or a.blocks or a.periodic:
     if a.polycrystal:
         principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
         sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
@@ -168,6 +171,12 @@ if a.uniaxial or a.blocks:
     if a.uniaxial:
         r, wall = timed(lambda: driver.uniaxial_homogenization_tensor(a.n, tag, sigma_grid=sgrid, **kw))
         print(json.dumps({"config": f"uniaxial_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
+                          **common, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"], "tensor": r["tensor"].tolist(),
+                          "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
+        sys.exit(0)
+    if a.periodic:
+        r, wall = timed(lambda: driver.periodic_homogenization_tensor(a.n, tag, sigma_grid=sgrid, **kw))
+        print(json.dumps({"config": f"periodic_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
                           **common, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"], "tensor": r["tensor"].tolist(),
                           "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
         sys.exit(0)
