@@ -47,6 +47,10 @@ SIGNATURES = {
     "hmg_grid_fine_elements": (c_i64, [vp, c_int]),
     "hmg_cell_extrema_where": (c_int, [vp, vp, p_f64, p_f64, c_int, p_f64, p_f64, p_i32]),
     "hmg_grid_element_vertices": (c_int, [vp, c_int, c_i64, p_i32, p_i32]),
+    "hmg_histogram_nbins": (c_i64, [c_int, c_int, c_int]),
+    "hmg_histogram_edges": (c_int, [c_int, c_int, c_int, p_f64]),
+    "hmg_histogram_bin": (c_int, [c_i64, p_f64, c_int, c_int, c_int, p_i32]),
+    "hmg_cell_histogram": (c_int, [vp, vp, p_f64, p_f64, c_int, c_int, c_int, p_i64]),
     "hmg_grid_locate": (c_int, [vp, c_int, c_i64, p_f64, p_i32, p_i32, p_f64, p_f64]),
     "hmg_sample": (c_int, [vp, c_int, vp, p_f64, c_i64, p_f64, p_f64, p_f64, p_i32]),
     "hmg_sample_raster": (c_int, [vp, c_int, vp, p_f64, p_f64, p_f64, p_f64, c_i64, c_i64, p_f64, p_f64, p_i32]),

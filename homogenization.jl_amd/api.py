@@ -774,6 +774,77 @@ def _cell_extrema(v, implicit, xi, form, thresholds, located):
     return res
 
 
+def histogram_nbins(emin: int, emax: int, sub_bits: int = 3) -> int:
+    """Bins of the floating-point buckets (hmg_histogram_nbins): nreg + 3 with nreg = (emax - emin) 2^sub_bits regular bins, one
+    below 2^emin, one from 2^emax up, one for NaN.  -1022 <= emin < emax <= 1023, sub_bits 0 to 5; anything else is refused with
+    a message naming the parameter.  (cell_histogram serves nreg <= 1024.)"""
+    n = int(L.load().hmg_histogram_nbins(int(emin), int(emax), int(sub_bits)))
+    if n < 0:
+        raise L.HmgError(L.load().hmg_last_error().decode())
+    return n
+
+
+def histogram_edges(emin: int, emax: int, sub_bits: int = 3):
+    """The nreg + 1 edges E_i = 2^(emin + i div 2^s) (1 + (i mod 2^s) / 2^s) of the regular bins (hmg_histogram_edges), every one an
+    exact double: bin b = 1 .. nreg of cell_histogram is [E_(b-1), E_b)."""
+    edges = np.zeros(histogram_nbins(emin, emax, sub_bits) - 2)
+    L.check(L.load().hmg_histogram_edges(int(emin), int(emax), int(sub_bits), edges.ctypes.data_as(L.p_f64)))
+    return edges
+
+
+def histogram_bin(q, emin: int, emax: int, sub_bits: int = 3):
+    """The bin of every entry of q (hmg_histogram_bin; host only, no grid): int32, the shape of q.  For a q that is no NaN the
+    number of edges <= q -- np.searchsorted(histogram_edges(...), q, "right"): 0 below 2^emin (zeros, negatives, denormals),
+    nreg + 1 from 2^emax up --, nreg + 2 for a NaN.  The text the kernel of cell_histogram runs."""
+    x = np.ascontiguousarray(q, dtype=np.float64)
+    bins = np.zeros(x.shape, dtype=np.int32)
+    L.check(L.load().hmg_histogram_bin(x.size, x.ctypes.data_as(L.p_f64), int(emin), int(emax), int(sub_bits),
+                                       bins.ctypes.data_as(L.p_i32)))
+    return bins
+
+
+def cell_histogram(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=None, *, emin: int, emax: int, sub_bits: int = 3):
+    """Per coarse cell the histogram, over its fine elements T, of q_T = grad u . Q_c grad u with u = xi.x + v (xi None: 0)
+    (hmg_cell_histogram): counts (Ne, nbins) int64, nbins = histogram_nbins(emin, emax, sub_bits) <= 1027.  `xi` and `form` are
+    cell_extrema's -- the symmetric Q_c per cell, (Ne, d, d), or (Ne, d) for diagonals; None is the identity -- and so are the
+    values, bit for bit: counts[:, b:].sum(1) for an edge E_(b-1) equals cell_extrema's count for the threshold
+    nextafter(E_(b-1), -inf).  Bins: histogram_edges / histogram_bin; column 0 is everything below 2^emin (zeros, negatives),
+    column nreg + 1 everything from 2^emax up, the last column the NaN elements; a row sums to fine_elements.  The vector as
+    stored; 3D levels 1 to 6 and 2D levels 1 to 8; larger cells are refused whatever "cell_extrema_windows" says (no window
+    kernels).  One pass of 8 B/DOF; integer counts, the same in every run and for every launch shape.  On a
+    dist.PartitionedGrid Ne is the number of LOCAL cells, as in cell_extrema; shrunk and periodic grids are served.
+    Counters: "cell_histogram_launches", "cell_histogram_kernel_ns".
+    What to do with the result: fields.histogram_volume, fields.histogram_quantile, fields.histogram_tail.  No counterpart in
+    the reference."""
+    lib = L.load()
+    d = implicit.base.dim
+    ne = implicit.ncells()
+    nbins = histogram_nbins(emin, emax, sub_bits)
+    xi, xp = _vec_of(implicit, "xi", xi)
+    fp = None
+    if form is not None:
+        packed = _packed_form(form, ne, d)
+        fp = packed.ctypes.data_as(L.p_f64)
+    counts = np.zeros((ne, nbins), dtype=np.int64)
+    L.check(lib.hmg_cell_histogram(implicit.h, v.h, xp, fp, int(emin), int(emax), int(sub_bits), counts.ctypes.data_as(L.p_i64)))
+    return counts
+
+
+def _packed_form(form, ne, d):
+    """a symmetric form per cell, (ne, d, d) or (ne, d) diagonals, as the nq numbers per cell the C entry points take"""
+    q = np.asarray(form, dtype=np.float64)
+    iu = np.triu_indices(d)
+    if q.shape == (ne, d):
+        full = np.zeros((ne, d, d))
+        full[:, np.arange(d), np.arange(d)] = q
+        q = full
+    if q.shape != (ne, d, d):
+        raise ValueError(f"form must have shape ({ne}, {d}, {d}) or ({ne}, {d}), not {q.shape}")
+    if not np.array_equal(q, np.swapaxes(q, 1, 2)):
+        raise ValueError("form must be symmetric in every cell")
+    return np.ascontiguousarray(q[:, iu[0], iu[1]])
+
+
 def _points_of(implicit, points):
     d = implicit.base.dim
     p = np.ascontiguousarray(points, dtype=np.float64)

@@ -303,6 +303,9 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_extrema_where_launches") return ctx->extrema_where_launches;     // launches of the located kernels, either family
     if (n == "cell_extrema_window_launches") return ctx->extrema_window_launches;   // launches of its window kernels (option "cell_extrema_windows")
     if (n == "cell_extrema_windows") return ctx->extrema_windows;                   // ... and that option's value
+    if (n == "cell_histogram_kernel_ns") return ctx->histogram_kernel_ns;           // the last hmg_cell_histogram: kernel alone
+    if (n == "cell_histogram_launches") return ctx->histogram_launches;             // launches of its kernel
+    if (n == "cell_histogram_variant") return ctx->histogram_variant;               // option of that name
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;    // as the RCCL communicator was created; 0: none
     return -1;
 }
@@ -376,6 +379,11 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         if (value < 0 || value > 2)
             throw std::runtime_error("option cell_extrema_windows: 0, 1 or 2");
         ctx->extrema_windows = (int)value;
+    }
+    else if (n == "cell_histogram_variant") {   // how hmg_cell_histogram's counts reach the LDS histogram: 0 one add per element,
+        if (value < 0 || value > 2)             // 1 = default: a node's elements combined first, 2: and the wave's first bin summed
+            throw std::runtime_error("option cell_histogram_variant: 0, 1 or 2");   // across lanes (A/B knob: the same ints from each)
+        ctx->histogram_variant = (int)value;
     }
     else if (n == "coarse_poly")           // Chebyshev iterates per preconditioner application of the level-1 PCG (1 = Jacobi)
         ctx->coarse_poly = std::max<int>(1, std::min<int>(16, (int)value));

@@ -225,12 +225,8 @@ ElementTables build_element_tables(const LevelTables &T)
     return E;
 }
 
-}  // namespace hmg
-
-namespace {
-
 // the device copy of a level's element mask, uploaded at the first call on that level
-const uint8_t *device_mask(hmg_grid *g, int level)
+const uint8_t *device_element_mask(hmg_grid *g, int level)
 {
     FieldState &F = g->fields;
     if (F.d_mask.size() != (size_t)g->nlevels) F.d_mask.resize(g->nlevels);
@@ -243,69 +239,20 @@ const uint8_t *device_mask(hmg_grid *g, int level)
     return buf->p;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t hmg_grid_fine_elements(const hmg_grid *g, int level)
-{
-    if (!g || level < 1 || level > g->nlevels) return -1;
-    return (int64_t)1 << (g->dim * (level - 1));
-}
-
-}  // extern "C"
-
-namespace {
-
-// hmg_cell_extrema (located = false) and hmg_cell_extrema_where: one text of the checks, the rows and the launch; `who` names the
-// call in every message.  where: host, 2 (dim + 1) ints per cell.
-void cell_extrema_call(const std::string &who, bool located, hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr,
-                       const double *thresholds, double *out, int32_t *where)
+// One row per cell for the kernels of the pass over the fine elements (hmg_cell_extrema, hmg_cell_extrema_where,
+// hmg_cell_histogram): Q~ = M^T Q M, then xi~ = M^-1 xi, M = m Jinv B^-T -- cell_extrema_nrow(dim) numbers per current cell.
+// form: nq numbers per cell or null (the identity); xi: dim numbers or null (0); both checked by the caller.  One text of the
+// arithmetic for every caller: the same rows, bit for bit.  `who` names the call in the messages.
+std::vector<double> cell_form_rows(const std::string &who, const hmg_grid *g, int level, const double *xi, const double *form)
 {
     auto need = [&](bool c, const char *msg) {
         if (!c) throw std::runtime_error(who + ": " + msg);
     };
-    hmg::need(g != nullptr, "null grid");
-    need(out != nullptr, "null output array");
-    need(!located || where != nullptr, "null where array");
-    need(g->ctx != nullptr, "this grid was created without a device context (host tables only): no compute path exists on the CPU");
-    need(v != nullptr, "null vector");
-    need(v->g == g, "vector belongs to another grid");
-    if (nthr < 0 || nthr > EX_MAX_THRESHOLDS)
-        throw std::runtime_error(who + ": " + std::to_string(nthr) + " thresholds; 0 to 8 are served");
-    need(nthr == 0 || thresholds != nullptr, "null thresholds");
-    ExtremaThresholds thr;
-    for (int j = 0; j < EX_MAX_THRESHOLDS; ++j) {
-        thr.t[j] = j < nthr ? thresholds[j] : HUGE_VAL;
-        if (j < nthr && !std::isfinite(thr.t[j])) throw std::runtime_error(who + ": threshold " + std::to_string(j) + " is not finite");
-    }
-    check_vec(g, v->level, v, "v");
-    const LevelDev &lv = lev(g, v->level);
+    const LevelDev &lv = lev(g, level);
     const int dim = g->dim, nq = sym_ncomp(dim), nrow = cell_extrema_nrow(dim);
-    // the kernel: k_cell_extrema where the cell fits the LDS, the window kernels by the option "cell_extrema_windows" (1: levels
-    // that do not fit; 2: every level they address)
-    const SlabTables st = slab_tables(g, lv);
-    const bool fits = cell_extrema_ok(lv) && cell_moments_ok(lv, true), can = cell_extrema_window_ok(lv, st);
-    const int mode = g->ctx->extrema_windows;
-    const bool window = mode != 0 && can && (mode == 2 || !fits);
-    if (!window && !fits)
-        throw std::runtime_error(who + ": one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
-                                 " nodes) does not fit the LDS; the per-cell extrema serve " +
-                                 (dim == 3 ? "3D levels up to 6" : "2D levels up to 8") +
-                                 (can ? "; the context option \"cell_extrema_windows\" = 1 takes larger cells through the window kernels"
-                                      : "; no window kernel addresses this level"));
     const MeshTables &M = g->cur();
     const int64_t nc = g->md.ncells;
-    if (form)
-        for (int64_t q = 0; q < nc * nq; ++q)
-            if (!std::isfinite(form[q]))
-                throw std::runtime_error(who + ": the form of cell " + std::to_string(q / nq) + " is not finite");
-    if (xi)
-        for (int a = 0; a < dim; ++a) need(std::isfinite(xi[a]), "xi is not finite");
-    if (nc == 0) return;
-    const ElementTables &E = g->fields.elem.at(v->level - 1);
-
-    // ---- one row per cell: Q~ = M^T Q M, xi~ = M^-1 xi, M = m Jinv B^-T ----
+    const ElementTables &E = g->fields.elem.at(level - 1);
     double Bm[3][3] = {{0}}, Binv[3][3];
     for (int b = 0; b < dim; ++b)
         for (int a = 0; a < dim; ++a) Bm[a][b] = E.dirs[(size_t)b * dim + a];        // columns a, b, c
@@ -352,10 +299,74 @@ void cell_extrema_call(const std::string &who, bool located, hmg_grid *g, hmg_ve
         }
     });
     need(!singular, "a cell's geometry is singular");
+    return rows;
+}
+
+}  // namespace hmg
+
+extern "C" {
+
+int64_t hmg_grid_fine_elements(const hmg_grid *g, int level)
+{
+    if (!g || level < 1 || level > g->nlevels) return -1;
+    return (int64_t)1 << (g->dim * (level - 1));
+}
+
+}  // extern "C"
+
+namespace {
+
+// hmg_cell_extrema (located = false) and hmg_cell_extrema_where: one text of the checks, the rows and the launch; `who` names the
+// call in every message.  where: host, 2 (dim + 1) ints per cell.
+void cell_extrema_call(const std::string &who, bool located, hmg_grid *g, hmg_vec *v, const double *xi, const double *form, int nthr,
+                       const double *thresholds, double *out, int32_t *where)
+{
+    auto need = [&](bool c, const char *msg) {
+        if (!c) throw std::runtime_error(who + ": " + msg);
+    };
+    hmg::need(g != nullptr, "null grid");
+    need(out != nullptr, "null output array");
+    need(!located || where != nullptr, "null where array");
+    need(g->ctx != nullptr, "this grid was created without a device context (host tables only): no compute path exists on the CPU");
+    need(v != nullptr, "null vector");
+    need(v->g == g, "vector belongs to another grid");
+    if (nthr < 0 || nthr > EX_MAX_THRESHOLDS)
+        throw std::runtime_error(who + ": " + std::to_string(nthr) + " thresholds; 0 to 8 are served");
+    need(nthr == 0 || thresholds != nullptr, "null thresholds");
+    ExtremaThresholds thr;
+    for (int j = 0; j < EX_MAX_THRESHOLDS; ++j) {
+        thr.t[j] = j < nthr ? thresholds[j] : HUGE_VAL;
+        if (j < nthr && !std::isfinite(thr.t[j])) throw std::runtime_error(who + ": threshold " + std::to_string(j) + " is not finite");
+    }
+    check_vec(g, v->level, v, "v");
+    const LevelDev &lv = lev(g, v->level);
+    const int dim = g->dim, nq = sym_ncomp(dim);
+    // the kernel: k_cell_extrema where the cell fits the LDS, the window kernels by the option "cell_extrema_windows" (1: levels
+    // that do not fit; 2: every level they address)
+    const SlabTables st = slab_tables(g, lv);
+    const bool fits = cell_extrema_ok(lv) && cell_moments_ok(lv, true), can = cell_extrema_window_ok(lv, st);
+    const int mode = g->ctx->extrema_windows;
+    const bool window = mode != 0 && can && (mode == 2 || !fits);
+    if (!window && !fits)
+        throw std::runtime_error(who + ": one cell of level " + std::to_string(lv.level) + " (" + std::to_string(lv.nf) +
+                                 " nodes) does not fit the LDS; the per-cell extrema serve " +
+                                 (dim == 3 ? "3D levels up to 6" : "2D levels up to 8") +
+                                 (can ? "; the context option \"cell_extrema_windows\" = 1 takes larger cells through the window kernels"
+                                      : "; no window kernel addresses this level"));
+    const int64_t nc = g->md.ncells;
+    if (form)
+        for (int64_t q = 0; q < nc * nq; ++q)
+            if (!std::isfinite(form[q]))
+                throw std::runtime_error(who + ": the form of cell " + std::to_string(q / nq) + " is not finite");
+    if (xi)
+        for (int a = 0; a < dim; ++a) need(std::isfinite(xi[a]), "xi is not finite");
+    if (nc == 0) return;
+    const ElementTables &E = g->fields.elem.at(v->level - 1);
+    const std::vector<double> rows = cell_form_rows(who, g, v->level, xi, form);
 
     hmg_ctx *c = g->ctx;
     HIPCHK(hipSetDevice(c->device));
-    const uint8_t *d_mask = device_mask(g, v->level);
+    const uint8_t *d_mask = device_element_mask(g, v->level);
     const size_t nout = (size_t)(2 + nthr) * (size_t)nc;
     const size_t row_bytes = sizeof(double) * rows.size(), out_bytes = sizeof(double) * nout;
     const size_t code_bytes = sizeof(int32_t) * 2 * (size_t)nc;

@@ -203,6 +203,45 @@ __device__ __forceinline__ void extrema_node(const double *xs, int L, int len, i
         }
 }
 
+// The values of one node alone, for a kernel that does something else with them (hmg_histogram.hip): extrema_node's reads and
+// expressions, and behind them the fence of its located form, so that what the caller does with the values cannot reach back into
+// how the products are fused -- the bits of hmg_cell_extrema.  q[k] of an element whose bit of the mask is clear is some number.
+template <int DIM>
+__device__ __forceinline__ void extrema_values(const double *xs, int L, int len, int A, int B, int lo, int hi, const double *Q,
+                                               const double *X, double *q)
+{
+    constexpr int NEL = DIM == 3 ? 6 : 2;
+    auto at = [&](int off) { return lds_ld(xs + min(max(L + off, lo), hi)); };
+    const double u0 = lds_ld(xs + L);
+    if constexpr (DIM == 3) {
+        const double ua = at(A), ub = at(len + 1 - B), uc = at(-len), uab = at(len), uac = at(A + 1 - len), ubc = at(1 - B),
+                     us = at(1);
+        auto form = [&](double ga, double gb, double gc) {
+            ga += X[0];
+            gb += X[1];
+            gc += X[2];
+            return ga * (Q[0] * ga + Q[1] * gb + Q[2] * gc) + gb * (Q[3] * gb + Q[4] * gc) + gc * (Q[5] * gc);
+        };
+        q[0] = form(ua - u0, uab - ua, us - uab);      // a, b, c
+        q[1] = form(ua - u0, us - uac, uac - ua);      // a, c, b
+        q[2] = form(uab - ub, ub - u0, us - uab);      // b, a, c
+        q[3] = form(us - ubc, ub - u0, ubc - ub);      // b, c, a
+        q[4] = form(uac - uc, us - uac, uc - u0);      // c, a, b
+        q[5] = form(us - ubc, ubc - uc, uc - u0);      // c, b, a
+    } else {
+        const double ua = at(len), ub = at(-len), us = at(1);
+        auto form = [&](double ga, double gb) {
+            ga += X[0];
+            gb += X[1];
+            return ga * (Q[0] * ga + Q[1] * gb) + gb * (Q[2] * gb);
+        };
+        q[0] = form(ua - u0, us - ua);                 // a, b
+        q[1] = form(us - ub, ub - u0);                 // b, a
+    }
+#pragma unroll
+    for (int k = 0; k < NEL; ++k) asm volatile("" : "+v"(q[k]));
+}
+
 // One cell's results: lanes by data-parallel moves, waves through LDS (red: [NW][2] maximum, minimum; redc: [NW][8]), one thread
 // per output, out[cell][0 .. 2 + nthr).  The barrier inside also says that every wave is done with the cell's image.
 // (out and cell apart: the row's address formed here, behind the loops, keeps k_cell_extrema<3, *> free of scalar spills)

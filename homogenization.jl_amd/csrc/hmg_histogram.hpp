@@ -1,0 +1,31 @@
+// Per-cell histograms of a quadratic form of the fine-element gradients of a level vector (include/hmg.h: hmg_cell_histogram):
+// what the host module (hmg_histogram.cpp) and the kernel (hmg_histogram.hip) share.  The binning rule itself is
+// hmg_histogram_device.hpp.
+#pragma once
+
+#include "hmg_device.hpp"
+#include "hmg_histogram_device.hpp"
+
+namespace hmg {
+
+// How a workgroup brings its counts into the LDS histogram (the context option "cell_histogram_variant"; the counts are the same
+// integers from each, DESIGN section 4 has what each costs):
+//   HIST_PLAIN  one LDS add per existing element
+//   HIST_NODE   the 6 (2D: 2) elements of a node are combined in registers first: one add per distinct bin of the node (the
+//               default: the flattest of the three -- a field that is constant over a cell costs what a random one costs)
+//   HIST_WAVE   ... and per element slot the bin of the wave's first active lane is summed across the wave and added once by one
+//               lane; lanes with another bin add for themselves
+constexpr int HIST_PLAIN = 0, HIST_NODE = 1, HIST_WAVE = 2, HIST_VARIANTS = 3;
+constexpr int HIST_DEFAULT = HIST_NODE;
+
+// LDS of one workgroup: the lattice image with its guard, behind it nbins counters
+size_t cell_histogram_lds_bytes(const LevelDev &lv, int nbins);
+// the levels served: those whose cell fits the LDS together with the largest histogram (3D up to 6, 2D up to 8)
+bool cell_histogram_ok(const LevelDev &lv);
+// out[c * nbins + b], nbins = rule.nreg + 3: the number of fine elements of cell c whose value falls into bin b, for the first
+// ncells columns of v (column stride lv.ld).  elem_mask and rows are those of launch_cell_extrema, and so are the values, bit for
+// bit.  Integer counts, no global atomics: the same ints in every run, for every grid size and from every variant.
+void launch_cell_histogram(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const uint8_t *elem_mask,
+                           const double *rows, const HistogramRule &rule, int variant, int *out);
+
+}  // namespace hmg

@@ -10,6 +10,7 @@
 //   hmg_fcg.cpp      flexible CG around the V-cycle
 //   hmg_fields.cpp   per-cell gradient moments of a level vector and of a pair of them, through the LDS-resident or the window kernels
 //   hmg_extrema.cpp  fine-element table of a level; per-cell extrema and exceedance counts of a quadratic form of the gradient
+//   hmg_histogram.cpp  the binning rule's host twin; per-cell histograms of that form over the fine elements
 //   hmg_sample.cpp   locator of the current cells; a level vector's value, gradient and cell at points and on raster slices
 //   hmg_capi.cpp     vector operations, primitives, right-hand sides, integrals: argument checks and one call each
 //
@@ -271,6 +272,9 @@ struct hmg_ctx {
     int64_t extrema_kernel_ns = 0;           // the last hmg_cell_extrema: its kernel (device events)
     int64_t extrema_where_kernel_ns = 0;     // the last hmg_cell_extrema_where, likewise: a counter of its own, so that one process times both
     int64_t extrema_where_launches = 0;      // launches of the located kernels (hmg_ctx_counter "cell_extrema_where_launches")
+    int64_t histogram_kernel_ns = 0;         // the last hmg_cell_histogram: its kernel (device events)
+    int64_t histogram_launches = 0;          // launches of k_cell_histogram (hmg_ctx_counter "cell_histogram_launches")
+    int histogram_variant = 1;               // option "cell_histogram_variant": how counts reach the LDS histogram (hmg_histogram.hpp: HIST_DEFAULT; the same ints from each)
     int64_t sample_launches = 0;             // launches of k_sample (hmg_sample, hmg_sample_raster)
     int64_t sample_kernel_ns = 0, sample_download_ns = 0;   // the last of those calls: its kernel (device events), its downloads (host clock)
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window
@@ -585,6 +589,13 @@ void release_weight_cache(hmg_grid *g);
 // the level's rolling-window lists (those set_slab hands to the operator apply), without touching the grid's launch state: what
 // the window kernels of the per-cell moments and extrema walk
 SlabTables slab_tables(const hmg_grid *g, const LevelDev &lv);
+
+// ---- hmg_extrema.cpp ----
+// what the calls of the pass over the fine elements share (hmg_cell_extrema, hmg_cell_extrema_where; hmg_histogram.cpp:
+// hmg_cell_histogram): the device copy of a level's element mask, uploaded at the first call on that level, and the folded row of
+// every current cell -- Q~ = M^T Q M and xi~ = M^-1 xi, cell_extrema_nrow(dim) numbers --, one text of the arithmetic
+const uint8_t *device_element_mask(hmg_grid *g, int level);
+std::vector<double> cell_form_rows(const std::string &who, const hmg_grid *g, int level, const double *xi, const double *form);
 
 // ---- hmg_sample.cpp ----
 // hmg_ctx_counter "sample_locator_builds" (0), "sample_locator_bytes" (1), "sample_locator_max_candidates" (2): locators built in

@@ -640,11 +640,29 @@ def _large_cells(ctx, on: bool):
             ctx.set_option(name, prev[name])
 
 
+def _histogram_rule(histogram):
+    """The `histogram` argument of dirichlet_homogenization as keywords of api.cell_histogram: None / False -> None, True -> the
+    default rule, a dict of "emin", "emax" and, optionally, "sub_bits" -> itself, checked (api.histogram_nbins refuses parameters
+    outside the rule, and the driver more bins than api.cell_histogram serves, before anything is solved)."""
+    if histogram is None or histogram is False:
+        return None
+    if histogram is True:
+        rule = {"emin": -24, "emax": 8, "sub_bits": 3}
+    else:
+        rule = dict(histogram)
+        if not {"emin", "emax"} <= set(rule) <= {"emin", "emax", "sub_bits"}:
+            raise ValueError('histogram must be True or a dict of "emin", "emax" and, optionally, "sub_bits"')
+        rule = {"emin": int(rule["emin"]), "emax": int(rule["emax"]), "sub_bits": int(rule.get("sub_bits", 3))}
+    if api.histogram_nbins(**rule) > 1027:
+        raise ValueError("histogram: api.cell_histogram serves at most 1024 regular bins ((emax - emin) 2^sub_bits)")
+    return rule
+
+
 def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None, *, ctx=None, sigma_grid=None, seed: int = 0,
                              values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                              fields: bool = False, save=None, cond=None, smoothing_steps: int = 3, max_cycles: int = 200,
                              large_cells: bool = False, extrema: bool = False, thresholds=None, slices=None,
-                             locations: bool = False):
+                             locations: bool = False, histogram=None):
     """The plain Dirichlet cell problem on `hypercube(eltype, n)`: find v, zero on the boundary, with
     a(v, w) = -int sigma xi . grad w for all such w (lambda = 0), on `refinements` + 1 grids; then, from the per-cell gradient
     moments of u = xi.x + v (api.cell_moments), the row of the homogenized tensor in two forms:
@@ -676,7 +694,13 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     `slices`: a list of rasters (origin, du, dv, nu, nv) -- pixel (a, b) at origin + a du + b dv --; u = xi.x + v is sampled on each
     from the converged corrector on the device (api.sample_raster; any top level) and "slices" in the returned dict is a list of
     dicts with "value", "cell" (nv, nu), "gradient", "flux" (nv, nu, dim) and "energy_density" (nv, nu), NaN / -1 outside the
-    domain; with `save` slice i is written to `save`_slice<i>.vts (vtk.export_slice).  No counterpart in the reference."""
+    domain; with `save` slice i is written to `save`_slice<i>.vts (vtk.export_slice).
+    `histogram`: one more pass over the fine elements (api.cell_histogram with Q = sigma_c / energy_form: the bins are in units
+    of the mean energy density and need no guessing) says how the energy density is distributed.  A dict of "emin", "emax",
+    "sub_bits", or True for emin = -24, emax = 8, sub_bits = 3.  Adds "energy_density_histogram": a dict of "edges"
+    (api.histogram_edges), "counts" (Ne, nbins) and "volume" (nbins: the volume of the domain per bin, fields.histogram_volume;
+    fields.histogram_quantile reads medians and tails off it).  Top levels up to 6 in 3D and 8 in 2D: `large_cells` does not extend
+    it.  Every other entry keeps its bits.  No counterpart in the reference."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -684,6 +708,7 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     xi = random_unit_vec(dim) if xi is None else np.asarray(xi, dtype=np.float64)
     if xi.shape != (dim,):
         raise ValueError(f"xi must have {dim} entries")
+    hist_rule = _histogram_rule(histogram)
     base = hypercube(eltype, n)
     if cond is None:
         if sigma_grid is None:
@@ -734,6 +759,11 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
             if save is not None:
                 vtk.export_points(f"{save}_peaks", peaks["peak_location"], {"peak_energy_density": qmax, "cell": cells})
         out.update(peaks)
+    if hist_rule is not None:
+        counts = api.cell_histogram(xv, implicit, xi, cell_fields.energy_form(cond) / out["energy_form"], **hist_rule)
+        out["energy_density_histogram"] = {
+            "edges": api.histogram_edges(**hist_rule), "counts": counts,
+            "volume": cell_fields.histogram_volume(counts, vol, api.fine_elements(implicit, total_grids))}
     if slices is not None:
         out["slices"] = []
         for i, (origin, du, dv, nu, nv) in enumerate(slices):

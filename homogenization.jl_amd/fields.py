@@ -3,7 +3,8 @@ What one does with a corrector once it is solved, from two per-cell quantities (
 hmg_cell_moments): the mean gradient `mean` (Ne, d) and the Gram tensor of the gradient `gram` (Ne, d, d) of u = xi.x + v over
 every coarse cell -- and, for two correctors, from their symmetrised cross moment `pair` (Ne, d, d) (api.cell_pair_moments:
 pair_energy, tensor_sensitivity) -- and, for the pass over the fine elements (api.cell_extrema), the forms to give it and what
-its extrema and counts mean (energy_form, flux_form, exceedance_volume, concentration) -- and, for point samples (api.sample,
+its extrema and counts mean (energy_form, flux_form, exceedance_volume, concentration) and what its histograms say
+(api.cell_histogram: histogram_volume, histogram_quantile, histogram_tail) -- and, for point samples (api.sample,
 api.sample_raster), the flux and the energy density at every point (sample_flux, sample_energy_density, line_points).  Plain numpy on those arrays; nothing here touches a level vector or the device.
 
 `cond` is the conductivity per cell as `L2PlusDivAGrad` takes it: (Ne, d), the diagonals of diagonal tensors, or (Ne, d, d), full
@@ -158,6 +159,67 @@ def exceedance_volume(counts, volumes, nel):
 def concentration(qmax, mean_density):
     """Peak over mean: qmax (Ne,) over a mean density -- a number (the homogenized energy density, say) or one per cell."""
     return np.asarray(qmax, dtype=np.float64) / np.asarray(mean_density, dtype=np.float64)
+
+
+# ---- histograms over the fine elements (api.cell_histogram): counts (Ne, nbins), nbins = nreg + 3 -- column 0 below the first
+# edge, columns 1 .. nreg between the edges, column nreg + 1 from the last edge up, the last column NaN ---------------------------
+def histogram_volume(counts, volumes, nel, labels=None):
+    """Volume per bin over all cells: sum_c counts[c, b] |c| / nel, (nbins,) -- the fine elements of a cell all have the volume
+    |c| / nel, nel = api.fine_elements(implicit, level); the entries sum to the volume of the cells.  With `labels` (Ne,): one such
+    row per label, {label: (nbins,)} over the cells that carry it (the convention of phase_moments); the rows add up to the row
+    without labels."""
+    counts = np.asarray(counts)
+    vol = np.asarray(volumes, dtype=np.float64)
+    if counts.ndim != 2 or vol.shape != (counts.shape[0],):
+        raise ValueError("counts must be (Ne, nbins) and volumes (Ne,)")
+    if nel <= 0:
+        raise ValueError("nel must be positive")
+    w = vol / float(nel)
+    if labels is None:
+        return w @ counts.astype(np.float64)
+    labels = np.asarray(labels)
+    if labels.shape != vol.shape:
+        raise ValueError("labels must be (Ne,)")
+    out = {}
+    for lab in np.unique(labels):
+        sel = labels == lab
+        out[lab.item() if hasattr(lab, "item") else lab] = w[sel] @ counts[sel].astype(np.float64)
+    return out
+
+
+def histogram_quantile(volume_per_bin, edges, p):
+    """The interval (lo, hi) of the bin that contains the p-quantile of q, 0 <= p <= 1, by volume: the first bin at which the
+    cumulated volume reaches p times the total.  An interval, not an interpolated number: within a bin nothing is known.  The
+    bin below the first edge is (-inf, E_0), the one from the last edge up (E_nreg, inf).  volume_per_bin is histogram_volume's
+    row, (len(edges) + 2,); a NaN bin behind it must be empty (a NaN has no place in an order)."""
+    vol = np.asarray(volume_per_bin, dtype=np.float64)
+    edges = np.asarray(edges, dtype=np.float64)
+    n = edges.shape[0] + 1
+    if vol.ndim != 1 or vol.shape[0] not in (n, n + 1):
+        raise ValueError(f"volume_per_bin must have {n} entries (or {n + 1} with the NaN bin) for {edges.shape[0]} edges")
+    if vol.shape[0] == n + 1 and vol[n] != 0.0:
+        raise ValueError("the NaN bin is not empty: no quantiles")
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("p must lie in [0, 1]")
+    vol = vol[:n]
+    if (vol < 0.0).any() or not vol.sum() > 0.0:
+        raise ValueError("volume_per_bin must be non-negative and not all zero")
+    cum = np.cumsum(vol)
+    b = int(np.searchsorted(cum, p * cum[-1], side="left"))
+    b = min(b, n - 1)
+    while vol[b] == 0.0:                                              # (p = 0: the first bin that holds something)
+        b += 1
+    bounds = np.concatenate(([-np.inf], edges, [np.inf]))
+    return float(bounds[b]), float(bounds[b + 1])
+
+
+def histogram_tail(counts):
+    """Elements at or above each edge: (Ne, nreg + 1) int64, column i = the number of fine elements with q >= E_i (the NaN bin
+    takes no part).  Column i equals api.cell_extrema's count for the threshold nextafter(E_i, -inf)."""
+    counts = np.asarray(counts)
+    if counts.ndim != 2 or counts.shape[1] < 4:
+        raise ValueError("counts must be (Ne, nbins) with nbins >= 4")
+    return np.ascontiguousarray(np.cumsum(counts[:, -2:0:-1].astype(np.int64), axis=1)[:, ::-1])
 
 
 # ---- point samples (api.sample, api.sample_raster): the flux and the energy density of u at every point --------------------

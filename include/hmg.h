@@ -518,6 +518,51 @@ int hmg_cell_extrema_where(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, 
 int hmg_grid_element_vertices(const hmg_grid *grid, int level, int64_t n, const int32_t *codes /* n */,
                               int32_t *nodes /* (dim+1)*n: 0-based HIERARCHICAL row ids */);
 
+/* ---- per-cell histograms over the fine elements (no counterpart in the reference) ---------------------------------------
+ * How q_T of hmg_cell_extrema is DISTRIBUTED over the fine elements of every coarse cell: counts per bin, one pass, no threshold
+ * to guess.
+ * The binning rule.  Bins are floating-point buckets: emin < emax (integers, -1022 <= emin, emax <= 1023) and sub_bits s in
+ * 0..5 give nreg = (emax - emin) 2^s regular bins with the edges
+ *     E_i = 2^(emin + i div 2^s) (1 + (i mod 2^s) / 2^s),     i = 0 .. nreg          (every edge an exact double)
+ * and nbins = nreg + 3:  bin(q) = the number of edges <= q (numpy: searchsorted(E, q, side = "right")) for every q that is no
+ * NaN -- bin 0 holds everything below 2^emin (zeros of either sign, negatives, -inf, denormals), bin b = 1..nreg is
+ * [E_(b-1), E_b), bin nreg + 1 holds q >= 2^emax (+inf included) -- and a NaN of either sign goes to bin nreg + 2.  The bin is
+ * found by integer arithmetic on the double's high word (positive doubles order like their bit patterns): no logarithm, no
+ * rounding, one text for host and device.
+ * hmg_histogram_nbins: nreg + 3, or -1 (hmg_last_error set) for parameters outside the rule.  hmg_histogram_edges: the nreg + 1
+ * edges.  hmg_histogram_bin: the rule's host twin, bins[i] = bin(q[i]) for n values; no grid needed.  All three refuse parameters
+ * outside the rule with a message that names the call and the parameter: sub_bits outside 0..5, emin or emax outside
+ * -1022..1023, emin >= emax.  These three serve every rule, up to (-1022, 1023, 5); hmg_cell_histogram keeps a cell's histogram
+ * in LDS and serves nreg <= 1024 (nbins <= 1027).
+ *
+ * hmg_cell_histogram: counts[c * nbins + b] = the number of fine elements T of the current coarse cell c with bin(q_T) = b.
+ * q_T, xi, form and the row of 9 (2D: 5) numbers per cell are exactly hmg_cell_extrema's -- the same host function folds the
+ * rows, the kernel evaluates a node with the same expressions: the values are hmg_cell_extrema's bit for bit, so the number of
+ * elements at or above an edge E equals hmg_cell_extrema's count for the threshold nextafter(E, -inf).  Every existing fine
+ * element is counted exactly once: a row sums to hmg_grid_fine_elements, and the NaN bin counts the elements hmg_cell_extrema
+ * would turn into NaN extrema.
+ * One kernel of its own reads the column once (8 B/DOF) and one byte of element mask per node; the histogram of a cell sits in
+ * LDS behind the lattice image, is written with LDS integer adds and flushed as one row of nbins 32-bit counts.  No global atomics
+ * and no floating-point sums: the same ints in every run and for every launch shape.
+ * Otherwise the rules of hmg_cell_extrema: the vector as stored, the current cells after a shrink, the local cells of a
+ * partitioned grid with nothing exchanged (form and counts indexed by LOCAL cell), periodic grids served; it allocates from the
+ * pool (rows, nbins * ncells 32-bit counts; the level's element mask once) and synchronises.  hmg_ctx_counter
+ * "cell_histogram_launches" counts the kernel launches, "cell_histogram_kernel_ns" is the last call's kernel time.
+ * Served: 3D levels 1 to 6, 2D levels 1 to 8 -- the levels whose cell fits the LDS together with the largest histogram.  Larger
+ * cells (3D level 7, 2D levels 9-11) are refused with a message naming the call and the level, whatever "cell_extrema_windows"
+ * says: this call has no window kernels.
+ * Refused as well, with a message naming the call: a grid without a device context, a null v or counts, a vector of another grid,
+ * bin parameters outside the rule (as above) or more than 1024 regular bins, xi or form entries that are not finite.
+ * hmg_ctx_set_option "cell_histogram_variant" (0, 1 = default, 2) chooses how a workgroup brings its counts into LDS -- one add
+ * per element, a node's elements combined in registers first, and on top of that the wave's first bin summed across its lanes: a
+ * measurement knob, the counts are the same ints from each. */
+int64_t hmg_histogram_nbins(int emin, int emax, int sub_bits);
+int hmg_histogram_edges(int emin, int emax, int sub_bits, double *edges /* nreg + 1 */);
+int hmg_histogram_bin(int64_t n, const double *q /* n */, int emin, int emax, int sub_bits, int32_t *bins /* n */);
+int hmg_cell_histogram(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
+                       const double *form /* nq*ncells, or NULL */, int emin, int emax, int sub_bits,
+                       int64_t *counts /* host, nbins*ncells, row per cell */);
+
 /* ---- sampling a level vector at points and on raster slices (no counterpart in the reference) --------------------------
  * For a point x of physical space, a level and a level vector v of that level, as stored (no interface sum, no mask):
  *   cell      the current coarse cell (the prefix after hmg_grid_shrink) that contains x: all barycentric coordinates of x in it

@@ -437,6 +437,36 @@ function element_vertices(g::HipGrid{dim}, level::Integer, codes::AbstractVector
     check(ccall((:hmg_grid_element_vertices, LIB), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Int32}, Ptr{Int32}), g.h, level, length(c), c, nodes))
     nodes
 end
+# per-cell histograms over the fine elements (hmg_cell_histogram; api.cell_histogram): how the q of cell_extrema is distributed.
+# Bins are floating-point buckets: emin < emax and sub_bits in 0:5 give nreg = (emax - emin) 2^sub_bits regular bins with exact edges
+# (histogram_edges, nreg + 1 of them) and nbins = nreg + 3 (histogram_nbins): bin 1 of the result holds everything below 2^emin, bins
+# 2:nreg+1 the intervals [E_(b-1), E_b), bin nreg+2 everything from 2^emax up, bin nreg+3 the NaNs.  counts is nbins x Ne, a column per
+# cell that sums to fine_elements; the values are cell_extrema's, bit for bit.  histogram_bin is the rule on the host (0-based bins).
+# 3D levels up to 6, 2D levels up to 8 and nreg <= 1024; larger cells are refused (no window kernels).
+histogram_nbins(emin::Integer, emax::Integer, sub_bits::Integer = 3) =
+    Int(ccall((:hmg_histogram_nbins, LIB), Int64, (Cint, Cint, Cint), emin, emax, sub_bits))
+function histogram_edges(emin::Integer, emax::Integer, sub_bits::Integer = 3)
+    n = histogram_nbins(emin, emax, sub_bits)
+    edges = zeros(Float64, max(n - 2, 1))
+    check(ccall((:hmg_histogram_edges, LIB), Cint, (Cint, Cint, Cint, Ptr{Float64}), emin, emax, sub_bits, edges))
+    edges
+end
+function histogram_bin(q::AbstractVector{Float64}, emin::Integer, emax::Integer, sub_bits::Integer = 3)
+    x = collect(Float64, q)
+    bins = zeros(Int32, length(x))
+    check(ccall((:hmg_histogram_bin, LIB), Cint, (Int64, Ptr{Float64}, Cint, Cint, Cint, Ptr{Int32}), length(x), x, emin, emax, sub_bits, bins))
+    bins
+end
+function cell_histogram(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}} = nothing,
+                        form::Union{Nothing,AbstractMatrix{Float64}} = nothing; emin::Integer, emax::Integer, sub_bits::Integer = 3)
+    g = v.grid
+    nbins = histogram_nbins(emin, emax, sub_bits)
+    counts = zeros(Int64, max(nbins, 0), ncells(g))
+    check(ccall((:hmg_cell_histogram, LIB), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint, Ptr{Int64}),
+                g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), form === nothing ? C_NULL : Matrix{Float64}(form),
+                emin, emax, sub_bits, counts))
+    counts
+end
 # Point samples of a level vector (hmg_grid_locate, hmg_sample, hmg_sample_raster; api.locate / sample / sample_raster): points is
 # dim x n.  locate (host, a grid without a context too): cell (n; -1: none), nodes ((dim+1) x n, 0-BASED hierarchical ids: add 1 for
 # rows of Matrix(v)), weights ((dim+1) x n), gweights (dim x (dim+1) x n).  sample / sample_raster: u = ξ⋅x + v, its gradient
