@@ -282,10 +282,10 @@ def test_partitioned_grid_is_indexed_by_local_cell(ctx, shapes, name, level):
 
 
 def test_periodic_grid(ctx):
-    """A torus (driver.periodic_mesh, Tri64, n = 3, level 4).  The statement's helpers (tests/_cell_extrema_form.py) take the fine
-    nodes' positions from the oracle's construct_full_grid, which knows no period: they cannot express the minimal-image corners.
-    So here the invariants -- shape, row sums, an empty NaN bin, the same bits twice -- and the exact cross-check against
-    hmg_cell_extrema, which serves the torus with the same rows."""
+    """A torus (driver.periodic_mesh, Tri64, n = 3, level 4): the invariants -- shape, row sums, an empty NaN bin, the same bits
+    twice -- and the exact cross-check against hmg_cell_extrema, which serves the torus with the same rows.  The histogram of a
+    torus against the statement (on the cells as disjoint simplices, whose corners are the minimal-image ones) and against an
+    ordinary grid of those simplices, bit for bit, is tests/test_gpu_periodic_fields.py::test_cell_histogram."""
     level = 4
     mesh = driver.periodic_mesh(hmg.Tri64, 3)
     g = hmg.ImplicitFineGrid(ctx, mesh, level)

@@ -4,7 +4,8 @@ apply, smoother or interface kernel knows about the torus: the tests hold every 
 solve on the complement of the constants, converged correctors, the exact savings of hmg_vcycle and the driver to statements
 that never see the torus connectivity (tests/_periodic_form.py): the cell-local part from the oracle on the cells as disjoint
 simplices, the sum over copies from a grouping of the fine nodes by position modulo the period, converged answers from a sparse
-direct solve of the textbook system on the explicitly refined disjoint simplices.  Tolerances are the project's: primitives 1e-11,
+direct solve of the textbook system on the explicitly refined disjoint simplices.  The grid, its oracle twin and the check of
+the primitives are tests/_periodic_device.py's, shared with tests/test_gpu_periodic_general.py (general tori, full tensors).  Tolerances are the project's: primitives 1e-11,
 level-1 solve 1e-10 (tests/test_gpu_coarse_solve.py), converged answers and drivers 1e-8 at tolerance 1e-12.
 """
 import numpy as np
@@ -14,17 +15,14 @@ import homogenization_jl_amd as hmg
 from homogenization_jl_amd import driver
 
 import _coarse_form as CF
-from _periodic_form import TorusSystem, broadcast, disjoint, fine_ids, node_sum
+import _tensor_sigma_form as TS
+from _periodic_device import Torus, check_primitives, per_cube, relerr
+from _periodic_form import DEN, TorusSystem, fine_ids, general_torus
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-11
 EXACT_OPTIONS = ("lean_post", "lazy_post", "lazy_top", "lazy_dead", "lazy_pre", "fold_x", "swap_rp", "fold_prolong", "prolong_in_image",
                  "fold_faces", "fold_restrict", "fold_coarse_x", "zero_entry", "cell_order", "lazy_r", "lazy_ap", "lazy_x")
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 @pytest.fixture(scope="module")
@@ -32,93 +30,6 @@ def ctx():
     c = hmg.Context(0)
     yield c
     c.close()
-
-
-def per_cube(mesh, sgrid):
-    """a field per unit cube, C order of the cube's multi-index, on the cells of driver.periodic_mesh"""
-    ncubes = mesh.nodes.shape[0]
-    return np.repeat(np.asarray(sgrid).reshape((ncubes,) + np.shape(sgrid)[mesh.dim:]), mesh.elements.shape[0] // ncubes, axis=0)
-
-
-class Torus:
-    """3 x 3 (x 3) unit cubes on a torus, sigma in {1, 9} per cube and direction: the device grid, and the oracle on the disjoint
-    simplices (no interface: cell-local operators only)."""
-
-    def __init__(self, O, ctx, dim, levels, seed, classes=0):
-        self.O, self.dim, self.levels = O, dim, levels
-        self.mesh = driver.periodic_mesh(hmg.Tet64 if dim == 3 else hmg.Tri64, 3)
-        self.rng = np.random.default_rng(seed)
-        self.sig = per_cube(self.mesh, self.rng.choice([1.0, 9.0], size=(3,) * dim + (dim,)))
-        nodes, elements = disjoint(self.mesh)
-        self.dmesh = O.Mesh(nodes, elements)
-        self.impl = O.ImplicitFineGrid.create(self.dmesh, levels)
-        self.cons = O.ZeroDirichletConstraint(*O.list_boundary_nodes_edges_faces(self.dmesh))      # (never applied)
-        ctx.set_option("weight_cache_classes", classes)                  # (read where the operator is set)
-        try:
-            self.g = hmg.ImplicitFineGrid(ctx, self.mesh, levels)
-            self.A = hmg.L2PlusDivAGrad(self.g, 0.7, self.sig)
-        finally:
-            ctx.set_option("weight_cache_classes", 0)
-        self._parts, self._ids = {}, {}
-
-    def op(self, lev, lam):
-        O = self.O
-        if lev not in self._parts:
-            l = self.impl.reference.levels[lev - 1]
-            self._parts[lev] = (O.build_local_diffusion_operators(l), O.mass_matrix(l))
-        return O.L2PlusDivAGrad(*self._parts[lev], self.cons, lam, self.sig)
-
-    def ids(self, lev):
-        if lev not in self._ids:
-            self._ids[lev] = fine_ids(self.g, lev)
-        return self._ids[lev]
-
-    def rand(self, lev):
-        return np.asfortranarray(self.rng.standard_normal((self.impl.nf(lev), self.mesh.elements.shape[0])))
-
-    def dev(self, lev, a):
-        return hmg.DeviceMatrix(self.g, lev).from_host(a)
-
-    def close(self):
-        self.g.close()
-
-
-def check_primitives(c, levels_checked, lams=(0.7, 0.0)):
-    """hmg_apply_ex and hmg_residual against the oracle's cell-local mul! on the disjoint simplices; hmg_interface_sum against the
-    sum over the copies of every torus node, found by position; the copies agree bitwise; hmg_vec_norm_unique counts a node once"""
-    O = c.O
-    for lev in levels_checked:
-        ids, n = c.ids(lev)
-        for lam in lams:
-            c.A.lam = lam
-            x, src = c.rand(lev), c.rand(lev)
-            want = src.copy(order="F")
-            O.mul(-1.3, c.dmesh, c.op(lev, lam), x, want)
-            out = hmg.DeviceMatrix(c.g, lev)
-            dx, dsrc = c.dev(lev, x), c.dev(lev, src)
-            c.A._bind()
-            hmg.apply_ex(-1.3, c.g, dx, dsrc, out, constrain=True)
-            e_apply = relerr(out.to_host(), want)
-            wres = src.copy(order="F")
-            O.mul(-1.0, c.dmesh, c.op(lev, lam), x, wres)
-            dst = hmg.LevelState(c.g, lev)
-            dst.x.from_host(x)
-            dst.b.from_host(src)
-            hmg.local_residual(c.g, c.A, dst, lev)
-            e_res = relerr(dst.r.to_host(), wres)
-            hmg.broadcast_interfaces(out, c.g, lev)
-            got = out.to_host()
-            e_sum = relerr(got, broadcast(want, ids, n))
-            u = np.zeros(n)
-            u[ids.ravel()] = got.ravel()
-            np.testing.assert_array_equal(u[ids], got)                   # every copy of a torus node holds the same bits
-            nu = hmg.norm_unique(out)
-            e_norm = abs(nu - np.linalg.norm(u)) / np.linalg.norm(u)
-            print(f"level {lev}, lambda {lam}: apply_ex {e_apply:.2e}  residual {e_res:.2e}  interface sum {e_sum:.2e}  norm_unique {e_norm:.2e}")
-            assert e_apply <= TOL and e_res <= TOL and e_sum <= TOL and e_norm <= TOL, (lev, lam, e_apply, e_res, e_sum, e_norm)
-            for v in (out, dx, dsrc):
-                v.close()
-            dst.close()
 
 
 @pytest.fixture(scope="module")
@@ -220,21 +131,47 @@ def test_level_1_solve_against_the_pseudo_inverse(ctx, shape, contrast):
 
 
 # ---- converged correctors ------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module", params=[(2, 2), (3, 1)], ids=["2d", "3d"])
-def converged(request, oracle):
-    """the torus, a random two-valued sigma per cube and direction, and the direct solution of the corrector of e_1"""
-    dim, refinements = request.param
-    mesh = driver.periodic_mesh(hmg.Tet64 if dim == 3 else hmg.Tri64, 3)
-    cond = per_cube(mesh, np.random.default_rng(21 + dim).choice([1.0, 9.0], size=(3,) * dim + (dim,)))
-    sys = TorusSystem(oracle, mesh, cond, refinements)
+def _full_per_cube(dim, mesh):
+    """one full SPD tensor per cube: 3D the grains of driver.generate_polycrystal(3, 3, 8), 2D nine of random_spd"""
+    sg = driver.generate_polycrystal(3, 3, 8) if dim == 3 else TS.random_spd(np.random.default_rng(8), 9, 2).reshape(3, 3, 2, 2)
+    return per_cube(mesh, sg)
+
+
+def _converged_case(oracle, dim, refinements, general, full):
+    """the torus, its medium, and the direct solution of the corrector of e_1"""
+    if general:
+        mesh, den = general_torus((3,) * dim, 19 + dim), DEN
+    else:
+        mesh, den = driver.periodic_mesh(hmg.Tet64 if dim == 3 else hmg.Tri64, 3), 1
+    if full:
+        cond = _full_per_cube(dim, mesh)
+    else:
+        cond = per_cube(mesh, np.random.default_rng(21 + dim).choice([1.0, 9.0], size=(3,) * dim + (dim,)))
+    sys = TorusSystem(oracle, mesh, cond, refinements, den=den)
     xi = np.eye(dim)[0]
     v = sys.corrector(xi)
     return dim, refinements, mesh, cond, sys, xi, v, sys.energy(v, xi)
 
 
-@pytest.mark.parametrize("how", ["cg", "jacobi", "chebyshev", "fcg"])
-def test_converged_corrector(ctx, converged, how):
-    dim, refinements, mesh, cond, sys, xi, v, sigma11 = converged
+@pytest.fixture(scope="module", params=[(2, 2), (3, 1)], ids=["2d", "3d"])
+def converged(request, oracle):
+    """the unit-cube torus, a random two-valued sigma per cube and direction, and the direct solution of the corrector of e_1"""
+    return _converged_case(oracle, *request.param, general=False, full=False)
+
+
+MEDIA = {"full": (False, True), "general-diagonal": (True, False), "general-full": (True, True)}
+
+
+@pytest.fixture(scope="module", params=[(d, r, m) for d, r in ((2, 2), (3, 1)) for m in MEDIA],
+                ids=lambda p: f"{p[0]}d-{p[2]}")
+def converged_media(request, oracle):
+    """the other three media of a dimension: a full SPD tensor per cube, and both on a moved and stretched torus"""
+    dim, refinements, medium = request.param
+    return _converged_case(oracle, dim, refinements, *MEDIA[medium])
+
+
+def _check_converged(ctx, case, how):
+    dim, refinements, mesh, cond, sys, xi, v, sigma11 = case
     levels = refinements + 1
     g = hmg.ImplicitFineGrid(ctx, mesh, levels)
     g.set_smoother("cg" if how == "fcg" else how)
@@ -247,7 +184,7 @@ def test_converged_corrector(ctx, converged, how):
     cycles, rnorm, r0 = driver._dirichlet_solve(g, op, bl, states, xv, fcg, xi, 3, 1e-12, 200, "test")
     assert rnorm <= 1e-12 * r0, (cycles, rnorm / r0)
     x = xv.to_host()
-    ids, n = fine_ids(g, levels)
+    ids, n = fine_ids(g, levels, sys.den)
     u = np.zeros(n)
     u[ids.ravel()] = x.ravel()
     np.testing.assert_array_equal(u[ids], x)                             # a consistent level vector
@@ -255,7 +192,7 @@ def test_converged_corrector(ctx, converged, how):
     err = np.linalg.norm((got - got.mean()) - v) / np.linalg.norm(v)
     mean, gram = hmg.cell_moments(xv, g, xi)
     entry = float(hmg.fields.energy(cond, gram).sum() / hmg.fields.cell_volumes(mesh).sum())
-    print(f"{dim}D, {how}: {cycles} cycles, corrector {err:.2e}, Sigma_11 {entry:.12g} / {sigma11:.12g}")
+    print(f"{dim}D, {how}, sigma {cond.shape[1:]}: {cycles} cycles, corrector {err:.2e}, Sigma_11 {entry:.12g} / {sigma11:.12g}")
     assert err <= 1e-8, err
     assert abs(entry - sigma11) <= 1e-8 * abs(sigma11)
     if accelerate:
@@ -264,6 +201,16 @@ def test_converged_corrector(ctx, converged, how):
     for s in states:
         s.close()
     g.close()
+
+
+@pytest.mark.parametrize("how", ["cg", "jacobi", "chebyshev", "fcg"])
+def test_converged_corrector(ctx, converged, how):
+    _check_converged(ctx, converged, how)
+
+
+def test_converged_corrector_on_the_other_media(ctx, converged_media):
+    """the CG smoother on full tensors per cube, and on a general torus with either medium"""
+    _check_converged(ctx, converged_media, "cg")
 
 
 # ---- exact savings ---------------------------------------------------------------------------------------------------------------
@@ -378,3 +325,57 @@ def test_polycrystal_runs_and_gives_an_spd_tensor(ctx):
     assert np.abs(S - S.T).max() == 0.0 and np.linalg.eigvalsh(S)[0] > 0.0
     assert np.abs(out["tensor_flux"] - S).max() <= 1e-6 * np.abs(S).max()
     assert max(out["residual"]) <= 1e-10
+
+
+@pytest.mark.parametrize("medium", ["diagonal", "full"])
+@pytest.mark.parametrize("dim,refinements", [(2, 2), (3, 1)], ids=["2d", "3d"])
+def test_periodic_driver_against_the_direct_solve(oracle, ctx, dim, refinements, medium):
+    """every entry of both forms of the tensor against the energies of the d direct correctors on the explicitly refined torus;
+    the mean gradient over the torus is e_k (the corrector's gradient is mean-free: every wrapped cell's geometry enters)"""
+    n = 3
+    mesh = driver.periodic_mesh(hmg.Tet64 if dim == 3 else hmg.Tri64, n)
+    if medium == "full":
+        sgrid = driver.generate_polycrystal(3, 3, 8) if dim == 3 else TS.random_spd(np.random.default_rng(8), 9, 2).reshape(3, 3, 2, 2)
+    else:
+        sgrid = driver.generate_conductivity(dim, n, 5)                  # (seed 5: off-diagonal entries in 2D and in 3D)
+    sys = TorusSystem(oracle, mesh, per_cube(mesh, sgrid), refinements)
+    eye = np.eye(dim)
+    V = [sys.corrector(eye[k]) for k in range(dim)]
+    want = np.array([[sys.energy(V[k], eye[k], eye[l], V[l]) for l in range(dim)] for k in range(dim)])
+    off = np.abs(want[np.triu_indices(dim, 1)])
+    assert off.min() > 1e-3 * np.abs(want).max(), want                   # (on the reference: the off-diagonal entries are there)
+    out = driver.periodic_homogenization_tensor(n, hmg.Tet64 if dim == 3 else hmg.Tri64, refinements, ctx=ctx, sigma_grid=sgrid,
+                                                tolerance=1e-12, fields=True)
+    scale = np.abs(want).max()
+    e_t, e_f = np.abs(out["tensor"] - want).max() / scale, np.abs(out["tensor_flux"] - want).max() / scale
+    vol = out["volumes"]
+    grad = np.einsum("c,kcd->kd", vol, out["means"]) / vol.sum()
+    e_g = np.abs(grad - eye).max()
+    print(f"{dim}D, {medium}: cycles {out['cycles']}, tensor {e_t:.2e}, flux form {e_f:.2e}, mean gradient {e_g:.2e}, "
+          f"off-diagonal {off.min() / scale:.2e} of the largest entry")
+    assert e_t <= 1e-8 and e_f <= 1e-8
+    assert e_g <= 1e-11
+    for k in range(dim):
+        for l in range(dim):
+            assert np.array_equal(out["pairs"][k, l], out["pairs"][l, k])
+
+
+def test_periodic_driver_on_large_cells(ctx):
+    """the laminate of test_periodic_driver_is_exact_for_a_laminate on 3 x 3 cubes at level 9 (18 cells larger than the LDS): exact
+    through the window kernels of the moments, refused -- after the solve, by hmg_fields.cpp -- without `large_cells`"""
+    from homogenization_jl_amd._lib import HmgError
+    n = 3
+    layers, sgrid = _laminate(2, n)
+    want = np.diag([n / (1.0 / layers[:, 0]).sum(), layers[:, 1].mean()])
+    kw = dict(ctx=ctx, sigma_grid=sgrid, tolerance=1e-12)
+    n0 = ctx.counter("cell_moments_window_launches")
+    out = driver.periodic_homogenization_tensor(n, hmg.Tri64, 8, large_cells=True, **kw)
+    launches = ctx.counter("cell_moments_window_launches") - n0
+    print(f"cycles {out['cycles']}, tensor error {np.abs(out['tensor'] - want).max():.3e}, flux error "
+          f"{np.abs(out['tensor_flux'] - want).max():.3e}, {launches} window launches")
+    assert np.abs(out["tensor"] - want).max() <= 1e-8 * np.abs(want).max()
+    assert np.abs(out["tensor_flux"] - want).max() <= 1e-8 * np.abs(want).max()
+    assert launches >= 3                                                 # (two correctors and their pair)
+    assert ctx.counter("cell_moments_windows") == 0                      # (the option is back where it was)
+    with pytest.raises(HmgError, match=r"level 9 .*does not fit the LDS.*cell_moments_windows"):
+        driver.periodic_homogenization_tensor(n, hmg.Tri64, 8, **kw)

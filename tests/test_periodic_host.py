@@ -10,7 +10,8 @@ from homogenization_jl_amd import driver
 from homogenization_jl_amd._lib import HmgError
 
 import _coarse_form as CF
-from _periodic_form import coarse_ids, disjoint, keys, stiffness
+import _tensor_sigma_form as TS
+from _periodic_form import DEN, TorusSystem, coarse_ids, disjoint, general_torus, keys, stiffness
 from _periodic_golden import ordinary_mesh, ordinary_tables
 from _textbook_fem import TextbookP1
 
@@ -281,3 +282,159 @@ def test_element_points_on_a_torus():
     assert wraps.any() and (np.abs(hmg.fields.element_centroids(g, 2, cells, nodes).reshape(ne, 2, 2).mean(axis=1)
                                    - X.mean(axis=1)) <= 1e-15).all()
     g.close()
+
+
+# ---- general tori: moved, stretched and re-represented nodes (tests/_periodic_form.py: general_torus) ---------------------------
+def _rot90(dim, axis=0):
+    """a rotation by 90 degrees: in 2D of the plane, in 3D about `axis` -- a signed permutation, so a box stays a box"""
+    Q = np.zeros((dim, dim))
+    if dim == 2:
+        Q[0, 1], Q[1, 0] = -1.0, 1.0
+        return Q
+    a, b = [k for k in range(3) if k != axis]
+    Q[axis, axis], Q[a, b], Q[b, a] = 1.0, -1.0, 1.0
+    return Q
+
+
+@pytest.mark.parametrize("shape,refinements", [((4, 3), 2), ((3, 3, 3), 1)], ids=["4x3", "3x3x3"])
+def test_the_extended_statement(oracle, shape, refinements):
+    """general_torus without jitter or stretch is driver.periodic_mesh, and TorusSystem on it the matrix it was, bit for bit; the
+    count of distinct fine positions of a moved and stretched torus is shape m^d; the full-tensor K is symmetric with the
+    constants -- and nothing else -- in its kernel; and for sigma = Q D Q^T with one Q in every cell it is the diagonal
+    statement on the mesh x -> Q^T x (the pattern of tests/test_tensor_sigma_statement.py), at 1e-13"""
+    d = len(shape)
+    plain = general_torus(shape, 3, jitter=False, scale=(1.0, 1.0, 1.0))
+    old = torus(shape)
+    assert np.array_equal(plain.nodes, old.nodes) and np.array_equal(plain.elements, old.elements) and np.array_equal(plain.period, old.period)
+    rng = np.random.default_rng(5)
+    ne = old.elements.shape[0]
+    D = rng.choice([1.0, 9.0], size=(ne, d))
+    a, b = TorusSystem(oracle, old, D, refinements), TorusSystem(oracle, plain, D, refinements, den=DEN)
+    assert a.n == b.n and np.array_equal(a.ids, b.ids)
+    A, B = a.K.tocsr(), b.K.tocsr()
+    A.sum_duplicates(), B.sum_duplicates()
+    assert np.array_equal(A.indptr, B.indptr) and np.array_equal(A.indices, B.indices)
+    assert np.array_equal(A.data.view(np.int64), B.data.view(np.int64))
+    assert np.array_equal(a.corrector(np.eye(d)[0]).view(np.int64), b.corrector(np.eye(d)[0]).view(np.int64))
+
+    mesh = general_torus(shape, 3)
+    sig = TS.random_spd(rng, ne, d)
+    full = TorusSystem(oracle, mesh, sig, refinements, den=DEN)
+    assert full.n == int(np.prod(shape)) * full.m ** d
+    K = full.K.toarray()
+    assert np.abs(K - K.T).max() <= 1e-13 * np.abs(K).max()
+    assert np.abs(K.sum(axis=1)).max() <= 1e-13 * np.abs(K).max()
+    w = np.linalg.eigvalsh(0.5 * (K + K.T))
+    assert abs(w[0]) <= 1e-12 * w[-1] and w[1] > 1e-6 * w[-1]
+    # the load of full tensors against the diagonal one where both exist
+    diag = TorusSystem(oracle, mesh, D, refinements, den=DEN)
+    as_full = TorusSystem(oracle, mesh, D[:, :, None] * np.eye(d)[None], refinements, den=DEN)
+    xi = rng.standard_normal(d)
+    F = np.bincount(diag.ids, weights=diag.T.load(diag.a, xi), minlength=diag.n)
+    np.testing.assert_allclose(as_full.load(xi), F, rtol=0, atol=1e-13 * np.abs(F).max())
+    np.testing.assert_allclose(as_full.K.toarray(), diag.K.toarray(), rtol=0, atol=1e-13 * np.abs(K).max())
+
+    for axis in range(d if d == 3 else 1):
+        Q = _rot90(d, axis)
+        rot = hmg.Mesh(np.ascontiguousarray(mesh.nodes @ Q), mesh.elements.copy(), np.abs(mesh.period @ Q))
+        want = TorusSystem(oracle, rot, D, refinements, lam=0.7, den=DEN)
+        got = TorusSystem(oracle, mesh, np.einsum("ij,cj,kj->cik", Q, D, Q), refinements, lam=0.7, den=DEN)
+        at = want.index(np.mod(got.pos @ Q, want.period))
+        assert np.array_equal(np.sort(at), np.arange(want.n))
+        W = want.K.toarray()[at][:, at]
+        err = np.abs(got.K.toarray() - W).max() / np.abs(W).max()
+        v, vw = got.corrector(xi), want.corrector(Q.T @ xi)
+        e_v = np.abs(v - vw[at]).max() / np.abs(vw).max()
+        e_e = abs(got.energy(v, xi) - want.energy(vw, Q.T @ xi)) / abs(want.energy(vw, Q.T @ xi))
+        print(f"{shape}, rotation about axis {axis}: K {err:.2e}  corrector {e_v:.2e}  energy {e_e:.2e}")
+        assert err <= 1e-13 and e_e <= 1e-13 and e_v <= 1e-11            # (the corrector passes through a solve: kappa eps)
+
+
+GENERAL = [dict(jitter=False, scale=(1.0, 1.0, 1.0)), dict()]
+
+
+def _host_tables(mesh, sig, lam=0.0):
+    g = hmg.ImplicitFineGrid(None, mesh, 2)
+    g.set_operator(sig, lam)
+    g.coarse_setup()
+    out = {"coef": g.table_f64("coef"), "dmask": g.table_i32("dmask"), "mult": g.table_i32("mult"),
+           "rowptr": g.table_i32("coarse_rowptr"), "colidx": g.table_i32("coarse_colidx"), "val": g.table_f64("coarse_val"),
+           "volumes": hmg.fields.cell_volumes(mesh)}
+    g.close()
+    return out
+
+
+@pytest.mark.parametrize("kw", GENERAL, ids=["plain", "moved"])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_representatives_do_not_matter(shape, kw):
+    """a node stored whole periods away is the same node: every table that reads a coordinate keeps its bits"""
+    a, b = general_torus(shape, 11, **kw), general_torus(shape, 11, shift=True, **kw)
+    assert np.array_equal(a.elements, b.elements) and not np.array_equal(a.nodes, b.nodes)
+    assert np.array_equal(np.mod(a.nodes, a.period), np.mod(b.nodes, b.period))
+    rng = np.random.default_rng(12)
+    ne, d = a.elements.shape[0], a.dim
+    for sig in (rng.random((ne, d)) + 0.5, TS.random_spd(rng, ne, d)):
+        ta, tb = _host_tables(a, sig), _host_tables(b, sig)
+        for k, v in ta.items():
+            assert v.size > 0 and v.dtype == tb[k].dtype and v.tobytes() == tb[k].tobytes(), (shape, k)
+    np.testing.assert_array_equal(a.cell_corners() - a.cell_corners()[:, :1], b.cell_corners() - b.cell_corners()[:, :1])
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_general_geometry_is_that_of_the_disjoint_simplices_bit_for_bit(shape):
+    """test_geometry_is_that_of_the_disjoint_simplices_bit_for_bit on a moved, stretched torus, diagonal and full tensors"""
+    mesh = general_torus(shape, 13)
+    g, twin = hmg.ImplicitFineGrid(None, mesh, 2), hmg.ImplicitFineGrid(None, ordinary_twin(mesh), 2)
+    rng = np.random.default_rng(1)
+    ne, d = mesh.elements.shape[0], mesh.dim
+    for sig in (np.ones((ne, d)), rng.choice([1.0, 9.0], size=(ne, d)), rng.random((ne, d)) + 0.5, TS.random_spd(rng, ne, d)):
+        g.set_operator(sig, 0.0)
+        twin.set_operator(sig, 0.0)
+        a, b = g.table_f64("coef"), twin.table_f64("coef")
+        assert a.size == 8 * ne and np.array_equal(a.view(np.int64), b.view(np.int64))
+    np.testing.assert_array_equal(hmg.fields.cell_volumes(mesh).view(np.int64),
+                                  hmg.fields.cell_volumes(ordinary_twin(mesh)).view(np.int64))
+    twin.close()
+    g.close()
+
+
+@pytest.mark.parametrize("lam", [0.0, 0.7])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_general_level_1_matrix_with_full_tensors(shape, lam):
+    """test_level_1_matrix on a moved, stretched torus with a full SPD tensor per cell"""
+    mesh = general_torus(shape, 14)
+    rng = np.random.default_rng(2)
+    ne, n = mesh.elements.shape[0], mesh.nodes.shape[0]
+    sig = TS.random_spd(rng, ne, mesh.dim)
+    g = hmg.ImplicitFineGrid(None, mesh, 2)
+    g.set_operator(sig, lam)
+    g.coarse_setup()
+    A, interior = CF.matrix(g)
+    g.close()
+    np.testing.assert_array_equal(interior, np.arange(n))
+    ids = coarse_ids(mesh, DEN)
+    np.testing.assert_array_equal(ids, (mesh.elements - 1).ravel())
+    nodes, elements = disjoint(mesh)
+    want = stiffness(TextbookP1(nodes, elements), sig, ids, n, lam).toarray()
+    got = A.toarray()
+    np.testing.assert_allclose(got, want, rtol=1e-13, atol=1e-13 * np.abs(want).max())
+    # entries (i, j) and (j, i) add their cells' parts in different orders: equal bits on the integer positions of
+    # driver.periodic_mesh only; here the bound tests/test_coarse_solve_host.py sets for every level-1 matrix
+    assert np.abs(got - got.T).max() <= 1e-14 * np.abs(got).max()
+    if lam == 0.0:
+        assert np.abs(got.sum(axis=1)).max() <= 1e-13 * np.abs(got).max()
+
+
+def test_a_jitter_that_reaches_half_a_period_is_refused():
+    """3 x 3 cubes stretched to a 6 x 1.5 box: node (0, 0) moved by half a cube along axis 0 makes its edges to the nodes of the
+    next column 1.5 cubes long, half the period; the first cell that has such an edge is named"""
+    mesh = general_torus((3, 3), 15, jitter=False)
+    nodes = mesh.nodes.copy()
+    nodes[0, 0] -= 0.5 * 2.0
+    X = hmg.Mesh(nodes, mesh.elements, mesh.period).cell_corners()
+    spans = np.abs(X[:, :, None, 0] - X[:, None, :, 0]).max(axis=(1, 2)) >= 0.5 * mesh.period[0]
+    assert spans.any() and not spans.all()
+    first = int(np.flatnonzero(spans)[0])
+    raises_creating(hmg.Mesh(nodes, mesh.elements, mesh.period), rf"cell {first} has an edge that spans half the period of axis 0")
+    nodes[0, 0] += 0.125 * 2.0                                           # three eighths of a cube: inside, accepted
+    hmg.ImplicitFineGrid(None, hmg.Mesh(nodes, mesh.elements, mesh.period), 2).close()
