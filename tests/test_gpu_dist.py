@@ -106,7 +106,8 @@ def _worker(rank, world, port, width, levels, overlap, q, own_stream=False, thre
 @pytest.mark.parametrize("world,width,levels,overlap,own_stream",
                          [(2, 4, 4, True, False), (2, 4, 4, False, False), (2, 2, 7, True, False), (4, 2, 4, True, False),
                           (3, "delaunay3", 3, True, False), (2, "delaunay2", 5, True, False), (2, "delaunay2", 5, False, False),
-                          (2, 4, 4, True, True), (2, 4, 4, False, True)])
+                          (2, 4, 4, True, True), (2, 4, 4, False, True),
+                          (8, 2, 3, True, False)])               # octants of a 4^3 brick: eight processes on the one GPU
 def test_multi_rank_vcycle_matches_serial_oracle(world, width, levels, overlap, own_stream):
     """overlap=True: cut-adjacent cells first, asynchronous sum over ranks in flight during the rest."""
     import multiprocessing as mp
