@@ -348,7 +348,9 @@ class ImplicitFineGrid:
 
 
 class DeviceMatrix:
-    """A level vector: the reference's `Nf x Ne` matrix, resident in HBM."""
+    """A level vector: the reference's `Nf x Ne` matrix, resident in HBM.  `device_ptr` wraps caller-owned memory of ld * Ne
+    doubles (hmg_vec_wrap): device_ptr must be 16-byte aligned -- the vector kernels move pairs of doubles --; any other pointer is
+    refused."""
 
     def __init__(self, implicit: ImplicitFineGrid, level: int, device_ptr=None):
         self._lib = L.load()

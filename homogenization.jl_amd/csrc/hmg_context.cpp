@@ -511,6 +511,8 @@ int hmg_vec_wrap(hmg_grid *g, int level, void *device_ptr, hmg_vec **out)
 {
     HMG_TRY
     need(g && out && device_ptr, "null argument");
+    // (the streaming kernels read and write the storage as double2, hmg_kernels.hip; checked before anything is allocated)
+    need(((uintptr_t)device_ptr & 15u) == 0, "hmg_vec_wrap: device_ptr must be 16-byte aligned (the vector kernels move pairs of doubles)");
     ensure_reduce_scratch(g->ctx, (int64_t)lev(g, level).ld * g->md.ncells);
     std::unique_ptr<hmg_vec> v(new hmg_vec);
     v->g = g;

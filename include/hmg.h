@@ -339,6 +339,7 @@ int hmg_grid_table_f64(const hmg_grid *grid, int level, const char *which, doubl
 
 /* ---- level vectors: the five matrices of LevelState (src/multigrid.jl:7-25) ------------------- */
 int hmg_vec_create(hmg_grid *grid, int level, hmg_vec **out);                 /* zeros(Nf, Ne) */
+/* device_ptr must be 16-byte aligned -- the vector kernels move pairs of doubles --; any other pointer is refused. */
 int hmg_vec_wrap(hmg_grid *grid, int level, void *device_ptr, hmg_vec **out); /* caller-owned ld*Ne doubles */
 int hmg_vec_destroy(hmg_vec *v);
 /* The device pointer of the vector.  From this call on the library assumes that the memory is read behind its back: a pending

@@ -635,7 +635,8 @@ function table_f64(g::HipGrid, which::String, level::Integer = 1)
     out
 end
 
-# level vectors over caller-owned device memory (api.DeviceMatrix.wrap): ld(g, level) * ncells(g) doubles
+# level vectors over caller-owned device memory (api.DeviceMatrix.wrap): ld(g, level) * ncells(g) doubles.
+# device_ptr must be 16-byte aligned -- the vector kernels move pairs of doubles --; any other pointer is refused.
 function HipMatrix(g::HipGrid, level::Int, device_ptr::Ptr{Cvoid})
     h = Ref{Ptr{Cvoid}}()
     check(ccall((:hmg_vec_wrap, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), g.h, level, device_ptr, h))

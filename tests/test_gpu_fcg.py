@@ -88,7 +88,11 @@ def test_device_matches_the_global_form(oracle, ctx, dim, n, grids, steps):
     d.close()
 
 
-def _against_local(O, ctx, mesh, sig, lam, levels, steps, nsteps, rng):
+def _against_local(O, ctx, mesh, sig, lam, levels, steps, nsteps, rng, full=None, check_residual_norm=False):
+    """full = (mesh, sig) of a larger grid of which `mesh` holds a prefix of the cells and of the nodes: the device objects are
+    created on it and shrunk to `mesh` before the start (tests/test_gpu_stream_lengths.py: odd lengths).
+    check_residual_norm: after the steps, hmg_fcg_residual_norm against the first-copy norm of the statement's interface-summed
+    R, at the 1e-9 test_setup_memory_counters_and_stale_state allows that number."""
     implicit = O.ImplicitFineGrid.create(mesh, levels)
     constraint = O.ZeroDirichletConstraint(*O.list_boundary_nodes_edges_faces(mesh))
     ops = [O.L2PlusDivAGrad(O.build_local_diffusion_operators(m), O.mass_matrix(m), constraint, lam, sig)
@@ -97,7 +101,15 @@ def _against_local(O, ctx, mesh, sig, lam, levels, steps, nsteps, rng):
     shape = states[-1].x.shape
     x0 = _consistent(O, implicit, constraint, levels, rng.random(shape))
     b = np.asfortranarray(rng.standard_normal(shape))
-    d = Device(ctx, mesh, sig, lam, levels, steps, x0, b)
+    if full is None:
+        d = Device(ctx, mesh, sig, lam, levels, steps, x0, b)
+    else:
+        fmesh, fsig = full
+        pad = lambda a: np.asfortranarray(np.concatenate([a, np.zeros((shape[0], fmesh.nelements() - shape[1]))], axis=1))
+        d = Device(ctx, fmesh, fsig, lam, levels, steps, pad(x0), pad(b))
+        d.g.shrink(mesh.nelements(), mesh.nnodes())
+        d.bl = hmg.BaseLevel(d.g)
+        assert d.x.shape == shape
     d.fcg.start(d.x, d.b)
     R0 = d.fcg.vec("R")
     r0 = np.abs(R0).max()
@@ -111,6 +123,13 @@ def _against_local(O, ctx, mesh, sig, lam, levels, steps, nsteps, rng):
         print(f"step {it + 1}: x {ex:.2e}  R {eR:.2e}  alpha {alpha:.12g} / {wa:.12g}  beta {beta:.12g} / {wb:.12g}")
         assert ex <= 1e-9 and eR <= 1e-8, (it, ex, eR)
         assert _close(alpha, wa, 1e-8) and _close(beta, wb, 1e-8), (it, alpha, wa, beta, wb)
+    if check_residual_norm:
+        summed = np.asfortranarray(wR.copy())
+        O.broadcast_interfaces(summed, implicit, levels)
+        O.zero_out_all_but_one(summed, implicit, levels)
+        want, got = float(np.linalg.norm(summed)), d.fcg.residual_norm()
+        print(f"residual norm {got:.12e} / {want:.12e}")
+        assert abs(got - want) <= 1e-9 * want, (got, want)
     d.close()
 
 
