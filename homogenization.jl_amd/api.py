@@ -812,8 +812,10 @@ def cell_histogram(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=No
     values, bit for bit: counts[:, b:].sum(1) for an edge E_(b-1) equals cell_extrema's count for the threshold
     nextafter(E_(b-1), -inf).  Bins: histogram_edges / histogram_bin; column 0 is everything below 2^emin (zeros, negatives),
     column nreg + 1 everything from 2^emax up, the last column the NaN elements; a row sums to fine_elements.  The vector as
-    stored; 3D levels 1 to 6 and 2D levels 1 to 8; larger cells are refused whatever "cell_extrema_windows" says (no window
-    kernels).  One pass of 8 B/DOF; integer counts, the same in every run and for every launch shape.  On a
+    stored; 3D levels 1 to 6 and 2D levels 1 to 8; larger cells (3D level 7, 2D levels 9 to 11) are refused whatever
+    "cell_extrema_windows" says, unless the context option "cell_histogram_windows" -- this call's own, 0 by default -- is 1: then
+    they walk through a rolling LDS window and give the same ints (2 sends every level the window kernels address through them;
+    counter "cell_histogram_window_launches"; "cell_histogram_variant" has no say in the window kernels).  One pass of 8 B/DOF; integer counts, the same in every run and for every launch shape.  On a
     dist.PartitionedGrid Ne is the number of LOCAL cells, as in cell_extrema; shrunk and periodic grids are served.
     Counters: "cell_histogram_launches", "cell_histogram_kernel_ns".
     What to do with the result: fields.histogram_volume, fields.histogram_quantile, fields.histogram_tail.  No counterpart in
@@ -830,6 +832,65 @@ def cell_histogram(v: DeviceMatrix, implicit: ImplicitFineGrid, xi=None, form=No
     counts = np.zeros((ne, nbins), dtype=np.int64)
     L.check(lib.hmg_cell_histogram(implicit.h, v.h, xp, fp, int(emin), int(emax), int(sub_bits), counts.ctypes.data_as(L.p_i64)))
     return counts
+
+
+def histogram_group_sum(counts, group_of_cell, ngroups, weights):
+    """The statement of hmg_cell_histogram_groups' FP64 sum in numpy, in the documented order: per group the cells by ascending
+    cell id, s = 0.0, then s = s + w[c] * float(counts[c, b]) cell after cell -- the product rounded, then the sum (numpy never
+    fuses them).  counts (Ne, nbins) integers, group_of_cell (Ne,) in -1 .. ngroups - 1, weights (Ne,): (ngroups, nbins) float64,
+    the bits the device gives."""
+    counts = np.asarray(counts)
+    group_of_cell = np.asarray(group_of_cell)
+    w = np.asarray(weights, dtype=np.float64)
+    out = np.zeros((int(ngroups), counts.shape[1]), dtype=np.float64)
+    for c in range(counts.shape[0]):                                  # ascending cell id
+        k = int(group_of_cell[c])
+        if k >= 0:
+            out[k] = out[k] + w[c] * counts[c].astype(np.float64)
+    return out
+
+
+def cell_histogram_groups(v: DeviceMatrix, implicit: ImplicitFineGrid, labels, xi=None, form=None, weights=None, *, emin: int,
+                          emax: int, sub_bits: int = 3):
+    """cell_histogram summed over groups of cells ON THE DEVICE (hmg_cell_histogram_groups): returns (group_labels, counts,
+    volume).  `labels` (Ne,) integers, one per cell; group_labels = np.unique of the labels that are >= 0, sorted -- a NEGATIVE
+    label (or a masked entry of a numpy masked array) puts the cell into no group.  counts (G, nbins) int64: counts[k] =
+    cell_histogram(...)[labels == group_labels[k]].sum(0), exactly.  `weights` (Ne,) finite floats (a cell's volume over
+    fine_elements gives volumes per bin) or None: volume (G, nbins) float64 = sum_c weights[c] * counts_c, summed per group by
+    ASCENDING CELL ID from 0.0 with product and sum rounded separately (histogram_group_sum is that order in numpy: the same
+    bits, in every run and on every device), or None without weights.  G * nbins numbers come down instead of Ne * nbins.  The
+    pass, its levels, options ("cell_histogram_windows") and counters are cell_histogram's; the group kernel's time is the counter
+    "cell_histogram_groups_kernel_ns".  No labels >= 0 at all: G = 0 and empty arrays, nothing is launched.  On a
+    dist.PartitionedGrid labels and weights go by LOCAL cell.  No counterpart in the reference."""
+    lib = L.load()
+    d = implicit.base.dim
+    ne = implicit.ncells()
+    nbins = histogram_nbins(emin, emax, sub_bits)
+    lab = np.ma.asarray(labels)
+    if lab.shape != (ne,) or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"labels must be ({ne},) integers")
+    lab = np.ma.filled(lab.astype(np.int64), -1)
+    group_labels = np.unique(lab[lab >= 0])
+    ngroups = int(group_labels.size)
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (ne,):
+            raise ValueError(f"weights must be ({ne},)")
+    counts = np.zeros((ngroups, nbins), dtype=np.int64)
+    volume = None if w is None else np.zeros((ngroups, nbins), dtype=np.float64)
+    if ngroups == 0:
+        return group_labels, counts, volume
+    group_of_cell = np.where(lab >= 0, np.searchsorted(group_labels, lab), -1).astype(np.int32)
+    xi, xp = _vec_of(implicit, "xi", xi)
+    fp = None
+    if form is not None:
+        packed = _packed_form(form, ne, d)
+        fp = packed.ctypes.data_as(L.p_f64)
+    L.check(lib.hmg_cell_histogram_groups(implicit.h, v.h, xp, fp, int(emin), int(emax), int(sub_bits), ngroups,
+                                          group_of_cell.ctypes.data_as(L.p_i32), None if w is None else w.ctypes.data_as(L.p_f64),
+                                          counts.ctypes.data_as(L.p_i64), None if volume is None else volume.ctypes.data_as(L.p_f64)))
+    return group_labels, counts, volume
 
 
 def _packed_form(form, ne, d):

@@ -306,6 +306,9 @@ int64_t hmg_ctx_counter(hmg_ctx *ctx, const char *name)
     if (n == "cell_histogram_kernel_ns") return ctx->histogram_kernel_ns;           // the last hmg_cell_histogram: kernel alone
     if (n == "cell_histogram_launches") return ctx->histogram_launches;             // launches of its kernel
     if (n == "cell_histogram_variant") return ctx->histogram_variant;               // option of that name
+    if (n == "cell_histogram_window_launches") return ctx->histogram_window_launches;   // launches of its window kernels (option "cell_histogram_windows")
+    if (n == "cell_histogram_windows") return ctx->histogram_windows;               // ... and that option's value
+    if (n == "cell_histogram_groups_kernel_ns") return ctx->histogram_groups_kernel_ns;   // the last hmg_cell_histogram_groups: its group-sum kernel alone
     if (n == "comm_nranks") return ctx->comm ? ctx->comm_nranks : 0;    // as the RCCL communicator was created; 0: none
     return -1;
 }
@@ -379,6 +382,11 @@ int hmg_ctx_set_option(hmg_ctx *ctx, const char *name, int64_t value)
         if (value < 0 || value > 2)
             throw std::runtime_error("option cell_extrema_windows: 0, 1 or 2");
         ctx->extrema_windows = (int)value;
+    }
+    else if (n == "cell_histogram_windows") {   // the same for hmg_cell_histogram (hmg_histogram_window.hip): 0 = default, 1, 2
+        if (value < 0 || value > 2)
+            throw std::runtime_error("option cell_histogram_windows: 0, 1 or 2");
+        ctx->histogram_windows = (int)value;
     }
     else if (n == "cell_histogram_variant") {   // how hmg_cell_histogram's counts reach the LDS histogram: 0 one add per element,
         if (value < 0 || value > 2)             // 1 = default: a node's elements combined first, 2: and the wave's first bin summed

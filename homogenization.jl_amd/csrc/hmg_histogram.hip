@@ -37,11 +37,6 @@ namespace {
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
 
-__device__ __forceinline__ void lds_count(int *hist, int bin, int n)
-{
-    (void)__hip_atomic_fetch_add(hist + bin, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 template <int DIM, int NT, int VAR>
 __global__ void __launch_bounds__(NT)
 k_cell_histogram(LevelDev lv, const double *v, int64_t ncells, int g1, const uint8_t *__restrict__ elem_mask,
@@ -76,42 +71,25 @@ k_cell_histogram(LevelDev lv, const double *v, int64_t ncells, int g1, const uin
             double q[NEL];
             extrema_values<DIM>(xs, L, len, A, B, 0, hi, Q, X, q);
             int bin[NEL], cnt[NEL];
-#pragma unroll
-            for (int k = 0; k < NEL; ++k) {
-                bin[k] = histogram_bin((uint32_t)__double2hiint(q[k]), (uint32_t)__double2loint(q[k]), rule);
-                cnt[k] = (int)((mk >> k) & 1u);
-            }
+            histogram_node_bins<NEL>(q, mk, rule, bin, cnt);
             if constexpr (VAR == HIST_PLAIN) {
 #pragma unroll
                 for (int k = 0; k < NEL; ++k)
                     if (cnt[k]) lds_count(hist, bin[k], 1);
+            } else if constexpr (VAR == HIST_NODE) {
+                histogram_node_add<NEL>(hist, bin, cnt);         // (hmg_histogram_device.hpp: the text the window kernels run)
             } else {
-                // the node's elements with one bin become one count: the first of them takes the others' (an element folded into
-                // an earlier one has 0 left and takes nothing: whatever shares its bin went the same way)
+                histogram_node_combine<NEL>(bin, cnt);
 #pragma unroll
-                for (int k = 0; k < NEL; ++k)
-#pragma unroll
-                    for (int j = k + 1; j < NEL; ++j) {
-                        const int take = (bin[j] == bin[k] && cnt[k] > 0) ? cnt[j] : 0;
-                        cnt[k] += take;
-                        cnt[j] -= take;
-                    }
-                if constexpr (VAR == HIST_NODE) {
-#pragma unroll
-                    for (int k = 0; k < NEL; ++k)
-                        if (cnt[k] > 0) lds_count(hist, bin[k], cnt[k]);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < NEL; ++k) {
-                        const bool act = cnt[k] > 0;
-                        const uint64_t who = __builtin_amdgcn_ballot_w64(act);
-                        if (who == 0) continue;                                  // (scalar)
-                        const int b0 = __builtin_amdgcn_readlane(bin[k], (int)__builtin_ctzll(who));
-                        const bool same = act && bin[k] == b0;
-                        const int sum = wave_isum63(same ? cnt[k] : 0);          // lane 63: all of the wave's counts for b0
-                        if (lane == 63) lds_count(hist, b0, sum);
-                        if (act && !same) lds_count(hist, bin[k], cnt[k]);
-                    }
+                for (int k = 0; k < NEL; ++k) {
+                    const bool act = cnt[k] > 0;
+                    const uint64_t who = __builtin_amdgcn_ballot_w64(act);
+                    if (who == 0) continue;                                  // (scalar)
+                    const int b0 = __builtin_amdgcn_readlane(bin[k], (int)__builtin_ctzll(who));
+                    const bool same = act && bin[k] == b0;
+                    const int sum = wave_isum63(same ? cnt[k] : 0);          // lane 63: all of the wave's counts for b0
+                    if (lane == 63) lds_count(hist, b0, sum);
+                    if (act && !same) lds_count(hist, bin[k], cnt[k]);
                 }
             }
         }
@@ -163,7 +141,75 @@ void launch_var(const Launch &L, const LevelDev &lv, int64_t ncells, const doubl
         launch_dim<2, VAR>(L, lv, ncells, v, elem_mask, rows, rule, out);
 }
 
+constexpr int HG_NT = 256;           // threads per workgroup of k_histogram_groups: bins blockIdx.x * 256 ..
+constexpr int HG_AHEAD = 8;          // rows in flight per thread
+
+// Group sums of the per-cell rows (hmg_histogram.hpp: launch_histogram_groups).  blockIdx.y is the group, a thread takes one bin and
+// walks the group's cells in the order of the list: the loads of a trip are 256 consecutive ints of one row.  HG_AHEAD rows are
+// requested before the first of them is added; the additions themselves run in list order, one cell after the other -- the order is
+// the interface's, whatever the launch shape.  int64 for the counts (a group may hold more than 2^31 elements); for the volume the
+// product and the sum are rounded separately (mul_rn, add_rn below: never contracted into a multiply-add).
+// A product and a sum that each round once, to nearest.  (This toolchain's __dmul_rn / __dadd_rn are a plain `x * y` and `x + y`
+// compiled under the default contraction: inlined next to each other they come out as one v_fma_f64 -- seen in the ISA and in the
+// last bits.  Here the contraction is off where the operations are written.)
+__device__ __forceinline__ double mul_rn(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x * y;
+}
+__device__ __forceinline__ double add_rn(double x, double y)
+{
+#pragma clang fp contract(off)
+    return x + y;
+}
+
+template <bool WEIGHTED>
+__global__ void __launch_bounds__(HG_NT)
+k_histogram_groups(int nbins, const int *__restrict__ rows, const int *__restrict__ group_ptr, const int *__restrict__ group_cells,
+                   const double *__restrict__ w, long long *__restrict__ counts, double *__restrict__ volume)
+{
+    const int b = blockIdx.x * HG_NT + threadIdx.x, grp = blockIdx.y;
+    if (b >= nbins) return;
+    const int p0 = group_ptr[grp], p1 = group_ptr[grp + 1];
+    long long n = 0;
+    double vol = 0.0;
+    for (int p = p0; p < p1; p += HG_AHEAD) {
+        int c[HG_AHEAD], r[HG_AHEAD];
+        double wc[HG_AHEAD];
+#pragma unroll
+        for (int a = 0; a < HG_AHEAD; ++a) c[a] = group_cells[min(p + a, p1 - 1)];   // (a trip is completed with copies of the last cell)
+#pragma unroll
+        for (int a = 0; a < HG_AHEAD; ++a) {
+            r[a] = rows[(int64_t)c[a] * nbins + b];
+            if constexpr (WEIGHTED) wc[a] = w[c[a]];
+        }
+#pragma unroll
+        for (int a = 0; a < HG_AHEAD; ++a)
+            if (p + a < p1) {
+                n += r[a];
+                if constexpr (WEIGHTED) vol = add_rn(vol, mul_rn(wc[a], (double)r[a]));
+            }
+    }
+    counts[(int64_t)grp * nbins + b] = n;
+    if constexpr (WEIGHTED) volume[(int64_t)grp * nbins + b] = vol;
+}
+
 }  // namespace
+
+void launch_histogram_groups(const Launch &L, int nbins, int ngroups, const int *rows, const int *group_ptr, const int *group_cells,
+                             const double *w, long long *counts, double *volume)
+{
+    if (nbins < 1 || nbins > HIST_MAX_BINS) throw std::runtime_error("histogram groups: number of bins out of range");
+    if (ngroups < 1 || ngroups > HIST_MAX_GROUPS) throw std::runtime_error("histogram groups: 1 to 65535 groups");
+    if ((w == nullptr) != (volume == nullptr)) throw std::runtime_error("histogram groups: weights and volume go together");
+    if (!rows || !group_ptr || !group_cells || !counts) throw std::runtime_error("histogram groups: null device pointer");
+    const dim3 grid((unsigned)((nbins + HG_NT - 1) / HG_NT), (unsigned)ngroups);
+    if (w)
+        hipLaunchKernelGGL(k_histogram_groups<true>, grid, dim3(HG_NT), 0, L.stream, nbins, rows, group_ptr, group_cells, w, counts, volume);
+    else
+        hipLaunchKernelGGL(k_histogram_groups<false>, grid, dim3(HG_NT), 0, L.stream, nbins, rows, group_ptr, group_cells, w, counts, volume);
+    check_launch();
+}
 
 size_t cell_histogram_lds_bytes(const LevelDev &lv, int nbins)
 {

@@ -1,5 +1,5 @@
 // The binning rule of the per-cell histograms (include/hmg.h: hmg_histogram_bin, hmg_cell_histogram): ONE text for the host twin
-// of hmg_histogram.cpp and for the kernel of hmg_histogram.hip.
+// of hmg_histogram.cpp and for the kernels of hmg_histogram.hip and hmg_histogram_window.hip.
 //
 // Bins are floating-point buckets: emin < emax (-1022 <= emin, emax <= 1023) and s = sub_bits in 0 .. 5 give
 //   nreg = (emax - emin) 2^s regular bins with the edges E_i = 2^(emin + i div 2^s) (1 + (i mod 2^s) / 2^s),
@@ -28,6 +28,7 @@ namespace hmg {
 constexpr int HIST_MAX_SUB_BITS = 5;
 constexpr int HIST_MAX_REGULAR = 1024;                     // regular bins the kernel serves at most
 constexpr int HIST_MAX_BINS = HIST_MAX_REGULAR + 3;
+constexpr int HIST_MAX_GROUPS = 65535;                     // groups of hmg_cell_histogram_groups: the second dimension of its launch
 
 // the rule as the kernel takes it
 struct HistogramRule {
@@ -70,6 +71,50 @@ HMG_HD uint64_t histogram_edge_bits(int i, int emin, int sub_bits)
 {
     const uint64_t key = (uint64_t)(((int64_t)(emin + 1023) << sub_bits) + i);
     return key << (52 - sub_bits);
+}
+
+// ---- what the kernels alone share (hmg_histogram.hip: k_cell_histogram; hmg_histogram_window.hip: its slab and row-band forms) ----
+
+// one workgroup-scope integer add to the LDS histogram
+__device__ __forceinline__ void lds_count(int *hist, int bin, int n)
+{
+    (void)__hip_atomic_fetch_add(hist + bin, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// the bins of a node's NEL values q and what each has to add: 1 where the element's bit of the mask mk is set, else 0
+template <int NEL>
+__device__ __forceinline__ void histogram_node_bins(const double *q, unsigned mk, const HistogramRule &rule, int *bin, int *cnt)
+{
+#pragma unroll
+    for (int k = 0; k < NEL; ++k) {
+        bin[k] = histogram_bin((uint32_t)__double2hiint(q[k]), (uint32_t)__double2loint(q[k]), rule);
+        cnt[k] = (int)((mk >> k) & 1u);
+    }
+}
+
+// the node's elements with one bin become one count: the first of them takes the others' (an element folded into an earlier one
+// has 0 left and takes nothing: whatever shares its bin went the same way)
+template <int NEL>
+__device__ __forceinline__ void histogram_node_combine(const int *bin, int *cnt)
+{
+#pragma unroll
+    for (int k = 0; k < NEL; ++k)
+#pragma unroll
+        for (int j = k + 1; j < NEL; ++j) {
+            const int take = (bin[j] == bin[k] && cnt[k] > 0) ? cnt[j] : 0;
+            cnt[k] += take;
+            cnt[j] -= take;
+        }
+}
+
+// the HIST_NODE form (hmg_histogram.hpp) of a node: combined in registers, one LDS add per distinct bin
+template <int NEL>
+__device__ __forceinline__ void histogram_node_add(int *hist, const int *bin, int *cnt)
+{
+    histogram_node_combine<NEL>(bin, cnt);
+#pragma unroll
+    for (int k = 0; k < NEL; ++k)
+        if (cnt[k] > 0) lds_count(hist, bin[k], cnt[k]);
 }
 
 }  // namespace hmg

@@ -275,6 +275,10 @@ struct hmg_ctx {
     int64_t histogram_kernel_ns = 0;         // the last hmg_cell_histogram: its kernel (device events)
     int64_t histogram_launches = 0;          // launches of k_cell_histogram (hmg_ctx_counter "cell_histogram_launches")
     int histogram_variant = 1;               // option "cell_histogram_variant": how counts reach the LDS histogram (hmg_histogram.hpp: HIST_DEFAULT; the same ints from each)
+    int histogram_windows = 0;               // option "cell_histogram_windows": the three values of "cell_extrema_windows" for hmg_cell_histogram and
+                                             // its window kernels (hmg_histogram_window.hip); an option of its own, off by default
+    int64_t histogram_window_launches = 0;   // launches of those (hmg_ctx_counter "cell_histogram_window_launches")
+    int64_t histogram_groups_kernel_ns = 0;  // the last hmg_cell_histogram_groups: its group-sum kernel (device events)
     int64_t sample_launches = 0;             // launches of k_sample (hmg_sample, hmg_sample_raster)
     int64_t sample_kernel_ns = 0, sample_download_ns = 0;   // the last of those calls: its kernel (device events), its downloads (host clock)
     int moments_windows = 0;                 // option "cell_moments_windows": 0 cells larger than the LDS are refused; 1 they take the window

@@ -38,4 +38,28 @@ __device__ __forceinline__ int rows_row_of(int m, int L)
     return j;
 }
 
+// Row of lattice position L (0 <= L < nf), as rows_row_of, without its loops.  RO(j) <= L is j^2 - b j + 2 L >= 0, b = 2 m + 3, so
+// the row is the floor of the smaller root (b - sqrt(b^2 - 8 L)) / 2.  b^2 <= 4 206 601 and 8 L are integers below 2^24 and their
+// difference is at least 9: exact in float; the root, the difference from b and the halving each round once, an absolute error
+// below 1e-3: the truncated estimate is at most one row off, and two steps either way correct it with one to spare.  (The loops
+// of rows_row_of, inlined four times into the load phase next to k_cell_extrema_rows' counters, cost it 40 scalar registers and spills.)
+__device__ __forceinline__ int rows_row_near(int m, int L)
+{
+    const float b = (float)(2 * m + 3);
+    int j = (int)((b - __builtin_sqrtf(b * b - 8.0f * (float)L)) * 0.5f);
+    j = j < 0 ? 0 : j > m ? m : j;
+    j -= (j > 0 && rows_ro(m, j) > L) ? 1 : 0;
+    j -= (j > 0 && rows_ro(m, j) > L) ? 1 : 0;
+    j += (j < m && rows_ro(m, j + 1) <= L) ? 1 : 0;
+    j += (j < m && rows_ro(m, j + 1) <= L) ? 1 : 0;
+    return j;
+}
+// ... and the node's storage slot: i is clamped into the row, so that the slot lies inside the column whatever j is
+__device__ __forceinline__ int rows_slot_at(int m, int L, int j, int nei, int off_int)
+{
+    const int i = min(max(L - rows_ro(m, j), 0), m - j);
+    int cls;
+    return rows_slot(m, i, j, nei, off_int, cls);
+}
+
 }  // namespace hmg

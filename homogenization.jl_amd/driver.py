@@ -621,14 +621,14 @@ def _dirichlet_solve(implicit, op, base_level, states, xv, fcg, xi, smoothing_st
 
 @contextlib.contextmanager
 def _large_cells(ctx, on: bool):
-    """Around the per-cell passes of the Dirichlet drivers: with `on`, the context options "cell_moments_windows" and
-    "cell_extrema_windows" are at least 1 inside (cells larger than the LDS -- 3D level 7, 2D levels 9-11 -- go through the window
-    kernels of the moments and of the extrema) and back at their previous values behind, also when a pass raises.  The context may
-    be the caller's."""
+    """Around the per-cell passes of the Dirichlet drivers: with `on`, the context options "cell_moments_windows",
+    "cell_extrema_windows" and "cell_histogram_windows" are at least 1 inside (cells larger than the LDS -- 3D level 7, 2D levels
+    9-11 -- go through the window kernels of the moments, of the extrema and of the histograms) and back at their previous values
+    behind, also when a pass raises.  The context may be the caller's."""
     if not on:
         yield
         return
-    names = ("cell_moments_windows", "cell_extrema_windows")
+    names = ("cell_moments_windows", "cell_extrema_windows", "cell_histogram_windows")
     prev = {name: ctx.counter(name) for name in names}
     try:
         for name in names:
@@ -699,8 +699,9 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
     of the mean energy density and need no guessing) says how the energy density is distributed.  A dict of "emin", "emax",
     "sub_bits", or True for emin = -24, emax = 8, sub_bits = 3.  Adds "energy_density_histogram": a dict of "edges"
     (api.histogram_edges), "counts" (Ne, nbins) and "volume" (nbins: the volume of the domain per bin, fields.histogram_volume;
-    fields.histogram_quantile reads medians and tails off it).  Top levels up to 6 in 3D and 8 in 2D: `large_cells` does not extend
-    it.  Every other entry keeps its bits.  No counterpart in the reference."""
+    fields.histogram_quantile reads medians and tails off it).  Top levels up to 6 in 3D and 8 in 2D; with `large_cells` 3D level 7
+    and 2D levels 9-11 too ("cell_histogram_windows" = 1 around the pass), without it such a level is refused after the solve.
+    Every other entry keeps its bits.  No counterpart in the reference."""
     dim = api._dim_of(eltype)
     own_ctx = ctx is None
     if own_ctx:
@@ -760,7 +761,8 @@ def dirichlet_homogenization(n: int, eltype=Tri64, refinements: int = 2, xi=None
                 vtk.export_points(f"{save}_peaks", peaks["peak_location"], {"peak_energy_density": qmax, "cell": cells})
         out.update(peaks)
     if hist_rule is not None:
-        counts = api.cell_histogram(xv, implicit, xi, cell_fields.energy_form(cond) / out["energy_form"], **hist_rule)
+        with _large_cells(ctx, large_cells):
+            counts = api.cell_histogram(xv, implicit, xi, cell_fields.energy_form(cond) / out["energy_form"], **hist_rule)
         out["energy_density_histogram"] = {
             "edges": api.histogram_edges(**hist_rule), "counts": counts,
             "volume": cell_fields.histogram_volume(counts, vol, api.fine_elements(implicit, total_grids))}

@@ -551,18 +551,48 @@ int hmg_grid_element_vertices(const hmg_grid *grid, int level, int64_t n, const 
  * "cell_histogram_launches" counts the kernel launches, "cell_histogram_kernel_ns" is the last call's kernel time.
  * Served: 3D levels 1 to 6, 2D levels 1 to 8 -- the levels whose cell fits the LDS together with the largest histogram.  Larger
  * cells (3D level 7, 2D levels 9-11) are refused with a message naming the call and the level, whatever "cell_extrema_windows"
- * says: this call has no window kernels.
+ * says, unless hmg_ctx_set_option "cell_histogram_windows" -- an option of this call's own, 0 by default -- is 1: then such a
+ * level walks through a rolling window of the LDS ([window | nbins counters]; slabs of planes in 3D, bands of rows in 2D, one
+ * workgroup per cell), each node evaluated and counted with the functions the other kernel calls: the same ints.  2 sends every
+ * level the window kernels address through them (3D levels with slab tables, 2D levels 2 and up); the message of the refusal names
+ * the option where it would help.  "cell_histogram_window_launches" counts the launches of the window kernels (they count in
+ * "cell_histogram_launches" too), "cell_histogram_windows" reads the option back.  Partitioned, shrunk and periodic grids are
+ * served as by hmg_cell_extrema with its window option.
  * Refused as well, with a message naming the call: a grid without a device context, a null v or counts, a vector of another grid,
  * bin parameters outside the rule (as above) or more than 1024 regular bins, xi or form entries that are not finite.
  * hmg_ctx_set_option "cell_histogram_variant" (0, 1 = default, 2) chooses how a workgroup brings its counts into LDS -- one add
  * per element, a node's elements combined in registers first, and on top of that the wave's first bin summed across its lanes: a
- * measurement knob, the counts are the same ints from each. */
+ * measurement knob, the counts are the same ints from each.  The window kernels have the second form alone; the option has no
+ * say there.
+ *
+ * hmg_cell_histogram_groups: the same pass -- the same checks, kernel choice, options and counters -- whose per-cell rows stay on
+ * the device, where a second kernel sums them over groups of cells; ngroups * nbins numbers come down instead of ncells * nbins.
+ *   group_of_cell  int32[ncells], values in -1 .. ngroups - 1; -1: the cell is in no group (current / local cells, as counts above)
+ *   weights        double[ncells], finite, or NULL
+ *   counts         int64[ngroups * nbins], row per group: counts[g * nbins + b] = the sum over the cells c of group g of
+ *                  hmg_cell_histogram's counts[c * nbins + b], in 64-bit integers
+ *   volume         double[ngroups * nbins], NULL exactly when weights is NULL: volume[g * nbins + b] = sum_c weights[c] *
+ *                  counts[c * nbins + b]
+ * THE ORDER OF THE FP64 SUM is part of the interface: per (g, b) the cells of group g are taken by ASCENDING CELL ID, s = 0.0,
+ * then s = fl(s + fl(weights[c] * (double)count_c)) cell after cell -- product and sum rounded separately, never a fused
+ * multiply-add --, cells with a zero count included.  (numpy: s = 0.0; for c in sorted cells: s = s + w[c] * float(n[c, b]).)
+ * Independent of launch shape, device and run: the same bits everywhere.  An empty group gives rows of zeros.  No global atomics.
+ * Refused before any device work, each with a message naming the call and what failed: ngroups < 1 (or above 65535), a null
+ * counts, weights without volume or volume without weights, a null group_of_cell, a group id outside -1 .. ngroups - 1 (the cell
+ * is named), a weight that is not finite (the cell is named); then everything hmg_cell_histogram refuses.
+ * hmg_ctx_counter "cell_histogram_groups_kernel_ns" is the group-sum kernel's time in the last call; "cell_histogram_kernel_ns"
+ * and the launch counters behave as for hmg_cell_histogram. */
 int64_t hmg_histogram_nbins(int emin, int emax, int sub_bits);
 int hmg_histogram_edges(int emin, int emax, int sub_bits, double *edges /* nreg + 1 */);
 int hmg_histogram_bin(int64_t n, const double *q /* n */, int emin, int emax, int sub_bits, int32_t *bins /* n */);
 int hmg_cell_histogram(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
                        const double *form /* nq*ncells, or NULL */, int emin, int emax, int sub_bits,
                        int64_t *counts /* host, nbins*ncells, row per cell */);
+int hmg_cell_histogram_groups(hmg_grid *grid, hmg_vec *v, const double *xi /* dim, or NULL */,
+                              const double *form /* nq*ncells, or NULL */, int emin, int emax, int sub_bits, int ngroups,
+                              const int32_t *group_of_cell /* ncells */, const double *weights /* ncells, or NULL */,
+                              int64_t *counts /* host, nbins*ngroups, row per group */,
+                              double *volume /* host, nbins*ngroups, or NULL with weights */);
 
 /* ---- sampling a level vector at points and on raster slices (no counterpart in the reference) --------------------------
  * For a point x of physical space, a level and a level vector v of that level, as stored (no interface sum, no mask):

@@ -442,7 +442,8 @@ end
 # (histogram_edges, nreg + 1 of them) and nbins = nreg + 3 (histogram_nbins): bin 1 of the result holds everything below 2^emin, bins
 # 2:nreg+1 the intervals [E_(b-1), E_b), bin nreg+2 everything from 2^emax up, bin nreg+3 the NaNs.  counts is nbins x Ne, a column per
 # cell that sums to fine_elements; the values are cell_extrema's, bit for bit.  histogram_bin is the rule on the host (0-based bins).
-# 3D levels up to 6, 2D levels up to 8 and nreg <= 1024; larger cells are refused (no window kernels).
+# 3D levels up to 6, 2D levels up to 8 and nreg <= 1024; larger cells (3D level 7, 2D levels 9-11) once
+# set_option!(ctx, "cell_histogram_windows", 1) was called (the window kernels: the same ints).
 histogram_nbins(emin::Integer, emax::Integer, sub_bits::Integer = 3) =
     Int(ccall((:hmg_histogram_nbins, LIB), Int64, (Cint, Cint, Cint), emin, emax, sub_bits))
 function histogram_edges(emin::Integer, emax::Integer, sub_bits::Integer = 3)
@@ -466,6 +467,24 @@ function cell_histogram(v::HipMatrix, ξ::Union{Nothing,AbstractVector{Float64}}
                 g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), form === nothing ? C_NULL : Matrix{Float64}(form),
                 emin, emax, sub_bits, counts))
     counts
+end
+# ... summed over groups of cells on the device (hmg_cell_histogram_groups; api.cell_histogram_groups): group_of_cell holds 0-BASED
+# group ids in -1:ngroups-1 per cell (-1: in no group), weights one finite number per cell or nothing.  counts is nbins x ngroups
+# (Int64), volume nbins x ngroups (Float64; nothing without weights): sum_c weights[c] * counts_c per group by ascending cell id
+# from 0.0, product and sum rounded separately -- the same bits in every run.
+function cell_histogram_groups(v::HipMatrix, ngroups::Integer, group_of_cell::AbstractVector{<:Integer},
+                               ξ::Union{Nothing,AbstractVector{Float64}} = nothing, form::Union{Nothing,AbstractMatrix{Float64}} = nothing,
+                               weights::Union{Nothing,AbstractVector{Float64}} = nothing; emin::Integer, emax::Integer, sub_bits::Integer = 3)
+    g = v.grid
+    nbins = histogram_nbins(emin, emax, sub_bits)
+    counts = zeros(Int64, max(nbins, 0), max(ngroups, 0))
+    volume = weights === nothing ? nothing : zeros(Float64, max(nbins, 0), max(ngroups, 0))
+    check(ccall((:hmg_cell_histogram_groups, LIB), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Cint, Cint, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                g.h, v.h, ξ === nothing ? C_NULL : collect(Float64, ξ), form === nothing ? C_NULL : Matrix{Float64}(form),
+                emin, emax, sub_bits, ngroups, collect(Int32, group_of_cell), weights === nothing ? C_NULL : collect(Float64, weights),
+                counts, volume === nothing ? C_NULL : volume))
+    counts, volume
 end
 # Point samples of a level vector (hmg_grid_locate, hmg_sample, hmg_sample_raster; api.locate / sample / sample_raster): points is
 # dim x n.  locate (host, a grid without a context too): cell (n; -1: none), nodes ((dim+1) x n, 0-BASED hierarchical ids: add 1 for

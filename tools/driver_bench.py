@@ -36,8 +36,9 @@ one and the counters "sample_kernel_ns", "sample_download_ns", "sample_locator_b
 --histogram: driver.dirichlet_homogenization on hypercube(n) with histogram=True (one solve, the moment pass, then the histogram
 pass over the fine elements with Q = sigma_c / energy_form, 259 bins over 2^-24 .. 2^8 times the mean energy density): the volume
 fraction of every occupied bin as a text table, the intervals that hold the median and the 99 % quantile, then one line with the
-wall time of a run after --warmup untimed ones and the counters "cell_histogram_kernel_ns", "cell_histogram_launches".  Top
-levels up to 6 in 3D (--refinements 5) and 8 in 2D.
+wall time of a run after --warmup untimed ones and the counters "cell_histogram_kernel_ns", "cell_histogram_launches",
+"cell_histogram_window_launches".  Top levels up to 6 in 3D (--refinements 5) and 8 in 2D; with --large-cells 3D level 7 and 2D
+levels 9-11 too, through the histogram's window kernels.
 --uniaxial: driver.uniaxial_homogenization_tensor on hypercube(n) (d solves on one grid, the two faces normal to e_k as the grid's
 Dirichlet set in front of solve k): one line with the wall time of a run after --warmup untimed ones, the cycles and the tensor.
 --periodic: driver.periodic_homogenization_tensor on periodic_mesh(n) (d solves of the periodic cell problem on a torus of n^d unit
@@ -65,7 +66,7 @@ ap.add_argument("--tensor", action="store_true", help="one tensor run against d 
 ap.add_argument("--polycrystal", action="store_true", help="one rotated tensor per unit cube (implies --no-cpu)")
 ap.add_argument("--field-seed", type=int, default=5, help="seed of the coefficient field")
 ap.add_argument("--dirichlet-tensor", action="store_true", help="the Dirichlet tensor driver on hypercube(n): wall time, counters")
-ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor or --extrema: per-cell passes of cells larger than the LDS")
+ap.add_argument("--large-cells", action="store_true", help="with --dirichlet-tensor, --extrema or --histogram: per-cell passes of cells larger than the LDS")
 ap.add_argument("--extrema", action="store_true", help="the Dirichlet driver with the pass over the fine elements: wall time, counters")
 ap.add_argument("--locations", action="store_true", help="with --extrema: where the peaks sit; prints the ten hottest spots")
 ap.add_argument("--histogram", action="store_true", help="the Dirichlet driver with the histogram pass: volume fractions per bin, "
@@ -166,7 +167,7 @@ if a.histogram:
         sgrid = driver.generate_conductivity(a.dim, a.n, a.field_seed, values=(1.0, a.contrast))
     xi = np.ones(a.dim) / np.sqrt(a.dim)
     kw = dict(refinements=a.refinements, xi=xi, tolerance=a.tolerance, ctx=ctx, sigma_grid=sgrid, accelerate=a.accelerate,
-              smoother=a.smoother, histogram=True)
+              smoother=a.smoother, histogram=True, large_cells=a.large_cells)
     for _ in range(a.warmup):
         driver.dirichlet_homogenization(a.n, tag, **kw)
     ctx.sync()
@@ -188,14 +189,15 @@ if a.histogram:
         median, q99 = fields.histogram_quantile(vol, E, 0.5), fields.histogram_quantile(vol, E, 0.99)
         print(f"median in [{median[0]:.5e}, {median[1]:.5e}), 99 % quantile in [{q99[0]:.5e}, {q99[1]:.5e}) times the mean")
     print(json.dumps({"config": f"dirichlet_homogenization({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}, "
-                                f"histogram=True)",
+                                f"histogram=True{', large_cells=True' if a.large_cells else ''})",
                       "accelerate": a.accelerate, "smoother": a.smoother, "contrast": a.contrast, "polycrystal": a.polycrystal,
                       "warmup": a.warmup, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"],
                       "energy_form": r["energy_form"], "bins": int(vol.shape[0]), "bins_occupied": int((vol > 0.0).sum()),
                       "median_interval": list(median), "q99_interval": list(q99),
                       "cell_moments_kernel_ns": ctx.counter("cell_moments_kernel_ns"),
                       "cell_histogram_kernel_ns": ctx.counter("cell_histogram_kernel_ns"),
-                      "cell_histogram_launches": ctx.counter("cell_histogram_launches")}))
+                      "cell_histogram_launches": ctx.counter("cell_histogram_launches"), "large_cells": a.large_cells,
+                      "cell_histogram_window_launches": ctx.counter("cell_histogram_window_launches")}))
     sys.exit(0)
 if a.uniaxial or a.blocks or a.periodic:
     if a.polycrystal:
