@@ -28,12 +28,12 @@ bool cell_histogram_ok(const LevelDev &lv);
 void launch_cell_histogram(const Launch &L, const LevelDev &lv, int64_t ncells, const double *v, const uint8_t *elem_mask,
                            const double *rows, const HistogramRule &rule, int variant, int *out);
 
-// Cells larger than the LDS (hmg_histogram_window.hip): the same rows from a rolling window of the LDS, walked as the extrema window
-// kernels walk it (hmg_extrema_window.hip) -- slabs of k-planes in 3D (st: the level's SlabTables), bands of lattice rows in 2D
-// (closed forms, st unused).  LDS: [window | nbins counters].  A node is evaluated and counted with the functions k_cell_histogram
-// calls, in its HIST_NODE form alone (the variant has no say here): the same ints on a level both serve.
-// can the window kernels address this level?  cell_extrema_window_ok's layout checks, and the window fits the LDS together with
-// HIST_MAX_BINS counters (3D: one workgroup per CU; 2D: two)
+// Cells larger than the LDS (hmg_histogram_window.hip): the same rows from a rolling window of the LDS, with the walk every window
+// kernel of the per-cell results shares (hmg_cell_window.hpp) -- slabs of k-planes in 3D (st: the level's SlabTables), bands of
+// lattice rows in 2D (closed forms, st unused).  LDS: [window | nbins counters].  A node is evaluated and counted with the functions
+// k_cell_histogram calls, in its HIST_NODE form alone (the variant has no say here): the same ints on a level both serve.
+// can the window kernels address this level?  the walk's layout checks, and the window fits the LDS together with HIST_MAX_BINS
+// counters (3D: one workgroup per CU; 2D: two)
 bool cell_histogram_window_ok(const LevelDev &lv, const SlabTables &st);
 // out[c * nbins + b] for the first ncells columns; throws on a level it cannot address, on bin parameters outside the rule, on null
 // bases and on more than 2^31 - 1 cells before any launch; the same ints in every run and for every number of cells

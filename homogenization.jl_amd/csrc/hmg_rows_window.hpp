@@ -1,5 +1,5 @@
-// Row bands of a 2D cell larger than the LDS: the window geometry that k_apply_rows (hmg_apply_rows.hip) and
-// k_cell_pair_moments_rows (hmg_fields_window.hip) share.  The lattice image is L(i,j) = RO(j) + i, row j holds m+1-j nodes; a
+// Row bands of a 2D cell larger than the LDS: the window geometry that k_apply_rows (hmg_apply_rows.hip) and the rows walk of the
+// per-cell results (hmg_cell_window.hpp) share.  The lattice image is L(i,j) = RO(j) + i, row j holds m+1-j nodes; a
 // band evaluates rows [j0, j1) from a window that holds rows [j0-1, j1] and a zero guard.  Closed forms: no per-level tables.
 #pragma once
 

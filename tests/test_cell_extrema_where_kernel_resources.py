@@ -57,7 +57,7 @@ def constant(fname, name):
 def rows_lds_bytes():
     """LDS of one workgroup of the located rows form: per-wave partials [16][2] doubles, [16][8] ints and [16][2] ints of codes,
     then the window"""
-    nt = constant("hmg_extrema_window.hip", "EW_NT")
+    nt = constant("hmg_cell_window.hpp", "CW_NT")
     assert nt == 1024 and constant("hmg_rows_window.hpp", "RW_NT") == nt
     nw = nt // 64
     return 8 * 2 * nw + 4 * 8 * nw + 4 * 2 * nw + 8 * constant("hmg_rows_window.hpp", "RW_WIN")

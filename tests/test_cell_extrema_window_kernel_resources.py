@@ -52,7 +52,7 @@ def constant(fname, name):
 
 def rows_lds_bytes():
     """LDS of one workgroup of the rows form: per-wave partials [16][2] doubles and [16][8] ints, then the window."""
-    nt = constant(FNAME, "EW_NT")
+    nt = constant("hmg_cell_window.hpp", "CW_NT")
     assert nt == 1024 and constant("hmg_rows_window.hpp", "RW_NT") == nt
     nw = nt // 64
     return 8 * 2 * nw + 4 * 8 * nw + 8 * constant("hmg_rows_window.hpp", "RW_WIN")

@@ -55,7 +55,7 @@ def constant(fname, name):
 def rows_lds_bytes():
     """LDS of one workgroup of the rows form at the largest histogram: the window, then HIST_MAX_REGULAR + 3 int32 counters
     (an even number of them)."""
-    assert constant(FNAME, "HW_NT") == 1024 == constant("hmg_rows_window.hpp", "RW_NT")
+    assert constant("hmg_cell_window.hpp", "CW_NT") == 1024 == constant("hmg_rows_window.hpp", "RW_NT")
     nbins = constant("hmg_histogram_device.hpp", "HIST_MAX_REGULAR") + 3
     assert nbins == 1027
     return 8 * constant("hmg_rows_window.hpp", "RW_WIN") + 4 * ((nbins + 1) // 2 * 2)
