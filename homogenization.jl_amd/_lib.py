@@ -52,6 +52,8 @@ SIGNATURES = {
     "hmg_histogram_bin": (c_int, [c_i64, p_f64, c_int, c_int, c_int, p_i32]),
     "hmg_cell_histogram": (c_int, [vp, vp, p_f64, p_f64, c_int, c_int, c_int, p_i64]),
     "hmg_cell_histogram_groups": (c_int, [vp, vp, p_f64, p_f64, c_int, c_int, c_int, c_int, p_i32, p_f64, p_i64, p_f64]),
+    "hmg_grid_set_periodic_sampling": (c_int, [vp, c_int]),
+    "hmg_grid_periodic_sampling": (c_int, [vp, vp]),
     "hmg_grid_locate": (c_int, [vp, c_int, c_i64, p_f64, p_i32, p_i32, p_f64, p_f64]),
     "hmg_sample": (c_int, [vp, c_int, vp, p_f64, c_i64, p_f64, p_f64, p_f64, p_i32]),
     "hmg_sample_raster": (c_int, [vp, c_int, vp, p_f64, p_f64, p_f64, p_f64, c_i64, c_i64, p_f64, p_f64, p_i32]),

@@ -300,6 +300,17 @@ class ImplicitFineGrid:
     def mean_free(self) -> bool:
         return int(self._lib.hmg_grid_mean_free(self.h)) == 1
 
+    def set_periodic_sampling(self, on=True):
+        """Let `locate`, `sample` and `sample_raster` serve this periodic grid (include/hmg.h: hmg_grid_set_periodic_sampling;
+        default off: they refuse it).  Points are taken modulo the period, xi . x at the point as given, so a raster over several
+        periods tiles.  Drops the locator; launches nothing.  Refused on a grid that is not periodic."""
+        L.check(self._lib.hmg_grid_set_periodic_sampling(self.h, 1 if on else 0))
+
+    def periodic_sampling(self) -> bool:
+        on = ctypes.c_int()
+        L.check(self._lib.hmg_grid_periodic_sampling(self.h, ctypes.byref(on)))
+        return on.value == 1
+
     def reserve_spare(self, enable=True):
         """The sixth finest-level vector of the default V-cycle form (include/hmg.h: hmg_grid_reserve_spare): True reserves it now
         and raises if the memory is not there, False releases it (the reference's five vectors per level)."""

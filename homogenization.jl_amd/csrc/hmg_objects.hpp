@@ -189,6 +189,7 @@ struct FieldState {
 // host-only grid: grid creation and its allocations are what they were.
 struct SampleState {
     bool ready = false, on_device = false;
+    bool torus = false;                                      // hmg_grid_set_periodic_sampling: a periodic grid is served
     int nb[3] = {1, 1, 1};
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, inv_h[3] = {0, 0, 0};
     std::vector<int32_t> bin_ptr, bin_cell;                  // CSR: per bin its candidate cells, ascending

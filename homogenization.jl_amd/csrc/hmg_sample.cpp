@@ -19,6 +19,14 @@
 // levels get a table over the (m + 1)^3 lattice box from slot_ijk, built per level used (level 7: 1.1 MB).  The basis the device
 // text hard-codes is compared with ElementTables::dirs first.
 //
+// Grids on a torus (hmg_grid_set_periodic_sampling; off by default, and then refused as before): the bin grid covers exactly the
+// box [0, period) -- fixed by the period alone, not by where the node representatives are stored --, a cell's X0 is its first
+// vertex reduced into the box, A comes from the unwrapped edges (cell_edge_vectors, the rule cell_geo reads), and a cell is
+// listed in every bin that one of its images X0 + s P, s in {-1, 0, 1} per axis, meets: every edge is below half a period, so
+// the cell's box lies inside (-P / 2, 3 P / 2) and these images are all that reach the box.  Slack and face-plane pruning are
+// applied to the image as they are to a cell of an ordinary grid.  The inside test takes x - X0 to its minimal image
+// (sample_in_cell_torus), so the lists need no image code.
+//
 // Device memory: the locator's tables are one allocation of setup memory, a 3D level's table one more, both made by the first device
 // call that needs them.  Points and results of a call are one block from the context's pool of level-vector memory, its size
 // rounded up to 64 KiB so that calls of similar size reuse it.  The calls synchronise.  Not on a V-cycle's path.
@@ -61,12 +69,8 @@ SampleLocator host_locator(const SampleState &S)
 // A = J^-1 (row-major), J's columns X_k - X_0: formed and inverted in long double and rounded once.  MeshTables::jinv carries the
 // rounding of a double inverse, eps times the cell's condition number; on a flat cell of an unstructured mesh that alone is
 // above the 16 (dim + 1) eps m / h_min a sampled gradient is held to (tests/_sample_form.py).
-bool inverse_jacobian(int dim, const double *coords, const int32_t *el, double *A)
+bool invert_jacobian(int dim, const long double (&J)[3][3], double *A)
 {
-    long double J[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int col = 0; col < dim; ++col)
-        for (int a = 0; a < dim; ++a)
-            J[a][col] = (long double)coords[(size_t)el[col + 1] * dim + a] - (long double)coords[(size_t)el[0] * dim + a];
     long double C[3][3];                                  // cofactors (a 2D cell: J[2][2] = 1 and the rest of row / column 2 zero)
     for (int r = 0; r < 3; ++r)
         for (int s = 0; s < 3; ++s) {
@@ -80,12 +84,31 @@ bool inverse_jacobian(int dim, const double *coords, const int32_t *el, double *
     return true;
 }
 
+bool inverse_jacobian(int dim, const double *coords, const int32_t *el, double *A)
+{
+    long double J[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int col = 0; col < dim; ++col)
+        for (int a = 0; a < dim; ++a)
+            J[a][col] = (long double)coords[(size_t)el[col + 1] * dim + a] - (long double)coords[(size_t)el[0] * dim + a];
+    return invert_jacobian(dim, J, A);
+}
+
+// the same from a cell's unwrapped edge vectors (cell_edge_vectors: a grid on a torus)
+bool inverse_jacobian(int dim, const double (&d)[4][3], double *A)
+{
+    long double J[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int col = 0; col < dim; ++col)
+        for (int a = 0; a < dim; ++a) J[a][col] = (long double)d[col + 1][a];
+    return invert_jacobian(dim, J, A);
+}
+
 void build_locator(hmg_grid *g)
 {
     SampleState &S = g->sample;
     const MeshTables &M = g->cur();
     const int dim = g->dim, N = dim + 1, ng = dim + dim * dim;
     const int64_t nc = M.ncells;
+    const bool torus = M.periodic();
     need(nc >= 1, "sampling: the grid has no cells");
     S.ready = false;
     S.on_device = false;
@@ -94,6 +117,33 @@ void build_locator(hmg_grid *g)
     for (int64_t c = 0; c < nc; ++c) {
         const int32_t *el = &M.cells[c * N];
         double *G = &S.geo[(size_t)c * ng];
+        if (torus) {
+            // X0 reduced into the box, A and the cell's box from the unwrapped edges
+            double d[4][3];
+            cell_edge_vectors(M, c, d);
+            if (!inverse_jacobian(dim, d, G + dim)) throw std::runtime_error("sampling: degenerate cell " + std::to_string(c));
+            double *B = &box[(size_t)c * 6];
+            double ext = 0.0;
+            for (int a = 0; a < dim; ++a) {
+                const double P = M.period[a], x = M.coords[(size_t)el[0] * dim + a];
+                need(std::isfinite(x), "sampling: a node coordinate of the base mesh is not finite");
+                double x0 = x - P * std::floor(x / P);
+                if (x0 < 0.0) x0 += P;
+                if (x0 >= P) x0 -= P;
+                G[a] = x0;
+                double mn = 0.0, mx = 0.0;
+                for (int q = 1; q < N; ++q) {
+                    mn = std::min(mn, d[q][a]);
+                    mx = std::max(mx, d[q][a]);
+                }
+                need(std::isfinite(mn) && std::isfinite(mx), "sampling: a node coordinate of the base mesh is not finite");
+                B[a] = x0 + mn;
+                B[3 + a] = x0 + mx;
+                ext = std::max(ext, mx - mn);
+            }
+            slack[c] = SLACK_PHYS * ext;
+            continue;
+        }
         for (int a = 0; a < dim; ++a) G[a] = M.coords[(size_t)el[0] * dim + a];
         if (!inverse_jacobian(dim, M.coords.data(), el, G + dim)) throw std::runtime_error("sampling: degenerate cell " + std::to_string(c));
         double *B = &box[(size_t)c * 6];
@@ -120,6 +170,10 @@ void build_locator(hmg_grid *g)
             lo[a] = std::min(lo[a], box[(size_t)c * 6 + a]);
             hi[a] = std::max(hi[a], box[(size_t)c * 6 + 3 + a]);
         }
+        if (torus) {                             // the box is the period's, whatever the cells' boxes reach
+            lo[a] = 0.0;
+            hi[a] = M.period[a];
+        }
         gext = std::max(gext, hi[a] - lo[a]);
         vol *= hi[a] - lo[a];
     }
@@ -134,8 +188,8 @@ void build_locator(hmg_grid *g)
         S.lo[a] = S.hi[a] = 0.0;
         S.inv_h[a] = 0.0;
         if (a >= dim) continue;
-        S.lo[a] = lo[a] - grow;
-        S.hi[a] = hi[a] + grow;
+        S.lo[a] = torus ? lo[a] : lo[a] - grow;      // (a torus: the bins cover exactly the box)
+        S.hi[a] = torus ? hi[a] : hi[a] + grow;
         const double n = std::ceil((hi[a] - lo[a]) / h);
         S.nb[a] = (int)std::max(1.0, std::min(4096.0, n));
         nbins *= S.nb[a];
@@ -151,12 +205,19 @@ void build_locator(hmg_grid *g)
     for (int a = 0; a < dim; ++a) S.inv_h[a] = (double)S.nb[a] / (S.hi[a] - S.lo[a]);
     SampleLocator L = host_locator(S);
 
-    // f(bin) for every bin cell c is listed in
-    auto visit = [&](int64_t c, auto &&f) {
-        const double *B = &box[(size_t)c * 6], *G = &S.geo[(size_t)c * ng];
+    // f(bin) for every bin that cell c, moved by `move`, is listed in (an ordinary grid: move = 0, the cell as it stands)
+    auto visit_image = [&](int64_t c, const double *move, auto &&f) {
+        const double *G0 = &S.geo[(size_t)c * ng];
+        double B[6], G[3] = {0, 0, 0};
+        for (int a = 0; a < dim; ++a) {
+            B[a] = box[(size_t)c * 6 + a] + move[a];
+            B[3 + a] = box[(size_t)c * 6 + 3 + a] + move[a];
+            G[a] = G0[a] + move[a];
+        }
         const double s = slack[c] + 1e-12 * gext;
         int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
         for (int a = 0; a < dim; ++a) {
+            if (B[3 + a] + s < S.lo[a] || B[a] - s > S.hi[a]) return;      // (an image that does not reach the box)
             b0[a] = sample_bin(L, a, std::max(B[a] - s, S.lo[a]));
             b1[a] = sample_bin(L, a, std::min(B[3 + a] + s, S.hi[a]));
         }
@@ -175,8 +236,8 @@ void build_locator(hmg_grid *g)
                     for (int b = 0; b < dim && keep; ++b) {
                         double v = 0.0, r = 0.0;
                         for (int a = 0; a < dim; ++a) {
-                            v += G[dim + b * dim + a] * ctr[a];
-                            r += std::fabs(G[dim + b * dim + a]) * half[a];
+                            v += G0[dim + b * dim + a] * ctr[a];
+                            r += std::fabs(G0[dim + b * dim + a]) * half[a];
                         }
                         keep = v + r >= -PLANE_MARGIN;
                         l0c -= v;
@@ -184,13 +245,32 @@ void build_locator(hmg_grid *g)
                     if (keep) {
                         for (int a = 0; a < dim; ++a) {
                             double col = 0.0;
-                            for (int b = 0; b < dim; ++b) col += G[dim + b * dim + a];
+                            for (int b = 0; b < dim; ++b) col += G0[dim + b * dim + a];
                             l0h += std::fabs(col) * half[a];
                         }
                         keep = l0c + l0h >= -PLANE_MARGIN;
                     }
                     if (keep) f(((int64_t)bz * S.nb[1] + by) * S.nb[0] + bx);
                 }
+    };
+    // f(bin) for every bin cell c is listed in, each bin once.  On a torus: the bins of its images X0 + s P, s in {-1, 0, 1}
+    // per axis, ascending (two images of a cell can meet one bin where an axis has few bins)
+    auto visit = [&](int64_t c, auto &&f) {
+        const double still[3] = {0.0, 0.0, 0.0};
+        if (!torus) {
+            visit_image(c, still, f);
+            return;
+        }
+        std::vector<int64_t> bins;
+        for (int sz = (dim == 3 ? -1 : 0); sz <= (dim == 3 ? 1 : 0); ++sz)
+            for (int sy = -1; sy <= 1; ++sy)
+                for (int sx = -1; sx <= 1; ++sx) {
+                    const double move[3] = {sx * M.period[0], sy * M.period[1], sz * M.period[2]};
+                    visit_image(c, move, [&](int64_t bin) { bins.push_back(bin); });
+                }
+        std::sort(bins.begin(), bins.end());
+        bins.erase(std::unique(bins.begin(), bins.end()), bins.end());
+        for (int64_t bin : bins) f(bin);
     };
     std::vector<int64_t> first(nc + 1, 0);
     parallel_for(nc, [&](int64_t c0, int64_t c1) {
@@ -280,8 +360,8 @@ void prepare(hmg_grid *g, int level, const char *call)
 {
     need(g != nullptr, "null grid");
     if (g->part) throw std::runtime_error(std::string(call) + ": partitioned grids are not served (sample on an unpartitioned grid)");
-    // (the locator reads M.coords of a cell's nodes as they stand: on a torus they may sit on opposite sides of the box)
-    if (g->cur().periodic()) throw std::runtime_error(std::string(call) + ": periodic grids are not served (point location on a torus is not built)");
+    // (on a torus the nodes of a cell may sit on opposite sides of the box: served once hmg_grid_set_periodic_sampling says so)
+    if (g->cur().periodic() && !g->sample.torus) throw std::runtime_error(std::string(call) + ": periodic grids are not served (point location on a torus is not built)");
     if (level < 1 || level > g->nlevels)
         throw std::runtime_error(std::string(call) + ": level " + std::to_string(level) + " out of range (1 to " + std::to_string(g->nlevels) + ")");
 }
@@ -293,15 +373,17 @@ void ensure_host_tables(hmg_grid *g, int level)
 }
 
 template <int DIM>
-void locate_points(const SampleLocator &L, const SampleLevel &lv, const LevelTables &T, int64_t n, const double *points, int32_t *cell,
-                   int32_t *nodes, double *weights, double *gweights)
+void locate_points(const SampleLocator &L, const double *period, const SampleLevel &lv, const LevelTables &T, int64_t n,
+                   const double *points, int32_t *cell, int32_t *nodes, double *weights, double *gweights)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     parallel_for(n, [&](int64_t p0, int64_t p1) {
         for (int64_t p = p0; p < p1; ++p) {
             const double *x = points + p * DIM;
-            double xh[DIM];
-            const int c = sample_find_cell<DIM>(L, x, xh);
+            double xh[DIM], xr[DIM];
+            const int c = !period                       ? sample_find_cell<DIM>(L, x, xh)
+                          : sample_wrap<DIM>(period, x, xr) ? sample_find_cell_torus<DIM>(L, period, xr, xh)
+                                                            : -1;
             if (cell) cell[p] = c;
             if (c < 0) {
                 for (int q = 0; q <= DIM; ++q) {
@@ -430,7 +512,7 @@ void sample(hmg_grid *g, int level, const void *column, const double *xi, int64_
         HIPCHK(hipEventCreate(&ev1));
         if (points) HIPCHK(hipMemcpyAsync(blk, points, sizeof(double) * (size_t)n * dim, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipEventRecord(ev0, c->stream));
-        launch_sample(c->stream, dim, points == nullptr, a);
+        launch_sample(c->stream, dim, points == nullptr, a, g->cur().periodic() ? g->cur().period : nullptr);
         c->sample_launches += 1;
         HIPCHK(hipEventRecord(ev1, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -476,10 +558,32 @@ int hmg_grid_locate(hmg_grid *g, int level, int64_t npoints, const double *point
     const SampleLocator L = host_locator(g->sample);
     const SampleLevel lv = host_level(g, level);
     const LevelTables &T = g->lt[level - 1];
+    const double *period = g->cur().periodic() ? g->cur().period : nullptr;
     if (g->dim == 3)
-        locate_points<3>(L, lv, T, npoints, points, cell, nodes, weights, gweights);
+        locate_points<3>(L, period, lv, T, npoints, points, cell, nodes, weights, gweights);
     else
-        locate_points<2>(L, lv, T, npoints, points, cell, nodes, weights, gweights);
+        locate_points<2>(L, period, lv, T, npoints, points, cell, nodes, weights, gweights);
+    HMG_END
+}
+
+int hmg_grid_set_periodic_sampling(hmg_grid *g, int on)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(g->cur().periodic(), "hmg_grid_set_periodic_sampling: the grid is not periodic (an ordinary grid is sampled as it is)");
+    need(on == 0 || on == 1, "hmg_grid_set_periodic_sampling: on must be 0 or 1");
+    SampleState &S = g->sample;
+    S.torus = on == 1;
+    S.ready = S.on_device = false;               // (the locator goes; the next call that is served builds it)
+    HMG_END
+}
+
+int hmg_grid_periodic_sampling(hmg_grid *g, int *on)
+{
+    HMG_TRY
+    need(g != nullptr, "null grid");
+    need(on != nullptr, "hmg_grid_periodic_sampling: null result");
+    *on = g->sample.torus ? 1 : 0;
     HMG_END
 }
 

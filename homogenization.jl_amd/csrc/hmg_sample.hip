@@ -59,31 +59,10 @@ __global__ __launch_bounds__(SAMPLE_NT) void k_sample(const SampleArgs a)
     }
 }
 
-// smallest power of two >= n, as its exponent (1 <= n <= 16)
-int log2_ceil(int64_t n)
-{
-    int e = 0;
-    while (((int64_t)1 << e) < n) ++e;
-    return e;
-}
-
 template <int DIM, bool RASTER>
 void launch(hipStream_t stream, SampleArgs a)
 {
-    int64_t grid;
-    if (RASTER) {
-        // 16 x 16 pixels per workgroup; a raster thinner than 16 pixels one way takes tiles as thin as it is (a line: 256 x 1): a
-        // raster of 2^31 - 1 pixels in one line stays a launch of 2^31 threads (square tiles would ask for 2^35), and whatever the
-        // shape a raster of that many pixels stays below 32 / 17 of them, inside what a launch accepts
-        a.tile_log2w = 4;
-        if (a.nv < SAMPLE_TILE)
-            a.tile_log2w = 8 - log2_ceil(a.nv);
-        else if (a.nu < SAMPLE_TILE)
-            a.tile_log2w = log2_ceil(a.nu);
-        const int64_t tw = (int64_t)1 << a.tile_log2w, th = SAMPLE_NT / tw;
-        grid = ((a.nu + tw - 1) / tw) * ((a.nv + th - 1) / th);
-    } else
-        grid = (a.npoints + SAMPLE_NT - 1) / SAMPLE_NT;
+    const int64_t grid = sample_launch_grid(RASTER, a);
     if (grid <= 0) return;
     if (grid * SAMPLE_NT > 0xffffffffll) throw std::runtime_error("k_sample: the launch would exceed 2^32 - 1 threads");
     hipLaunchKernelGGL((k_sample<DIM, RASTER>), dim3((unsigned)grid), dim3(SAMPLE_NT), 0, stream, a);
@@ -92,8 +71,15 @@ void launch(hipStream_t stream, SampleArgs a)
 
 }  // namespace
 
-void launch_sample(hipStream_t stream, int dim, bool raster, const SampleArgs &a)
+void launch_sample(hipStream_t stream, int dim, bool raster, const SampleArgs &a, const double *period)
 {
+    if (period) {                                // a grid on a torus: k_sample_torus (hmg_sample_torus.hip)
+        SampleTorusArgs t{};
+        t.s = a;
+        for (int k = 0; k < dim; ++k) t.period[k] = period[k];
+        launch_sample_torus(stream, dim, raster, t);
+        return;
+    }
     if (dim == 3)
         raster ? launch<3, true>(stream, a) : launch<3, false>(stream, a);
     else

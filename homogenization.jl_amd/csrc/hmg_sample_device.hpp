@@ -182,4 +182,66 @@ HMG_HD void sample_gradient(const SampleLevel &lv, const SampleElement<DIM> &E, 
     }
 }
 
+// ---- grids on a torus (hmg_grid_set_periodic_sampling) ----------------------------------------------------------------------
+// The locator's box is [0, period[a]) per axis, fixed by the period alone; a cell's X0 is its first vertex reduced into that box
+// and A comes from its unwrapped edges.  A point is reduced into the box for the bin lookup only; whether it lies in a cell is
+// asked of the minimal image of x - X0, which is the only image that can: every point of a cell lies within half a period of the
+// cell's first vertex on each axis.  A hit is therefore a hit on the torus, and the lists carry no image code.  xi . x is taken at
+// the caller's point (sample_value is handed that one), so u = xi . x + v grows across periods while v repeats.
+
+// x reduced into the box, x - P floor(x / P) per axis; false: a coordinate is not finite.  The rounding of x / P next to a whole
+// number of periods can leave the difference just below 0: it gets one period more.  (A result that rounds to P stays; sample_bin
+// clamps it into the last bin, whose lists hold the images that reach P.)
+template <int DIM>
+HMG_HD bool sample_wrap(const double *period, const double *x, double *xr)
+{
+#pragma clang fp contract(off)
+    bool finite = true;
+    for (int a = 0; a < DIM; ++a) {
+        const double P = period[a];
+        double r = x[a] - P * floor(x[a] / P);
+        if (r < 0.0) r += P;
+        xr[a] = r;
+        finite = finite && r >= 0.0 && r <= P;       // (NaN and inf compare false)
+    }
+    return finite;
+}
+
+// sample_in_cell on a torus: x - X0 by the minimal image
+template <int DIM>
+HMG_HD bool sample_in_cell_torus(const double *geo, const double *period, const double *x, double *xh)
+{
+#pragma clang fp contract(off)
+    double d[DIM];
+    for (int a = 0; a < DIM; ++a) {
+        d[a] = x[a] - geo[a];
+        d[a] -= period[a] * rint(d[a] / period[a]);
+    }
+    const double *A = geo + DIM;
+    double l0 = 1.0;
+    bool in = true;
+    for (int b = 0; b < DIM; ++b) {
+        double v = A[b * DIM] * d[0];
+        for (int a = 1; a < DIM; ++a) v = __builtin_fma(A[b * DIM + a], d[a], v);
+        xh[b] = v;
+        l0 -= v;
+        in = in && v >= -SAMPLE_TAU;
+    }
+    return in && l0 >= -SAMPLE_TAU;
+}
+
+// the lowest cell that contains xr (a point of the box: sample_wrap) on the torus; -1 only where the lists fail the point
+template <int DIM>
+HMG_HD int sample_find_cell_torus(const SampleLocator &L, const double *period, const double *xr, double *xh)
+{
+    int bin = 0;
+    for (int a = DIM - 1; a >= 0; --a) bin = bin * L.nb[a] + sample_bin(L, a, xr[a]);
+    const int q1 = L.bin_ptr[bin + 1];
+    for (int q = L.bin_ptr[bin]; q < q1; ++q) {
+        const int c = L.bin_cell[q];
+        if (sample_in_cell_torus<DIM>(L.geo + (size_t)c * (DIM + DIM * DIM), period, xr, xh)) return c;
+    }
+    return -1;
+}
+
 }  // namespace hmg

@@ -833,12 +833,14 @@ def _hypercube_problem(n, eltype, sigma_grid, seed, values, cond):
 
 
 def _tensor_run(who, faces, base, cond, refinements, ctx, tolerance, smoother, accelerate, fields, save, smoothing_steps,
-                max_cycles, large_cells):
+                max_cycles, large_cells, slices=None):
     """The d corrector solves and moment passes behind `dirichlet_homogenization_tensor` and the drivers that differ from it in
     the base mesh and the constrained set only.  base, cond: the mesh (a torus where `base.period` is set) and the conductivity
     per cell.  faces: None -- the grid's default set, no call --, a function base -> one face array, set once
     before the solves, or base -> a list of d of them, set in front of solve k.  A set of the caller's is taken back behind the
-    solves, also when one raises."""
+    solves, also when one raises.  slices: rasters (origin, du, dv, nu, nv) every u_k = e_k.x + v_k is sampled on behind the
+    solves ("slices": per raster a list over k of what `dirichlet_homogenization(slices=...)` returns per slice); on a torus
+    sampling is switched on around these passes only."""
     dim = base.dim
     own_ctx = ctx is None
     if own_ctx:
@@ -890,6 +892,25 @@ def _tensor_run(who, faces, base, cond, refinements, ctx, tolerance, smoother, a
             tensor[k, l] = tensor[l, k] = float(cell_fields.pair_energy(cond, pairs[k, l]).sum() / omega)
     out = {"tensor": tensor, "tensor_flux": np.stack([cell_fields.flux_row(base, cond, means[k]) for k in range(dim)]),
            "cycles": cycles, "residual": residual, "volume": omega}
+    if slices is not None:
+        torus = getattr(base, "period", None) is not None
+        if torus:
+            implicit.set_periodic_sampling(True)
+        try:
+            out["slices"] = []
+            for i, (origin, du, dv, nu, nv) in enumerate(slices):
+                per_k = []
+                for k in range(dim):
+                    s = api.sample_raster(V[k], implicit, origin, du, dv, nu, nv, xi=eye[k])
+                    s["flux"] = cell_fields.sample_flux(cond, s["cell"], s["gradient"])
+                    s["energy_density"] = cell_fields.sample_energy_density(cond, s["cell"], s["gradient"])
+                    per_k.append(s)
+                    if save is not None:
+                        vtk.export_slice(f"{save}_slice{i}_u{k + 1}", origin, du, dv, s)
+                out["slices"].append(per_k)
+        finally:
+            if torus:
+                implicit.set_periodic_sampling(False)
     if save is not None:
         cells = {"a": cond}
         for k in range(dim):
@@ -934,7 +955,7 @@ def periodic_mesh(eltype, shape) -> Mesh:
 def periodic_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *, ctx=None, sigma_grid=None, seed: int = 0,
                                    values=(1.0, 9.0), tolerance: float = 1e-10, smoother: str = "cg", accelerate: bool = False,
                                    fields: bool = False, save=None, smoothing_steps: int = 3, max_cycles: int = 200,
-                                   large_cells: bool = False):
+                                   large_cells: bool = False, slices=None):
     """The homogenized tensor of the PERIODIC cell problem -- its definition for periodic media, and for random media the boundary
     condition with the smallest boundary-layer error: on the torus of n^d unit cubes (`periodic_mesh`, n >= 3) find v_k periodic
     with a(v_k, w) = -int sigma e_k . grad w for all periodic w (lambda = 0, no constrained node), then "tensor" and "tensor_flux"
@@ -945,7 +966,13 @@ def periodic_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *
     corrector is fixed up to a constant -- nothing is normalised, every quantity returned depends on gradients only.  The space of
     `dirichlet_homogenization_tensor` on the same `sigma_grid` is a subspace of the periodic one, so this diagonal is at most
     that one's.  The tensor does not depend on where the period starts (in 3D up to the discretisation: the cells that wrap
-    choose their interior diagonals differently).  No counterpart in the reference."""
+    choose their interior diagonals differently).
+    `slices`: a list of rasters (origin, du, dv, nu, nv) -- pixel (a, b) at origin + a du + b dv, anywhere: a point is taken
+    modulo the period --; behind the solves every u_k = e_k.x + v_k is sampled on each on the device (api.sample_raster with the
+    grid's periodic sampling switched on for these passes) and "slices" in the returned dict is, per raster, a list over k of
+    dicts "value", "gradient", "cell", "flux" and "energy_density" as `dirichlet_homogenization(slices=...)` returns them.  Over
+    several periods e_k.x grows while v_k, the gradient and the flux repeat.  `save` writes `<save>_slice<i>_u<k>.vts`.  The
+    tensor does not depend on `slices`.  No counterpart in the reference."""
     dim = api._dim_of(eltype)
     base = periodic_mesh(eltype, n)
     if sigma_grid is None:
@@ -956,7 +983,7 @@ def periodic_homogenization_tensor(n: int, eltype=Tri64, refinements: int = 2, *
     per_cube = base.elements.shape[0] // n ** dim
     cond = np.ascontiguousarray(np.repeat(sg.reshape((n ** dim,) + sg.shape[dim:]), per_cube, axis=0))
     return _tensor_run("periodic_homogenization_tensor", None, base, cond, refinements, ctx, tolerance, smoother, accelerate,
-                       fields, save, smoothing_steps, max_cycles, large_cells)
+                       fields, save, smoothing_steps, max_cycles, large_cells, slices)
 
 
 def faces_on_plane(base: Mesh, axis: int, value: float):

@@ -254,7 +254,8 @@ int64_t hmg_grid_dirichlet_faces(const hmg_grid *grid, int64_t *out, int64_t cap
  * degenerate cell; and a period that is not positive and finite.  The grid takes hmg_grid_set_operator*, _set_lambda,
  * _set_dirichlet_faces (a plane of fixed potential inside the torus: any faces of the mesh; nfaces = -1 is the empty set here),
  * the smoothers, hmg_fcg_*, the right-hand sides, integrals and per-cell fields.  It refuses, with "periodic" in the message,
- * hmg_grid_shrink, hmg_grid_locate, hmg_sample and hmg_sample_raster; there is no partitioned form.  hmg_grid_mean_free is 1. */
+ * hmg_grid_shrink and -- until hmg_grid_set_periodic_sampling switches them on -- hmg_grid_locate, hmg_sample and
+ * hmg_sample_raster; there is no partitioned form.  hmg_grid_mean_free is 1. */
 int hmg_grid_create_periodic(hmg_ctx *ctx, int dim, int nlevels, int64_t nnodes, const double *coords /* dim*nnodes */,
                              int64_t ncells, const int64_t *cells /* (dim+1)*ncells, 1-based */, const double *period /* dim */,
                              hmg_grid **out);
@@ -635,9 +636,23 @@ int hmg_cell_histogram_groups(hmg_grid *grid, hmg_vec *v, const double *xi /* di
  * a grid without a context has a locator and nothing else to ask.
  * A raster of any shape up to 2^31 - 1 pixels is one launch: a workgroup takes 16 x 16 pixels, on a raster thinner than 16 pixels
  * one way a tile as thin as the raster (a line of pixels: 256 x 1).
- * Refused with a message, nothing launched and nothing changed: a partitioned grid; a level out of range; null points / origin /
+ * Refused with a message, nothing launched and nothing changed: a partitioned grid; a periodic grid on which
+ * hmg_grid_set_periodic_sampling has not switched sampling on; a level out of range; null points / origin /
  * du / dv; npoints or nu * nv above 2^31 - 1 or negative (0: success, nothing written); all outputs NULL; and, for the two
  * device calls, a grid without a context or a column that fails the check above. */
+/* Sampling on a periodic grid, switched on per grid (default 0: the three calls below refuse a periodic grid).  With it on:
+ *   box       the torus is looked at through the box [0, period[a]) per axis, fixed by the period alone -- not by where the
+ *             node representatives are stored; a mesh whose nodes are moved by whole periods gives the same bits.
+ *   cell      a point is taken modulo the period; whether it lies in a cell is asked of the MINIMAL IMAGE of x - X0 (X0 the
+ *             cell's first vertex), d - period rint(d / period) per axis, with the cell's edges unwrapped by the same rule.
+ *             Every finite point has a cell; ties go to the lowest cell id, as everywhere.
+ *   value     xi . x is taken at the CALLER'S point, not the reduced one: u = xi . x + v grows across periods while v
+ *             repeats, and a raster over several periods tiles.  The gradient is periodic.
+ * The call launches nothing, touches no vector and no pending record, and drops the locator (the next call that is served
+ * builds it).  A grid without a context takes it (hmg_grid_locate is then what it serves).  Refused: a grid that is not
+ * periodic; on other than 0 and 1. */
+int hmg_grid_set_periodic_sampling(hmg_grid *grid, int on);
+int hmg_grid_periodic_sampling(hmg_grid *grid, int *on);
 int hmg_grid_locate(hmg_grid *grid, int level, int64_t npoints, const double *points /* point-major, dim each */,
                     int32_t *cell /* npoints */, int32_t *nodes /* (dim+1) per point: 0-based HIERARCHICAL row ids */,
                     double *weights /* (dim+1) per point */, double *gweights /* dim*(dim+1) per point, or NULL */);

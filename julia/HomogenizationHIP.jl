@@ -491,6 +491,15 @@ end
 # rows of Matrix(v)), weights ((dim+1) x n), gweights (dim x (dim+1) x n).  sample / sample_raster: u = ξ⋅x + v, its gradient
 # (dim x n) and the cell, evaluated on the device from the vector as stored; the raster's pixel (a, b) is origin + a du + b dv at
 # index a + 1, b + 1 of nu x nv arrays.  They read v through device_ptr(v) (a pending r-update of v is settled, v counts as exposed).
+# On a periodic grid the three refuse until set_periodic_sampling!(g) switches them on: points are then taken modulo the period,
+# ξ⋅x at the point as given (a raster over several periods tiles).  Drops the locator, launches nothing.
+set_periodic_sampling!(g::HipGrid, on::Bool = true) =
+    (check(ccall((:hmg_grid_set_periodic_sampling, LIB), Cint, (Ptr{Cvoid}, Cint), g.h, on ? 1 : 0)); g)
+function periodic_sampling(g::HipGrid)
+    on = Ref{Cint}(0)
+    check(ccall((:hmg_grid_periodic_sampling, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), g.h, on))
+    on[] == 1
+end
 function locate(g::HipGrid{dim}, level::Integer, points::AbstractMatrix{Float64}) where {dim}
     n = size(points, 2)
     cell = zeros(Int32, n); nodes = zeros(Int32, dim + 1, n); w = zeros(Float64, dim + 1, n); gw = zeros(Float64, dim, dim + 1, n)

@@ -43,6 +43,10 @@ levels 9-11 too, through the histogram's window kernels.
 Dirichlet set in front of solve k): one line with the wall time of a run after --warmup untimed ones, the cycles and the tensor.
 --periodic: driver.periodic_homogenization_tensor on periodic_mesh(n) (d solves of the periodic cell problem on a torus of n^d unit
 cubes, n >= 3, lambda = 0, the level-1 solve on the complement of the constants): the same line.
+--periodic --slice N: the same driver with slices=[one axis-aligned N x N raster over two periods per axis, from half a period in
+front of the box, through the middle of the third axis]: every corrector u_k is sampled on it (hmg_sample_raster on the torus);
+the line also carries the pixels, the pixels with a cell (all of them, on a torus), the largest difference of a gradient between
+pixels one period apart, and the sampling counters of the last pass.
 --blocks B: driver.block_homogenization_tensor(n, B) (the Dirichlet cell problems of all (n / B)^d blocks in d solves on one grid)
 against the same number of dirichlet_homogenization_tensor(B) runs on the blocks' own meshes, in one process: the two wall times
 after --warmup untimed rounds of both, their ratio and the largest relative difference of a block's tensor."""
@@ -88,7 +92,7 @@ else:
     sgrid = driver.generate_conductivity(a.dim, width, a.field_seed, values=(1.0, a.contrast))
 tag = hmg.Tet64 if a.dim == 3 else hmg.Tri64
 ctx = hmg.Context(0)
-if a.slice:
+if a.slice and not a.periodic:
     if a.polycrystal:
         principal = (1.0, a.contrast) if a.dim == 2 else (1.0, a.contrast, a.contrast ** 0.5)
         sgrid = driver.generate_polycrystal(a.dim, a.n, a.field_seed, principal)
@@ -224,10 +228,29 @@ if a.uniaxial or a.blocks or a.periodic:
                           "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
         sys.exit(0)
     if a.periodic:
+        extra, what = {}, ""
+        if a.slice:
+            if a.slice % 2:
+                sys.exit("--periodic --slice N: N must be even (two periods, whole pixels per period)")
+            step = 2.0 * a.n / a.slice
+            origin = np.full(a.dim, -0.5 * a.n + 0.25 * step)        # the torus periodic_mesh(n) has the box [0, n)^dim
+            if a.dim == 3:
+                origin[2] = 0.5 * a.n + 0.3 * step                   # off the lattice planes
+            du, dv = np.zeros(a.dim), np.zeros(a.dim)
+            du[0] = dv[1] = step
+            kw["slices"] = [(origin, du, dv, a.slice, a.slice)]
+            what = f", slices=[{a.slice} x {a.slice}]"
         r, wall = timed(lambda: driver.periodic_homogenization_tensor(a.n, tag, sigma_grid=sgrid, **kw))
-        print(json.dumps({"config": f"periodic_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance})",
+        if a.slice:
+            per_k, h = r["slices"][0], a.slice // 2
+            extra = {"pixels": int(per_k[0]["cell"].size), "pixels_inside": int((per_k[0]["cell"] >= 0).sum()),
+                     "max_gradient_diff_one_period_apart": max(float(np.abs(s["gradient"][:h, :h] - s["gradient"][h:, h:]).max()) for s in per_k),
+                     "sample_kernel_ns": ctx.counter("sample_kernel_ns"), "sample_download_ns": ctx.counter("sample_download_ns"),
+                     "sample_locator_bytes": ctx.counter("sample_locator_bytes"),
+                     "sample_locator_max_candidates": ctx.counter("sample_locator_max_candidates")}
+        print(json.dumps({"config": f"periodic_homogenization_tensor({a.n}, {tag}, refinements={a.refinements}, tolerance={a.tolerance}{what})",
                           **common, "wall_s": wall, "cycles": r["cycles"], "residual": r["residual"], "tensor": r["tensor"].tolist(),
-                          "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max())}))
+                          "max_abs_diff_to_flux_form": float(np.abs(r["tensor"] - r["tensor_flux"]).max()), **extra}))
         sys.exit(0)
     nb = a.n // a.blocks
     subs = {idx: np.ascontiguousarray(sgrid[tuple(slice(a.blocks * i, a.blocks * (i + 1)) for i in idx)]) for idx in np.ndindex(*(nb,) * a.dim)}
